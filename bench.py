@@ -2,12 +2,17 @@
 (n = 16384, m = 4, p = 8, nonlinear + linear output dependencies, markov = 2, dense Cholesky, fp64), layers sharded
 over the GPUs of one node (one process per GPU; RCCL only for the 8-byte sum of layer log-likelihoods).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 16384 --m 4 --p 8] [--no-extras] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 16384 --m 4 --p 8] [--dump-outputs DIR]
+    python bench.py --full [--no-extras] [--no-cpu] [--no-isolated] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one evaluation of the model's log marginal likelihood on one synthetic data set whose inputs are
 already resident in HBM (Gram build -> augmented Cholesky -> quadratic form, for each of the p layers).  Rank 0
-prints ONE JSON line.  Besides the contract fields it carries
+prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the contract fields (`ms_per_step`: the
+wall-clock of one timed step); `--dump-outputs DIR` also writes what the last timed step returned, the log marginal likelihood,
+as DIR/logpdf.npy (float64; the inputs are seeded, so two builds can be compared output for output).  With `--full` the line
+also carries
+  parity_pin    a hash of tests/golden/reference_cases.json, or "absent";
   roofline      the trailing-update SYRK of the blocked Cholesky (the dominant kernel): algorithmic flops
                 (rem * (rem + 1) * kb per launch) / hipEvent-measured time, against the fp64 matrix peak;
   cpu_baseline  the reference's CPU path restated on torch-CPU fp64 operators (oracle/torch_cpu.py, kind "port"), timed
@@ -69,11 +74,16 @@ def main():
     ap.add_argument("--n", "--rows", dest="n", type=int, default=16384)  # --rows: torchrun's parser chokes on --n
     ap.add_argument("--m", type=int, default=4)
     ap.add_argument("--p", type=int, default=8)
-    ap.add_argument("--no-extras", action="store_true", help="skip the fit + predict leg")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the log marginal likelihood) as DIR/logpdf.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (profiled timed steps, isolated evaluation), fit + predict, the other "
+                         "configurations, small-n, CPU baselines; off by default")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fit + predict leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-isolated", action="store_true",
-                    help="skip the extra, untimed layer-after-layer evaluation behind roofline.isolated (the PMC passes use this: every "
-                         "dispatch of the update kernel in their trace then belongs to the one lock-step evaluation)")
+                    help="with --full: skip the extra, untimed layer-after-layer evaluation behind roofline.isolated (the PMC passes "
+                         "use this: every dispatch of the update kernel in their trace then belongs to the one lock-step evaluation)")
     ap.add_argument("--extras-timeout", type=float, default=600.0,
                     help="seconds the fit + predict / CPU-baseline / teardown part may take before every rank exits (rank 0 prints the line first)")
     ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU work the bounded torch-CPU baseline may spend on full-size layers")
@@ -185,8 +195,9 @@ def main():
     value = None
     for _ in range(args.warmup):
         value = step()
-    lib.gpar_profile_read(None, None, None, None, 1)
-    lib.gpar_profile_enable(1)
+    if args.full:   # (hipEvents around every trailing-update launch of the timed steps: the roofline's figures)
+        lib.gpar_profile_read(None, None, None, None, 1)
+        lib.gpar_profile_enable(1)
     barrier()
     timing.clear()
     t0 = time.perf_counter()
@@ -194,11 +205,16 @@ def main():
         value = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    lib.gpar_profile_enable(0)
     import ctypes
 
     launches, ms, busy, flops = ctypes.c_int(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-    lib.gpar_profile_read(ctypes.byref(launches), ctypes.byref(ms), ctypes.byref(busy), ctypes.byref(flops), 1)
+    if args.full:
+        lib.gpar_profile_enable(0)
+        lib.gpar_profile_read(ctypes.byref(launches), ctypes.byref(ms), ctypes.byref(busy), ctypes.byref(flops), 1)
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives: the total log marginal likelihood of the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logpdf.npy"), np.asarray(float(value), dtype=np.float64))
     busy_ms = [1e3 * timing.get("busy_s", 0.0) / max(args.steps, 1)]
     collective_ms = [1e3 * timing.get("collective_s", 0.0) / max(args.steps, 1)]
     if world > 1:
@@ -238,11 +254,12 @@ def main():
         # 8-byte all-reduce (for a fast rank: the wait for the slowest)
         "per_rank_busy_ms": busy_ms,
         "per_rank_collective_ms": collective_ms,
-        # is the oracle pinned against the real reference?  tests/golden/reference_cases.json is written by
-        # tests/golden/make_reference_golden.py wherever gpar + stheno are installed (not here: no network)
-        "parity_pin": parity_pin(),
     }
-    if launches.value > 0 and busy.value > 0:
+    if args.full:
+        # is the oracle pinned against the real reference?  tests/golden/reference_cases.json is written by
+        # tests/golden/make_reference_golden.py wherever gpar + stheno are installed
+        out["parity_pin"] = parity_pin()
+    if args.full and launches.value > 0 and busy.value > 0:
         # The layers of an evaluation are factored in lock-step (one batched launch per trailing update); the narrow
         # look-ahead update of step k + 1 and the rest of step k's run on two streams, so more than one launch is often in
         # flight and each one's own duration covers work of the other.  The kernel's rate is therefore taken over the UNION
@@ -274,7 +291,7 @@ def main():
     # The timed region overlaps the trailing SYRK of panel k with the fused factorisation of panel k+1 (look-ahead on a
     # second stream), so the live number above is the kernel's rate WHILE SHARING the chip.  One extra, untimed evaluation with look-ahead and layer pipelining switched off gives the same kernel's
     # per-launch rate when it has the GPU to itself (concurrency 1: flops per launch / average launch duration).
-    if not args.no_isolated:  # every rank takes part (the evaluation contains a collective), whether or not it owns a layer
+    if args.full and not args.no_isolated:  # every rank takes part (the evaluation contains a collective), whether or not it owns a layer
         os.environ["GPAR_POTRF_LOOKAHEAD"] = "0"
         os.environ["GPAR_LAYER_PIPELINE"] = "0"
         try:
@@ -302,9 +319,10 @@ def main():
                                        "`avg_launch_ms` is the plain per-launch average that `rocprofv3 --stats` reports; see `isolated` "
                                        "for the kernel alone")
 
-    # The headline is measured by now.  Everything below (the fit + predict leg with its collectives, the CPU baseline, the
+    # The headline is measured by now.  Everything below (with --full: the fit + predict leg with its collectives, the CPU baseline; the
     # process-group teardown) runs under a watchdog: should a peer die or a collective hang, every rank leaves after
     # `--extras-timeout` seconds and rank 0 still prints the one JSON line, with the leg marked as timed out.
+    extras, cpu = args.full and not args.no_extras, args.full and not args.no_cpu
     printed = []
 
     def emit():
@@ -314,7 +332,7 @@ def main():
             print(json.dumps(out), flush=True)
 
     def bail():
-        if not args.no_extras:
+        if extras:
             out.setdefault("fit_predict", {"error": f"timed out after {args.extras_timeout} s", "n_gpus": world})
         emit()
         os._exit(0)
@@ -323,19 +341,19 @@ def main():
     watchdog.daemon = True
     watchdog.start()
     small_gpu = None
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_cpu and (n, m, p) == (16384, 4, 8):
+    if rank == 0 and world == 1 and extras and cpu and (n, m, p) == (16384, 4, 8):
         try:
             small_gpu = small_n_gpu_leg(eng)   # (right behind the headline: see small_n_leg)
         except Exception as exc:  # noqa: BLE001 - the headline must survive
             small_gpu = {"error": f"{type(exc).__name__}: {exc}"}
-    if not args.no_extras:  # every rank takes part (sharded fit / predict contain collectives)
+    if extras:  # every rank takes part (sharded fit / predict contain collectives)
         try:
             leg = fit_predict_leg(eng, x_np, y_np, n, m, p, world)
         except Exception as exc:  # the headline line must survive a failure of the extra leg
             leg = {"error": f"{type(exc).__name__}: {exc}", "n_gpus": world}
         if rank == 0:
             out["fit_predict"] = leg
-    if rank == 0 and world == 1 and not args.no_extras and (n, m, p) == (16384, 4, 8):
+    if rank == 0 and world == 1 and extras and (n, m, p) == (16384, 4, 8):
         # the other BASELINE.json configurations on the same GPU, in the same run (parity-test cases, not the headline)
         del x, y, w
         try:
@@ -350,12 +368,12 @@ def main():
             if isinstance(small_gpu, dict) and "error" in small_gpu:
                 out["small_n"] = small_gpu
             else:
-                out["small_n"] = small_n_leg(eng, small_gpu) if not args.no_cpu else None
+                out["small_n"] = small_n_leg(eng, small_gpu) if cpu else None
         except Exception as exc:
             out["small_n"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not args.no_cpu and "error" not in out["config_grid"]:
+        if cpu and "error" not in out["config_grid"]:
             config_grid_cpu_legs(out["config_grid"])   # (every GPU leg of the line has run by now)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and cpu:
         out["cpu_baseline"] = cpu_baseline_leg(x_np, y_np, m, p, budget_s=args.cpu_budget)
     emit()
     if world > 1:

@@ -72,7 +72,7 @@ def test_two_ranks_on_the_hip_engine_agree_with_one():
     all-reduce the layer log-likelihoods and run the sharded fit + predict leg; the log marginal likelihood must equal the
     single-process value to rounding."""
     def run(gpus, extra_env):
-        cmd = [sys.executable, BENCH, "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--rows", "1536", "--p", "4", "--no-cpu"]
+        cmd = [sys.executable, BENCH, "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--rows", "1536", "--p", "4", "--full", "--no-cpu"]
         out = subprocess.run(cmd, env=dict(_env(), **extra_env), capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
         return _last_json(out.stdout)
@@ -84,6 +84,24 @@ def test_two_ranks_on_the_hip_engine_agree_with_one():
     for line in (one, two):   # the sharded fit (layer pi trained on rank pi mod 2, latents broadcast) and sample-parallel predict ran
         assert "error" not in line["fit_predict"], line["fit_predict"]
         assert line["fit_predict"]["fit_evaluations"] > 20 and np.isfinite(line["fit_predict"]["predict_mean_abs"])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_value(tmp_path):
+    """A plain run (no --full) prints the contract fields of the timed steps and nothing of the legs behind --full;
+    --dump-outputs writes the log marginal likelihood of the last timed step, the same number the line reports."""
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "1536", "--p", "4",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = _last_json(out.stdout)
+    assert line["metric"] == "logpdf_per_s" and line["unit"] == "logpdf/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-6 * 1e3
+    for leg in ("roofline", "fit_predict", "config_grid", "small_n", "cpu_baseline", "parity_pin"):
+        assert leg not in line, leg
+    got = np.load(tmp_path / "out" / "logpdf.npy")
+    assert got.dtype == np.float64 and got.shape == () and float(got) == line["config"]["logpdf"]
 
 
 _RCCL_PROBE = r"""

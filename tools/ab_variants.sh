@@ -3,7 +3,7 @@ cp gpar_amd/libgpar_hip.so /tmp/keep.so
 for rep in 1 2 3; do
   for v in "$@"; do
     cp gpar_amd/libv_$v.so gpar_amd/libgpar_hip.so
-    python bench.py --no-extras --no-cpu --steps 8 --warmup 2 2>/dev/null | python -c "
+    python bench.py --full --no-extras --no-cpu --steps 8 --warmup 2 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('$v: ms/step', round(d['ms_per_step'],2), 'live', round(r['achieved'],1), 'iso', round(r['isolated']['achieved'],1))"

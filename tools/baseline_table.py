@@ -1,4 +1,4 @@
-"""BASELINE.md section 4's results table from ONE bench.py line (+ the Gram timings of tools/time_gram_configs.py):
+"""BASELINE.md section 4's results table from ONE `bench.py --full` line (+ the Gram timings of tools/time_gram_configs.py):
     python tools/baseline_table.py profiles/r06_bench_n1.json profiles/r06_gram_configs.jsonl > profiles/r06_baseline_table.md
 Every number is read from those two files; cells the harness cannot fill on one GPU say why."""
 import json, sys

@@ -21,7 +21,7 @@ def table(sub):
 
 
 out = {"source": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 GRBM_GUI_ACTIVE, and --pmc MfmaUtil, "
-                 "of `python bench.py --steps 1 --warmup 0 --no-extras --no-cpu` (tools/pmc_mfma.sh); `syrk`: the same counters on "
+                 "of `python bench.py --full --steps 1 --warmup 0 --no-extras --no-cpu` (tools/pmc_mfma.sh); `syrk`: the same counters on "
                  "tools/time_gemm.py 16384 512 1024 (bare K = 512 / 1024 trailing-update shape)",
        "kernels": {}}
 raw, util = table("bench"), table("util")
