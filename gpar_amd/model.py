@@ -141,26 +141,18 @@ def _retry_unfused(evaluate, layers=(), inputs=(), rewind=False):
       16 x 16 blocks with one refinement step (backward error 2.8e-15 where substitution, the unfused path and LAPACK, leave
       1.9e-15) and so fails on a few more: two of forty sparse fuzz cases where numpy's Cholesky does not.  The unfused path
       is the arithmetic of LAPACK's; an error it repeats is reported (for `fit`: a failed evaluation, as in varz).  The
-      evaluation builds its graph afresh, so this retry is taken under autograd too."""
-    from .engine import HandOffTimeoutError, NotPositiveDefiniteError
+      evaluation builds its graph afresh, so this retry is taken under autograd too.
 
+    Which errors qualify is `_retryable`'s rule, which `parallel.sharded_logpdf` applies too."""
     if getattr(_RETRYING, "active", False):
         return evaluate()  # already inside the second attempt of an enclosing evaluation
     calls = getattr(get_engine(), "_calls", None) if rewind else None
     try:
         return evaluate()
-    except (HandOffTimeoutError, NotPositiveDefiniteError) as e:
-        eng = get_engine()
-        if not hasattr(eng, "safe_mode"):
+    except Exception as e:
+        if not _retryable(e, layers, inputs):
             raise
-        if isinstance(e, NotPositiveDefiniteError):
-            if not notpd_retry_enabled():
-                raise
-        elif torch.is_grad_enabled():
-            if any(_is_torch(t) and t.requires_grad for t in inputs):
-                raise
-            if any(_differentiable(*model()) for model in layers):
-                raise
+        eng = get_engine()
         if calls is not None:
             eng._calls = calls  # `rewind`: the repetition draws the same random numbers as the failed attempt
         _RETRYING.active = True
@@ -169,6 +161,37 @@ def _retry_unfused(evaluate, layers=(), inputs=(), rewind=False):
                 return evaluate()
         finally:
             _RETRYING.active = False
+
+
+def _retryable(e, layers=(), inputs=()):
+    """May an evaluation of `layers` at `inputs` that raised `e` be repeated in the engine's safe mode (see `_retry_unfused`)?
+    A hand-off timeout may, unless the evaluation is part of an objective under autograd; a non-positive pivot may, unless
+    GPAR_NOTPD_RETRY=0; nothing else may, nor anything on an engine without a safe mode."""
+    from .engine import HandOffTimeoutError, NotPositiveDefiniteError
+
+    if not isinstance(e, (HandOffTimeoutError, NotPositiveDefiniteError)) or not hasattr(get_engine(), "safe_mode"):
+        return False
+    if isinstance(e, NotPositiveDefiniteError):
+        return notpd_retry_enabled()
+    if not torch.is_grad_enabled():
+        return True
+    return not (any(_is_torch(t) and t.requires_grad for t in inputs) or any(_differentiable(*model()) for model in layers))
+
+
+class _AllLayers:
+    """Which layers this process evaluates, and how a column one of them feeds forward reaches the processes that read it:
+    in one process, every layer, and the column stays where it is made.  `parallel._Shard` divides the layers over ranks."""
+
+    @staticmethod
+    def owns(i):
+        return True
+
+    @staticmethod
+    def forward(i, col, ind_col):
+        pass
+
+
+ALL_LAYERS = _AllLayers()
 
 
 def _differentiable(f, noise):
@@ -402,7 +425,9 @@ class GPAR:
         """Posterior GPAR given data (x, y, w)."""
         return _retry_unfused(lambda: self._condition(x_y_w), self.layers, x_y_w)
 
-    def _condition(self, x_y_w):
+    def _condition(self, x_y_w, shard=ALL_LAYERS):
+        """`shard` says which layers this process factors; a layer that is not its own gets an empty factor, which the caller
+        fills (`parallel.sharded_condition`)."""
         x, y, w = self._prep(*x_y_w)
         x_ind = self._prep_ind(self.x_ind)
         post = self.copy()
@@ -413,13 +438,17 @@ class GPAR:
         pipe = eng.pipeline(rows=int(x.shape[0])) if self._independent(items) else None
         # ... or, when they are small, together in lock-step
         lockstep = pipe is not None and self._same_rows(items) and hasattr(eng, "factor_dense_batch") and 0 < int(x.shape[0]) <= eng.batch_rows()
-        pending = []
+        pending, stage = [], 0   # (stage: this process's layers so far)
         with eng.defer_checks(), _joining(pipe):  # streams are joined BEFORE the deferred info words are read
-            for stage, (is_last, ((yi, wi, mask), model)) in enumerate(last(zip(items, self.layers))):
+            for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers))):
                 complete = isinstance(mask, slice)
                 x = x[mask]
                 f, noise = model()
-                if pipe is not None and lockstep and not _differentiable(f, noise):
+                mine = shard.owns(i)
+                if not mine:
+                    obs = self._obs(x, x_ind, yi, wi, f, noise, complete=complete)
+                    obs.adopt_factor()
+                elif pipe is not None and lockstep and not _differentiable(f, noise):
                     obs = self._obs(x, x_ind, yi, wi, f, noise, complete=True)
                     pending.append(obs)
                 elif pipe is not None and not _differentiable(f, noise):
@@ -428,9 +457,10 @@ class GPAR:
                         obs.factor()
                 else:
                     obs = self._obs(x, x_ind, yi, wi, f, noise, complete=complete)
+                stage += mine
                 post.layers.append(construct_model(f | obs, noise))
                 if not is_last:
-                    x, x_ind = self._update_inputs(x, x_ind, yi, f, obs, complete=complete)
+                    x, x_ind = self._next_inputs(shard, i, x, x_ind, yi, f, obs, complete)
             if pipe is not None:
                 pipe.join()
             _lockstep_factors(eng, pending)
@@ -446,7 +476,9 @@ class GPAR:
         return _retry_unfused(lambda: self._logpdf(x, y, w, only_last_layer, sample_missing, return_inputs, x_ind, outputs),
                               self.layers, (x, y, w, x_ind))
 
-    def _logpdf(self, x, y, w, only_last_layer, sample_missing, return_inputs, x_ind, outputs):
+    def _logpdf(self, x, y, w, only_last_layer, sample_missing, return_inputs, x_ind, outputs, shard=ALL_LAYERS):
+        """`shard` says which layers this process evaluates (the others build nothing here) and carries the columns of posterior
+        means a layer feeds forward to the processes that read them (`_next_inputs`); the value is the sum over its layers."""
         x, y, w = self._prep(x, y, w)
         x_ind = self._prep_ind(self.x_ind if x_ind is None else x_ind)
         total = torch.zeros((), dtype=torch.float64)
@@ -463,36 +495,36 @@ class GPAR:
         onecall = (lockstep and outputs is None and hasattr(eng, "logpdf_lockstep") and _is_torch(y) and y.is_cuda and y.dim() == 2
                    and _is_torch(w) and w.shape == y.shape and getattr(eng, "cholesky_retry_factor", 1.0) <= 1.0 and one_call_enabled())
         if onecall:
-            for model in self.layers[:len(items)]:
-                f, noise = model()
-                if f.is_posterior or _differentiable(f, noise):
-                    onecall = False
-                    break
-        fast, visited = [], 0
+            for i, model in enumerate(self.layers[:len(items)]):
+                if shard.owns(i):
+                    f, noise = model()
+                    if f.is_posterior or _differentiable(f, noise):
+                        onecall = False
+                        break
+        fast = []
         with eng.defer_checks(), _joining(pipe):  # streams are joined BEFORE the deferred info words are read
-            for is_last, ((yi, wi, mask), model) in last(zip(items, self.layers), select=outputs):
+            for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
                 complete = isinstance(mask, slice)
                 x = x[mask]
-                f, noise = model()
-                if pipe is not None and not onecall and _differentiable(f, noise):   # (the one-call route has checked every layer)
+                mine = shard.owns(i)
+                wanted = mine and (not only_last_layer or is_last)
+                f = noise = obs = None
+                if mine:
+                    f, noise = model()
+                if pipe is not None and not onecall and mine and _differentiable(f, noise):   # (the one-call route has checked every layer)
                     pipe.join()
                     pipe = None  # an objective under autograd: keep everything on the caller's stream
                 if pipe is not None and onecall:
                     # the one-call route: nothing is built per layer; the design matrix [x, y_<i] is a prefix of one widest matrix
-                    if not only_last_layer or is_last:
-                        fast.append((visited, f, noise))
-                    visited += 1
+                    if wanted:
+                        fast.append((i, f, noise))
                     continue
-                if pipe is not None and lockstep:
-                    if not only_last_layer or is_last:
+                if pipe is not None:
+                    if wanted and lockstep:
                         obs = self._obs(x, x_ind, yi, wi, f, noise, complete=True)
                         obs.transient = True
                         pending.append((f, obs))
-                    if not is_last:
-                        x = torch.cat([x, yi], dim=1)
-                    continue
-                if pipe is not None:
-                    if not only_last_layer or is_last:
+                    elif wanted:
                         with pipe.stage(stage, x, yi, wi):
                             obs = self._obs(x, x_ind, yi, wi, f, noise, complete=True)
                             obs.transient = True   # nobody conditions on this layer: only its value is wanted
@@ -501,23 +533,24 @@ class GPAR:
                     if not is_last:
                         x = torch.cat([x, yi], dim=1)
                     continue
-                obs = self._obs(x, x_ind, yi, wi, f, noise, complete=complete)
-                if not only_last_layer or is_last:
+                if mine:
+                    obs = self._obs(x, x_ind, yi, wi, f, noise, complete=complete)
+                if wanted:
                     total = total + f.measure.logpdf(obs)
                 if not is_last:
-                    if sample_missing and not complete:
+                    if sample_missing and mine and not complete:
                         missing = torch.isnan(yi[:, 0])
                         if bool(missing.any()):
                             f_post = f | obs
                             drawn = f_post(x[missing], self._noise_over(noise, wi[missing])).sample()
                             yi = merge(yi, drawn, missing)
-                    x, x_ind = self._update_inputs(x, x_ind, yi, f, obs, complete=complete)
+                    x, x_ind = self._next_inputs(shard, i, x, x_ind, yi, f, obs, complete)
             if pipe is not None:
                 pipe.join()
             if fast:
                 got = _lockstep_total(eng, x, y, w, fast)
                 if got is None:   # no room for the batch: layer by layer
-                    xw = torch.cat([x, y[:, :visited]], dim=1)
+                    xw = torch.cat([x, y], dim=1)
                     for j, fj, nj in fast:
                         obs = self._obs(xw[:, :int(x.shape[1]) + j], x_ind, y[:, j:j + 1], w[:, j], fj, nj, complete=True)
                         obs.transient = True
@@ -697,15 +730,39 @@ class GPAR:
             return noise / w if noise.device == w.device or noise.dim() == 0 else noise.to(w.device) / w
         return GPAR._noise_over(noise, w)
 
+    def _feeds_estimate(self, y, complete):
+        """Does the column output y adds to the design matrix (or to the inducing inputs) hold posterior means, rather than the
+        observed y alone?  (With `complete`, no observation of y is missing.)"""
+        if self.sparse or self.replace:
+            return True
+        if complete or not self.impute:
+            return False
+        n_missing = getattr(y, "_n_missing", None)   # (planned on the host by per_output: no synchronisation)
+        return bool(n_missing) if n_missing is not None else bool(torch.isnan(y[:, 0]).any())
+
+    def _next_inputs(self, shard, i, x, x_ind, y, f, obs, complete):
+        """The design matrix (and inducing inputs) after layer i, whose output is y.  Observed data every process holds are
+        appended where they are; a column of posterior means is made by the owner of layer i (`_update_inputs`) and handed by
+        `shard` to the processes that read it."""
+        if not self._feeds_estimate(y, complete):
+            return torch.cat([x, y], dim=1), x_ind
+        if shard.owns(i):
+            x, x_ind = self._update_inputs(x, x_ind, y, f, obs, complete=complete)
+            shard.forward(i, x[:, -1:], None if x_ind is None else x_ind[:, -1:])
+            return x, x_ind
+        col = torch.empty(x.shape[0], 1, dtype=torch.float64, device=x.device)
+        ind_col = None if x_ind is None else torch.empty(x_ind.shape[0], 1, dtype=torch.float64, device=x.device)
+        shard.forward(i, col, ind_col)
+        return torch.cat([x, col], dim=1), (None if x_ind is None else torch.cat([x_ind, ind_col], dim=1))
+
     def _update_inputs(self, x, x_ind, y, f, obs, complete=False):
-        """Append output column y to the design matrix (and the estimated output to the inducing inputs)."""
+        """Append output column y to the design matrix (and the estimated output to the inducing inputs), with posterior means where
+        `impute` / `replace` ask for them (the layer loops call it for the columns `_feeds_estimate` marks)."""
         eng = get_engine()
         # (set by per_output when the NaN pattern is known on the host; read before the conversion below makes a new tensor object)
         n_missing, obs_rows, miss_rows = getattr(y, "_n_missing", None), getattr(y, "_obs_idx", None), getattr(y, "_miss_idx", None)
         x, y = eng.tensor(x), eng.tensor(y)
         x_ind = None if x_ind is None else eng.tensor(x_ind)
-        if complete and not self.sparse and not self.replace:
-            return torch.cat([x, y], dim=1), x_ind  # nothing to estimate: observed column, no host sync
         available = ~torch.isnan(y[:, 0]) if n_missing is None else None
         post = (f | obs) if obs else None
 

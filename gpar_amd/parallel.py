@@ -14,6 +14,11 @@ With `markov=k` a forwarded column is read by the next k layers only (reference 
 selects the last k outputs), so it is SENT to the owners of those layers alone (point-to-point) instead of broadcast; ranks
 that never read a column hold NaN in its place (a violation would be loud).
 
+The log marginal likelihood (`sharded_logpdf`) and the conditioning (`sharded_condition`) run the model's own layer loops
+(`GPAR._logpdf`, `GPAR._condition`) with a `_Shard`: which layers this rank owns, and
+how a forwarded column travels.  An evaluation that fails in a way `GPAR.logpdf` would retry in the engine's safe mode is retried
+here too: every rank repeats it when any rank asks for it (`sharded_logpdf`: NaN in the all-reduce, then one more small one).
+
 `fit(fix=True)` trains each layer on its owner (the optimiser only touches names "{i}/*", reference
 regression.py:453-454) and then broadcasts the trained latent variables so every rank holds the same `Vars`.
 `fit(fix=False)` (the joint objective, reference regression.py:447-456) shards the sum over layers the same way: every rank
@@ -24,12 +29,14 @@ REPLICATED: every rank runs the serial `fit` (`sharded_fit` returns which of the
 `predict` conditions layer-parallel (`sharded_condition`), splits the Monte-Carlo samples across ranks, all-gathers the
 device-resident sample stacks once and reduces them with `gpar_sample_stats` (`sharded_predict`).
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from .engine import get_engine
-from .model import host_masks, last, per_output
+from .model import host_masks, per_output
 
 __all__ = ["world", "sharded_logpdf", "sharded_fit", "sharded_condition", "sharded_sample", "sharded_predict", "forward_plan"]
 
@@ -40,12 +47,21 @@ def world(group=None):
     return 0, 1
 
 
-def _needs_estimate(gpar, yi, complete):
-    if gpar.sparse or gpar.replace:
-        return True
-    if complete or not gpar.impute:
-        return False
-    return bool(torch.isnan(yi[:, 0]).any())
+class _Shard:
+    """Layer i is evaluated by rank i mod G; a column of posterior means it feeds forward goes to the ranks that read it
+    (`needs`, from `forward_plan`) - what `GPAR._logpdf` / `GPAR._condition` ask of their `shard` argument."""
+
+    def __init__(self, rank, size, group, needs=None):
+        self.rank, self.size, self.group, self.needs = rank, size, group, needs
+
+    def owns(self, i):
+        return i % self.size == self.rank
+
+    def forward(self, i, col, ind_col):
+        mine = self.owns(i)
+        if mine:
+            col, ind_col = col.contiguous(), (None if ind_col is None else ind_col.contiguous())
+        _forward(col, ind_col, mine, i % self.size, self.needs[i], self.rank, self.size, self.group)
 
 
 def sharded_logpdf(gpar, x, y, w, group=None, timing=None):
@@ -53,29 +69,59 @@ def sharded_logpdf(gpar, x, y, w, group=None, timing=None):
     `timing` (a dict, optional) accumulates under "busy_s" the wall-clock this rank spent on its own layers, i.e. up to
     the collective, and under "collective_s" the time in the 8-byte all-reduce - which includes the wait for the slowest rank (what
     makes a multi-GPU run interpretable without a second one: the slowest rank's busy time bounds the step, a fast rank's
-    collective time is the imbalance)."""
+    collective time is the imbalance).
+
+    The retry of `GPAR.logpdf` (model._retry_unfused) is decided by all ranks together, as the forwarded columns of the dependent
+    regimes are collectives inside the evaluation and a rank must not repeat it alone: a rank whose evaluation failed adds NaN to
+    the all-reduce; only when the sum is not finite do the ranks exchange a second word - how many failed in a way that may be
+    retried (model._retryable) and how many fatally.  After a retryable failure every rank repeats the evaluation once in the
+    engine's safe mode; a failure in the repetition, or a fatal one, raises on every rank (the failing rank its own exception,
+    the others a RuntimeError); a sum that is NaN without a failure is returned.  This covers failures reported when the
+    evaluation's deferred checks are read, at its end - where the HIP engine reports them.  An exception raised in the middle of
+    the layer loop, before a forward (the oracle engine raises at once), leaves the other ranks waiting in that forward."""
     import time
+
+    from .model import _retryable
 
     t_start = time.perf_counter()
     rank, size = world(group)
+    if size == 1:
+        value = gpar.logpdf(x, y, w)
+        if timing is not None:
+            timing["busy_s"] = timing.get("busy_s", 0.0) + (time.perf_counter() - t_start)
+        return value
     eng = get_engine()
-    x, y, w = gpar._prep(x, y, w)
-    x_ind = gpar._prep_ind(gpar.x_ind)
-    local = torch.zeros((), dtype=torch.float64)
-    with eng.defer_checks():
-        local, x, x_ind = _sharded_layers(gpar, x, y, w, x_ind, rank, size, group, local)
-    if local.is_cuda:
-        local = local.cpu()
-    t_busy = time.perf_counter()
-    if timing is not None:
-        timing["busy_s"] = timing.get("busy_s", 0.0) + (t_busy - t_start)
-    if size > 1:
-        buf = local.detach().to(device=eng.device, dtype=torch.float64).reshape(1).clone()
+    m = int(x.shape[1]) if len(x.shape) == 2 else 1
+    shard = _Shard(rank, size, group, forward_plan(gpar, m, size))
+    for attempt in range(2):
+        failure = None
+        try:
+            with eng.safe_mode() if attempt else contextlib.nullcontext():
+                local = gpar._logpdf(x, y, w, False, False, False, None, None, shard)
+            buf = local.detach().to(device=eng.device, dtype=torch.float64).reshape(1).clone()
+        except Exception as e:  # noqa: BLE001 - every rank must reach the all-reduce below
+            failure = e
+            buf = torch.full((1,), float("nan"), dtype=torch.float64, device=eng.device)
+        t_busy = time.perf_counter()
+        if timing is not None:
+            timing["busy_s"] = timing.get("busy_s", 0.0) + (t_busy - t_start)
         dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
-        local = buf[0].cpu()
+        total = buf[0].cpu()
         if timing is not None:   # (includes the wait for the slowest rank: busy + collective = the step on every rank)
             timing["collective_s"] = timing.get("collective_s", 0.0) + (time.perf_counter() - t_busy)
-    return local
+        if torch.isfinite(total):
+            return total
+        retry = failure is not None and attempt == 0 and _retryable(failure, gpar.layers, (x, y, w))
+        flags = torch.tensor([float(retry), float(failure is not None and not retry)], dtype=torch.float64, device=eng.device)
+        dist.all_reduce(flags, op=dist.ReduceOp.SUM, group=group)
+        retries, fatal = (int(v) for v in flags.cpu().tolist())
+        if fatal:
+            if failure is not None:
+                raise failure
+            raise RuntimeError(f"sharded_logpdf failed on {retries + fatal} other rank(s) (their exception is raised there)")
+        if not retries:
+            return total   # a log-likelihood that is NaN on its own
+        t_start = time.perf_counter()
 
 
 def _columns_read(kernel, width):
@@ -139,98 +185,6 @@ def _forward(col, ind_col, mine, owner, receivers, rank, size, group):
             ind_col.fill_(float("nan"))
 
 
-def _sharded_layers(gpar, x, y, w, x_ind, rank, size, group, local):
-    from .model import _differentiable, _joining, _lockstep_values
-
-    items = list(per_output(y, w, keep=gpar.impute))
-    eng = get_engine()
-    needs = forward_plan(gpar, int(x.shape[1]), size) if size > 1 else None
-    # this rank's layers alternate over two streams when no layer feeds another (see HipEngine.pipeline) ...
-    pipe = eng.pipeline(rows=int(x.shape[0])) if gpar._independent(items) else None
-    # ... or are factored together in lock-step
-    lockstep = pipe is not None and gpar._same_rows(items) and hasattr(eng, "logpdf_dense_batch") and 0 < int(x.shape[0]) <= eng.batch_rows()
-    pending = []
-    values, stage = [], 0
-    # ... through ONE library call when y and w are whole device matrices and the layers are prior processes (model._lockstep_total)
-    from .model import _is_torch, _lockstep_total, one_call_enabled
-
-    onecall = (lockstep and hasattr(eng, "logpdf_lockstep") and _is_torch(y) and y.is_cuda and y.dim() == 2 and _is_torch(w)
-               and w.shape == y.shape and getattr(eng, "cholesky_retry_factor", 1.0) <= 1.0 and one_call_enabled())
-    if onecall:
-        for i, model in enumerate(gpar.layers[:len(items)]):
-            if i % size == rank:
-                f, noise = model()
-                if f.is_posterior or _differentiable(f, noise):
-                    onecall = False
-                    break
-    fast, x0 = [], x
-    with _joining(pipe):
-        for i, (is_last, ((yi, wi, mask), model)) in enumerate(last(zip(items, gpar.layers))):
-            complete = isinstance(mask, slice)
-            x = x[mask]
-            mine = (i % size) == rank
-            f = obs = None
-            if onecall:   # (independent layers, complete data: nothing is forwarded, no design matrix is formed per layer)
-                if mine:
-                    f, noise = model()
-                    fast.append((i, f, noise))
-                continue
-            if mine:
-                f, noise = model()
-                if pipe is not None and _differentiable(f, noise):
-                    pipe.join()
-                    pipe = None
-                if pipe is not None and lockstep:
-                    obs = gpar._obs(x, x_ind, yi, wi, f, noise, complete=True)
-                    obs.transient = True
-                    pending.append((f, obs))
-                elif pipe is not None:
-                    with pipe.stage(stage, x, yi, wi):
-                        values.append(f.measure.logpdf(gpar._obs(x, x_ind, yi, wi, f, noise, complete=True)))
-                    stage += 1
-                else:
-                    obs = gpar._obs(x, x_ind, yi, wi, f, noise, complete=complete)
-                    local = local + f.measure.logpdf(obs)
-            if is_last:
-                break
-            if not _needs_estimate(gpar, yi, complete):
-                x = torch.cat([x, yi], dim=1)  # observed data: already on every rank
-                continue
-            # dependent chain: the owner computes the forwarded column(s), everyone else receives them
-            n_i = x.shape[0]
-            col = torch.empty(n_i, 1, dtype=torch.float64, device=x.device)
-            ind_col = None if x_ind is None else torch.empty(x_ind.shape[0], 1, dtype=torch.float64, device=x.device)
-            if mine:
-                x_new, x_ind_new = gpar._update_inputs(x, x_ind, yi, f, obs, complete=complete)
-                col.copy_(x_new[:, -1:])
-                if ind_col is not None:
-                    ind_col.copy_(x_ind_new[:, -1:])
-            if size > 1:
-                _forward(col, ind_col, mine, i % size, needs[i], rank, size, group)
-            x = torch.cat([x, col], dim=1)
-            if ind_col is not None:
-                x_ind = torch.cat([x_ind, ind_col], dim=1)
-    if pipe is not None:
-        pipe.join()
-    if fast:
-        got = _lockstep_total(eng, x0, y, w, fast)
-        if got is None:   # no room for the batch: layer by layer
-            xw = torch.cat([x0, y[:, :len(items) - 1]], dim=1)
-            for j, fj, nj in fast:
-                obs = gpar._obs(xw[:, :int(x0.shape[1]) + j], x_ind, y[:, j:j + 1], w[:, j], fj, nj, complete=True)
-                obs.transient = True
-                pending.append((fj, obs))
-        else:
-            values.extend(got)
-    if pending:
-        values.extend(_lockstep_values(eng, pending))
-    for v in values:
-        local = local + v
-    if onecall:
-        x = torch.cat([x0, y[:, :len(items) - 1]], dim=1) if len(items) > 1 else x0
-    return local, x, x_ind
-
-
 def _global_rank(group_rank, group):
     if group is None:
         return group_rank
@@ -264,7 +218,6 @@ def sharded_fit(reg, x, y, w=None, group=None, fix=True, **kw_args):
                         regression.py:447-456) with the sum over layers divided over the ranks - see `_minimise_sharded`;
       "replicated"      layer inputs are posterior means of earlier layers (or, with fix=True, scales are tied): the chain is
                         sequential, every rank runs the serial `fit`."""
-    from .optimise import minimise_l_bfgs_b
     from .regression import _construct_gpar
 
     rank, size = world(group)
@@ -276,28 +229,28 @@ def sharded_fit(reg, x, y, w=None, group=None, fix=True, **kw_args):
         # inputs of layer pi depend on the trained layers < pi: the chain is sequential; train replicated
         reg.fit(x, y, w, fix=fix, **kw_args)
         return "replicated"
-    y_cached = {k: list(per_output(y_dev, w_dev, keep=k)) for k in [True, False]}
     # instantiate every variable on every rank (lazy creation, reference regression.py:92-180)
     with torch.no_grad():
         _construct_gpar(reg, reg.vs, reg.m, reg.p).logpdf(x_dev[:2], y_dev[:2], w_dev[:2])
-    # the design matrix of an owned layer, [x, y_<pi] with its rows: data only, so it is formed once
-    fixed = {}
-    for pi in range(reg.p):
-        if pi % size == rank:
+    owned = [pi for pi in range(reg.p) if pi % size == rank]
+    if not fix:
+        y_cached = {k: list(per_output(y_dev, w_dev, keep=k)) for k in [True, False]}
+        # the design matrix of an owned layer, [x, y_<pi] with its rows: data only, so it is formed once
+        fixed = {}
+        for pi in owned:
             gpar = _construct_gpar(reg, reg.vs, reg.m, pi + 1)
             fixed[pi] = gpar.logpdf(x_dev, y_cached, None, only_last_layer=True, outputs=list(range(pi)), return_inputs=True)
 
-    def term(vs, pi):
-        g = _construct_gpar(reg, vs, reg.m, pi + 1)
-        return -g.logpdf(fixed[pi][0], y_cached, None, only_last_layer=True, outputs=[pi], x_ind=fixed[pi][1])
+        def term(vs, pi):
+            g = _construct_gpar(reg, vs, reg.m, pi + 1)
+            return -g.logpdf(fixed[pi][0], y_cached, None, only_last_layer=True, outputs=[pi], x_ind=fixed[pi][1])
 
-    if not fix:
         for pi in range(reg.p):
-            owned = [i for i in range(pi + 1) if i % size == rank]
+            mine = [i for i in owned if i <= pi]
 
-            def local_objective(vs, owned=owned):
+            def local_objective(vs, mine=mine):
                 total = torch.zeros((), dtype=torch.float64)
-                for i in owned:
+                for i in mine:
                     total = total + term(vs, i)
                 return total
 
@@ -305,7 +258,7 @@ def sharded_fit(reg, x, y, w=None, group=None, fix=True, **kw_args):
         return "joint-sharded"
     # this rank's layers through the regressor's own layer-wise training: the prepared objective (gpar_amd/fastfit.py) and the
     # worker streams where they apply, the general route otherwise - what the single-process `fit` runs for the same layers
-    reg._train(sorted(fixed), fix=True, **kw_args)
+    reg._train(owned, fix=True, **kw_args)
     if size > 1:
         for pi in range(reg.p):
             names = reg.vs.match([f"{pi}/*"])
@@ -406,75 +359,44 @@ def _minimise_sharded(local_objective, vs, patterns, group, iters=1000, f_calls=
 
 def sharded_condition(reg, group=None):
     """The conditioned GPAR of `reg` (as `gpar | (x, y, w)`), with the p training-data factorisations divided over the
-    ranks when no layer feeds another: layer i is factored by rank i mod G (a rank's layers pipelined over its streams)
-    and the factor buffers - L and the row L^-1 y - are all-gathered in packed lower-triangular form, G layers per
-    collective; every rank ends up holding every factor, which is what sample-parallel prediction needs.  In the dependent regimes (imputation,
-    `replace`, inducing points) every rank conditions locally, as the chain is sequential anyway."""
-    from .model import construct_model
+    ranks when no layer feeds another: layer i is factored by rank i mod G (a rank's layers pipelined over its streams, or in
+    lock-step), through `GPAR._condition` and its retry in safe mode, and the factor buffers - L and the row L^-1 y - are then
+    all-gathered in packed lower-triangular form, G layers per collective; every rank ends up holding every factor, which is what
+    sample-parallel prediction needs.  In the dependent regimes (imputation, `replace`, inducing points) every rank conditions
+    locally, as the chain is sequential anyway."""
+    from .model import _retry_unfused
     from .regression import _construct_gpar
 
     rank, size = world(group)
     eng = get_engine()
     gpar = _construct_gpar(reg, reg.vs, reg.m, reg.p)
-    x, y, w = gpar._prep(reg.x, reg.y, reg.w)
+    data = (reg.x, reg.y, reg.w)
+    x, y, w = gpar._prep(*data)
     items = list(per_output(y, w, keep=gpar.impute))
     if size == 1 or not gpar._independent(items) or not gpar._same_rows(items):
         # (layers whose rows differ - `impute=False` with missing data - are independent too, but their factors do not share a
         # shape: they are conditioned locally rather than exchanged)
-        return gpar | (reg.x, reg.y, reg.w)
-    from .engine import joining
+        return gpar | data
+    shard = _Shard(rank, size, group)
 
-    from .model import _lockstep_factors
+    def condition():
+        post = gpar._condition(data, shard)
+        return post, [layer()[0]._obs.factor() for layer in post.layers]   # (the others' factors: the empty buffers installed)
 
-    post = gpar.copy()
-    pipe = eng.pipeline(rows=int(x.shape[0]))
-    # this rank's layers: in lock-step when they are small enough (DESIGN 3.7b), else over its streams
-    lockstep = pipe is not None and gpar._same_rows(items) and hasattr(eng, "factor_dense_batch") and 0 < int(x.shape[0]) <= eng.batch_rows()
-    factors, mine = [], []
-    with eng.defer_checks(), joining(pipe):
-        for i, (is_last, ((yi, wi, mask), model)) in enumerate(last(zip(items, gpar.layers))):
-            x = x[mask]
-            f, noise = model()
-            obs = gpar._obs(x, None, yi, wi, f, noise, complete=True)
-            if i % size == rank:
-                if lockstep:
-                    mine.append((i, obs))
-                    factors.append(None)
-                elif pipe is not None:
-                    with pipe.stage(i // size, x, yi, wi):
-                        factors.append(obs.factor())
-                else:
-                    factors.append(obs.factor())
-            else:
-                factors.append(obs.adopt_factor())
-            post.layers.append(construct_model(f | obs, noise))
-            if not is_last:
-                x = torch.cat([x, yi], dim=1)
-        if mine:
-            _lockstep_factors(eng, [o for _, o in mine])
-            for i, o in mine:
-                factors[i] = o.factor()
-    # The exchange step: layer i's factor (L and the row L^-1 y: the lower triangle of the (n + 1) x (n + 1) buffer) lives on
-    # rank i mod G.  Round k all-gathers layers k G .. k G + G - 1 in PACKED form - (n + 1)(n + 2) / 2 doubles each, half the
-    # bytes of the padded square buffers and one collective over all xGMI links per round instead of one broadcast (one
-    # root's links) per layer.  The streams were joined above, so the collective is ordered after the factorisations.
+    post, factors = _retry_unfused(condition, gpar.layers, data)
     _exchange_factors(eng, factors, rank, size, group)
     return post
 
 
 def _exchange_factors(eng, factors, rank, size, group):
+    """Layer i's factor (L and the row L^-1 y: the lower triangle of the (n + 1) x (n + 1) buffer; every layer has the same n)
+    lives on rank i mod G.  Round k all-gathers layers k G .. k G + G - 1 in PACKED form - (n + 1)(n + 2) / 2 doubles each, half
+    the bytes of the padded square buffers and one collective over all xGMI links per round instead of one broadcast (one root's
+    links) per layer.  The caller has joined its streams, so the collective is ordered after the factorisations."""
     count = len(factors)
     for first in range(0, count, size):
         mine = first + rank
-        sizes = [f.n + 1 for f in factors[first : first + size]]
-        if len(set(sizes)) != 1:
-            # ragged layers (sharded_condition only exchanges layers that share their rows; kept for direct callers): one
-            # broadcast per layer
-            for i in range(first, min(first + size, count)):
-                buf = factors[i].A._base if factors[i].A._base is not None else factors[i].A
-                dist.broadcast(buf, src=_global_rank(i % size, group), group=group)
-            continue
-        N = sizes[0]
+        N = factors[first].n + 1
         length = N * (N + 1) // 2
         send = torch.empty(length, dtype=torch.float64, device=eng.device)
         if mine < count:

@@ -318,3 +318,126 @@ def test_joint_fit_markov_sends_and_device_predict(size):
     for name in ("joint", "joint-tied"):
         assert all(results[r][name][3] == results[0][name][3] for r in range(size))
     assert all(results[r]["predict"][3] == results[0]["predict"][3] for r in range(size))
+
+
+def _deferred_failure_engine():
+    """Oracle engine with the HIP engine's deferred checks and safe-mode switch: while `fail` > 0, leaving the outermost
+    `defer_checks()` block raises a hand-off timeout (-77) - after everything inside it, collectives included, has run, which is
+    where the HIP engine reports one.  `sticky`: the failure repeats in safe mode."""
+    import contextlib
+
+    from gpar_amd.engine import HandOffTimeoutError
+
+    from oracle.engine import OracleEngine
+
+    class DeferredFailures(OracleEngine):
+        def __init__(self):
+            super().__init__(seed=5)
+            self.fail, self.sticky, self.safe_entries, self.in_safe, self.depth = 0, False, 0, False, 0
+
+        @contextlib.contextmanager
+        def safe_mode(self):
+            self.safe_entries += 1
+            self.in_safe = True
+            try:
+                yield
+            finally:
+                self.in_safe = False
+
+        @contextlib.contextmanager
+        def defer_checks(self):
+            self.depth += 1
+            try:
+                yield
+            finally:
+                self.depth -= 1
+            if self.depth == 0 and self.fail > 0 and (self.sticky or not self.in_safe):
+                self.fail -= 1
+                raise HandOffTimeoutError(-77)
+
+    return DeferredFailures()
+
+
+def _worker_retry(rank, size, port, results):
+    import datetime
+    import time
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=size, timeout=datetime.timedelta(seconds=60))
+    try:
+        from gpar_amd.engine import get_engine, set_engine
+        from gpar_amd.parallel import sharded_condition, sharded_logpdf
+        from gpar_amd.regression import GPARRegressor, _construct_gpar
+
+        eng = _deferred_failure_engine()
+        set_engine(eng)
+        out = {}
+        x, y, w = _data()
+        # a one-time failure on rank 1, reported when its deferred checks are read: independent layers, and a dependent chain
+        # whose columns are forwarded (Markov-limited) inside the evaluation
+        for name, kw in [("independent", dict(impute=False)), ("replace-markov", dict(replace=True, markov=1))]:
+            reg = GPARRegressor(nonlinear=True, noise=0.05, normalise_y=False, **kw)
+            gpar = _construct_gpar(reg, reg.vs, 2, 3)
+            serial = float(gpar.logpdf(x, y, w))
+            eng.safe_entries, eng.fail = 0, int(rank == 1)
+            sharded = float(sharded_logpdf(gpar, x, y, w))
+            out[name] = (serial, sharded, eng.safe_entries)
+        # conditioning with a one-time failure on the owner of layer 1: retried there, before the exchange
+        b = GPARRegressor(nonlinear=True, noise=0.1, impute=False)
+        b.condition(x, y, w)
+        eng.safe_entries, eng.fail = 0, int(rank == 1)
+        post = sharded_condition(b)
+        entries = eng.safe_entries
+        get_engine().seed(99)
+        via_exchange = np.stack(b.sample(x[:7], posterior=True, num_samples=3, _conditioned=post))
+        get_engine().seed(99)
+        local = np.stack(b.sample(x[:7], posterior=True, num_samples=3))
+        out["condition"] = (float(np.max(np.abs(via_exchange - local))), entries)
+        # a failure that repeats in safe mode: every rank raises, none waits for the collective timeout
+        reg = GPARRegressor(nonlinear=True, noise=0.05, normalise_y=False, replace=True, markov=1)
+        gpar = _construct_gpar(reg, reg.vs, 2, 3)
+        eng.safe_entries, eng.fail, eng.sticky = 0, 2 * int(rank == 1), True
+        t0 = time.perf_counter()
+        try:
+            sharded_logpdf(gpar, x, y, w)
+            raised = None
+        except Exception as e:  # noqa: BLE001
+            raised = type(e).__name__
+        out["repeated"] = (raised, time.perf_counter() - t0, eng.safe_entries)
+        results[rank] = out
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_sharded_retry_in_safe_mode_is_collective():
+    """A hand-off timeout reported at the end of one rank's evaluation (where the HIP engine's deferred checks report it): every
+    rank repeats the evaluation once in safe mode and returns the serial value; a failure that repeats raises on every rank, with
+    no rank left waiting in a collective; conditioning retries on the failing owner before the factor exchange."""
+    size = 2
+    ctx = mp.get_context("spawn")
+    manager = ctx.Manager()
+    results = manager.dict()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_retry, args=(r, size, port, results)) for r in range(size)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=240)
+    for p in procs:
+        if p.is_alive():
+            p.terminate()
+            p.join(timeout=10)
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+    for rank in range(size):
+        out = results[rank]
+        for name in ("independent", "replace-markov"):
+            serial, sharded, entries = out[name]
+            assert abs(serial - sharded) <= 1e-10 * abs(serial), (rank, name, serial, sharded)
+            assert entries == 1, (rank, name, entries)
+        maxdiff, entries = out["condition"]
+        assert maxdiff == 0.0 and entries == int(rank == 1), (rank, maxdiff, entries)
+        raised, seconds, entries = out["repeated"]
+        assert raised == ("HandOffTimeoutError" if rank == 1 else "RuntimeError"), (rank, raised)
+        assert seconds < 30.0 and entries == 1, (rank, seconds, entries)
