@@ -13,6 +13,7 @@ GPAR_MAX_TERMS = 8
 
 EMBED_ID, EMBED_SIN, EMBED_COS = 0, 1, 2
 K_EQ, K_RQ, K_LINEAR = 0, 1, 2
+K_MATERN12, K_MATERN32, K_MATERN52 = 3, 4, 5
 
 GRAM_LOWER = 1
 GEMM_C_LOWER = 1

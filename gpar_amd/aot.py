@@ -27,6 +27,9 @@ FAMILIES = {
     "rq": dict(linear=True, nonlinear=True, rq=True),
     "per": dict(linear=True, nonlinear=True, per=True),
     "per_rq": dict(linear=True, nonlinear=True, per=True, rq=True),
+    # (Matern 1/2 is left to the run-time compiler: the rough end of the family is the rare choice)
+    "matern32": dict(linear=True, nonlinear=True, matern=1.5),
+    "matern52": dict(linear=True, nonlinear=True, matern=2.5),
 }
 
 

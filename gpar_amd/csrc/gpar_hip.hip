@@ -466,18 +466,21 @@ long long gpar_jit_compile(int kind, const gpar_kspec_t* ks, int dz, const char*
 }
 
 // Fingerprint of the kernel generators: FNV-1a over the sources of every kernel kind for one probe structure that uses every factor
-// type (EQ x RQ product, a linear term, a constant term; six feature dims), + the ABI version.  Pure host code, needs no GPU.
+// type (EQ x RQ product, a linear term, a constant term, a product of the three Matern factors; nine feature dims), + the ABI version.  Pure host code, needs no GPU.
 unsigned long long gpar::aot_fingerprint() {
     static unsigned long long cached = 0ull;
     if (cached) return cached;
     gpar_kspec_t ks;
     memset(&ks, 0, sizeof ks);
-    ks.nterms = 3;
-    ks.nfactors = 3;
-    ks.coef[0] = 1.0; ks.coef[1] = 1.0; ks.coef[2] = 1.0;
+    ks.nterms = 4;
+    ks.nfactors = 6;
+    ks.coef[0] = 1.0; ks.coef[1] = 1.0; ks.coef[2] = 1.0; ks.coef[3] = 1.0;
     ks.factor[0] = gpar_factor_t{GPAR_K_EQ, 0, 0, 2, 0.0};
     ks.factor[1] = gpar_factor_t{GPAR_K_RQ, 0, 2, 2, 0.5};
     ks.factor[2] = gpar_factor_t{GPAR_K_LINEAR, 1, 4, 2, 0.0};
+    ks.factor[3] = gpar_factor_t{GPAR_K_MATERN12, 3, 6, 1, 0.0};
+    ks.factor[4] = gpar_factor_t{GPAR_K_MATERN32, 3, 7, 1, 0.0};
+    ks.factor[5] = gpar_factor_t{GPAR_K_MATERN52, 3, 8, 1, 0.0};
     unsigned long long h = 1469598103934665603ull;
     auto mix = [&](const std::string& text) {
         for (unsigned char ch : text) h = (h ^ ch) * 1099511628211ull;
@@ -487,15 +490,16 @@ unsigned long long gpar::aot_fingerprint() {
     for (int kind : kinds) {
         std::string source, entry;
         int jkind = 0, extra = 0;
-        if (jit_request(kind, ks, 6, jkind, extra, entry, source, true)) mix(entry + "\n" + source);
+        if (jit_request(kind, ks, 9, jkind, extra, entry, source, true)) mix(entry + "\n" + source);
         else mix("-");
     }
-    {   // ... and the wide form of the Gram generator (more than GRAM_JIT_MAX_DZ feature dims): the same factor types over 20 dims
+    {   // ... and the wide form of the Gram generator (more than GRAM_JIT_MAX_DZ feature dims): the same factor types over 23 dims
         gpar_kspec_t wide = ks;
         wide.factor[0].nd = 8; wide.factor[1].off = 8; wide.factor[1].nd = 7; wide.factor[2].off = 15; wide.factor[2].nd = 5;
+        wide.factor[3].off = 20; wide.factor[4].off = 21; wide.factor[5].off = 22;
         std::string source, entry;
         int jkind = 0, extra = 0;
-        if (jit_request(JIT_GRAM, wide, 20, jkind, extra, entry, source, true)) mix(entry + "\n" + source);
+        if (jit_request(JIT_GRAM, wide, 23, jkind, extra, entry, source, true)) mix(entry + "\n" + source);
         else mix("-");
     }
     mix("abi " + std::to_string(GPAR_ABI_VERSION));

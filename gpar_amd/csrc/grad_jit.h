@@ -18,7 +18,7 @@
 namespace gpar {
 
 // Code that evaluates term `t` on the micro-tile: for each of its factors f the squared distances / inner products s<f>[8] and
-// the factor values phi<f>[8]; for RQ factors also tq<f>[8] = s / 2 alpha and lg<f>[8] = log1p(tq).
+// the factor values phi<f>[8]; for RQ factors also tq<f>[8] = s / 2 alpha and lg<f>[8] = log1p(tq), for Matern factors dk<f>[8] = d phi / d s.
 static std::string grad_jit_term_values(const gpar_kspec_t& ks, int t, int f0, int nf) {
     std::string o;
     for (int k = 0; k < nf; ++k) {
@@ -32,6 +32,9 @@ static std::string grad_jit_term_values(const gpar_kspec_t& ks, int t, int f0, i
         } else if (fa.type == GPAR_K_EQ) {
             o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) phi" + F + "[e] = -0.5 * s" + F + "[e];\n";
             o += "            gram_exp8(phi" + F + ", tab);\n";
+        } else if (gram_jit_is_matern(fa.type)) {   // value and d k / d s (0 at r = 0 for nu = 1/2) from one exponential
+            o += "            double dk" + F + "[8];\n";
+            o += std::string("            gram_matern_grad8<") + gram_jit_matern_nu2(fa.type) + ">(s" + F + ", phi" + F + ", dk" + F + ", tab);\n";
         } else {
             o += "            double tq" + F + "[8], lg" + F + "[8];\n";
             o += "            {\n                const double alpha = ks.factor[" + F + "].alpha, h2a = 0.5 / alpha;\n";
@@ -172,6 +175,8 @@ extern "C" __global__ __launch_bounds__(256, 2) void gram_grad_jit(gj_kspec ks, 
                 o += "                        g[e] = wr * (-0.5 * ib);\n";
                 o += "                        al = fma(wr, tq" + F + "[e] * ib - lg" + F + "[e], al);\n";
                 o += "                    }\n                    accAl[" + F + "] = al;\n                }\n";
+            } else if (gram_jit_is_matern(fa.type)) {
+                o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e] * dk" + F + "[e];\n";
             } else {
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e];\n";
             }
@@ -317,11 +322,13 @@ extern "C" __global__ __launch_bounds__(256, 2) void gram_input_grad_jit(gj_kspe
             const std::string F = std::to_string(f0 + k), off = std::to_string(fa.off), nd = std::to_string(fa.nd);
             o += "            {   // factor " + F + "\n";
             o += grad_jit_rest(ks, t, f0, nf, k);
-            o += "                double g[8];   // W * rest * (2 d phi / d s for EQ / RQ, 1 for linear)\n";
+            o += "                double g[8];   // W * rest * (2 d phi / d s for EQ / RQ / Matern, 1 for linear)\n";
             if (fa.type == GPAR_K_EQ)
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = -w[e] * rest[e] * phi" + F + "[e];\n";
             else if (fa.type == GPAR_K_RQ)
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = -w[e] * rest[e] * phi" + F + "[e] / (1.0 + tq" + F + "[e]);\n";
+            else if (gram_jit_is_matern(fa.type))
+                o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = 2.0 * w[e] * rest[e] * dk" + F + "[e];\n";
             else
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e];\n";
             o += "                grad_rows_static<" + off + ", " + nd + ", " + (fa.type == GPAR_K_LINEAR ? "true" : "false") + ", DZ>(Za, Zb, ty, cb, g, accX);\n";

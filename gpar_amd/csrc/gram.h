@@ -13,7 +13,7 @@
 
 namespace gpar {
 
-// shared with the generated kernels (gram_jit.h), one text for both: typedefs, GRAM_T / GRAM_LD, gram_accum*, gram_exph8, gram_rqh8
+// shared with the generated kernels (gram_jit.h), one text for both: typedefs, GRAM_T / GRAM_LD, gram_accum*, gram_exph8, gram_rqh8, gram_maternh8
 #define GPAR_DEVICE_CODE(...) __VA_ARGS__
 #include "gram_math.inc"
 #undef GPAR_DEVICE_CODE
@@ -35,7 +35,22 @@ __global__ __launch_bounds__(256) void featurize_kernel(gpar_fspec_t fs, const d
 __device__ __forceinline__ double gram_nonlin(int type, double s, double alpha) {
     if (type == GPAR_K_EQ) return exp(-0.5 * s);
     if (type == GPAR_K_RQ) return exp(-alpha * log1p(s / (2.0 * alpha)));
+    if (type == GPAR_K_MATERN12) return exp(-sqrt(s));
+    if (type == GPAR_K_MATERN32) { const double cr = GRAM_SQRT3 * sqrt(s); return (1.0 + cr) * exp(-cr); }
+    if (type == GPAR_K_MATERN52) { const double cr = GRAM_SQRT5 * sqrt(s); return (1.0 + cr + GRAM_5_3 * s) * exp(-cr); }
     return s;
+}
+
+__device__ __forceinline__ bool gram_is_matern(int type) { return type >= GPAR_K_MATERN12 && type <= GPAR_K_MATERN52; }
+
+// d k / d s of a Matern factor (s the squared scaled distance, r = sqrt(s)).  nu = 1/2 is singular at r = 0, where it only ever
+// multiplies (z_a - z_b)^2 or (z_a - z_b) = 0: it is taken as 0 there, by selecting the divisor - no 0 / 0, no infinity is formed.
+__device__ __forceinline__ double gram_matern_dkds(int type, double s) {
+    const double r = sqrt(s);
+    if (type == GPAR_K_MATERN12) return r == 0.0 ? 0.0 : -0.5 * exp(-r) / (r == 0.0 ? 1.0 : r);
+    if (type == GPAR_K_MATERN32) return -1.5 * exp(-GRAM_SQRT3 * r);
+    const double cr = GRAM_SQRT5 * r;
+    return (-0.5 * GRAM_5_3) * (1.0 + cr) * exp(-cr);
 }
 
 // Two passes of a 4 x 2 micro-tile per thread.  Per product term the exponents of its EQ / RQ factors are SUMMED and
@@ -102,8 +117,14 @@ __global__ __launch_bounds__(256) void gram_kernel(gpar_kspec_t ks, const double
                     if (type == GPAR_K_EQ) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) expo[e] += s[e];   // doubled exponent: gram_exph8 takes exp(-E / 2)
-                    } else {   // RQ: (1 + s / 2 alpha)^-alpha = exp(-alpha log1p(s / 2 alpha))
+                    } else if (type == GPAR_K_RQ) {   // (1 + s / 2 alpha)^-alpha = exp(-alpha log1p(s / 2 alpha))
                         gram_rqh8(s, ks.factor[f].alpha, expo, tab);
+                    } else if (type == GPAR_K_MATERN12) {   // poly(r) exp(-c r): exponent into expo, polynomial into lin
+                        gram_maternh8<1>(s, expo, lin);
+                    } else if (type == GPAR_K_MATERN32) {
+                        gram_maternh8<3>(s, expo, lin);
+                    } else {
+                        gram_maternh8<5>(s, expo, lin);
                     }
                 }
                 ++f;
@@ -237,8 +258,14 @@ __global__ __launch_bounds__(256) void lockstep_build_kernel(LockstepSpecs sp, c
                     if (type == GPAR_K_EQ) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) expo[e] += s[e];
-                    } else {
+                    } else if (type == GPAR_K_RQ) {
                         gram_rqh8(s, ks.factor[f].alpha, expo, tab);
+                    } else if (type == GPAR_K_MATERN12) {
+                        gram_maternh8<1>(s, expo, lin);
+                    } else if (type == GPAR_K_MATERN32) {
+                        gram_maternh8<3>(s, expo, lin);
+                    } else {
+                        gram_maternh8<5>(s, expo, lin);
                     }
                 }
                 ++f;
@@ -477,7 +504,8 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(gpar_kspec_t ks, const d
                             const double tq = sv[ff][i][j] / (2.0 * fa.alpha), base = 1.0 + tq;
                             g[i][j] = w[i][j] * rest * (-0.5 * phi[ff][i][j] / base);
                             al = fma(w[i][j] * rest * phi[ff][i][j], tq / base - log1p(tq), al);
-                        } else g[i][j] = w[i][j] * rest;
+                        } else if (gram_is_matern(fa.type)) g[i][j] = w[i][j] * rest * gram_matern_dkds(fa.type, sv[ff][i][j]);
+                        else g[i][j] = w[i][j] * rest;
                     }
                 if (fa.type == GPAR_K_RQ) {
                     al = wave_sum(al);
@@ -623,7 +651,7 @@ __global__ __launch_bounds__(256) void gram_input_grad_kernel(gpar_kspec_t ks, c
             for (int ff = 0; ff < GRAD_MAXF; ++ff) {
                 if (ff >= nf) continue;
                 const gpar_factor_t fa = ks.factor[f0 + ff];
-                double g[4][4];   // W * rest * (d phi / d s * 2  for EQ / RQ,  1 for linear)
+                double g[4][4];   // W * rest * (d phi / d s * 2  for EQ / RQ / Matern,  1 for linear)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -634,6 +662,7 @@ __global__ __launch_bounds__(256) void gram_input_grad_kernel(gpar_kspec_t ks, c
                             if (f2 != ff) rest *= phi[f2][i][j];
                         if (fa.type == GPAR_K_EQ) g[i][j] = -w[i][j] * rest * phi[ff][i][j];
                         else if (fa.type == GPAR_K_RQ) g[i][j] = -w[i][j] * rest * phi[ff][i][j] / (1.0 + sv[ff][i][j] / (2.0 * fa.alpha));
+                        else if (gram_is_matern(fa.type)) g[i][j] = 2.0 * w[i][j] * rest * gram_matern_dkds(fa.type, sv[ff][i][j]);
                         else g[i][j] = w[i][j] * rest;
                     }
                 for (int d = fa.off; d < fa.off + fa.nd; ++d) {

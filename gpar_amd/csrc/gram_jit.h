@@ -26,9 +26,12 @@ struct gj_kspec { int nterms; int nfactors; double coef[8]; gj_factor factor[12]
 static_assert(GPAR_MAX_TERMS == 8 && GPAR_MAX_FACTORS == 12, "gram_jit.h mirrors gpar_kspec_t");
 static_assert(sizeof(gpar_factor_t) == 24 && sizeof(gpar_kspec_t) == 8 + 8 * 8 + 12 * 24, "gram_jit.h mirrors gpar_kspec_t");
 
+static bool gram_jit_is_matern(int type) { return type >= GPAR_K_MATERN12 && type <= GPAR_K_MATERN52; }
+static const char* gram_jit_matern_nu2(int type) { return type == GPAR_K_MATERN12 ? "1" : (type == GPAR_K_MATERN32 ? "3" : "5"); }
+
 // Straight-line evaluation of all terms into total[8] for the micro-tile (ty, cb).  Mirrors the interpreter's order of
-// operations exactly: per term expo = DOUBLED sum of factor exponents (EQ: expo += s - the first one a plain copy, 0 + s being s -; RQ: gram_rqh8), lin = coef * product of
-// linear factors, one gram_exph8 per term that has a nonlinear factor, total = fma(lin, expo, total) or total += lin.
+// operations exactly: per term expo = DOUBLED sum of factor exponents (EQ: expo += s - the first one a plain copy, 0 + s being s -; RQ: gram_rqh8; Matern: gram_maternh8), lin = coef * product of
+// linear factors and Matern polynomials, one gram_exph8 per term that has a nonlinear factor, total = fma(lin, expo, total) or total += lin.
 static std::string gram_jit_terms(const gpar_kspec_t& ks) {
     std::string o;
     int f = 0;
@@ -49,7 +52,8 @@ static std::string gram_jit_terms(const gpar_kspec_t& ks) {
                 any_exp = true;
                 o += "                gram_accum_static<" + off + ", " + nd + ", false>(Za, Zb, ty, cb, s);\n";
                 if (fa.type == GPAR_K_EQ) o += std::string("                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) expo[e] ") + (first_exp ? "= s[e];\n" : "+= s[e];\n");
-                else o += "                gram_rqh8(s, ks.factor[" + fs + "].alpha, expo, tab);\n";
+                else if (fa.type == GPAR_K_RQ) o += "                gram_rqh8(s, ks.factor[" + fs + "].alpha, expo, tab);\n";
+                else o += std::string("                gram_maternh8<") + gram_jit_matern_nu2(fa.type) + ">(s, expo, lin);\n";   // exponent into expo, polynomial into lin
                 first_exp = false;
             }
             o += "            }\n";
@@ -104,7 +108,12 @@ static std::string gram_jit_wide_terms(const gpar_kspec_t& ks) {
         const int f0 = f;
         int f1 = f0;
         bool has_lin = false, has_exp = false;
-        while (f1 < ks.nfactors && ks.factor[f1].term == t) { (ks.factor[f1].type == GPAR_K_LINEAR ? has_lin : has_exp) = true; ++f1; }
+        while (f1 < ks.nfactors && ks.factor[f1].term == t) {
+            const int ty_ = ks.factor[f1].type;
+            (ty_ == GPAR_K_LINEAR ? has_lin : has_exp) = true;
+            if (gram_jit_is_matern(ty_)) has_lin = true;   // (their polynomial multiplies into lin; lin = coef alone gives the same bits)
+            ++f1;
+        }
         o += "        {   // term " + ts + "\n";
         for (int g = f0; g < f1; ++g) {
             const gpar_factor_t& fa = ks.factor[g];
@@ -135,9 +144,13 @@ static std::string gram_jit_wide_terms(const gpar_kspec_t& ks) {
                 } else if (fa.type == GPAR_K_EQ) {
                     o += std::string("                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) expo[e] ") + (first_exp ? "= s" : "+= s") + gs + "[" + hs + "][e];\n";
                     first_exp = false;
-                } else {
+                } else if (fa.type == GPAR_K_RQ) {
                     if (first_exp) o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) expo[e] = 0.0;\n";
                     o += "                gram_rqh8(s" + gs + "[" + hs + "], ks.factor[" + gs + "].alpha, expo, tab);\n";
+                    first_exp = false;
+                } else {   // Matern
+                    if (first_exp) o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) expo[e] = 0.0;\n";
+                    o += std::string("                gram_maternh8<") + gram_jit_matern_nu2(fa.type) + ">(s" + gs + "[" + hs + "], expo, lin);\n";
                     first_exp = false;
                 }
             }

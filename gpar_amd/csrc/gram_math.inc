@@ -249,6 +249,52 @@ __device__ __forceinline__ void gram_rqh8(const double (&s)[8], double alpha, do
     }
 }
 
+// Matern factor of smoothness NU2 / 2 (NU2 = 1, 3, 5) in the same split: with r = sqrt(s), c = sqrt(NU2),
+//   k = poly(r) exp(-c r),   poly = 1 | 1 + c r | 1 + c r + c^2 s / 3:
+// the exponent joins the term's DOUBLED exponent sum (E += 2 c r; gram_exph8 evaluates exp(-E / 2)), the polynomial joins the
+// product of the linear factors.  The square root is the correctly rounded one (the bare v_sqrt_f64 is good to ~2^-23 only).
+// s == 0 gives r = 0, E += 0 and poly = 1 exactly: the diagonal of a Matern Gram matrix is exactly its coefficient.
+constexpr double GRAM_SQRT3 = 0x1.bb67ae8584caap+0;
+constexpr double GRAM_SQRT5 = 0x1.1e3779b97f4a8p+1;
+constexpr double GRAM_5_3 = 0x1.aaaaaaaaaaaabp+0;
+template <int NU2>
+__device__ __forceinline__ void gram_maternh8(const double (&s)[8], double (&expo)[8], double (&lin)[8]) {
+    _Pragma("clang fp contract(off)")
+    constexpr double C = NU2 == 1 ? 1.0 : (NU2 == 3 ? GRAM_SQRT3 : GRAM_SQRT5);
+    _Pragma("unroll")
+    for (int i = 0; i < 8; ++i) {
+        const double cr = C * __builtin_sqrt(s[i]);
+        expo[i] = fma(2.0, cr, expo[i]);
+        if (NU2 == 3) lin[i] *= 1.0 + cr;
+        if (NU2 == 5) lin[i] *= fma(GRAM_5_3, s[i], 1.0 + cr);
+    }
+}
+
+// ... and for the gradient passes of the generated kernels: value phi = k(s) and derivative dk = dk / ds of eight entries,
+//   nu = 1/2: -exp(-r) / (2 r), taken as 0 where r = 0 (it only ever multiplies (z_a - z_b)^2 or (z_a - z_b), which vanish there:
+//             the divisor is replaced, never a 0 / 0 or an infinity formed);   nu = 3/2: -(3/2) exp(-c r);
+//   nu = 5/2: -(5/6)(1 + c r) exp(-c r).
+template <int NU2>
+__device__ __forceinline__ void gram_matern_grad8(const double (&s)[8], double (&phi)[8], double (&dk)[8], const double* __restrict__ tab) {
+    constexpr double C = NU2 == 1 ? 1.0 : (NU2 == 3 ? GRAM_SQRT3 : GRAM_SQRT5);
+    double cr[8];
+    _Pragma("unroll")
+    for (int i = 0; i < 8; ++i) { cr[i] = C * __builtin_sqrt(s[i]); phi[i] = 2.0 * cr[i]; }
+    gram_exph8(phi, tab);   // exp(-c r)
+    _Pragma("unroll")
+    for (int i = 0; i < 8; ++i) {
+        if (NU2 == 1) {
+            dk[i] = cr[i] == 0.0 ? 0.0 : -0.5 * phi[i] / (cr[i] == 0.0 ? 1.0 : cr[i]);
+        } else if (NU2 == 3) {
+            dk[i] = -1.5 * phi[i];
+            phi[i] *= 1.0 + cr[i];
+        } else {
+            dk[i] = (-0.5 * GRAM_5_3) * (1.0 + cr[i]) * phi[i];
+            phi[i] *= fma(GRAM_5_3, s[i], 1.0 + cr[i]);
+        }
+    }
+}
+
 // ---- gradient passes (generated kernels only; grad_jit.h) ---------------------------------------------------------------------
 // Per-dim moment sums of one factor over a 4 x 2 micro-tile, dims [OFF, OFF + ND) at compile time:
 //   EQ / RQ:  accA[d] += g (za - zb)^2,   accP[d] += g (za - zb)(zda - zdb)   (HAS_ZD: frequency derivatives of periodic features)

@@ -2,7 +2,7 @@
 
 Host-side counterpart of the mlkernels subset the reference composes per layer
 (/root/reference/gpar/regression.py:92-180): `EQ`, `RQ`, `Linear`, `ZeroKernel`, `.stretch`, `.periodic`,
-`.select`, `+`, `*` and scalar offsets.  Instead of an expression tree evaluated term by term (one n x n
+`.select`, `+`, `*` and scalar offsets - plus the Matern kernels of smoothness 1/2, 3/2 and 5/2, which the reference lacks.  Instead of an expression tree evaluated term by term (one n x n
 temporary per node), a kernel here is kept in the normal form
 
     k(x, y) = sum_t coef_t * prod_{f in t} phi_f(z_f(x), z_f(y)),   z_f = stretch(periodic(select(x)))
@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Kernel", "EQ", "RQ", "Linear", "ZeroKernel", "OneKernel", "compile_kernel", "CompiledKernel", "linear_tail"]
+__all__ = ["Kernel", "EQ", "RQ", "Matern12", "Matern32", "Matern52", "Linear", "ZeroKernel", "OneKernel", "compile_kernel", "CompiledKernel", "linear_tail"]
 
 
 def _value(v):
@@ -199,6 +199,21 @@ def RQ(alpha):
     return Kernel([Term(1.0, [Factor("rq", alpha=alpha)])])
 
 
+def Matern12():
+    """exp(-r), r the scaled distance (the Ornstein-Uhlenbeck kernel: continuous, nowhere differentiable sample paths)."""
+    return Kernel([Term(1.0, [Factor("matern12")])])
+
+
+def Matern32():
+    """(1 + sqrt(3) r) exp(-sqrt(3) r): once differentiable sample paths."""
+    return Kernel([Term(1.0, [Factor("matern32")])])
+
+
+def Matern52():
+    """(1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r): twice differentiable sample paths."""
+    return Kernel([Term(1.0, [Factor("matern52")])])
+
+
 def Linear():
     return Kernel([Term(1.0, [Factor("linear")])])
 
@@ -211,7 +226,8 @@ def OneKernel():
     return Kernel([Term(1.0, [])])
 
 
-_TYPE_CODE = {"eq": _lib.K_EQ, "rq": _lib.K_RQ, "linear": _lib.K_LINEAR}
+_TYPE_CODE = {"eq": _lib.K_EQ, "rq": _lib.K_RQ, "linear": _lib.K_LINEAR, "matern12": _lib.K_MATERN12, "matern32": _lib.K_MATERN32,
+              "matern52": _lib.K_MATERN52}
 
 
 class CompiledKernel:

@@ -15,7 +15,7 @@ import torch
 
 from .engine import get_engine
 from .gp import GP, Measure
-from .kernels import EQ, RQ, Linear, ZeroKernel
+from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
 from .model import GPAR, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
 from .vars import Vars
@@ -81,13 +81,17 @@ def _uprank(x):
     return x
 
 
+#: `matern=` values of GPARRegressor -> the kernel that stands where the default model has EQ
+_MATERN = {0.5: Matern12, 1.5: Matern32, 2.5: Matern52}
+
+
 def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, per_decay, input_linear,
-                     input_linear_scale, linear, linear_scale, nonlinear, nonlinear_scale, rq, markov, noise):
+                     input_linear_scale, linear, linear_scale, nonlinear, nonlinear_scale, rq, markov, noise, matern=None):
     """Constructor of layer `pi`: kernel over the inputs + kernel over the selected previous outputs, and the
     observation-noise variance; hyper-parameters are created in `vs` on first use (reference regression.py:72-182)."""
 
     config = repr((m, pi, scale, scale_tie, per, per_period, per_scale, per_decay, input_linear, input_linear_scale, linear,
-                   linear_scale, nonlinear, nonlinear_scale, rq, markov, noise))
+                   linear_scale, nonlinear, nonlinear_scale, rq, markov, noise) + (() if matern is None else (matern,)))
 
     def model():
         return vs.memo(config, build)
@@ -97,6 +101,8 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
         k_in, k_out = ZeroKernel(), ZeroKernel()
 
         def nonlinear_kernel(prefix):
+            if matern is not None:   # (same variables as EQ: a Matern kernel has no parameter beyond its scales)
+                return _MATERN[matern]()
             return RQ(vs.bnd(name=f"{prefix}/alpha", init=1e-2, lower=1e-3, upper=1e3)) if rq else EQ()
 
         # nonlinear kernel over the inputs
@@ -214,7 +220,7 @@ class GPARRegressor:
     def __init__(self, replace=False, impute=True, scale=1.0, scale_tie=False, per=False, per_period=1.0,
                  per_scale=1.0, per_decay=10.0, input_linear=False, input_linear_scale=100.0, linear=True,
                  linear_scale=100.0, nonlinear=False, nonlinear_scale=1.0, rq=False, markov=None, noise=0.1,
-                 x_ind=None, normalise_y=True, transform_y=(lambda x: x, lambda x: x), sparse_method="vfe"):
+                 x_ind=None, normalise_y=True, transform_y=(lambda x: x, lambda x: x), sparse_method="vfe", matern=None):
         self.replace = replace
         if sparse_method not in ("vfe", "fitc", "dtc"):
             raise ValueError('sparse_method must be "vfe", "fitc" or "dtc"')
@@ -228,6 +234,15 @@ class GPARRegressor:
             "linear": linear, "linear_scale": linear_scale, "nonlinear": nonlinear,
             "nonlinear_scale": nonlinear_scale, "rq": rq, "markov": markov, "noise": noise,
         }
+        # an addition behind the reference's keywords: `matern` = 0.5 | 1.5 | 2.5 puts the Matern kernel of that smoothness where the
+        # default model has EQ (the nonlinear input and output kernels; the locally periodic term keeps its EQ factors, as under rq)
+        if matern is not None:
+            if isinstance(matern, bool) or not isinstance(matern, (int, float, np.floating, np.integer)) or float(matern) not in _MATERN:
+                raise ValueError("matern must be None, 0.5, 1.5 or 2.5")
+            if rq:
+                raise ValueError("matern and rq=True exclude one another")
+            self.model_config["matern"] = float(matern)
+        self.matern = None if matern is None else float(matern)
         self.vs = Vars(dtype=torch.float64)
         self.is_conditioned = False
         self.x = self.y = self.w = None

@@ -59,7 +59,8 @@ extern "C" {
  *                  feature row z:  z[q] = embed_q(x[col[q]]) * inv_scale[q]
  *                  embed 0: identity   1: sin(freq*x)   2: cos(freq*x)   (mlkernels .periodic()).
  *   gpar_kspec_t : k(z, z') = sum_t coef[t] * prod_{f in term t} phi_f(z[off:off+nd], z'[off:off+nd])
- *                  phi EQ: exp(-r2/2); RQ: (1 + r2/(2 alpha))^-alpha; LINEAR: <z, z'>; r2 = |z - z'|^2.
+ *                  phi EQ: exp(-r2/2); RQ: (1 + r2/(2 alpha))^-alpha; LINEAR: <z, z'>; r2 = |z - z'|^2;
+ *                  MATERN12 / 32 / 52: the Matern kernels of smoothness 1/2, 3/2, 5/2 in r = sqrt(r2) (codes below).
  *                  A term without factors is the constant kernel `coef`.
  */
 #define GPAR_MAX_DIMS 96
@@ -73,6 +74,9 @@ extern "C" {
 #define GPAR_K_EQ 0
 #define GPAR_K_RQ 1
 #define GPAR_K_LINEAR 2
+#define GPAR_K_MATERN12 3 /* Matern nu = 1/2, 3/2, 5/2 with r = sqrt(r2):  exp(-r);  (1 + sqrt(3) r) exp(-sqrt(3) r); */
+#define GPAR_K_MATERN32 4 /* (1 + sqrt(5) r + 5 r2 / 3) exp(-sqrt(5) r).  No parameter beyond the scales; k(x, x) = 1.  The  */
+#define GPAR_K_MATERN52 5 /* derivative of nu = 1/2 with respect to r2 is singular at r = 0: every gradient pass takes it as 0 there */
 
 typedef struct {
     int32_t dz;                      /* number of feature dims (<= GPAR_MAX_DIMS) */
@@ -87,7 +91,7 @@ typedef struct {
     int32_t type; /* GPAR_K_* */
     int32_t term; /* index of the product term this factor multiplies into */
     int32_t off;  /* first feature dim */
-    int32_t nd;   /* number of feature dims (0 allowed: EQ/RQ -> 1, LINEAR -> 0) */
+    int32_t nd;   /* number of feature dims (0 allowed: EQ/RQ/MATERN -> 1, LINEAR -> 0) */
     double alpha; /* RQ shape */
 } gpar_factor_t;
 

@@ -1,6 +1,11 @@
 """Gram-build timing on the layer kernels of the BASELINE configs (the HBM-bound kernel north_star names): the widest
 layer's symmetric lower-triangle build for C2 / C3 / C5 and the n x M cross-Gram of C4, alone on the GPU.
-Prints one JSON line per kernel: algorithmic bytes (8 per stored entry) / time against the 8 TB/s HBM peak."""
+Prints one JSON line per kernel: algorithmic bytes (8 per stored entry) / time against the 8 TB/s HBM peak.
+
+    python tools/time_gram_configs.py [--matern NU] [C2 C3 C4 C5]
+
+`--matern 0.5|1.5|2.5`: the same layer structures with the Matern kernel of that smoothness where the configuration has EQ
+(GPARRegressor(matern=...); configurations with rq=True cannot take it)."""
 import json
 import os
 import sys
@@ -14,6 +19,7 @@ from gpar_amd import hip
 from gpar_amd.engine import HipEngine, set_engine
 from gpar_amd.kernels import compile_kernel
 from gpar_amd.regression import _construct_gpar
+from gpar_amd.regression import GPARRegressor
 from tools.run_config import CONFIGS, build
 
 HBM_PEAK_TBS = 8.0
@@ -41,9 +47,21 @@ def timeit(fn, reps=120):
     return {"burst": float(np.mean(ms[1:6])), "sustained": float(np.mean(ms[-20:])), "best": float(min(ms))}
 
 
+argv = sys.argv[1:]
+matern = None
+if "--matern" in argv:
+    at = argv.index("--matern")
+    matern = float(argv[at + 1])
+    del argv[at:at + 2]
+
 out = []
-for name in sys.argv[1:] or ["C2", "C3", "C4", "C5"]:
+for name in argv or ["C2", "C3", "C4", "C5"]:
     cfg, reg, x, y = build(name, eng)
+    if matern is not None:
+        kw = dict(cfg["kw"], normalise_y=False, matern=matern)
+        if reg.x_ind is not None:
+            kw["x_ind"] = reg.x_ind
+        reg = GPARRegressor(**kw)
     n, m, p = cfg["n"], cfg["m"], cfg["p"]
     with torch.no_grad():
         reg.logpdf(x[:64], y[:64])  # instantiate the hyper-parameters
@@ -64,7 +82,7 @@ for name in sys.argv[1:] or ["C2", "C3", "C4", "C5"]:
         ms = timeit(lambda: hip.gram(ck, z, None, out=K, lower=True, diag_add=d, diag_const=1e-12))
         nbytes, kind = 8.0 * n * (n + 1) / 2, f"symmetric lower, n = {n}"
     terms = [[fa.type for fa in t.factors] for t in ck.kernel.terms]
-    rec = {"config": name, "kernel": kind, "layer": p - 1, "feature_dims": int(ck.dz), "terms": terms, "ms": ms["sustained"], "ms_burst": ms["burst"],
+    rec = {"config": name, "matern": matern, "kernel": kind, "layer": p - 1, "feature_dims": int(ck.dz), "terms": terms, "ms": ms["sustained"], "ms_burst": ms["burst"],
            "ms_best": ms["best"], "algorithmic_bytes": nbytes}
     for key in ("sustained", "burst"):
         rec["tb_per_s_" + key] = nbytes / ms[key] * 1e-9
