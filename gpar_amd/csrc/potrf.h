@@ -392,9 +392,105 @@ __global__ __launch_bounds__(64) void potrf_small_update_kernel(double* __restri
     if (threadIdx.x == 0) A[(size_t)(org + i) * lda + org + j] -= s;
 }
 
-static int potrf_gemm_update(const PotrfCtx& c, int k0, int kend, int col_end, hipStream_t stream, int role = 0) {
+// The companion of a matrix-core update that leaves the augmented rows out (potrf_run, "tail split"): the same rank-K update for
+// the T <= 4 rows [r0, r0 + T) below the factored part,
+//     A[r0 + t, j] -= A[r0 + t, k0:k0 + K) . A[j, k0:k0 + K)     for j in [c0, c1), j <= r0 + t.
+// A 128 x 128 tile of the GEMM kernel per 128 columns for these few rows runs every MFMA of a full tile and stores one row of it.
+// Here the T operand rows are staged in LDS once per workgroup and every wave walks rows j of the panel (c0 + wave, + the
+// launch's waves, ...): one pass over the panel, 16-byte loads where the geometry allows (V2), lanes stride K, butterfly sum.  It is
+// bound by that pass and is issued where the caller's stream would otherwise wait.  A modest grid of large workgroups (1024 threads, few
+// registers): next to a trailing update that owns the registers of every SIMD a workgroup only ever gets the half of a compute
+// unit an update workgroup has just left, and holds it until its last wave is done - so each one carries many loads in flight.
+constexpr int POTRF_TAIL_T = 4;          // operand rows per launch
+constexpr int POTRF_TAIL_KMAX = 2048;    // K per launch: T x K doubles of LDS
+constexpr int POTRF_TAIL_THREADS = 1024;
+template <bool V2>
+__global__ __launch_bounds__(POTRF_TAIL_THREADS) void potrf_tail_update_kernel(double* __restrict__ A, int lda, int r0, int T, int k0, int K, int c0, int c1,
+                                                                                long long batch_a) {
+    extern __shared__ __attribute__((aligned(16))) double tail_rows[];   // [T][K]
+    A += (size_t)blockIdx.y * batch_a;
+    for (int idx = threadIdx.x; idx < T * K; idx += POTRF_TAIL_THREADS) {
+        const int t = idx / K, k = idx - t * K;
+        tail_rows[idx] = A[(size_t)(r0 + t) * lda + k0 + k];
+    }
+    __syncthreads();
+    constexpr int NW = POTRF_TAIL_THREADS / 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int j = c0 + (int)blockIdx.x * NW + w; j < c1; j += (int)gridDim.x * NW) {
+        const double* Pj = A + (size_t)j * lda + k0;
+        double acc[POTRF_TAIL_T] = {0.0, 0.0, 0.0, 0.0};
+        if (V2) {   // K, k0, lda even, A 16-byte aligned
+            const gpar::gpar_d2* P2 = reinterpret_cast<const gpar::gpar_d2*>(Pj);
+            const int K2 = K >> 1;
+            int k = lane;
+            for (; k + 192 < K2; k += 256) {
+                gpar::gpar_d2 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = P2[k + 64 * u];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int t = 0; t < POTRF_TAIL_T; ++t)
+                        if (t < T) {
+                            const gpar::gpar_d2 x = *reinterpret_cast<const gpar::gpar_d2*>(tail_rows + t * K + 2 * (k + 64 * u));
+                            acc[t] = fma(x[1], v[u][1], fma(x[0], v[u][0], acc[t]));
+                        }
+            }
+            for (; k < K2; k += 64) {
+                const gpar::gpar_d2 v = P2[k];
+#pragma unroll
+                for (int t = 0; t < POTRF_TAIL_T; ++t)
+                    if (t < T) {
+                        const gpar::gpar_d2 x = *reinterpret_cast<const gpar::gpar_d2*>(tail_rows + t * K + 2 * k);
+                        acc[t] = fma(x[1], v[1], fma(x[0], v[0], acc[t]));
+                    }
+            }
+        } else {
+            for (int k = lane; k < K; k += 64) {
+                const double v = Pj[k];
+#pragma unroll
+                for (int t = 0; t < POTRF_TAIL_T; ++t)
+                    if (t < T) acc[t] = fma(tail_rows[t * K + k], v, acc[t]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < POTRF_TAIL_T; ++t) {
+            if (t >= T) break;
+            double s = acc[t];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            if (lane == 0 && j <= r0 + t) A[(size_t)(r0 + t) * lda + j] -= s;   // (the corner: its lower part only)
+        }
+    }
+}
+
+// A[nf:N, c0:c1) -= A[nf:N, k0:kend) A[c0:c1, k0:kend)^T (of the corner, c1 > nf, the lower part): launches of at most POTRF_TAIL_T
+// rows and POTRF_TAIL_KMAX columns of K each, in a fixed order.
+static int potrf_tail_update(double* A, int N, int lda, int batch, long long batch_a, int nf, int k0, int kend, int c0, int c1, hipStream_t stream) {
+    if (c1 <= c0 || kend <= k0 || N <= nf) return 0;
+    const int ncols = c1 - c0;
+    int gx = gpar_ceil_div(ncols, 4 * (POTRF_TAIL_THREADS / 64));   // at least four rows of the panel per wave
+    const int gmax = batch >= 256 ? 1 : 256 / batch;
+    if (gx > gmax) gx = gmax;
+    if (gx < 1) gx = 1;
+    for (int ks = k0; ks < kend; ks += POTRF_TAIL_KMAX) {
+        const int K = kend - ks < POTRF_TAIL_KMAX ? kend - ks : POTRF_TAIL_KMAX;
+        const bool v2 = gpar_aligned16(A) && (lda % 2 == 0) && (batch_a % 2 == 0) && (ks % 2 == 0) && (K % 2 == 0);
+        for (int r0 = nf; r0 < N; r0 += POTRF_TAIL_T) {
+            const int T = N - r0 < POTRF_TAIL_T ? N - r0 : POTRF_TAIL_T;
+            const size_t lds = (size_t)T * K * sizeof(double);
+            if (v2) hipLaunchKernelGGL(potrf_tail_update_kernel<true>, dim3(gx, batch), dim3(POTRF_TAIL_THREADS), lds, stream, A, lda, r0, T, ks, K, c0, c1, batch_a);
+            else hipLaunchKernelGGL(potrf_tail_update_kernel<false>, dim3(gx, batch), dim3(POTRF_TAIL_THREADS), lds, stream, A, lda, r0, T, ks, K, c0, c1, batch_a);
+        }
+    }
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+// `row_end` > 0: the update stops at that row (the augmented rows below it go to potrf_tail_update: potrf_run's tail split).
+static int potrf_gemm_update(const PotrfCtx& c, int k0, int kend, int col_end, hipStream_t stream, int role = 0, int row_end = 0) {
     // A[kend:N, kend:col_end] -= A[kend:N, k0:kend] A[kend:col_end, k0:kend]^T   (lower part only)
-    const int rows = c.N - kend, cols = col_end - kend;
+    const int rows = (row_end > 0 ? row_end : c.N) - kend, cols = col_end - kend;
     if (rows <= 0 || cols <= 0) return 0;
     if (rows <= POTRF_SMALL_ROWS && env_int("GPAR_POTRF_SMALL_UPDATE", 1)) {
         hipLaunchKernelGGL(potrf_small_update_kernel, dim3(rows * cols, c.batch), dim3(64), 0, stream, c.A, c.lda, kend, k0, kend - k0, rows, cols, c.batch_a);
@@ -432,8 +528,8 @@ static int potrf_la_update(const PotrfCtx& c, int k0, int kend, int la_end, hipS
 
 // Everything to the right of the next step's columns: A[from:N, from:N] -= P P^T (lower), P = A[from:N, k0:kend).  A handful of rows
 // (the augmented row once the last panel is next) by the one-wave kernel, else the batched GEMM.
-static int potrf_rest_update(const PotrfCtx& c, int k0, int kend, int from, hipStream_t stream) {
-    const int rows = c.N - from;
+static int potrf_rest_update(const PotrfCtx& c, int k0, int kend, int from, hipStream_t stream, int row_end = 0) {
+    const int rows = (row_end > 0 ? row_end : c.N) - from;
     if (rows <= 0) return 0;
     if (rows <= POTRF_SMALL_ROWS && env_int("GPAR_POTRF_SMALL_UPDATE", 1)) {
         hipLaunchKernelGGL(potrf_small_update_kernel, dim3(rows * rows, c.batch), dim3(64), 0, stream, c.A, c.lda, from, k0, kend - k0, rows, rows, c.batch_a);
@@ -687,6 +783,31 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
     };
     auto fusable2 = [&](int k) { return fuse_panels(k) > 0; };
     auto panel_end = [&](int k) { return fusable2(k) ? k + fuse_panels(k) * nbo : (k + nbo >= nf ? nf : k + nbo); };
+    // Tail split: a matrix with a short unfactored tail - 0 < N - nf <= POTRF_SMALL_ROWS, the augmented row(s) [y^T, 0] of the log
+    // marginal likelihood; not the posterior's n* appended rows - gave every matrix-core update below a last tile row for those few
+    // rows: (T + 1)(T + 2) / 2 tiles where T (T + 1) / 2 cover the factor, and the surplus ones end the launch.  An update whose first
+    // row is `r0` stops at row nf, and the tail rows receive the same rank-K update from potrf_tail_update, whenever leaving them out
+    // removes a tile row: ceil((N - r0) / 128) > ceil((nf - r0) / 128).  (Where it removes none - nf - r0 not within N - nf of a
+    // multiple of 128 from below - the update keeps all rows: the split would add a launch and save nothing.)  Geometry only.
+    // Every companion is issued on the CALLER's stream, in the same order with and without look-ahead: the one of a look-ahead slice
+    // or in-group update right behind it (the next panel reads those entries), the one of a rest update behind the NEXT step's
+    // panel launches, where the caller's stream otherwise waits for the side stream - it reads finished panel columns and writes
+    // tail rows only, which no matrix-core launch of a split update touches, so it needs no event.
+    // Lock-step batches only: there the surplus tiles are `batch` times as many and the panel chain hides under the batched update.  In a
+    // LONE factorisation the companion in front of every panel lengthens the serial chain by what the tile row saved or more (measured,
+    // parent / split: n = 16384 25.05 / 25.06 ms, n = 8192 4.63 / 4.68; batches of 2 / 4 / 16 at n = 8192 8.4 / 8.4, 13.8 / 13.6, 48.4 / 47.4 ms,
+    // 3 x 6656 6.58 / 6.45, 2 x 16384 47.5 / 47.2, C3 - 8 x 16384 - 182.3 / 179.9: profiles/r08_tail_split_bench.txt).
+    const bool tail_on = batch > 1 && N - nf > 0 && N - nf <= POTRF_SMALL_ROWS;
+    auto tail_split = [&](int r0) { return tail_on && r0 < nf && gpar_ceil_div(N - r0, GEMM_BM) > gpar_ceil_div(nf - r0, GEMM_BM); };
+    auto tail_update = [&](int ks, int ke, int c0, int c1) { return potrf_tail_update(A, N, lda, batch, batch_a, nf, ks, ke, c0, c1, stream); };
+    struct { int k0, kend, from; bool on; } tail_pend = {0, 0, 0, false};   // companion of the last rest update, not yet issued
+    // the rest update of [k0, kend) from row / column `from` on; with a split its companion becomes pending
+    auto rest_update = [&](int k0, int kend, int from, hipStream_t s) {
+        const bool sp = tail_split(from);
+        const int rc = potrf_rest_update(c, k0, kend, from, s, sp ? nf : 0);
+        if (sp) tail_pend = {k0, kend, from, true};
+        return rc;
+    };
     for (int k0 = 0, knext = 0; k0 < nf; k0 = knext) {
         int kend = panel_end(k0);
         // a ragged tail (nf not a multiple of 64) becomes its own narrow panel so the wide part stays fusable
@@ -699,8 +820,9 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
                 if (i > 0) {   // this panel's columns: one update by the i panels of the group factored so far
                     bool pb;
                     prof_begin(stream, pb, N - ks);
-                    rc = potrf_gemm_update(c, k0, ks, ks + nbo, stream, 1);
+                    rc = potrf_gemm_update(c, k0, ks, ks + nbo, stream, 1, tail_split(ks) ? nf : 0);
                     prof_end(stream, pb, N - ks, nbo, (ks - k0) * batch);
+                    if (!rc && tail_split(ks)) rc = tail_update(k0, ks, ks, ks + nbo);
                 }
                 if (!rc) rc = potrf_panel_any(A, N, lda, ks, nbo, logdet, info, stream, prezero, batch, batch_a);
             }
@@ -725,6 +847,11 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
         }
         knext = kend;
         if (rc) return rc;
+        if (tail_pend.on) {   // (see the tail split above)
+            tail_pend.on = false;
+            rc = tail_update(tail_pend.k0, tail_pend.kend, tail_pend.from, N);
+            if (rc) return rc;
+        }
         if (kend >= N) break;
         // columns the next step factors (one panel, or two if it pairs): [kend, next_end)
         const int next_end = groupable(kend) ? kend + G * nbo : panel_end(kend);
@@ -738,7 +865,7 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
                 rc = potrf_la_update(c, k0, kend, next_end, stream);
                 if (!rc) {
                     prof_begin(stream, pa, N - next_end);
-                    rc = potrf_rest_update(c, k0, kend, next_end, stream);
+                    rc = rest_update(k0, kend, next_end, stream);
                     prof_end(stream, pa, N - next_end, N - next_end, (kend - k0) * batch);
                 }
                 if (rc) return rc;
@@ -749,11 +876,12 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
                 // the update kernel picks its tile shape by the size of the launch, and a tile that preloads C rounds differently
                 // from one that adds it at the end, so ONE launch over everything would not return the look-ahead schedule's bits)
                 prof_begin(stream, pa, N - kend);
-                rc = potrf_gemm_update(c, k0, kend, next_end, stream, 1);
+                rc = potrf_gemm_update(c, k0, kend, next_end, stream, 1, tail_split(kend) ? nf : 0);
                 prof_end(stream, pa, N - kend, next_end - kend, (kend - k0) * batch);
+                if (!rc && tail_split(kend)) rc = tail_update(k0, kend, kend, next_end);
                 if (!rc) {
                     prof_begin(stream, pa, N - next_end);
-                    rc = potrf_rest_update(c, k0, kend, next_end, stream);
+                    rc = rest_update(k0, kend, next_end, stream);
                     prof_end(stream, pa, N - next_end, N - next_end, (kend - k0) * batch);
                 }
                 if (rc) return rc;
@@ -778,8 +906,9 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
             rc = potrf_la_update(c, k0, kend, la_end, stream);
         } else {
             prof_begin(stream, pa, N - kend);
-            rc = potrf_gemm_update(c, k0, kend, la_end, stream, 1);   // same kernel symbol: it is part of the trailing update
+            rc = potrf_gemm_update(c, k0, kend, la_end, stream, 1, tail_split(kend) ? nf : 0);   // same kernel symbol: it is part of the trailing update
             prof_end(stream, pa, N - kend, la_end - kend, (kend - k0) * batch);
+            if (!rc && tail_split(kend)) rc = tail_update(k0, kend, kend, la_end);
         }
         if (rc) return rc;
         // (2) everything to the right of the next step's columns, on the side stream
@@ -788,13 +917,17 @@ static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* inf
             const int rows = N - next_end, cols = N - next_end;
             if (rows > 0) {
                 prof_begin(side, pa, rows);
-                rc = potrf_rest_update(c, k0, kend, next_end, side);
+                rc = rest_update(k0, kend, next_end, side);
                 prof_end(side, pa, rows, cols, (kend - k0) * batch);
                 if (rc) return rc;
             }
         }
         trail_done = la_event();
         GPAR_HIP_TRY(hipEventRecord(trail_done, side));
+    }
+    if (tail_pend.on) {   // (cannot happen: a rest update with rows of the factor left is followed by another step)
+        const int rc = tail_update(tail_pend.k0, tail_pend.kend, tail_pend.from, N);
+        if (rc) return rc;
     }
     if (trail_done) GPAR_HIP_TRY(hipStreamWaitEvent(stream, trail_done, 0));   // join
     GPAR_LAUNCH_CHECK();
