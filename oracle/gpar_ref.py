@@ -33,15 +33,28 @@ def _indices(m, pi, markov):
     return list(range(m)), list(range(m + p_start, m + p_last + 1))
 
 
+_MATERN = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
+
+
 def layer_spec(hypers, m, pi, config):
     """Kernel dict (oracle/kernels.py format) and noise variance of layer `pi` (regression.py:92-180)."""
     g = lambda name: np.asarray(hypers[name], dtype=np.float64)
     m_inds, p_inds = _indices(m, pi, config.get("markov"))
     rq = config.get("rq", False)
+    # `matern` (0.5 | 1.5 | 2.5; the product's addition behind the reference's keywords): the Matern kernel of that smoothness
+    # stands where the default model has EQ - the two nonlinear kernels; the locally periodic term keeps its EQ factors.  Same
+    # variable names as EQ (no parameter beyond the scales).
+    matern = config.get("matern")
+    if matern is not None:
+        if isinstance(matern, bool) or not isinstance(matern, (int, float, np.floating, np.integer)) or float(matern) not in _MATERN:
+            raise ValueError("matern must be None, 0.5, 1.5 or 2.5")
+        if rq:
+            raise ValueError("matern and rq=True exclude one another")
+    base = "rq" if rq else "eq" if matern is None else _MATERN[float(matern)]
     terms = []
 
     def nonlin(prefix, cols, scales):
-        f = {"type": "rq" if rq else "eq", "cols": cols, "scales": list(np.atleast_1d(scales)), "periods": None, "alpha": 0.0}
+        f = {"type": base, "cols": cols, "scales": list(np.atleast_1d(scales)), "periods": None, "alpha": 0.0}
         if rq:
             f["alpha"] = float(g(f"{prefix}/alpha"))
         return f

@@ -12,6 +12,16 @@ oracle/__init__.py, "parity unpinned"):
     k.select(i)   k(x[:, i], y[:, i])                               (regression.py:178)
     c * k, k + k', k * k', k + c                                    (regression.py:110,127-129,138)
 
+and the Matern kernels of include/gpar_hip.h, which the reference lacks (Rasmussen & Williams 2006, eq. 4.14-4.17), in
+r = sqrt(|x - y|^2):
+
+    matern12      k = exp(-r)                                        dk/dr2 = -exp(-r) / (2 r), TAKEN AS 0 AT r = 0
+    matern32      k = (1 + sqrt(3) r) exp(-sqrt(3) r)                dk/dr2 = -(3/2) exp(-sqrt(3) r)
+    matern52      k = (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)    dk/dr2 = -(5/6) (1 + sqrt(5) r) exp(-sqrt(5) r)
+
+(nu = 1/2 has a kink at r = 0: its derivative with respect to r2 is singular there, and every gradient - here as in the
+product - leaves coincident pairs out of the sums.)
+
 A kernel is handed around as a plain dict (no product classes are imported here):
 
     {"terms": [{"coef": float,
@@ -27,6 +37,36 @@ symmetric and exactly zero on the diagonal; the HIP kernel uses the same formula
 import numpy as np
 
 __all__ = ["features", "factor_matrix", "gram", "gram_diag", "spec_to_dict"]
+
+STATIONARY = ("eq", "rq", "matern12", "matern32", "matern52")   # functions of r2 alone, 1 at r2 = 0
+
+
+def _stationary(factor, r2):
+    """(k, dk/dr2) of a stationary factor at the matrix of squared distances `r2`."""
+    kind = factor["type"]
+    if kind == "eq":
+        F = np.exp(-0.5 * r2)
+        return F, -0.5 * F
+    if kind == "rq":
+        alpha = float(factor["alpha"])
+        F = np.exp(-alpha * np.log1p(r2 / (2.0 * alpha)))
+        return F, -0.5 * F / (1.0 + r2 / (2.0 * alpha))
+    if kind == "matern12":
+        r = np.sqrt(r2)
+        F = np.exp(-r)
+        away = r > 0.0
+        dF = np.zeros_like(F)
+        dF[away] = -F[away] / (2.0 * r[away])
+        return F, dF
+    if kind == "matern32":
+        a = np.sqrt(3.0) * np.sqrt(r2)
+        e = np.exp(-a)
+        return (1.0 + a) * e, -1.5 * e
+    if kind == "matern52":
+        a = np.sqrt(5.0) * np.sqrt(r2)
+        e = np.exp(-a)
+        return (1.0 + a + 5.0 * r2 / 3.0) * e, -(5.0 / 6.0) * (1.0 + a) * e
+    raise ValueError(f"unknown factor type {kind!r}")
 
 
 def features(factor, x):
@@ -45,6 +85,8 @@ def features(factor, x):
 
 
 def factor_matrix(factor, x1, x2):
+    if factor["type"] != "linear" and factor["type"] not in STATIONARY:
+        raise ValueError(f"unknown factor type {factor['type']!r}")
     z1, z2 = features(factor, x1), features(factor, x2)
     if factor["type"] == "linear":
         out = np.zeros((z1.shape[0], z2.shape[0]))
@@ -55,12 +97,7 @@ def factor_matrix(factor, x1, x2):
     for d in range(z1.shape[1]):
         diff = z1[:, d][:, None] - z2[:, d][None, :]
         r2 += diff * diff
-    if factor["type"] == "eq":
-        return np.exp(-0.5 * r2)
-    if factor["type"] == "rq":
-        alpha = float(factor["alpha"])
-        return np.exp(-alpha * np.log1p(r2 / (2.0 * alpha)))
-    raise ValueError(f"unknown factor type {factor['type']!r}")
+    return _stationary(factor, r2)[0]
 
 
 def gram(spec, x1, x2=None, noise_diag=None, jitter=0.0):
@@ -84,6 +121,7 @@ def gram(spec, x1, x2=None, noise_diag=None, jitter=0.0):
 
 
 def gram_diag(spec, x):
+    """k(x_a, x_a): every stationary factor (EQ, RQ, the Matern kernels) is 1 on the diagonal, a linear factor |z_a|^2."""
     x = np.asarray(x, dtype=np.float64)
     out = np.zeros(x.shape[0])
     for term in spec["terms"]:
@@ -92,6 +130,8 @@ def gram_diag(spec, x):
             if factor["type"] == "linear":
                 z = features(factor, x)
                 prod = prod * np.sum(z * z, axis=1)
+            elif factor["type"] not in STATIONARY:
+                raise ValueError(f"unknown factor type {factor['type']!r}")
         out += prod
     return out
 
@@ -122,7 +162,8 @@ def spec_to_dict(kernel):
 
 def kernel_grads(spec, x, W):
     """d/d(theta) of  1/2 sum_ab W_ab K_ab(theta)  for every parameter of the kernel `spec` (W symmetric, n x n):
-    term coefficients, per-feature length scales, per-column periods and RQ alphas.  Each derivative matrix
+    term coefficients, per-feature length scales, per-column periods and RQ alphas (the Matern kernels have none beyond their
+    scales; nu = 1/2 contributes nothing at r = 0, see the module docstring).  Each derivative matrix
     dK/dtheta is formed explicitly (test sizes only) — deliberately a different route from the HIP kernel, which
     accumulates per-feature moment sums in one pass.  Verified against central finite differences in
     tests/test_oracle.py."""
@@ -156,13 +197,9 @@ def kernel_grads(spec, x, W):
                     d = z[:, q][:, None] - z[:, q][None, :]
                     diffs.append(d)
                     r2 += d * d
-                if f["type"] == "eq":
-                    F = np.exp(-0.5 * r2)
-                    dF_dr2 = -0.5 * F
-                else:
+                F, dF_dr2 = _stationary(f, r2)
+                if f["type"] == "rq":
                     alpha = float(f["alpha"])
-                    F = np.exp(-alpha * np.log1p(r2 / (2 * alpha)))
-                    dF_dr2 = -0.5 * F / (1.0 + r2 / (2 * alpha))
                     t = r2 / (2 * alpha)
                     g["alpha"] = 0.5 * np.sum(W * rest * F * (t / (1 + t) - np.log1p(t)))
                 for q in range(nd):
@@ -210,11 +247,7 @@ def kernel_input_grads(spec, x1, x2, W):
                 r2 = np.zeros_like(rest)
                 for q in range(z1.shape[1]):
                     r2 += (z1[:, q][:, None] - z2[:, q][None, :]) ** 2
-                if f["type"] == "eq":
-                    dF_dr2 = -0.5 * np.exp(-0.5 * r2)
-                else:
-                    alpha = float(f["alpha"])
-                    dF_dr2 = -0.5 * np.exp(-alpha * np.log1p(r2 / (2 * alpha))) / (1.0 + r2 / (2 * alpha))
+                dF_dr2 = _stationary(f, r2)[1]
             for q in range(z1.shape[1]):
                 j = q % ncol if ncol else 0
                 c = cols[j]

@@ -31,8 +31,19 @@ def _factor_entry(factor, za, zb):
     r2 = mp.fsum((a - b) ** 2 for a, b in zip(za, zb))
     if factor["type"] == "eq":
         return mp.exp(-r2 / 2)
-    alpha = mp.mpf(factor["alpha"])
-    return (1 + r2 / (2 * alpha)) ** (-alpha)
+    if factor["type"] == "rq":
+        alpha = mp.mpf(factor["alpha"])
+        return (1 + r2 / (2 * alpha)) ** (-alpha)
+    # the Matern kernels of smoothness 1/2, 3/2, 5/2 (include/gpar_hip.h) in r = sqrt(r2)
+    if factor["type"] == "matern12":
+        return mp.exp(-mp.sqrt(r2))
+    if factor["type"] == "matern32":
+        a = mp.sqrt(3 * r2)
+        return (1 + a) * mp.exp(-a)
+    if factor["type"] == "matern52":
+        a = mp.sqrt(5 * r2)
+        return (1 + a + 5 * r2 / 3) * mp.exp(-a)
+    raise ValueError(f"unknown factor type {factor['type']!r}")
 
 
 def gram(spec, x1, x2=None, noise_diag=None, jitter=0):

@@ -82,8 +82,10 @@ def _factor_matrix(factor, x1, x2):
     r2 = _pw_dists2(z1, z2)
     if factor["type"] == "eq":
         return torch.exp(-0.5 * r2)
-    alpha = factor["alpha"]
-    return (1.0 + r2 / (2.0 * alpha)) ** (-alpha)
+    if factor["type"] == "rq":
+        alpha = factor["alpha"]
+        return (1.0 + r2 / (2.0 * alpha)) ** (-alpha)
+    raise ValueError(f"unknown factor type {factor['type']!r} (the reference's CPU path has EQ, RQ and Linear only)")
 
 
 def gram(spec, x1, x2=None):

@@ -105,6 +105,41 @@ MICRO = [
 ]
 
 
+# The Matern kernels (`matern` = 0.5 | 1.5 | 2.5: the product's addition behind the reference's keywords, which the reference cannot
+# evaluate; pinned by scikit-learn and 50-digit arithmetic instead, tests/test_oracle_sklearn.py, tests/test_oracle_precision.py).
+# Drawn from a stream of their own and appended, so every earlier vector keeps its bytes.
+MATERN_CASES = [
+    ("matern12-weights", dict(n=16, m=2, p=3, config=dict(linear=True, nonlinear=True, matern=0.5), impute=False, replace=False, missing=0.0, weights=True)),
+    ("matern32-markov1", dict(n=14, m=1, p=4, config=dict(linear=True, nonlinear=True, matern=1.5, markov=1), impute=False, replace=False, missing=0.0, weights=False)),
+    ("matern52-per-inputlinear", dict(n=18, m=2, p=2, config=dict(linear=True, nonlinear=True, matern=2.5, per=True, input_linear=True), impute=False, replace=False, missing=0.0, weights=True)),
+    ("matern12-missing-impute", dict(n=20, m=1, p=3, config=dict(linear=True, nonlinear=True, matern=0.5), impute=True, replace=False, missing=0.25, weights=True)),
+    ("matern52-replace", dict(n=15, m=1, p=3, config=dict(linear=True, nonlinear=True, matern=2.5), impute=True, replace=True, missing=0.15, weights=False)),
+    ("matern32-inducing", dict(n=24, m=1, p=3, config=dict(linear=True, nonlinear=True, matern=1.5), impute=True, replace=False, missing=0.2, weights=False, x_ind=8)),
+]
+
+
+def dense_case(name, c, rng):
+    """One entry of the "gpar_logpdf" group, drawn as the entries of CASES are."""
+    n, m, p = c["n"], c["m"], c["p"]
+    x = rng.uniform(-1.5, 1.5, (n, m))
+    y = rng.standard_normal((n, p))
+    if c["missing"]:
+        y[rng.random((n, p)) < c["missing"]] = np.nan
+        y[0] = rng.standard_normal(p)  # at least one complete row
+    w = (rng.random((n, p)) + 0.5) if c["weights"] else None
+    hypers = hypers_for(m, p, c["config"], rng)
+    x_ind = None if c.get("x_ind") is None else np.linspace(-1.5, 1.5, c["x_ind"])[:, None] * np.ones((1, m))
+    value = gpar_ref.gpar_logpdf(x, y, w, hypers, c["config"], impute=c["impute"], replace=c["replace"], x_ind=x_ind)
+    out = {
+        "name": name, "config": c["config"], "impute": c["impute"], "replace": c["replace"],
+        "x": x.tolist(), "y": [[None if np.isnan(v) else v for v in row] for row in y.tolist()],
+        "w": None if w is None else w.tolist(), "hypers": hypers, "logpdf": value,
+    }
+    if x_ind is not None:
+        out["x_ind"] = x_ind.tolist()
+    return out
+
+
 def micro_case(name, c, rng):
     n, m, p = c["n"], c["m"], c["p"]
     x = rng.uniform(-1.0, 1.0, (n, m))
@@ -190,6 +225,19 @@ def main():
         out["single_gp"].append({"name": name, "config": config, "hypers": hypers, "x": x.tolist(), "y": y.tolist(),
                                  "noise": noise.tolist(), "xs": xs.tolist(), "logpdf": gp_ref.logpdf(spec, x, y, noise),
                                  "mean": mean.tolist(), "cov": cov.tolist()})
+    matern_rng = np.random.default_rng(20261016)   # (a stream of its own, see MATERN_CASES)
+    for name, nu in [("matern12", 0.5), ("matern32", 1.5), ("matern52-per", 2.5)]:
+        config = dict(linear=False, matern=nu, **(dict(per=True) if name.endswith("-per") else {}))
+        n, m = 14, 2
+        x, xs = matern_rng.uniform(-1, 1, (n, m)), matern_rng.uniform(-1, 1, (6, m))
+        y = matern_rng.standard_normal(n)
+        noise = matern_rng.uniform(0.05, 0.2, n)
+        hypers = hypers_for(m, 1, config, matern_rng)
+        spec, _ = gpar_ref.layer_spec(hypers, m, 0, config)
+        mean, cov = gp_ref.posterior(spec, x, y, noise, xs)
+        out["single_gp"].append({"name": name, "config": config, "hypers": hypers, "x": x.tolist(), "y": y.tolist(),
+                                 "noise": noise.tolist(), "xs": xs.tolist(), "logpdf": gp_ref.logpdf(spec, x, y, noise),
+                                 "mean": mean.tolist(), "cov": cov.tolist()})
     # inducing points
     for name, nz in [("vfe-few", 5), ("vfe-many", 12)]:
         n, m = 30, 1
@@ -203,6 +251,18 @@ def main():
         out["vfe"].append({"name": name, "config": config, "hypers": hypers, "x": x.tolist(), "y": y.tolist(), "noise": noise.tolist(),
                            "z": z.tolist(), "xs": xs.tolist(), "bound": gp_ref.vfe_bound(spec, x, y, noise, z),
                            "mean": mean.tolist(), "cov": cov.tolist()})
+    for name, nz, nu in [("vfe-matern12", 6, 0.5), ("vfe-matern32", 9, 1.5), ("vfe-matern52", 12, 2.5)]:
+        n, m = 30, 1
+        config = dict(linear=False, matern=nu)
+        x, xs, z = matern_rng.uniform(-2, 2, (n, m)), matern_rng.uniform(-2, 2, (7, m)), np.linspace(-2, 2, nz)[:, None]
+        y = np.sin(2 * x[:, 0]) + 0.1 * matern_rng.standard_normal(n)
+        noise = matern_rng.uniform(0.05, 0.1, n)
+        hypers = hypers_for(m, 1, config, matern_rng)
+        spec, _ = gpar_ref.layer_spec(hypers, m, 0, config)
+        mean, cov = gp_ref.vfe_posterior(spec, x, y, noise, z, xs)
+        out["vfe"].append({"name": name, "config": config, "hypers": hypers, "x": x.tolist(), "y": y.tolist(), "noise": noise.tolist(),
+                           "z": z.tolist(), "xs": xs.tolist(), "bound": gp_ref.vfe_bound(spec, x, y, noise, z),
+                           "mean": mean.tolist(), "cov": cov.tolist()})
     # appended after everything else so that the earlier vectors keep their values (one shared random stream)
     wl_rng = np.random.default_rng(20260929)
     for name, c in WORKLOADS:
@@ -210,6 +270,8 @@ def main():
     micro_rng = np.random.default_rng(20260930)   # (a stream of its own: the vectors above keep their values)
     for name, c in MICRO:
         out["gpar_logpdf"].append(micro_case(name, c, micro_rng))
+    for name, c in MATERN_CASES:
+        out["gpar_logpdf"].append(dense_case(name, c, matern_rng))
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpar_cases.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)

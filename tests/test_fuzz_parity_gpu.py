@@ -6,13 +6,34 @@
 over randomly drawn model options (every kernel switch of gpar/regression.py:264-286, markov orders, tied scales, inducing
 points with each approximation), ragged sizes (n = 2 .. 160, m = 1 .. 3, p = 1 .. 4), random missing patterns (including a
 fully observed and a nearly empty output) and random weights.  The cases are fixed by their seeds; what the parametrised parity
-tests cover by design, this covers by accident."""
+tests cover by design, this covers by accident.
+
+Seeds from MATERN_FIRST on are the same draws with `matern` = 0.5 / 1.5 / 2.5 set in addition (which excludes rq): the Matern
+kernels under missing data, weights, markov orders, tied scales, the three inducing-point approximations, impute / replace and
+posterior samples on the shared stream, at the tolerances of every other case.  tests/test_fuzz_cases.py (CPU) checks what the
+block contains.  The tests print their error / tolerance ratios for these seeds (pytest -s)."""
 import numpy as np
 import pytest
 
 from .conftest import make_engine, to_np
 
 pytestmark = pytest.mark.gpu
+
+
+MATERN_FIRST = 1000                                   # first seed of the Matern block (the seeds below it keep their cases)
+MATERN_SEEDS = list(range(MATERN_FIRST, MATERN_FIRST + 48))
+MATERN_GRADIENT_SEEDS = list(range(MATERN_FIRST + 100, MATERN_FIRST + 115))
+MATERN_MID_SEEDS = list(range(MATERN_FIRST, MATERN_FIRST + 6))
+
+
+def _matern(seed):
+    """Smoothness of a seed of the Matern block (each value every third seed), None below the block."""
+    return None if seed < MATERN_FIRST else [0.5, 1.5, 2.5][(seed - MATERN_FIRST) % 3]
+
+
+def _report(label, seed, ratios):
+    if seed >= MATERN_FIRST:
+        print(f"[matern] {label} seed={seed} nu={_matern(seed)}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
 
 
 def _case(seed):
@@ -25,6 +46,8 @@ def _case(seed):
         markov=[None, None, 0, 1, 2][int(rng.integers(5))],
         impute=bool(rng.integers(2)), replace=bool(rng.integers(3) == 0),
     )
+    if _matern(seed) is not None:   # (nothing is drawn for it: the stream below is that of every other seed)
+        kw["matern"], kw["rq"] = _matern(seed), False
     if kw["per"]:
         kw["per_period"] = float(rng.uniform(0.3, 1.2))
     if rng.integers(3) == 0 and n >= 6:
@@ -73,7 +96,7 @@ def _run(kind, kw, x, y, w, xs):
         set_engine(previous)
 
 
-@pytest.mark.parametrize("seed", [-s - 1 for s in range(24)] + list(range(96)))
+@pytest.mark.parametrize("seed", [-s - 1 for s in range(24)] + list(range(96)) + MATERN_SEEDS + [-s - 1 for s in MATERN_SEEDS[:12]])
 def test_random_configuration(seed, monkeypatch):
     """(negative seeds: case -seed - 1 once more with GPAR_HOST_MASKS=0 - boolean device masks computed layer by layer, the
     path every engine but the HIP one still takes - so that both ways through the missing-data bookkeeping stay covered)"""
@@ -89,11 +112,18 @@ def test_random_configuration(seed, monkeypatch):
     # inducing-point chains go through K_zz^-1 with a 1e-12 jitter: conditioning-limited, everything else to rounding
     tol = 1e-6 if sparse else 1e-9
     scale = max(abs(o_prior), 1.0)
+    ratios = {"prior": abs(prior - o_prior) / (tol * scale), "posterior": abs(post - o_post) / (tol * max(abs(o_post), 1.0)),
+              "sample": float(np.max(np.abs(sample - o_sample))) / ((1e-4 if sparse else 1e-7) * max(1.0, np.abs(o_sample).max()))}
+    want = None
+    if kw.get("sparse_method", "vfe") == "vfe":   # the independent restatement implements the reference's default approximation
+        want = gpar_ref.gpar_logpdf(x, y, w, hypers, config, impute=kw["impute"], replace=kw["replace"], x_ind=kw.get("x_ind"))
+        ratios["restatement"] = abs(prior - want) / (tol * max(abs(want), 1.0))
+    _report("fuzz", seed, ratios)
+    assert config.get("matern") == _matern(seed)
     assert abs(prior - o_prior) <= tol * scale, (kw, prior, o_prior)
     assert abs(post - o_post) <= tol * max(abs(o_post), 1.0), (kw, post, o_post)
     np.testing.assert_allclose(sample, o_sample, rtol=0, atol=(1e-4 if sparse else 1e-7) * max(1.0, np.abs(o_sample).max()))
-    if kw.get("sparse_method", "vfe") == "vfe":   # the independent restatement implements the reference's default approximation
-        want = gpar_ref.gpar_logpdf(x, y, w, hypers, config, impute=kw["impute"], replace=kw["replace"], x_ind=kw.get("x_ind"))
+    if want is not None:
         assert abs(prior - want) <= tol * max(abs(want), 1.0), (kw, prior, want)
 
 
@@ -119,14 +149,22 @@ def _grads(kind, kw, x, y, w):
         set_engine(previous)
 
 
-@pytest.mark.parametrize("seed", range(32))
+def _gradient_ratios(sparse, value, o_value, got, ref):
+    big = max(np.max(np.abs(ref)), 1e-3)
+    rtol, atol = (1e-4, 1e-5 * big) if sparse else (1e-6, 1e-7 * big)
+    return {"value": abs(value - o_value) / ((1e-6 if sparse else 1e-9) * max(abs(o_value), 1.0)),
+            "gradient": float(np.max(np.abs(got - ref) / (atol + rtol * np.abs(ref))))}
+
+
+@pytest.mark.parametrize("seed", list(range(32)) + MATERN_GRADIENT_SEEDS)
 def test_random_configuration_gradient(seed):
     """d logpdf / d(every hyper-parameter) - the joint objective of fit(fix=False), through imputed / replaced columns and
     extended inducing inputs where the drawn configuration has them - HIP kernels against the numpy engine."""
-    kw, x, y, w, _ = _case(200 + seed)
+    kw, x, y, w, _ = _case(seed if seed >= MATERN_FIRST else 200 + seed)   # (the Matern block's seeds are taken as they are)
     sparse = "x_ind" in kw
     value, got = _grads("hip", kw, x, y, w)
     o_value, ref = _grads("oracle", kw, x, y, w)
+    _report("fuzz gradient", seed, _gradient_ratios(sparse, value, o_value, got, ref))
     assert abs(value - o_value) <= (1e-6 if sparse else 1e-9) * max(abs(o_value), 1.0)
     big = max(np.max(np.abs(ref)), 1e-3)
     np.testing.assert_allclose(got, ref, rtol=1e-4 if sparse else 1e-6, atol=(1e-5 if sparse else 1e-7) * big, err_msg=str(kw))
@@ -141,6 +179,8 @@ def _mid_case(seed):
     kw = dict(scale=float(rng.uniform(0.3, 1.0)), noise=float(rng.uniform(0.05, 0.3)), normalise_y=False, linear=True,
               nonlinear=bool(rng.integers(2)), rq=bool(rng.integers(2)), per=bool(rng.integers(4) == 0),
               markov=[None, 1, 2][int(rng.integers(3))], impute=bool(rng.integers(2)), replace=bool(rng.integers(4) == 0))
+    if _matern(seed) is not None:
+        kw["matern"], kw["rq"] = _matern(seed), False
     if rng.integers(3) == 0:
         kw["x_ind"] = rng.uniform(0, 1, (int(rng.integers(40, 321)), m))
     x = rng.uniform(0, 1, (n, m))
@@ -158,12 +198,13 @@ def _mid_case(seed):
     return kw, x, y, w
 
 
-@pytest.mark.parametrize("seed", range(20))
+@pytest.mark.parametrize("seed", list(range(20)) + MATERN_MID_SEEDS)
 def test_random_configuration_at_blocked_sizes(seed):
     kw, x, y, w = _mid_case(seed)
     sparse = "x_ind" in kw
     value, got = _grads("hip", kw, x, y, w)
     o_value, ref = _grads("oracle", kw, x, y, w)
+    _report("fuzz blocked sizes", seed, _gradient_ratios(sparse, value, o_value, got, ref))
     assert abs(value - o_value) <= (1e-6 if sparse else 1e-9) * max(abs(o_value), 1.0), (kw, value, o_value)
     big = max(np.max(np.abs(ref)), 1e-3)
     np.testing.assert_allclose(got, ref, rtol=1e-4 if sparse else 1e-6, atol=(1e-5 if sparse else 1e-7) * big, err_msg=str(kw))

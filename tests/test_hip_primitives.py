@@ -364,7 +364,49 @@ def _kernels(m, p_cols):
         Linear().stretch(np.zeros(0)) + 0.6 * EQ().stretch(np.zeros(0))
     ).select([])
     zoo["zero"] = ZeroKernel()
+    # The Matern kernels (names "matern..."), drawn from a generator of their own so that the entries above keep their values: each
+    # smoothness stretched; a sum with a linear and a constant term; a Matern factor on the periodic embedding times a Matern factor
+    # (period gradients through dk/dr2 of a Matern factor); a GPAR layer with Matern input and output factors; a zero-width Matern
+    # output factor (nd = 0 -> 1; for nu = 1/2 the r = 0 guard on every entry).
+    from gpar_amd.kernels import Matern12, Matern32, Matern52
+
+    mrng = np.random.default_rng(1000 + 10 * m + len(p_cols))
+    u = lambda k: mrng.uniform(0.5, 2.0, k)
+    for tag, make in (("12", Matern12), ("32", Matern32), ("52", Matern52)):
+        zoo[f"matern{tag}"] = (1.3 * make().stretch(u(m))).select(mi)
+        zoo[f"matern{tag}+lin+const"] = (2.0 * make().stretch(u(m)) + Linear().stretch(u(m)) + 0.5).select(mi)
+        if p_cols:
+            zoo[f"matern{tag}-gpar-layer"] = (1.0 * make().stretch(u(m))).select(mi) + (
+                Linear().stretch(u(len(p_cols))) + 0.8 * make().stretch(u(len(p_cols)))
+            ).select(p_cols)
+    for tag, make in (("32", Matern32), ("12", Matern12)):
+        zoo[f"matern{tag}-locally-periodic"] = (
+            1.1 * make().stretch(u(m)) + 0.9 * make().stretch(u(2 * m)).periodic(u(m)) * make().stretch(10 * u(m))
+        ).select(mi)
+    zoo["matern12-zero-width-outputs"] = (1.0 * Matern12().stretch(u(m))).select(mi) + (
+        Linear().stretch(np.zeros(0)) + 0.6 * Matern12().stretch(np.zeros(0))
+    ).select([])
     return zoo
+
+
+def _ratio(got, ref, rtol, atol):
+    """Largest |got - ref| / (atol + rtol |ref|): <= 1 is what np.allclose(got, ref, rtol, atol) accepts."""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    return float(np.max(np.abs(got - ref) / (atol + rtol * np.abs(ref)))) if ref.size else 0.0
+
+
+class _Worst:
+    """Worst error / tolerance ratio over the Matern entries of the zoo, printed at the end of a test (pytest -s shows it)."""
+
+    def __init__(self, label):
+        self.label, self.value, self.where = label, 0.0, None
+
+    def see(self, name, ratio):
+        if name.startswith("matern") and ratio > self.value:
+            self.value, self.where = ratio, name
+
+    def report(self):
+        print(f"[matern] {self.label}: worst error / tolerance = {self.value:.3g} ({self.where})")
 
 
 @pytest.mark.parametrize("m,p_cols", [(1, []), (2, [2]), (3, [3, 4, 5]), (4, [6, 7])])
@@ -377,16 +419,19 @@ def test_gram_matches_oracle(env, m, p_cols, n1, n2):
     width = m + (max(p_cols) - m + 1 if p_cols else 0)
     rng = np.random.default_rng(n1 * 7 + n2)
     x1, x2 = rng.standard_normal((n1, width)), rng.standard_normal((n2, width))
+    worst = _Worst(f"gram m={m} n1={n1} n2={n2}")
     for name, k in _kernels(m, p_cols).items():
         ck = compile_kernel(k, width)
         spec = ok.spec_to_dict(k.resolve(width))
         z1, z2 = hip.featurize(ck, to_dev(x1)), hip.featurize(ck, to_dev(x2))
         got = hip.gram(ck, z1, z2).cpu().numpy()
         ref = ok.gram(spec, x1, x2)
+        worst.see(name, _ratio(got, ref, 1e-13, 1e-14))
         assert np.allclose(got, ref, rtol=1e-13, atol=1e-14), name
         # rows scaled in the same pass (the D^-1/2 K_xz of the inducing-point path)
         rs = rng.uniform(0.5, 3.0, n1)
         got = hip.gram(ck, z1, z2, row_scale=to_dev(rs)).cpu().numpy()
+        worst.see(name, _ratio(got, ref * rs[:, None], 1e-13, 1e-14))
         assert np.allclose(got, ref * rs[:, None], rtol=1e-13, atol=1e-14), name
         # symmetric, lower-only, with noise diagonal + jitter
         noise = rng.uniform(0.01, 0.1, n1)
@@ -395,8 +440,10 @@ def test_gram_matches_oracle(env, m, p_cols, n1, n2):
         got = K.cpu().numpy()
         ref = ok.gram(spec, x1, None, noise_diag=noise, jitter=1e-12)
         il = np.tril_indices(n1)
+        worst.see(name, _ratio(got[il], ref[il], 1e-13, 1e-14))
         assert np.allclose(got[il], ref[il], rtol=1e-13, atol=1e-14), name
         assert np.allclose(hip.gram_diag(ck, z1).cpu().numpy(), ok.gram_diag(spec, x1), rtol=1e-13, atol=1e-14), name
+    worst.report()
 
 
 @pytest.mark.parametrize("m,p_cols", [(1, []), (2, [2]), (3, [3, 4, 5])])
@@ -415,6 +462,7 @@ def test_kernel_gradients_match_oracle(env, m, p_cols, n):
     Wfull = rng.standard_normal((n, n))
     Wfull = Wfull + Wfull.T
     Wdev = to_dev(np.tril(Wfull) + np.triu(np.full((n, n), np.nan), 1))
+    worst = _Worst(f"kernel_grads m={m} n={n}")
     for name, k in _kernels(m, p_cols).items():
         if name == "zero":
             continue
@@ -423,12 +471,15 @@ def test_kernel_gradients_match_oracle(env, m, p_cols, n):
         ref = ok.kernel_grads(ok.spec_to_dict(k.resolve(width)), x, Wfull)
         scale = np.abs(Wfull).sum()
         for t in range(len(ref["coef"])):
+            worst.see(name, abs(got["coef"][t] - ref["coef"][t]) / (1e-12 * scale))
             assert abs(got["coef"][t] - ref["coef"][t]) <= 1e-12 * scale, (name, "coef", t)
             for fi, (gf, rf) in enumerate(zip(got["factors"][t], ref["factors"][t])):
                 for key in ("scales", "periods", "alpha"):
                     if rf[key] is None:
                         continue
+                    worst.see(name, _ratio(gf[key], rf[key], 1e-10, 1e-12 * scale))
                     assert np.allclose(gf[key], rf[key], rtol=1e-10, atol=1e-12 * scale), (name, key, t, fi)
+    worst.report()
 
 
 @pytest.mark.parametrize("n,M", [(70, 9), (257, 65), (130, 200)])
@@ -450,6 +501,7 @@ def test_cross_and_diagonal_gradient_passes_match_oracle(env, n, M):
     Wuu = rng.standard_normal((M, M))
     Wuu = Wuu + Wuu.T
     wd = rng.standard_normal(n)
+    worst = _Worst(f"kernel_grads_vfe n={n} M={M}")
     for name, k in _kernels(m, p_cols).items():
         if name == "zero":
             continue
@@ -459,12 +511,15 @@ def test_cross_and_diagonal_gradient_passes_match_oracle(env, n, M):
         ref = ora.kernel_grads_vfe(ora.compile(k, width), torch.tensor(x), torch.tensor(z), torch.tensor(Wfu), torch.tensor(Wuu), torch.tensor(wd))
         scale = np.abs(Wfu).sum() + np.abs(Wuu).sum() + np.abs(wd).sum()
         for t in range(len(ref["coef"])):
+            worst.see(name, abs(got["coef"][t] - ref["coef"][t]) / (1e-12 * scale))
             assert abs(got["coef"][t] - ref["coef"][t]) <= 1e-12 * scale, (name, "coef", t)
             for fi, (gf, rf) in enumerate(zip(got["factors"][t], ref["factors"][t])):
                 for key in ("scales", "periods", "alpha"):
                     if rf[key] is None:
                         continue
+                    worst.see(name, _ratio(gf[key], rf[key], 1e-10, 1e-12 * scale))
                     assert np.allclose(gf[key], rf[key], rtol=1e-10, atol=1e-12 * scale), (name, key, t, fi)
+    worst.report()
 
 
 @pytest.mark.parametrize("n", [1, 50, 64, 129, 700, 1500, 4200, 1024, 1536, 2560, 4096])
@@ -636,6 +691,9 @@ def test_batched_downdate_and_draws(env, ns, n, batch):
     # gpar_gram_batch: the prior covariances of all samples in one launch
     from gpar_amd.kernels import EQ, Linear, compile_kernel
 
+    from gpar_amd.kernels import Matern12, Matern32, Matern52
+    from oracle import kernels as ok
+
     ck = compile_kernel(0.7 * EQ().stretch(np.array([0.5, 0.8])).select([0, 1]) + Linear().stretch(np.array([3.0])).select([2]), 3)
     xs = to_dev(rng.uniform(0, 1, (batch * ns, 3)))
     z_all = hip.featurize(ck, xs)
@@ -645,6 +703,29 @@ def test_batched_downdate_and_draws(env, ns, n, batch):
     for b in range(batch):
         one = hip.gram(ck, z_all[b * ns:(b + 1) * ns], lower=True, diag_add=noise, diag_const=1e-9)
         assert torch.equal(torch.tril(Ks[b * ns:(b + 1) * ns]), torch.tril(one))
+    # the same with Matern factors (second kernels, on the points and the noise drawn above): all three smoothnesses in one sum,
+    # and a product with a Matern factor on the periodic embedding; equal to the single launches bit for bit, and to the oracle
+    matern_kernels = [
+        0.7 * Matern32().stretch(np.array([0.5, 0.8])).select([0, 1]) + 0.4 * Matern12().stretch(np.array([0.6])).select([2])
+        + 0.3 * Matern52().stretch(np.array([0.9, 0.4, 0.7])).select([0, 1, 2]) + Linear().stretch(np.array([3.0])).select([2]),
+        0.9 * (Matern12().stretch(np.array([0.8, 1.2])).periodic(np.array([0.7])) * Matern52().stretch(np.array([2.0]))).select([1]) + 0.2,
+    ]
+    il = np.tril_indices(ns)
+    worst = 0.0
+    for km in matern_kernels:
+        ckm = compile_kernel(km, 3)
+        zm = hip.featurize(ckm, xs)
+        Km = hip.alloc_matrix(batch * ns, ns, dev)
+        hip.gram_batch_(ckm, zm, batch, Km, lower=True, diag_add=noise, diag_const=1e-9)
+        spec = ok.spec_to_dict(km.resolve(3))
+        for b in range(batch):
+            one = hip.gram(ckm, zm[b * ns:(b + 1) * ns], lower=True, diag_add=noise, diag_const=1e-9)
+            assert torch.equal(torch.tril(Km[b * ns:(b + 1) * ns]), torch.tril(one))
+            ref = ok.gram(spec, xs[b * ns:(b + 1) * ns].cpu().numpy(), None, noise_diag=noise.cpu().numpy(), jitter=1e-9)
+            got = Km[b * ns:(b + 1) * ns].cpu().numpy()
+            worst = max(worst, _ratio(got[il], ref[il], 1e-13, 1e-14))
+            assert np.allclose(got[il], ref[il], rtol=1e-13, atol=1e-14)   # (the tolerance of test_gram_matches_oracle)
+    print(f"[matern] gram_batch ns={ns} batch={batch}: worst error / tolerance = {worst:.3g}")
     Ls = np.tril(rng.standard_normal((batch * ns, ns)))
     Z = rng.standard_normal((ns, batch))
     M = rng.standard_normal((batch * ns, 1))
@@ -786,6 +867,7 @@ def test_kernel_input_gradients_match_oracle(env, m, p_cols, n1, n2):
     W = rng.standard_normal((n1, n2))
     Ws = rng.standard_normal((n1, n1))
     Ws = Ws + Ws.T
+    worst = _Worst(f"kernel_input_grads m={m} n1={n1} n2={n2}")
     for name, k in _kernels(m, p_cols).items():
         if name == "zero":
             continue
@@ -794,17 +876,93 @@ def test_kernel_input_gradients_match_oracle(env, m, p_cols, n1, n2):
         got = eng.kernel_input_grads(ck, to_dev(x1), to_dev(x2), to_dev(W)).cpu().numpy()
         ref = ok.kernel_input_grads(spec, x1, x2, W)
         scale = max(1.0, np.max(np.abs(ref)))
+        worst.see(name, np.max(np.abs(got - ref)) / (1e-11 * scale))
         assert np.max(np.abs(got - ref)) <= 1e-11 * scale, name
         lower = to_dev(np.tril(Ws) + np.triu(np.full((n1, n1), np.nan), 1))
         got = eng.kernel_input_grads(ck, to_dev(x1), None, lower, sym=True).cpu().numpy()
         ref = 2.0 * ok.kernel_input_grads(spec, x1, x1, Ws)
+        worst.see(name, np.max(np.abs(got - ref)) / (1e-11 * max(1.0, np.max(np.abs(ref)))))
         assert np.max(np.abs(got - ref)) <= 1e-11 * max(1.0, np.max(np.abs(ref))), name
+    worst.report()
+
+
+@pytest.mark.parametrize("m,p_cols", [(1, []), (2, [2]), (3, [3, 4, 5])])
+@pytest.mark.parametrize("n", [37, 130])
+def test_matern_gradients_at_coincident_points_match_oracle(env, m, p_cols, n):
+    """The r = 0 convention of nu = 1/2 (include/gpar_hip.h: dk/dr2 taken as 0 there) on the device, for every Matern entry of the
+    zoo: a third of the rows are copies of other rows, and the second argument of the rectangular pass shares rows with the first.
+    Parameter and input gradients must be finite and equal the oracle's sums, which leave the coincident pairs out
+    (tests/test_oracle.py pins those pair by pair); tolerances of the two tests above."""
+    torch, hip, dev, to_dev = env
+    from gpar_amd.engine import HipEngine
+    from gpar_amd.kernels import compile_kernel
+    from oracle import kernels as ok
+
+    eng = HipEngine()
+    width = m + (max(p_cols) - m + 1 if p_cols else 0)
+    rng = np.random.default_rng(7 * n + m)
+    x = rng.uniform(-1, 1, (n, width))
+    copies = rng.choice(n, n // 3, replace=False)
+    x[copies] = x[rng.choice(np.setdiff1d(np.arange(n), copies), copies.size)]
+    assert np.unique(x, axis=0).shape[0] < n
+    x2 = np.concatenate([x[: n // 2], rng.uniform(-1, 1, (9, width))])
+    Wfull = rng.standard_normal((n, n))
+    Wfull = Wfull + Wfull.T
+    Wdev = to_dev(np.tril(Wfull) + np.triu(np.full((n, n), np.nan), 1))
+    W = rng.standard_normal((n, x2.shape[0]))
+    worst = _Worst(f"coincident points m={m} n={n}")
+    for name, k in _kernels(m, p_cols).items():
+        if not name.startswith("matern"):
+            continue
+        ck = compile_kernel(k, width)
+        spec = ok.spec_to_dict(k.resolve(width))
+        got = eng.kernel_grads(ck, to_dev(x), Wdev)
+        ref = ok.kernel_grads(spec, x, Wfull)
+        scale = np.abs(Wfull).sum()
+        for t in range(len(ref["coef"])):
+            worst.see(name, abs(got["coef"][t] - ref["coef"][t]) / (1e-12 * scale))
+            assert abs(got["coef"][t] - ref["coef"][t]) <= 1e-12 * scale, (name, "coef", t)
+            for fi, (gf, rf) in enumerate(zip(got["factors"][t], ref["factors"][t])):
+                for key in ("scales", "periods"):
+                    if rf[key] is None:
+                        continue
+                    assert np.all(np.isfinite(gf[key])), (name, key, t, fi)
+                    worst.see(name, _ratio(gf[key], rf[key], 1e-10, 1e-12 * scale))
+                    assert np.allclose(gf[key], rf[key], rtol=1e-10, atol=1e-12 * scale), (name, key, t, fi)
+        got = eng.kernel_input_grads(ck, to_dev(x), to_dev(x2), to_dev(W)).cpu().numpy()
+        ref = ok.kernel_input_grads(spec, x, x2, W)
+        assert np.all(np.isfinite(got)), name
+        worst.see(name, np.max(np.abs(got - ref)) / (1e-11 * max(1.0, np.max(np.abs(ref)))))
+        assert np.max(np.abs(got - ref)) <= 1e-11 * max(1.0, np.max(np.abs(ref))), name
+        got = eng.kernel_input_grads(ck, to_dev(x), None, Wdev, sym=True).cpu().numpy()
+        ref = 2.0 * ok.kernel_input_grads(spec, x, x, Wfull)
+        assert np.all(np.isfinite(got)), name
+        worst.see(name, np.max(np.abs(got - ref)) / (1e-11 * max(1.0, np.max(np.abs(ref)))))
+        assert np.max(np.abs(got - ref)) <= 1e-11 * max(1.0, np.max(np.abs(ref))), name
+    worst.report()
 
 
 # ---- per-specification (run-time compiled) Gram kernels --------------------------------------------------------------------
 
+#: (name, GPARRegressor keywords, m, layer).  The first five are the families of the reference (gpar/regression.py:92-180); the Matern
+#: structures follow them (so the earlier test ids keep their cases): a narrow one (markov=2), nu = 1/2 with the locally periodic
+#: term, a wide one (42 feature dims: the 4 x 4 micro-tile form of the generated Gram kernel), and nu = 1/2 over zero columns.
+_JIT_SPECS = [
+    ("eq-lin-eq", dict(scale=0.5, linear=True, nonlinear=True, markov=2), 4, 7),
+    ("eq-only", dict(scale=0.5, linear=False), 2, 0),
+    ("per-rq-wide", dict(scale=0.5, per=True, rq=True, linear=True, nonlinear=True), 3, 15),
+    ("rq-inputlinear-const", dict(scale=0.7, rq=True, input_linear=True, linear=True, nonlinear=True), 2, 3),
+    ("markov0-constant-term", dict(linear=True, nonlinear=True, markov=0), 1, 2),
+    ("matern32-lin-matern32", dict(scale=0.5, linear=True, nonlinear=True, markov=2, matern=1.5), 4, 7),
+    ("matern12-per", dict(scale=0.5, per=True, linear=True, nonlinear=True, matern=0.5), 2, 3),
+    ("matern52-per-wide", dict(scale=0.5, per=True, linear=True, nonlinear=True, matern=2.5), 3, 15),
+    ("matern12-inputlinear-const", dict(scale=0.7, input_linear=True, linear=True, nonlinear=True, matern=0.5), 2, 3),
+    ("matern12-markov0-constant-term", dict(linear=True, nonlinear=True, markov=0, matern=0.5), 1, 2),
+]
+
+
 def _jit_cases():
-    """(name, kernel, width): the kernel families GPARRegressor builds (gpar/regression.py:92-180) at several widths."""
+    """(name, kernel, width): the kernel families GPARRegressor builds (gpar/regression.py:92-180, and `matern=`) at several widths."""
     from gpar_amd.regression import GPARRegressor, _construct_gpar
     from gpar_amd.engine import set_engine
     from oracle.engine import OracleEngine
@@ -812,13 +970,7 @@ def _jit_cases():
     previous = set_engine(OracleEngine())   # (only to instantiate the hyper-parameters of the host-side model objects)
     try:
         out = []
-        for name, kw, m, layer in [
-            ("eq-lin-eq", dict(scale=0.5, linear=True, nonlinear=True, markov=2), 4, 7),
-            ("eq-only", dict(scale=0.5, linear=False), 2, 0),
-            ("per-rq-wide", dict(scale=0.5, per=True, rq=True, linear=True, nonlinear=True), 3, 15),
-            ("rq-inputlinear-const", dict(scale=0.7, rq=True, input_linear=True, linear=True, nonlinear=True), 2, 3),
-            ("markov0-constant-term", dict(linear=True, nonlinear=True, markov=0), 1, 2),
-        ]:
+        for name, kw, m, layer in _JIT_SPECS:
             reg = GPARRegressor(**kw)
             f, _ = _construct_gpar(reg, reg.vs, m, layer + 1).layers[layer]()
             out.append((name, f.kernel, m + layer))
@@ -827,7 +979,7 @@ def _jit_cases():
         set_engine(previous)
 
 
-@pytest.mark.parametrize("case", range(5))
+@pytest.mark.parametrize("case", range(len(_JIT_SPECS)))
 def test_generated_gram_kernel_is_bit_identical_to_the_interpreter(case, monkeypatch):
     """The kernel compiled at run time for a layer's STRUCTURE (csrc/gram_jit.h, hiprtc) and the ahead-of-time interpreter
     (csrc/gram.h) share their arithmetic verbatim (csrc/gram_math.inc): every entry must agree to the last bit - symmetric
@@ -875,6 +1027,8 @@ def test_generated_gram_kernel_is_bit_identical_to_the_interpreter(case, monkeyp
     from oracle import kernels as ok
 
     want = ok.gram(ok.spec_to_dict(kernel.resolve(width)), x.cpu().numpy(), x2.cpu().numpy()) * rs.cpu().numpy()[:, None]
+    if name.startswith("matern"):
+        print(f"[matern] generated gram {name}: worst error / tolerance against the oracle = {_ratio(got[1].cpu().numpy(), want, 1e-13, 1e-15):.3g}")
     np.testing.assert_allclose(got[1].cpu().numpy(), want, rtol=1e-13, atol=1e-15)
 
 
@@ -921,7 +1075,7 @@ def test_gram_exponential_over_its_whole_range():
     assert K[-1, 0] == 0.0 and K[-2, 0] == 0.0 and K[-3, 0] >= 0.0
 
 
-@pytest.mark.parametrize("case", range(5))
+@pytest.mark.parametrize("case", range(len(_JIT_SPECS)))
 def test_generated_gradient_kernels_match_the_interpreter(case, monkeypatch):
     """The run-time compiled gradient passes (csrc/grad_jit.h) against the ahead-of-time interpreter (csrc/gram.h): the moment sums
     of the parameter-gradient pass with symmetric and rectangular weights (ragged sizes; with frequency derivatives where the
@@ -966,9 +1120,13 @@ def test_generated_gradient_kernels_match_the_interpreter(case, monkeypatch):
     got = run()
     lib.gpar_jit_stats(*[ctypes.byref(c) for c in cs])
     assert cs[1].value == failures, "a generated gradient kernel failed to compile"
+    worst = 0.0
     for a, b in zip(got, ref):
         scale = float(b.abs().max()) + 1e-300
+        worst = max(worst, float((a - b).abs().max()) / (1e-11 * scale))
         assert float((a - b).abs().max()) <= 1e-11 * scale, (name, float((a - b).abs().max()), scale)
+    if name.startswith("matern"):
+        print(f"[matern] generated gradients {name}: worst error / tolerance = {worst:.3g}")
 
 
 def _rank_deficient(n, ell, jitter, seed=0):

@@ -1,7 +1,9 @@
 """Matern kernels (nu = 1/2, 3/2, 5/2) through libgpar_hip.so on the MI355X.
 
 The reference is scikit-learn's `Matern` / `GaussianProcessRegressor` and the numpy restatement of the three kernels and their
-derivatives below (`_phi`, `_dphi_ds`); never the code under test, and not `oracle/`, which does not know these types.
+derivatives below (`_phi`, `_dphi_ds`); never the code under test, and not `oracle/` - which has its own restatement of these types,
+written independently of this file, and carries them through the parity suites (tests/test_hip_primitives.py, test_parity_gpu.py,
+test_fuzz_parity_gpu.py, the golden vectors).
 
     type         k(s), r = sqrt(s)                        dk/ds
     Matern 1/2   exp(-r)                                  -exp(-r) / (2 r), 0 where r = 0

@@ -70,6 +70,85 @@ def test_kernel_closed_forms():
     np.testing.assert_allclose(ok.gram(zero_w, x), np.full((2, 2), 0.6))
     np.testing.assert_allclose(ok.gram_diag(eq, x), [2.0, 2.0])
     np.testing.assert_allclose(ok.gram_diag(lin, x), [0.5, 6.5])
+    # the Matern kernels at r = sqrt(13) (include/gpar_hip.h), 1 on the diagonal and over zero columns
+    for kind, value in (("matern12", np.exp(-np.sqrt(13.0))), ("matern32", (1 + np.sqrt(39.0)) * np.exp(-np.sqrt(39.0))),
+                        ("matern52", (1 + np.sqrt(65.0) + 65.0 / 3.0) * np.exp(-np.sqrt(65.0)))):
+        mat = {"terms": [{"coef": 2.0, "factors": [_f(kind, [0, 1], [1.0, 2.0])]}]}
+        np.testing.assert_allclose(ok.gram(mat, x), [[2.0, 2 * value], [2 * value, 2.0]], rtol=1e-14)
+        np.testing.assert_allclose(ok.gram_diag(mat, x), [2.0, 2.0])
+        np.testing.assert_allclose(ok.gram({"terms": [{"coef": 0.6, "factors": [_f(kind, [], [])]}]}, x), np.full((2, 2), 0.6))
+    # a Matern factor on the periodic embedding: the same (sin, cos) features, r instead of r2; invariant under shifts by the period
+    r = np.sqrt(np.sum((emb(u) - emb(v)) ** 2))
+    for kind, value in (("matern12", np.exp(-r)), ("matern32", (1 + np.sqrt(3.0) * r) * np.exp(-np.sqrt(3.0) * r)),
+                        ("matern52", (1 + np.sqrt(5.0) * r + 5.0 * r * r / 3.0) * np.exp(-np.sqrt(5.0) * r))):
+        mper = {"terms": [{"coef": 1.0, "factors": [_f(kind, [0], [0.7, 1.3], periods=[2.0])]}]}
+        np.testing.assert_allclose(ok.gram(mper, np.array([[u]]), np.array([[v]])), [[value]], rtol=1e-14)
+        np.testing.assert_allclose(ok.gram(mper, np.array([[u]]), np.array([[v + 2.0 * 3]])), [[value]], rtol=1e-12)
+
+
+def test_unknown_types_raise_everywhere():
+    """No branch treats an unnamed factor type as RQ (or as anything else), and `matern` outside 0.5 / 1.5 / 2.5 is refused."""
+    from oracle import mp_ref
+    from oracle import torch_cpu as tc
+
+    x = np.array([[0.0, 1.0], [3.0, 5.0], [-1.0, 0.5]])
+    bad = {"terms": [{"coef": 1.0, "factors": [_f("matern99", [0, 1], [1.0, 2.0])]}]}
+    W = np.ones((3, 3))
+    for call in (lambda: ok.gram(bad, x), lambda: ok.gram_diag(bad, x), lambda: ok.kernel_grads(bad, x, W),
+                 lambda: ok.kernel_input_grads(bad, x, x, W), lambda: mp_ref.gram(bad, x.tolist()),
+                 lambda: tc.gram(bad, torch.as_tensor(x))):
+        with pytest.raises(ValueError, match="unknown factor type"):
+            call()
+    # the reference's CPU path has no Matern kernel: it refuses one rather than evaluating it as RQ with alpha = 0
+    with pytest.raises(ValueError, match="unknown factor type"):
+        tc.gram({"terms": [{"coef": 1.0, "factors": [_f("matern32", [0, 1], [1.0, 2.0])]}]}, torch.as_tensor(x))
+    hypers = {"0/input/var": 1.0, "0/input/scales": [1.0], "0/noise": 0.1}
+    for nu in (0.7, 3.5, True, "1.5"):
+        with pytest.raises((ValueError, TypeError)):
+            gpar_ref.layer_spec(hypers, 1, 0, dict(linear=False, matern=nu))
+    with pytest.raises(ValueError, match="exclude"):
+        gpar_ref.layer_spec(dict(hypers, **{"0/input/alpha": 1.0}), 1, 0, dict(linear=False, matern=1.5, rq=True))
+
+
+def test_layer_spec_follows_the_regressor_for_matern():
+    """config["matern"] selects the type of the two nonlinear factors and of nothing else (gpar_amd/regression.py: the locally
+    periodic term keeps its EQ factors), under the variable names of the EQ model."""
+    rng = np.random.default_rng(5)
+    config = dict(linear=True, nonlinear=True, per=True, input_linear=True)
+    for nu, kind in ((None, "eq"), (0.5, "matern12"), (1.5, "matern32"), (2.5, "matern52")):
+        cfg = config if nu is None else dict(config, matern=nu)
+        import importlib.util
+
+        s = importlib.util.spec_from_file_location("make_golden", os.path.join(os.path.dirname(GOLDEN), "make_golden.py"))
+        mod = importlib.util.module_from_spec(s)
+        s.loader.exec_module(mod)
+        hypers = mod.hypers_for(2, 2, cfg, rng)
+        assert set(hypers) == set(mod.hypers_for(2, 2, config, np.random.default_rng(0)))
+        spec, _ = gpar_ref.layer_spec(hypers, 2, 1, cfg)
+        types = [[f["type"] for f in t["factors"]] for t in spec["terms"]]
+        assert types == [[kind], ["eq", "eq"], ["linear"], [], ["linear"], [kind]]
+
+
+_MATERN_CONFIGS = [dict(linear=True, nonlinear=True, matern=0.5), dict(linear=True, nonlinear=True, matern=1.5, per=True, input_linear=True),
+                   dict(linear=True, nonlinear=True, matern=2.5), dict(linear=True, nonlinear=True, matern=0.5, per=True)]
+
+
+def _smallest_distance(spec, x1, x2=None):
+    """Smallest distance, over the stationary factors of `spec`, between two different points in the factor's own (scaled, embedded)
+    features.  nu = 1/2 has a kink at r = 0: a finite-difference stencil that reaches across it has no limit, so the tests below
+    assert that this is far above the stencil's reach."""
+    best = np.inf
+    for term in spec["terms"]:
+        for f in term["factors"]:
+            if f["type"] == "linear" or not len(f["cols"]):
+                continue
+            z1 = ok.features(f, x1)
+            z2 = z1 if x2 is None else ok.features(f, x2)
+            d = np.sqrt(np.sum((z1[:, None, :] - z2[None, :, :]) ** 2, axis=2))
+            if x2 is None:
+                d = d[~np.eye(d.shape[0], dtype=bool)]
+            best = min(best, float(np.min(d)))
+    return best
 
 
 def _random_layer(rng, config, m=2, pi=1, p=2):
@@ -83,7 +162,8 @@ def _random_layer(rng, config, m=2, pi=1, p=2):
     return gpar_ref.layer_spec(hypers, m, pi, config)[0]
 
 
-@pytest.mark.parametrize("config", [dict(linear=True, nonlinear=True), dict(linear=True, nonlinear=True, rq=True, per=True, input_linear=True)])
+@pytest.mark.parametrize("config", [dict(linear=True, nonlinear=True), dict(linear=True, nonlinear=True, rq=True, per=True, input_linear=True)]
+                         + _MATERN_CONFIGS)
 def test_engine_cholesky_route_equals_slogdet_route(config):
     from gpar_amd.engine import set_engine
     from gpar_amd.gp import GP, Obs, PseudoObs
@@ -147,7 +227,8 @@ def test_partial_cholesky_is_schur_complement():
     assert int(info) == 4
 
 
-@pytest.mark.parametrize("config", [dict(linear=True, nonlinear=True), dict(linear=True, nonlinear=True, rq=True, per=True, input_linear=True)])
+@pytest.mark.parametrize("config", [dict(linear=True, nonlinear=True), dict(linear=True, nonlinear=True, rq=True, per=True, input_linear=True)]
+                         + _MATERN_CONFIGS)
 def test_kernel_gradients_match_finite_differences(config):
     rng = np.random.default_rng(8)
     spec = _random_layer(rng, config)
@@ -156,6 +237,9 @@ def test_kernel_gradients_match_finite_differences(config):
     W = rng.standard_normal((n, n))
     W = W + W.T
     grads = ok.kernel_grads(spec, x, W)
+    h = 1e-6
+    # (a parameter step of h moves a feature by ~h |z| / s: four orders below the closest pair)
+    assert _smallest_distance(spec, x) > 1e4 * h
 
     def value(s):
         return 0.5 * np.sum(W * ok.gram(s, x))
@@ -173,7 +257,6 @@ def test_kernel_gradients_match_finite_differences(config):
             s["terms"][ti]["factors"][fi][key][idx] += delta
         return s
 
-    h = 1e-6
     for ti, term in enumerate(spec["terms"]):
         fd = (value(bump((ti, None, "coef", None), h)) - value(bump((ti, None, "coef", None), -h))) / (2 * h)
         assert abs(fd - grads["coef"][ti]) < 1e-6 * (1 + abs(fd))
@@ -282,7 +365,8 @@ def regressor_from_case(case):
     return reg
 
 
-@pytest.mark.parametrize("config", [dict(linear=True, nonlinear=True), dict(linear=True, nonlinear=True, rq=True, per=True, input_linear=True)])
+@pytest.mark.parametrize("config", [dict(linear=True, nonlinear=True), dict(linear=True, nonlinear=True, rq=True, per=True, input_linear=True)]
+                         + _MATERN_CONFIGS)
 def test_kernel_input_gradients_match_finite_differences(config):
     """oracle/kernels.kernel_input_grads (the reference for the device pass gram_input_grad_kernel): derivative of
     sum_ab W_ab k(x1_a, x2_b) with respect to every entry of x1, against central differences."""
@@ -292,6 +376,7 @@ def test_kernel_input_gradients_match_finite_differences(config):
     x1, x2 = rng.uniform(-1, 1, (7, m + pi)), rng.uniform(-1, 1, (5, m + pi))
     W = rng.standard_normal((7, 5))
     got = ok.kernel_input_grads(spec, x1, x2, W)
+    assert _smallest_distance(spec, x1, x2) > 1e4 * 1e-6   # the stencil below moves a point by 1e-6 (features: times omega / s, ~10)
     fd = np.zeros_like(x1)
     for a in range(x1.shape[0]):
         for c in range(x1.shape[1]):
@@ -300,3 +385,90 @@ def test_kernel_input_gradients_match_finite_differences(config):
                 xp[a, c] += sgn * 1e-6
                 fd[a, c] += sgn * np.sum(W * ok.gram(spec, xp, x2)) / 2e-6
     np.testing.assert_allclose(got, fd, rtol=1e-6, atol=1e-8)
+
+
+@pytest.mark.parametrize("kind", ["matern12", "matern32", "matern52"])
+def test_matern_gradients_at_coincident_points(kind):
+    """The r = 0 convention (include/gpar_hip.h): dk/dr2 of nu = 1/2 is singular at r = 0 and every gradient takes it as 0 there.
+    With duplicated rows (and the diagonal, always) the gradients must be finite and equal the sums over the pairs that do not
+    coincide, written out pair by pair here; they also equal central differences in the scales and the period, because a coincident
+    pair has k = 1 for every value of those parameters (the kink is in the points, not in the parameters)."""
+    rng = np.random.default_rng(17)
+    n = 8
+    x = rng.uniform(-1, 1, (n, 2))
+    x[5], x[6], x[2] = x[0], x[1], x[0]
+    scales, pscales, period, coef = [0.7, 1.9], [0.8, 1.4], 1.3, 1.6
+    spec = {"terms": [{"coef": coef, "factors": [_f(kind, [0, 1], scales)]},
+                      {"coef": 0.5, "factors": [_f(kind, [1], pscales, periods=[period])]}]}
+    W = rng.standard_normal((n, n))
+    W = W + W.T
+    grads = ok.kernel_grads(spec, x, W)
+
+    def dk_dr2(r):
+        if kind == "matern12":
+            return -np.exp(-r) / (2 * r)
+        if kind == "matern32":
+            return -1.5 * np.exp(-np.sqrt(3.0) * r)
+        return -(5.0 / 6.0) * (1 + np.sqrt(5.0) * r) * np.exp(-np.sqrt(5.0) * r)
+
+    expect, coincident = np.zeros(2), 0
+    for a in range(n):
+        for b in range(n):
+            d = (x[a] - x[b]) / np.array(scales)
+            r = np.sqrt(np.sum(d * d))
+            if r == 0.0:
+                coincident += 1
+                continue
+            expect += 0.5 * W[a, b] * coef * dk_dr2(r) * (-2.0 * d * d / np.array(scales))
+    assert coincident == n + 2 * 3 + 2   # the diagonal, the triple (0, 2, 5) and the pair (1, 6)
+    got = grads["factors"][0][0]["scales"]
+    assert np.all(np.isfinite(got))
+    np.testing.assert_allclose(got, expect, rtol=1e-12)
+    for g in (grads["factors"][1][0]["scales"], grads["factors"][1][0]["periods"]):
+        assert np.all(np.isfinite(g))
+
+    import copy
+
+    h = 1e-6
+    for ti, key, idx in [(0, "scales", 0), (0, "scales", 1), (1, "scales", 0), (1, "scales", 1), (1, "periods", 0)]:
+        up, dn = copy.deepcopy(spec), copy.deepcopy(spec)
+        up["terms"][ti]["factors"][0][key][idx] += h
+        dn["terms"][ti]["factors"][0][key][idx] -= h
+        fd = 0.5 * np.sum(W * (ok.gram(up, x) - ok.gram(dn, x))) / (2 * h)
+        assert abs(fd - grads["factors"][ti][0][key][idx]) < 1e-5 * (1 + abs(fd)), (ti, key, idx)
+
+    # gradients with respect to the points: x1 shares rows with x2; the coincident pairs drop out of the row sums
+    x2 = x[:5]
+    V = rng.standard_normal((n, 5))
+    one = {"terms": [spec["terms"][0]]}
+    got = ok.kernel_input_grads(one, x, x2, V)
+    expect = np.zeros_like(x)
+    for a in range(n):
+        for b in range(5):
+            d = (x[a] - x2[b]) / np.array(scales)
+            r = np.sqrt(np.sum(d * d))
+            if r > 0.0:
+                expect[a] += V[a, b] * coef * dk_dr2(r) * 2.0 * d / np.array(scales)
+    assert np.all(np.isfinite(got))
+    np.testing.assert_allclose(got, expect, rtol=1e-12, atol=1e-15)
+    assert np.all(np.isfinite(ok.kernel_input_grads(spec, x, x2, V)))
+
+
+@pytest.mark.parametrize("name", ["matern12-weights", "matern32-markov1", "matern52-per-inputlinear", "matern12-missing-impute",
+                                  "matern32-inducing"])
+def test_matern_config_is_not_silently_evaluated_as_eq(name, oracle_engine):
+    """oracle/gpar_ref.layer_spec reads config["matern"]: the stand-alone numpy GPAR handed the `model_config` of a Matern regressor
+    (i) equals the product's host algebra on the oracle engine and (ii) differs, far beyond rounding, from the same call with
+    `matern` removed from the configuration - the value of the EQ model, which layer_spec once returned for every Matern model."""
+    case = next(c for c in _load_golden()["gpar_logpdf"] if c["name"] == name)
+    x, y = np.array(case["x"]), _nan_array(case["y"])
+    w = None if case["w"] is None else np.array(case["w"])
+    x_ind = None if case.get("x_ind") is None else np.array(case["x_ind"])
+    reg = regressor_from_case(case)
+    assert reg.model_config["matern"] == case["config"]["matern"]
+    kw = dict(impute=case["impute"], replace=case["replace"], x_ind=x_ind)
+    ref = gpar_ref.gpar_logpdf(x, y, w, case["hypers"], reg.model_config, **kw)
+    got = float(reg.logpdf(x, y, w))
+    assert abs(got - ref) <= 1e-9 * abs(ref), (got, ref)
+    as_eq = gpar_ref.gpar_logpdf(x, y, w, case["hypers"], {k: v for k, v in reg.model_config.items() if k != "matern"}, **kw)
+    assert abs(as_eq - ref) > 1e-3 * abs(ref), (as_eq, ref)

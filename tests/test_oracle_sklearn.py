@@ -9,6 +9,10 @@ published definitions the reference's kernels follow (Rasmussen & Williams 2006,
     mlkernels Linear()                   = <x, x'>                                = sklearn DotProduct(sigma_0=0)
     mlkernels EQ().stretch(s).periodic(p) = exp(-2 sin^2(pi d / p) / s^2)         = sklearn ExpSineSquared(s, p)
 
+and, for the Matern kernels that this project adds to the reference's set (oracle/kernels.py, include/gpar_hip.h; R&W eq. 4.14-4.17),
+
+    matern12 / matern32 / matern52 .stretch(s)                                    = sklearn Matern(length_scale=s, nu=0.5 / 1.5 / 2.5)
+
 so agreement of Gram matrices, log marginal likelihoods and posterior moments to ~1e-10 removes "the oracle and the
 product share a misreading of the formulas" as a failure mode.  Sums, products and constant scalings are exercised
 because GPAR's layer kernels are sums of products (gpar/regression.py:92-180 in the reference).
@@ -20,7 +24,7 @@ from oracle import gp_ref
 from oracle import kernels as ok
 
 sk_gp = pytest.importorskip("sklearn.gaussian_process")
-from sklearn.gaussian_process.kernels import RBF, ConstantKernel, DotProduct, ExpSineSquared, RationalQuadratic  # noqa: E402
+from sklearn.gaussian_process.kernels import RBF, ConstantKernel, DotProduct, ExpSineSquared, Matern, RationalQuadratic  # noqa: E402
 
 
 def _f(type, cols, scales, periods=None, alpha=0.0):
@@ -43,7 +47,25 @@ def _cases():
         ]
     }
     prod_sk = ConstantKernel(1.2) * ExpSineSquared(1.1, 0.7) * RationalQuadratic(0.5, 2.0) + ConstantKernel(0.3) * RBF(0.25)
-    return [("sum_eq_rq_linear", sum_spec, sum_sk, 2), ("periodic_times_rq_plus_eq", prod_spec, prod_sk, 1)]
+    cases = [("sum_eq_rq_linear", sum_spec, sum_sk, 2), ("periodic_times_rq_plus_eq", prod_spec, prod_sk, 1)]
+    # the Matern kernels: each smoothness at one and at three (anisotropic) feature dims, and one sum with a constant and a linear term
+    for kind, nu in (("matern12", 0.5), ("matern32", 1.5), ("matern52", 2.5)):
+        cases.append((f"{kind}_dz1", {"terms": [{"coef": 1.3, "factors": [_f(kind, [0], [0.45])]}]}, ConstantKernel(1.3) * Matern(0.45, nu=nu), 1))
+        scales = [0.4, 1.1, 2.3]
+        cases.append((f"{kind}_dz3_anisotropic", {"terms": [{"coef": 0.9, "factors": [_f(kind, [0, 1, 2], scales)]}]},
+                      ConstantKernel(0.9) * Matern(scales, nu=nu), 3))
+    matern_sum_spec = {
+        "terms": [
+            {"coef": 1.4, "factors": [_f("matern32", [0, 1], [0.7, 1.6])]},
+            {"coef": 0.6, "factors": [_f("matern12", [0, 1], [1.2, 0.5])]},
+            {"coef": 0.5, "factors": [_f("linear", [0, 1], [1.0, 1.0])]},
+            {"coef": 0.25, "factors": []},
+        ]
+    }
+    matern_sum_sk = (ConstantKernel(1.4) * Matern([0.7, 1.6], nu=1.5) + ConstantKernel(0.6) * Matern([1.2, 0.5], nu=0.5)
+                     + ConstantKernel(0.5) * DotProduct(0.0) + ConstantKernel(0.25))
+    cases.append(("matern_sum_linear_const", matern_sum_spec, matern_sum_sk, 2))
+    return cases
 
 
 @pytest.mark.parametrize("name,spec,sk_kernel,m", _cases(), ids=[c[0] for c in _cases()])

@@ -112,7 +112,17 @@ CONFIGS = {
     "C5-shape-per-rq": (dict(scale=0.5, per=True, rq=True, linear=True, nonlinear=True, noise=0.1), 200, 3, 5, 0.0),
     "missing-impute": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, impute=True), 257, 2, 3, 0.2),
     "replace": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, impute=True, replace=True), 190, 2, 3, 0.1),
+    # the Matern kernels (`matern=`): dense with a markov window, inducing points, missing data + impute
+    "matern32-markov2": (dict(scale=0.5, linear=True, nonlinear=True, markov=2, noise=0.1, matern=1.5), 300, 3, 6, 0.0),
+    "matern52-inducing": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, matern=2.5, x_ind=np.random.default_rng(9).uniform(0, 1, (48, 4))), 400, 4, 3, 0.0),
+    "matern12-missing-impute": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, impute=True, matern=0.5), 257, 2, 3, 0.2),
 }
+
+
+def _report(label, name, **ratios):
+    """The error / tolerance ratios of the Matern cases (pytest -s shows them)."""
+    if "matern" in str(name):
+        print(f"[matern] {label} {name}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
@@ -133,6 +143,9 @@ def test_logpdf_condition_predict_match_oracle(name):
 
     ref = _on("oracle", run)
     got = _on("hip", run)
+    _report("logpdf / condition / sample", name, prior=abs(got[0] - ref[0]) / (1e-10 * abs(ref[0])),
+            posterior=abs(got[1] - ref[1]) / (1e-8 * max(1.0, abs(ref[1]))),
+            samples=float(np.max(np.abs(got[2] - ref[2]) / (1e-7 + 1e-6 * np.abs(ref[2])))))
     assert abs(got[0] - ref[0]) <= 1e-10 * abs(ref[0]), (got[0], ref[0])
     assert abs(got[1] - ref[1]) <= 1e-8 * max(1.0, abs(ref[1])), (got[1], ref[1])
     # Latent samples are mean + chol(cov + 1e-12 I) z.  Where the test inputs are dense relative to the length scale
@@ -158,6 +171,8 @@ def test_logpdf_matches_the_independent_oracle_route(name, hip):
     want = gpar_ref.gpar_logpdf(x, y, None, reg.get_variables(), reg.model_config, impute=reg.impute, replace=reg.replace,
                                 x_ind=kw.get("x_ind"))
     tol = 1e-10 if kw.get("x_ind") is None else 1e-8  # inducing-point chains go through K_zz^-1 (jitter-conditioned)
+    _report("independent restatement", name, prior=abs(got - want) / (tol * abs(want)))
+    assert reg.model_config.get("matern") == kw.get("matern")
     assert abs(got - want) <= tol * abs(want), (got, want)
 
 
@@ -166,7 +181,10 @@ def test_logpdf_matches_the_independent_oracle_route(name, hip):
     dict(impute=False),
     dict(impute=True, replace=True),
     dict(impute=True, x_ind=np.random.default_rng(4).uniform(0, 1, (40, 2))),
-], ids=["impute", "no-impute", "replace", "inducing"])
+    dict(impute=True, matern=1.5),
+    dict(impute=True, replace=True, matern=0.5),
+    dict(impute=True, x_ind=np.random.default_rng(4).uniform(0, 1, (40, 2)), matern=2.5),
+], ids=["impute", "no-impute", "replace", "inducing", "matern32-impute", "matern12-replace", "matern52-inducing"])
 def test_sampled_imputations_match_the_oracle_on_a_shared_stream(kw):
     """`logpdf(sample_missing=True)` (reference gpar/model.py:229-237) with holes that are NOT closed downwards, n = 300, p = 4:
     the device draws its imputations from Philox stream (seed, call index), which the oracle restates bit for bit - same seed,
@@ -189,6 +207,9 @@ def test_sampled_imputations_match_the_oracle_on_a_shared_stream(kw):
     independent = gpar_ref.gpar_logpdf(x, y, None, hypers, config, impute=kw.get("impute", True), replace=kw.get("replace", False),
                                        x_ind=kw.get("x_ind"), sample_missing=True, seed=41)
     tol = 1e-8 if kw.get("x_ind") is None else 1e-7
+    _report("sampled imputations", "matern" if "matern" in kw else "", nu=kw.get("matern", 0.0), engine=abs(got - ref) / (tol * abs(ref)),
+            restatement=abs(got - independent) / ((tol if kw.get("x_ind") is None else 1e-5) * abs(independent)))
+    assert config.get("matern") == kw.get("matern")
     assert abs(got - ref) <= tol * abs(ref), (got, ref)
     # (inducing points: the independent route solves against K_zz + 1e-12 I directly, the product through its Cholesky factor -
     # with 40 random inducing inputs at scale 0.5 that matrix is conditioned ~1e9, and the drawn imputations inherit the difference)
@@ -311,8 +332,13 @@ def test_linear_output_dependence_samples_with_one_shared_solve(monkeypatch, kw,
         assert err < (1e-4 if latent else 1e-10), err
 
 
-@pytest.mark.parametrize("n,p,weights", [(700, 4, False), (512, 3, True), (1300, 5, True), (40, 70, True), (2100, 2, False)])
-def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, weights):
+_LOCKSTEP_ONE_CALL = [(700, 4, False, None), (512, 3, True, None), (1300, 5, True, None), (40, 70, True, None), (2100, 2, False, None),
+                      (512, 3, True, 1.5), (1300, 4, False, 2.5), (40, 70, True, 0.5), (300, 5, True, 0.5)]
+
+
+@pytest.mark.parametrize("n,p,weights,matern", _LOCKSTEP_ONE_CALL,
+                         ids=[f"{n}-{p}-{w}" + ("" if nu is None else f"-matern{nu}") for n, p, w, nu in _LOCKSTEP_ONE_CALL])
+def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, weights, matern):
     """gpar_logpdf_lockstep (ABI v5): the whole lock-step evaluation in one library call - no design matrix, noise tensor or
     observation object per layer - returns bit for bit what the per-layer build calls return (GPAR_ONE_CALL=0), with weights
     (noise / w divided on the device), with more layers than one launch of the preparing kernel takes (70 > 64), in chunks,
@@ -329,7 +355,7 @@ def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, w
 
     def run():
         eng = get_engine()
-        kw = dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3 if p > 6 else None, normalise_y=False)
+        kw = dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3 if p > 6 else None, normalise_y=False, matern=matern)
         out = {}
         for mode in ["1", "0"]:
             monkeypatch.setenv("GPAR_ONE_CALL", mode)
@@ -348,7 +374,8 @@ def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, w
     assert got["1"] == got["0"] and got["1last"] == got["0last"] and got["1chunks"] == got["0chunks"], got
     if n <= 600:
         ref = _on("oracle", lambda: float(GPARRegressor(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3 if p > 6 else None,
-                                                        normalise_y=False).logpdf(x, y, w)))
+                                                        normalise_y=False, matern=matern).logpdf(x, y, w)))
+        _report("one-call lock-step", f"matern{matern}" if matern else "", n=n, p=p, value=abs(got["1"] - ref) / (1e-9 * abs(ref)))
         assert abs(got["1"] - ref) <= 1e-9 * abs(ref), (got, ref)
 
 
@@ -533,7 +560,12 @@ def test_gradient_matches_oracle(hip):
     dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24)),
     dict(impute=True, replace=True),
     dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), sparse_method="fitc"),
-], ids=["impute+replace+inducing", "impute+replace", "impute+replace+fitc"])
+    dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), matern=1.5),
+    dict(impute=True, replace=True, matern=0.5),
+    dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), sparse_method="fitc", matern=2.5),
+    dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), sparse_method="dtc", matern=0.5),
+], ids=["impute+replace+inducing", "impute+replace", "impute+replace+fitc", "matern32+impute+replace+inducing", "matern12+impute+replace",
+        "matern52+impute+replace+fitc", "matern12+impute+replace+dtc"])
 def test_joint_gradient_matches_oracle(hip, kw):
     """The JOINT objective of fit(fix=False) (reference gpar/regression.py:447-456) in regimes where posterior means are fed
     forward - imputed AND replaced columns, inducing inputs extended layer by layer: d / d(every hyper-parameter) through
@@ -548,7 +580,8 @@ def test_joint_gradient_matches_oracle(hip, kw):
     y[0] = [0.1, 0.9, 0.0]
 
     def grads():
-        reg = GPARRegressor(scale=0.3, linear=True, linear_scale=3.0, nonlinear=True, rq=True, noise=0.05, normalise_y=False, **kw)
+        # (RQ kernels, or - `matern` excludes rq - the Matern kernel of the row)
+        reg = GPARRegressor(scale=0.3, linear=True, linear_scale=3.0, nonlinear=True, rq="matern" not in kw, noise=0.05, normalise_y=False, **kw)
         with torch.no_grad():
             reg.logpdf(x, y)
         reg.vs.requires_grad(True)
@@ -557,6 +590,8 @@ def test_joint_gradient_matches_oracle(hip, kw):
 
     ref, got = _on("oracle", grads), _on("hip", grads)
     assert np.max(np.abs(ref)) > 1e-2
+    _report("joint gradient", "matern" if "matern" in kw else "", nu=kw.get("matern", 0.0),
+            gradient=float(np.max(np.abs(got - ref) / (1e-7 * np.max(np.abs(ref)) + 1e-6 * np.abs(ref)))))
     np.testing.assert_allclose(got, ref, rtol=1e-6, atol=1e-7 * np.max(np.abs(ref)))
 
 
@@ -779,7 +814,9 @@ def test_nan_pattern_of_device_outputs_is_remembered_until_they_change(hip):
 
 
 @pytest.mark.parametrize("kw,n", [(dict(linear=True, nonlinear=True), 500), (dict(per=True, rq=True, linear=True, nonlinear=True), 300),
-                                  (dict(linear=True, nonlinear=False, input_linear=True), 1300)])
+                                  (dict(linear=True, nonlinear=False, input_linear=True), 1300),
+                                  (dict(linear=True, nonlinear=True, matern=0.5), 500), (dict(per=True, linear=True, nonlinear=True, matern=2.5), 300),
+                                  (dict(linear=True, nonlinear=True, input_linear=True, matern=1.5), 1300)])
 def test_one_call_objective_and_gradient_return_the_same_bits(monkeypatch, kw, n):
     """gpar_logpdf_dense_grad (ABI v5): a layer's training objective and the ingredients of its gradient in one library call -
     the launches of the separate entry points in their order, so value and gradient are bit for bit those of the two-step route
