@@ -1,7 +1,7 @@
 // Blocked right-looking Cholesky (partial), triangular solves.
 //
 // Two-level blocking: outer panels of NBO = 512 columns, each factored by ONE persistent fused kernel (panel.h), whose
-// trailing update is a SYRK-shaped MFMA GEMM with K = NBO (K = 2 NBO while panels are paired: potrf_run); the next
+// trailing update is a SYRK-shaped MFMA GEMM with K = NBO (K = 3 NBO while panels are grouped: potrf_schedule.h); the next
 // panel runs under that update on a side stream (look-ahead).  The leaf kernels below serve ragged tails, unaligned
 // inputs and the GPAR_POTRF_FUSED=0 fallback - inner steps of 64 columns inside a panel:
 //     potrf_diag64   one wave factors the 64 x 64 diagonal block: lane i owns row i in registers, the
@@ -11,6 +11,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_f64.h"
+#include "potrf_schedule.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -19,7 +20,7 @@
 
 namespace gpar {
 
-constexpr int POTRF_NBI = 64;   // inner block (diag / strip width)
+static_assert(POTRF_TILE_ROWS == GEMM_BM, "the tail split counts the tile rows of the matrix-core update");
 
 // ---------------------------------------------------------------------------------------------------
 // Panel kernels.  Both are written as SHORT LOOPS over 8-wide sub-blocks with the matrix resident in LDS and
@@ -306,64 +307,12 @@ __global__ __launch_bounds__(256) void chol_spread_kernel(const double* __restri
     }
 }
 
-// ---- blocking policy (overridable for experiments: GPAR_POTRF_NBO / GPAR_POTRF_NBM / GPAR_POTRF_LOOKAHEAD) ----------
-struct PotrfPolicy {
-    int nbo;        // top-level panel width: K of the trailing SYRK
-    int nbm;        // mid-level width inside a panel
-    int lookahead;  // overlap panel k+1 with the trailing update of panel k on a second stream
-    int split;      // factor the diagonal block first, then solve the rows below (see potrf_panel_split)
-    int fused;      // factor each top-level panel with the persistent fused kernel (panel.h)
-    int pair_rows;  // panels with at least this many rows left are factored in groups (one rank-group*nbo trailing update)
-    int group;      // panels per group
-};
-
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-static PotrfPolicy potrf_policy(int N) {
-    PotrfPolicy p;
-    // wider top-level panels amortise the read-modify-write of the trailing matrix over more flops (measured SYRK
-    // rate at n = 16384: K = 128 31, K = 256 42, K = 512 53 TFLOP/s); the panel itself is factored recursively
-    // with the fused panel kernel (panel.h) the panel is cheap, so the widest panel it supports wins at every size
-    // (measured n = 1024 .. 16384, profiles/r01_potrf_nbo_sweep.txt); the unfused fallback prefers narrower ones
-    p.fused = env_int("GPAR_POTRF_FUSED", 1);
-    if (p.fused) p.nbo = 512;
-    else if (N >= 12288) p.nbo = 512;
-    else if (N >= 6144) p.nbo = 256;
-    else if (N >= 1536) p.nbo = 128;
-    else p.nbo = 64;
-    p.nbm = p.nbo >= 512 ? 128 : 64;
-    // Look-ahead: the fused panel kernel of panel k+1 (70.8 KB LDS: fits on a CU beside one SYRK workgroup) runs on
-    // the caller's stream under the trailing update of panel k on a low-priority side stream.  Pays once the
-    // trailing updates are long enough to hide it (measured with half-tile workgroups for the small launches: n = 5120
-    // 3.12 -> 2.97 ms, 6144 4.06 -> 3.81, 8192 6.75 -> 5.98; a wash at 4096, a loss at 3072).  The unfused fallback keeps
-    // it off (its small kernels starve behind the SYRK).
-    // (round 4, with the small look-ahead update kernel and two panels per launch: n = 3072 1.152 -> 1.097 ms, 4096 1.767 -> 1.631, 4600
-    // 2.248 -> 1.96, a wash at 2048: profiles/r04_exp_potrf_fuse2.txt)
-    p.lookahead = (p.fused && N >= 2560) ? 1 : 0;
-    p.nbo = env_int("GPAR_POTRF_NBO", p.nbo);
-    p.nbm = env_int("GPAR_POTRF_NBM", p.nbm);
-    p.lookahead = env_int("GPAR_POTRF_LOOKAHEAD", p.lookahead);
-    p.split = env_int("GPAR_POTRF_SPLIT", 0);
-    // n = 8192 measured slower grouped (5.38 vs 5.19 ms alone).  From N = 12288 on panels stay grouped until 6144 rows are left:
-    // with two factorisations in flight (the pipelined C3 evaluation) the longer serial stretch hides under the other stream's
-    // updates, 197.9 -> 194.9 ms per evaluation; alone it costs 0.5 % at n = 16384 (tools/exp_pair_rows.sh).  The rule depends
-    // on the size only, so that a factorisation returns the same bits whatever runs beside it.
-    p.pair_rows = env_int("GPAR_POTRF_PAIR_ROWS", N >= 12288 ? 6144 : 9216);
-    p.group = env_int("GPAR_POTRF_GROUP", 3);
-    if (p.nbo < 64) p.nbo = 64;
-    if (p.nbm < 64) p.nbm = 64;
-    return p;
-}
-
 struct PotrfCtx {
     double* A;
     int N, lda;
     double* logdet;
     int* info;
-    int nbm;
+    const PotrfPolicy* pol;  // the call's policy (potrf_policy)
     int batch = 1;           // lock-step factorisation of `batch` matrices (matrix b at A + b * batch_a): the trailing updates
     long long batch_a = 0;   // are batched launches
 };
@@ -371,7 +320,6 @@ struct PotrfCtx {
 // The trailing update when only a few rows are left - the augmented rows under the last panel: [y^T, 0] of the log marginal
 // likelihood, whose corner becomes -|L^-1 y|^2 - one wave per stored element (i, j), j <= i: lanes stride K, butterfly sum.
 // A 64 x 64 tile of the GEMM kernel for ONE element is all latency (42 us per evaluation at every size; this: ~4 us).
-constexpr int POTRF_SMALL_ROWS = 16;
 // (org: first row / column of the updated block; the K columns [k0, k0 + K) of its rows are the operand)
 __global__ __launch_bounds__(64) void potrf_small_update_kernel(double* __restrict__ A, int lda, int org, int k0, int K, int rows, int cols, long long batch_a) {
     const int i = blockIdx.x / cols, j = blockIdx.x - i * cols;
@@ -392,7 +340,7 @@ __global__ __launch_bounds__(64) void potrf_small_update_kernel(double* __restri
     if (threadIdx.x == 0) A[(size_t)(org + i) * lda + org + j] -= s;
 }
 
-// The companion of a matrix-core update that leaves the augmented rows out (potrf_run, "tail split"): the same rank-K update for
+// The companion of a matrix-core update that leaves the augmented rows out (potrf_exec, "tail split"): the same rank-K update for
 // the T <= 4 rows [r0, r0 + T) below the factored part,
 //     A[r0 + t, j] -= A[r0 + t, k0:k0 + K) . A[j, k0:k0 + K)     for j in [c0, c1), j <= r0 + t.
 // A 128 x 128 tile of the GEMM kernel per 128 columns for these few rows runs every MFMA of a full tile and stores one row of it.
@@ -487,12 +435,36 @@ static int potrf_tail_update(double* A, int N, int lda, int batch, long long bat
     return 0;
 }
 
-// `row_end` > 0: the update stops at that row (the augmented rows below it go to potrf_tail_update: potrf_run's tail split).
-static int potrf_gemm_update(const PotrfCtx& c, int k0, int kend, int col_end, hipStream_t stream, int role = 0, int row_end = 0) {
-    // A[kend:N, kend:col_end] -= A[kend:N, k0:kend] A[kend:col_end, k0:kend]^T   (lower part only)
-    const int rows = (row_end > 0 ? row_end : c.N) - kend, cols = col_end - kend;
+// (`rows`: the rows of the update about to be launched.  An update of at most POTRF_SMALL_ROWS rows - the augmented row once the last
+// panel is next - is the one-wave kernel, not the matrix-core update: it is not counted, so that `launches` equals the dispatches of
+// gemm_f64_kernel<false, true, 1, *> a kernel trace of the same evaluation shows.)
+static void prof_begin(const PotrfPolicy& pol, hipStream_t s, bool& active, int rows) {
+    active = g_prof.on && g_prof.nev < ProfileState::MAXEV && !(rows <= POTRF_SMALL_ROWS && pol.small_update);
+    if (!active) return;
+    if (!g_prof.created) {
+        for (int i = 0; i < ProfileState::MAXEV; ++i)
+            if (hipEventCreate(&g_prof.ev[i][0]) != hipSuccess || hipEventCreate(&g_prof.ev[i][1]) != hipSuccess) { active = false; return; }
+        g_prof.created = true;
+    }
+    GPAR_HIP_IGNORE(hipEventRecord(g_prof.ev[g_prof.nev][0], s));
+}
+
+static void prof_end(hipStream_t s, bool active, int rows, int cols, int kb) {
+    if (!active) return;
+    GPAR_HIP_IGNORE(hipEventRecord(g_prof.ev[g_prof.nev][1], s));
+    g_prof.shape[g_prof.nev][0] = rows; g_prof.shape[g_prof.nev][1] = cols; g_prof.shape[g_prof.nev][2] = kb;
+    g_prof.nev++;
+    g_prof.launches++;
+    // algorithmic flops of the lower-trapezoid rank-kb update (SURVEY 8d): 2 * kb per stored element
+    g_prof.flops += 2.0 * (double)kb * ((double)cols * ((double)cols + 1.0) * 0.5 + (double)(rows - cols) * (double)cols);
+}
+
+// A[kend:row_end, kend:col_end] -= A[kend:row_end, k0:kend] A[kend:col_end, k0:kend]^T   (lower part only).  `row_end` is N, or nf
+// where the augmented rows below it go to potrf_tail_update (the tail split).
+static int potrf_gemm_update(const PotrfCtx& c, int k0, int kend, int col_end, hipStream_t stream, int role, int row_end) {
+    const int rows = row_end - kend, cols = col_end - kend;
     if (rows <= 0 || cols <= 0) return 0;
-    if (rows <= POTRF_SMALL_ROWS && env_int("GPAR_POTRF_SMALL_UPDATE", 1)) {
+    if (rows <= POTRF_SMALL_ROWS && c.pol->small_update) {
         hipLaunchKernelGGL(potrf_small_update_kernel, dim3(rows * cols, c.batch), dim3(64), 0, stream, c.A, c.lda, kend, k0, kend - k0, rows, cols, c.batch_a);
         return 0;
     }
@@ -501,43 +473,34 @@ static int potrf_gemm_update(const PotrfCtx& c, int k0, int kend, int col_end, h
                        GPAR_GEMM_C_LOWER, stream, role, c.batch, c.batch_a, c.batch_a, c.batch_a);
 }
 
-static int potrf_la_update_small(double* A, int N, int lda, int k0, int kend, int ncols, hipStream_t stream, int batch, long long batch_a);   // panel2.h
-
-// Does the update of the NEXT panel's columns [kend, la_end) take the one-tile-per-workgroup kernel (panel2.h) instead of the GEMM?
-// While it has at most GPAR_POTRF_LA_SMALL_TILES 64 x 64 tiles over the whole batch: then its duration is one tile's, and the
-// small kernel's tile is several times shorter.  The rule looks at the geometry only - never at the look-ahead setting - so that a
-// factorisation returns the same bits with and without look-ahead (potrf_run splits its single update accordingly).
-static bool potrf_la_is_small(const PotrfCtx& c, int k0, int kend, int la_end) {
-    const int cols = la_end - kend, K = kend - k0;
-    if (cols <= 0 || cols % 64 != 0 || K <= 0 || K % 64 != 0 || (c.lda & 1) || !gpar_aligned16(c.A) || (c.batch_a & 1) || (k0 & 1) || c.N - kend <= POTRF_SMALL_ROWS)
-        return false;
-    const int nc = cols / 64, tr = (c.N - kend + 63) / 64;
-    if (tr < nc) return false;
-    const long long tiles = ((long long)nc * (nc + 1) / 2 + (long long)(tr - nc) * nc) * c.batch;
-    // behind a fused pair of panels (K >= 1024, potrf_group_kernel) a tile is 16 chunks and the alternative a K = 1024 GEMM tile of
-    // ~200 us: several rounds of small tiles still win
-    if (K >= 1024) return tiles <= env_int("GPAR_POTRF_LA_SMALL_TILES2", 2048);
-    return tiles <= env_int("GPAR_POTRF_LA_SMALL_TILES", 512);
+// The update of a step's trailing columns [kend, col_end) by the panels [k0, kend), as part of the trailing update (role 1, one
+// profile event), and - where it stops at row_end = nf - its companion for the augmented rows right behind it: the next panel reads
+// those entries.
+static int potrf_slice_update(const PotrfCtx& c, int nf, int k0, int kend, int col_end, int row_end, hipStream_t stream) {
+    bool pa;
+    prof_begin(*c.pol, stream, pa, c.N - kend);
+    int rc = potrf_gemm_update(c, k0, kend, col_end, stream, 1, row_end);
+    prof_end(stream, pa, c.N - kend, col_end - kend, (kend - k0) * c.batch);
+    if (!rc && row_end < c.N) rc = potrf_tail_update(c.A, c.N, c.lda, c.batch, c.batch_a, nf, k0, kend, kend, col_end, stream);
+    return rc;
 }
 
-// The update of the next panel's columns by whichever kernel the rule picks.
-static int potrf_la_update(const PotrfCtx& c, int k0, int kend, int la_end, hipStream_t stream) {
-    if (potrf_la_is_small(c, k0, kend, la_end)) return potrf_la_update_small(c.A, c.N, c.lda, k0, kend, la_end - kend, stream, c.batch, c.batch_a);
-    return potrf_gemm_update(c, k0, kend, la_end, stream, 1);
-}
-
-// Everything to the right of the next step's columns: A[from:N, from:N] -= P P^T (lower), P = A[from:N, k0:kend).  A handful of rows
-// (the augmented row once the last panel is next) by the one-wave kernel, else the batched GEMM.
-static int potrf_rest_update(const PotrfCtx& c, int k0, int kend, int from, hipStream_t stream, int row_end = 0) {
-    const int rows = (row_end > 0 ? row_end : c.N) - from;
+// Everything to the right of the next step's columns: A[from:row_end, from:row_end] -= P P^T (lower), P = A[from:row_end, k0:kend).  A
+// handful of rows (the augmented row once the last panel is next) by the one-wave kernel, else the batched GEMM with its profile event.
+static int potrf_rest_update(const PotrfCtx& c, int k0, int kend, int from, int row_end, hipStream_t stream) {
+    const int rows = row_end - from;
     if (rows <= 0) return 0;
-    if (rows <= POTRF_SMALL_ROWS && env_int("GPAR_POTRF_SMALL_UPDATE", 1)) {
+    if (rows <= POTRF_SMALL_ROWS && c.pol->small_update) {
         hipLaunchKernelGGL(potrf_small_update_kernel, dim3(rows * rows, c.batch), dim3(64), 0, stream, c.A, c.lda, from, k0, kend - k0, rows, rows, c.batch_a);
         return 0;
     }
+    bool pa;
+    prof_begin(*c.pol, stream, pa, c.N - from);
     const double* P = c.A + (size_t)from * c.lda + k0;
-    return gemm_launch(0, 1, rows, rows, kend - k0, -1.0, P, c.lda, P, c.lda, 1.0, c.A + (size_t)from * c.lda + from, c.lda, GPAR_GEMM_C_LOWER, stream, 1,
-                       c.batch, c.batch_a, c.batch_a, c.batch_a);
+    const int rc = gemm_launch(0, 1, rows, rows, kend - k0, -1.0, P, c.lda, P, c.lda, 1.0, c.A + (size_t)from * c.lda + from, c.lda, GPAR_GEMM_C_LOWER,
+                               stream, 1, c.batch, c.batch_a, c.batch_a, c.batch_a);
+    prof_end(stream, pa, c.N - from, c.N - from, (kend - k0) * c.batch);
+    return rc;
 }
 
 // Factor columns [c0, c1) (already up to date with respect to all columns < c0): on exit rows c0..N of those
@@ -552,13 +515,13 @@ static int potrf_panel(const PotrfCtx& c, int c0, int c1, int nb, hipStream_t st
         launch_strip<true>(Acc, c.lda, w, c.A + (size_t)c1 * c.lda + c0, c.lda, c.N - c1, stream, c.batch, c.batch_a);
         return 0;
     }
-    if (nb >= w) nb = (w > c.nbm && c.nbm >= POTRF_NBI) ? c.nbm : POTRF_NBI;
-    const int next_nb = nb > c.nbm ? c.nbm : POTRF_NBI;
+    if (nb >= w) nb = (w > c.pol->nbm && c.pol->nbm >= POTRF_NBI) ? c.pol->nbm : POTRF_NBI;
+    const int next_nb = nb > c.pol->nbm ? c.pol->nbm : POTRF_NBI;
     for (int k0 = c0; k0 < c1; k0 += nb) {
         const int kend = (k0 + nb < c1) ? k0 + nb : c1;
         int rc = potrf_panel(c, k0, kend, next_nb, stream);
         if (rc) return rc;
-        rc = potrf_gemm_update(c, k0, kend, c1, stream);
+        rc = potrf_gemm_update(c, k0, kend, c1, stream, 0, c.N);
         if (rc) return rc;
     }
     return 0;
@@ -580,18 +543,16 @@ static int potrf_panel_split(const PotrfCtx& c, int k0, int kend, int nb, hipStr
     return rc;
 }
 
-// defined in panel.h (one launch per 64-row block of B for up to 8 column steps)
-// defined in panel.h (one persistent launch per panel)
+// defined in panel.h: the hand-off flags of all panels zeroed in one launch
 static void potrf_zero_flags(double* A, int N, int lda, hipStream_t stream, int batch, long long batch_a);
 // the fused panel kernels (panel2.h): left-looking row-block tasks, strips on the matrix cores
 static int potrf_panel_fused2(double* A, int N, int lda, int k0, int W, double* logdet, int* info, hipStream_t stream, bool prezeroed,
                               int batch = 1, long long batch_a = 0);
-static int trsm_block_fused2(const double* L, int n, int ldl, double* B, int nrows, int ldb, int c0, int S, int upper_tri,
-                             hipStream_t stream);
-static int potrf_la_update_small(double* A, int N, int lda, int k0, int kend, int ncols, hipStream_t stream, int batch, long long batch_a);
 static int potrf_group_fused(double* A, int N, int lda, int k0, int W, int G, double* logdet, int* info, hipStream_t stream, int batch,
                              long long batch_a, unsigned long long la_base);
-static int env_int(const char* name, int dflt);
+static int potrf_la_update_small(double* A, int N, int lda, int k0, int kend, int ncols, hipStream_t stream, int batch, long long batch_a);
+static int trsm_block_fused2(const double* L, int n, int ldl, double* B, int nrows, int ldb, int c0, int S, int upper_tri,
+                             hipStream_t stream);
 static int trinv_blocks_fused2(const double* L, int n, int ldl, double* X, int ldx, int S, hipStream_t stream);
 static int trsm_block_back_fused2(const double* L, int n, int ldl, double* B, int nrows, int ldb, int c0, int S, hipStream_t stream);
 
@@ -670,271 +631,89 @@ static hipStream_t la_side(hipStream_t caller) {
     return s;
 }
 
-// (`rows`: the rows of the update about to be launched.  An update of at most POTRF_SMALL_ROWS rows - the augmented row once the last
-// panel is next - is the one-wave kernel, not the matrix-core update: it is not counted, so that `launches` equals the dispatches of
-// gemm_f64_kernel<false, true, 1, *> a kernel trace of the same evaluation shows.)
-static void prof_begin(hipStream_t s, bool& active, int rows) {
-    active = g_prof.on && g_prof.nev < ProfileState::MAXEV && !(rows <= POTRF_SMALL_ROWS && env_int("GPAR_POTRF_SMALL_UPDATE", 1));
-    if (!active) return;
-    if (!g_prof.created) {
-        for (int i = 0; i < ProfileState::MAXEV; ++i)
-            if (hipEventCreate(&g_prof.ev[i][0]) != hipSuccess || hipEventCreate(&g_prof.ev[i][1]) != hipSuccess) { active = false; return; }
-        g_prof.created = true;
-    }
-    GPAR_HIP_IGNORE(hipEventRecord(g_prof.ev[g_prof.nev][0], s));
-}
-
-static void prof_end(hipStream_t s, bool active, int rows, int cols, int kb) {
-    if (!active) return;
-    GPAR_HIP_IGNORE(hipEventRecord(g_prof.ev[g_prof.nev][1], s));
-    g_prof.shape[g_prof.nev][0] = rows; g_prof.shape[g_prof.nev][1] = cols; g_prof.shape[g_prof.nev][2] = kb;
-    g_prof.nev++;
-    g_prof.launches++;
-    // algorithmic flops of the lower-trapezoid rank-kb update (SURVEY 8d): 2 * kb per stored element
-    g_prof.flops += 2.0 * (double)kb * ((double)cols * ((double)cols + 1.0) * 0.5 + (double)(rows - cols) * (double)cols);
-}
-
-// Top level: panels of `nbo` columns; the trailing update of panel k is split into the next panel's columns
-// (look-ahead part, stays on the caller's stream ahead of the next panel factorisation) and the rest (on a
-// low-priority side stream), so the serial diag/strip chain of panel k+1 runs under the big SYRK of panel k.
-static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* info, hipStream_t stream, int flags = 0, int batch = 1,
-                     long long batch_a = 0) {
-    if (nf > N) return GPAR_ARG_ERROR(1);
-    // The schedule below - panel widths, which steps are grouped, which are fused into one launch, the tile form of every update -
-    // is a function of the SHAPE (N, nf, lda alignment) AND OF `batch`, and of nothing else: the same bits with and without
-    // look-ahead, alone or beside other work, on any stream.  A matrix factored inside a lock-step batch takes another summation
-    // order than the same matrix alone (pair_rows, fuse2_rows and the half-tile rule of the updates all look at the batch): equal
-    // to rounding, not to the bit (tests/test_full_size_gpu.py::test_batch_geometry_changes_the_summation_order_not_the_factor).
-    PotrfPolicy pol = potrf_policy(N);
-    // a LONE large factorisation stops grouping earlier (from 7680 rows on the steps are single panels with look-ahead, the last 7680 rows
-    // then one fused launch of fifteen panels): n = 16384 25.10 -> 24.97 ms, n = 12288 11.84 -> 11.79; a lock-step batch keeps 6144 (C3:
-    // 180.2 against 180.7 ms with 7680; profiles/r05_exp_fuse_rows.txt)
-    if (batch == 1 && N >= 12288 && !getenv("GPAR_POTRF_PAIR_ROWS")) pol.pair_rows = 7680;
-    // a wide lock-step batch of large matrices groups its panels down to 2560 rows: its rank-1536 updates are `batch` times a lone
-    // matrix's and hide the longer serial stretch, and spare the launch-wide read and write of the trailing matrices two times in three
-    // (C5, 16 x 8193: 55.5 -> 53.7 ms; 12 x 8192 40.8 -> 39.5, 12 x 10240 73.7 -> 72.5; batches of 2-8 and matrices below 8192 rows:
-    // equal or slower, C3 - 8 x 16385 - equal: profiles/r05_exp_batch_pair.txt)
-    if (batch >= 12 && N >= 8192 && !getenv("GPAR_POTRF_PAIR_ROWS")) pol.pair_rows = 2560;
-    // the caller runs several factorisations at once (three or more layer streams): each one's look-ahead side stream would
-    // add a queue to an already over-subscribed chip (C5, three streams at n = 8192: 78 -> 72 ms per evaluation without)
-    if ((flags & GPAR_POTRF_NO_LOOKAHEAD) && !getenv("GPAR_POTRF_LOOKAHEAD")) pol.lookahead = 0;
-    if (flags & GPAR_POTRF_UNFUSED) {   // the caller's retry after a hand-off timeout: separate leaf kernels, nothing spins
-        pol.fused = 0;
-        pol.lookahead = 0;
-        pol.nbo = N >= 12288 ? 512 : (N >= 6144 ? 256 : (N >= 1536 ? 128 : 64));
-        pol.nbm = pol.nbo >= 512 ? 128 : 64;
-    }
-    PotrfCtx c{A, N, lda, logdet, info, pol.nbm};
-    c.batch = batch;
-    c.batch_a = batch_a;
-    // lock-step batch: its updates are `batch` times longer than one matrix's - long enough to hide a panel kernel behind at any N
-    if (batch > 1 && pol.fused && !getenv("GPAR_POTRF_LOOKAHEAD")) pol.lookahead = env_int("GPAR_POTRF_BATCH_LOOKAHEAD", 1);
-    const int nbo = pol.nbo;
+// Top level.  The schedule (potrf_schedule.h) gives the step that starts at each column: how its panels are factored, then its
+// trailing update - while a further step follows in two launches: (1) the next step's columns, on the caller's stream ahead of the
+// next panel factorisation, and (2) everything to their right.  Look-ahead puts (2) on a low-priority side stream, so that the serial
+// chain of step k+1 runs under the big SYRK of step k: it decides on which stream (2) goes and which events are recorded and waited
+// on, and nothing else - the launches are the same with and without it.
+// Tail split (potrf_policy): every companion of an update that leaves the augmented rows out is issued on the CALLER's stream, in the
+// same order with and without look-ahead: the one of (1) or of an in-group update right behind it (potrf_slice_update), the one of
+// (2) behind the NEXT step's panel launches, where the caller's stream otherwise waits for the side stream - it reads finished panel
+// columns and writes tail rows only, which no matrix-core launch of a split update touches, so it needs no event.
+static int potrf_exec(const PotrfPolicy& pol, const PotrfShape& sh, double* A, long long batch_a, double* logdet, int* info, hipStream_t stream) {
+    const int N = sh.N, nf = sh.nf, lda = sh.lda, batch = sh.batch, nbo = pol.nbo;
+    const PotrfCtx c{A, N, lda, logdet, info, &pol, batch, batch_a};
     hipStream_t side = (pol.lookahead && nf > nbo && la_init()) ? la_side(stream) : nullptr;
     const bool la = side != nullptr;
     hipEvent_t trail_done = nullptr;   // completion of the side-stream update issued in the previous step
-    // Early in the factorisation two panels are factored back to back (the second after a narrow update of its own
-    // columns by the first) and the rest of the matrix then receives ONE rank-2*nbo update: the trailing update reads and
-    // writes every remaining element once per 1024 columns instead of once per 512, and a K = 1024 SYRK runs ~8 % faster
-    // than two K = 512 ones.  The price is a longer serial stretch per step (two panels + the narrow update), so the
-    // pairing stops once the trailing update is too short to hide it (`pair_rows`).
-    const int G = pol.group;
-    // hand-off flags of all panels zeroed once, ahead of the first panel (panel.h)
-    const bool prezero = pol.fused && env_int("GPAR_POTRF_PREZERO", 1) && nf >= env_int("GPAR_POTRF_LOCKSTEP_MIN", 1);
-    if (prezero) potrf_zero_flags(A, N, lda, stream, batch, batch_a);
-    auto groupable = [&](int k) {
-        return G > 1 && k > 0 && pol.fused && nbo % 64 == 0 && k + G * nbo <= nf && (N - k) >= pol.pair_rows && (k % 2 == 0) && (lda % 2 == 0) &&
-               gpar_aligned16(A);
-    };
-    // (The last columns through ONE panel kernel of up to 16 column blocks - GPAR_POTRF_TAIL, round 3 - measured slower: n = 1024 0.43
-    // against 0.33 ms, C4 18.1 -> 19.7 ms; retired in round 6.)
-    // Two or more panels in ONE launch (potrf_group_kernel, panel2.h; at most GPAR_POTRF_FUSE_MAX) once the rows that are left make a step latency-bound: at most
-    // GPAR_POTRF_FUSE2_ROWS rows from the step's first column on (a lock-step batch: GPAR_POTRF_FUSE2_BATCH_ROWS over the batch - it
-    // fills the chip sooner).  Measured (tools/exp_potrf_fuse2.py, profiles/r04_exp_potrf_fuse2.txt): lone n = 1024 / 2048 / 3072 /
-    // 4096 0.333 -> 0.310 / 0.753 -> 0.651 / 1.246 -> 1.146 / 1.869 -> 1.765 ms with every step fused; where a trailing update runs
-    // beside the panels on the side stream (look-ahead, N >= 2560) the waiting tile workgroups cost it compute-unit slots, and only the
-    // last ~2500 rows gain (n = 8192 5.04 -> 4.92 ms, 5.30 fused from 5120 rows on; n = 4096 1.640 -> 1.579, 3072 1.130 -> 1.079, 2560
-    // 0.924 -> 0.866; n = 4600 1.94 / 1.95 / 2.00 / 2.18 ms fused never / from 2560 / 4200 / 5120 rows; n = 16384 inside the noise); a lock-step batch of
-    // four gains 1 % on its last pair of panels and loses when more are fused (4 x 4096: 2.74 -> 2.71 / 2.84 ms).  Geometry only, like
-    // every other rule here: the same bits with and without look-ahead.
-    // Round 5 (the next team's rows updated tile by tile, progressive hand-off): a factorisation of up to 5200 rows is ONE launch (n = 4096
-    // 1.56 -> 1.26 ms); a larger one fuses its last eight panels (profiles/r05_exp_fuse_rows.txt: n = 8192 4.77 / 4.72 / 4.60 / 4.71 / 4.66 / 4.79 ms
-    // fused from 5200 / 4700 / 4200 / 3600 / 3100 / 2560 rows; n = 5632 .. 16384 all flat within 2 % between 3600 and 4700).
-    // With the launch's tiles taking published column blocks without polling and fetching the next one under the current product
-    // (grp_la_tile: a tile's share of the earlier panels 6 -> ~3.5 us per column block) a lock-step batch gains from fusing too: four matrices
-    // of 4096 rows in ONE launch 3.55 -> 2.81 ms against 3.05 with their last 1536 rows fused (rows x batch <= 16500: C2, 4 x 3072 1.82 ->
-    // 1.62 ms, 8 x 2048 1.55 -> 1.36; C3 and C5 - the last 2048 / 1024 rows - unchanged; profiles/r05_exp_batch_fuse.txt).
-    const int fuse2_rows = batch == 1 ? env_int("GPAR_POTRF_FUSE2_ROWS", N <= 5200 ? 5200 : (N >= 12288 ? 8300 : 4200)) : env_int("GPAR_POTRF_FUSE2_BATCH_ROWS", 16500) / batch;
-    const bool fuse2_on = pol.fused && prezero && !(flags & GPAR_POTRF_UNFUSED) && nbo == 512 &&
-                          env_int("GPAR_PANEL_PAIRS", 1) && (lda % 2 == 0) && (batch_a % 2 == 0) && gpar_aligned16(A) && fuse2_rows > 0;
+    if (pol.prezero) potrf_zero_flags(A, N, lda, stream, batch, batch_a);
     unsigned long long fuse_counted = 0;   // tiles every row block below the fused launches so far has counted (panel2.h)
-    // (more than two panels per launch add little - between panels inside a launch the next team waits ~45 us for the last column
-    // blocks of its own rows, which the bulk row blocks of the panel before finish behind the chain - : n = 1536 0.497 -> 0.452 ms with
-    // three, n = 2048 0.647 -> 0.637 with four, nothing beyond; 4 measured equal or better than 2 / 3 / 8 at every size)
-    // (from N = 12288 on the last sixteen panels: with the faster update tiles n = 12288 12.0-12.1 -> 11.9 ms, n = 16384 25.4-25.5 -> 25.1-25.2;
-    // n = 8192 4.66-4.70 / 4.59 / 4.74-4.77 ms fused from 4200 / 6200 / 8300 rows: profiles/r05_exp_fuse_rows.txt)
-    const int fuse_max = env_int("GPAR_POTRF_FUSE_MAX", N >= 12288 ? 16 : 10);
-    // panels the step at column k takes in one launch (0: the step is not fused)
-    auto fuse_panels = [&](int k) {
-        if (!fuse2_on || groupable(k) || k % 64 != 0 || N - k > fuse2_rows) return 0;
-        int G = (nf - k) / nbo;
-        if (G > fuse_max) G = fuse_max;
-        return G >= 2 ? G : 0;
-    };
-    auto fusable2 = [&](int k) { return fuse_panels(k) > 0; };
-    auto panel_end = [&](int k) { return fusable2(k) ? k + fuse_panels(k) * nbo : (k + nbo >= nf ? nf : k + nbo); };
-    // Tail split: a matrix with a short unfactored tail - 0 < N - nf <= POTRF_SMALL_ROWS, the augmented row(s) [y^T, 0] of the log
-    // marginal likelihood; not the posterior's n* appended rows - gave every matrix-core update below a last tile row for those few
-    // rows: (T + 1)(T + 2) / 2 tiles where T (T + 1) / 2 cover the factor, and the surplus ones end the launch.  An update whose first
-    // row is `r0` stops at row nf, and the tail rows receive the same rank-K update from potrf_tail_update, whenever leaving them out
-    // removes a tile row: ceil((N - r0) / 128) > ceil((nf - r0) / 128).  (Where it removes none - nf - r0 not within N - nf of a
-    // multiple of 128 from below - the update keeps all rows: the split would add a launch and save nothing.)  Geometry only.
-    // Every companion is issued on the CALLER's stream, in the same order with and without look-ahead: the one of a look-ahead slice
-    // or in-group update right behind it (the next panel reads those entries), the one of a rest update behind the NEXT step's
-    // panel launches, where the caller's stream otherwise waits for the side stream - it reads finished panel columns and writes
-    // tail rows only, which no matrix-core launch of a split update touches, so it needs no event.
-    // Lock-step batches only: there the surplus tiles are `batch` times as many and the panel chain hides under the batched update.  In a
-    // LONE factorisation the companion in front of every panel lengthens the serial chain by what the tile row saved or more (measured,
-    // parent / split: n = 16384 25.05 / 25.06 ms, n = 8192 4.63 / 4.68; batches of 2 / 4 / 16 at n = 8192 8.4 / 8.4, 13.8 / 13.6, 48.4 / 47.4 ms,
-    // 3 x 6656 6.58 / 6.45, 2 x 16384 47.5 / 47.2, C3 - 8 x 16384 - 182.3 / 179.9: profiles/r08_tail_split_bench.txt).
-    const bool tail_on = batch > 1 && N - nf > 0 && N - nf <= POTRF_SMALL_ROWS;
-    auto tail_split = [&](int r0) { return tail_on && r0 < nf && gpar_ceil_div(N - r0, GEMM_BM) > gpar_ceil_div(nf - r0, GEMM_BM); };
-    auto tail_update = [&](int ks, int ke, int c0, int c1) { return potrf_tail_update(A, N, lda, batch, batch_a, nf, ks, ke, c0, c1, stream); };
-    struct { int k0, kend, from; bool on; } tail_pend = {0, 0, 0, false};   // companion of the last rest update, not yet issued
-    // the rest update of [k0, kend) from row / column `from` on; with a split its companion becomes pending
-    auto rest_update = [&](int k0, int kend, int from, hipStream_t s) {
-        const bool sp = tail_split(from);
-        const int rc = potrf_rest_update(c, k0, kend, from, s, sp ? nf : 0);
-        if (sp) tail_pend = {k0, kend, from, true};
-        return rc;
-    };
-    for (int k0 = 0, knext = 0; k0 < nf; k0 = knext) {
-        int kend = panel_end(k0);
-        // a ragged tail (nf not a multiple of 64) becomes its own narrow panel so the wide part stays fusable
-        if (pol.fused && (kend - k0) > 64 && (kend - k0) % 64 != 0) kend = k0 + (kend - k0) / 64 * 64;
+    PotrfStep prev{};                      // the step before: the companion of its update (2) is not yet issued
+    for (int col = 0; col < nf;) {
+        const PotrfStep st = potrf_step(pol, sh, col);
+        const int k0 = st.k0, kend = st.kend;
+        col = kend;
         int rc = 0;
-        if (groupable(k0)) {
-            kend = k0 + G * nbo;
-            for (int i = 0; i < G && !rc; ++i) {
-                const int ks = k0 + i * nbo;
-                if (i > 0) {   // this panel's columns: one update by the i panels of the group factored so far
-                    bool pb;
-                    prof_begin(stream, pb, N - ks);
-                    rc = potrf_gemm_update(c, k0, ks, ks + nbo, stream, 1, tail_split(ks) ? nf : 0);
-                    prof_end(stream, pb, N - ks, nbo, (ks - k0) * batch);
-                    if (!rc && tail_split(ks)) rc = tail_update(k0, ks, ks, ks + nbo);
-                }
-                if (!rc) rc = potrf_panel_any(A, N, lda, ks, nbo, logdet, info, stream, prezero, batch, batch_a);
+        switch (st.panel) {
+        case POTRF_PANEL_GROUPED:
+            for (int ks = k0; ks < kend && !rc; ks += nbo) {
+                // this panel's columns: one update by the panels of the group factored so far
+                if (ks > k0) rc = potrf_slice_update(c, nf, k0, ks, ks + nbo, potrf_tail_split(pol, sh, ks) ? nf : N, stream);
+                if (!rc) rc = potrf_panel_any(A, N, lda, ks, nbo, logdet, info, stream, pol.prezero, batch, batch_a);
             }
-        } else {
-            const int w = kend - k0;
-            const bool fused_ok = pol.fused && w % 64 == 0 && w <= 1024 && N - k0 >= 64 && (k0 % 2 == 0) && (lda % 2 == 0) && gpar_aligned16(A);
-            if (fusable2(k0) && w == fuse_panels(k0) * nbo) {
-                const int G = fuse_panels(k0);
-                rc = potrf_group_fused(A, N, lda, k0, nbo, G, logdet, info, stream, batch, batch_a, fuse_counted);
-                fuse_counted += 8ull * (unsigned long long)(G - 1);
-            } else if (fused_ok) {
-                rc = potrf_panel_any(A, N, lda, k0, w, logdet, info, stream, prezero, batch, batch_a);
-            } else {
-                if (batch > 1 && w <= POTRF_NBI && !pol.split) {   // a narrow (ragged last) panel of a lock-step batch: batched leaf kernels
-                    rc = potrf_panel(c, k0, kend, nbo, stream);
-                } else
-                for (int b = 0; b < batch && !rc; ++b) {   // leaf kernels (the unfused path): matrix by matrix
-                    PotrfCtx cb{A + (size_t)b * batch_a, N, lda, logdet ? logdet + b : nullptr, info ? info + b : nullptr, pol.nbm};
-                    rc = pol.split ? potrf_panel_split(cb, k0, kend, nbo, stream) : potrf_panel(cb, k0, kend, nbo, stream);
-                }
+            break;
+        case POTRF_PANEL_FUSED_GROUP:
+            rc = potrf_group_fused(A, N, lda, k0, nbo, st.G, logdet, info, stream, batch, batch_a, fuse_counted);
+            fuse_counted += 8ull * (unsigned long long)(st.G - 1);
+            break;
+        case POTRF_PANEL_FUSED:
+            rc = potrf_panel_any(A, N, lda, k0, kend - k0, logdet, info, stream, pol.prezero, batch, batch_a);
+            break;
+        case POTRF_PANEL_LEAF_BATCH:
+            rc = potrf_panel(c, k0, kend, nbo, stream);
+            break;
+        case POTRF_PANEL_LEAF:   // (the unfused path)
+            for (int b = 0; b < batch && !rc; ++b) {
+                const PotrfCtx cb{A + (size_t)b * batch_a, N, lda, logdet ? logdet + b : nullptr, info ? info + b : nullptr, &pol};
+                rc = st.leaf_split ? potrf_panel_split(cb, k0, kend, nbo, stream) : potrf_panel(cb, k0, kend, nbo, stream);
             }
+            break;
         }
-        knext = kend;
+        // (an update (2) that was split is followed by another step: next_end < nf)
+        if (!rc && prev.rest_tail) rc = potrf_tail_update(A, N, lda, batch, batch_a, nf, prev.k0, prev.kend, prev.next_end, N, stream);
         if (rc) return rc;
-        if (tail_pend.on) {   // (see the tail split above)
-            tail_pend.on = false;
-            rc = tail_update(tail_pend.k0, tail_pend.kend, tail_pend.from, N);
-            if (rc) return rc;
-        }
-        if (kend >= N) break;
-        // columns the next step factors (one panel, or two if it pairs): [kend, next_end)
-        const int next_end = groupable(kend) ? kend + G * nbo : panel_end(kend);
-        bool pa;
-        if (!la || kend >= nf) {
-            // no further panel to overlap with (or look-ahead off): one update of everything that is left
-            if (la && trail_done) { GPAR_HIP_TRY(hipStreamWaitEvent(stream, trail_done, 0)); trail_done = nullptr; }
-            if (kend < nf && next_end <= N && potrf_la_is_small(c, k0, kend, next_end)) {
-                // (the same split the look-ahead schedule makes, so that both produce the same bits: the next panel's columns by the
-                // small kernel, everything to their right by the GEMM)
-                rc = potrf_la_update(c, k0, kend, next_end, stream);
-                if (!rc) {
-                    prof_begin(stream, pa, N - next_end);
-                    rc = rest_update(k0, kend, next_end, stream);
-                    prof_end(stream, pa, N - next_end, N - next_end, (kend - k0) * batch);
-                }
-                if (rc) return rc;
-                continue;
-            }
-            if (kend < nf && next_end < N) {
-                // (the same two launches as the look-ahead schedule below - the next step's columns, then everything to their right:
-                // the update kernel picks its tile shape by the size of the launch, and a tile that preloads C rounds differently
-                // from one that adds it at the end, so ONE launch over everything would not return the look-ahead schedule's bits)
-                prof_begin(stream, pa, N - kend);
-                rc = potrf_gemm_update(c, k0, kend, next_end, stream, 1, tail_split(kend) ? nf : 0);
-                prof_end(stream, pa, N - kend, next_end - kend, (kend - k0) * batch);
-                if (!rc && tail_split(kend)) rc = tail_update(k0, kend, kend, next_end);
-                if (!rc) {
-                    prof_begin(stream, pa, N - next_end);
-                    rc = rest_update(k0, kend, next_end, stream);
-                    prof_end(stream, pa, N - next_end, N - next_end, (kend - k0) * batch);
-                }
-                if (rc) return rc;
-                continue;
-            }
-            prof_begin(stream, pa, N - kend);
-            rc = potrf_gemm_update(c, k0, kend, N, stream, 1);
-            prof_end(stream, pa, N - kend, N - kend, (kend - k0) * batch);
-            if (rc) return rc;
-            continue;
-        }
-        // (1) next panel's columns, on the caller's stream; they were last written by the previous side update.
+        prev = st;
+        if (st.update == POTRF_UPDATE_NONE) break;
+        const bool ahead = la && kend < nf;   // a further step to run under this one's update (2)
+        // (1) was last written by the previous side update.
         // (Measured negative and retired - NOTES.md section 7 and R5.11: updating only the first panel's columns of a following GROUP
         // ahead of it, GPAR_POTRF_LA_SPLIT (n = 16384 25.94 -> 26.12 ms, C3 180.5 -> 182.0); releasing the big update only after the
         // look-ahead update, GPAR_POTRF_REST_AFTER_LA / GPAR_POTRF_BATCH_REST_AFTER_LA; factoring the very first panel inside a group,
         // GPAR_POTRF_PAIR_FIRST.)
-        if (trail_done) GPAR_HIP_TRY(hipStreamWaitEvent(stream, trail_done, 0));
-        const int la_end = next_end;
-        hipEvent_t panel_done = la_event();
-        GPAR_HIP_TRY(hipEventRecord(panel_done, stream));
-        if (potrf_la_is_small(c, k0, kend, la_end)) {
-            rc = potrf_la_update(c, k0, kend, la_end, stream);
-        } else {
-            prof_begin(stream, pa, N - kend);
-            rc = potrf_gemm_update(c, k0, kend, la_end, stream, 1, tail_split(kend) ? nf : 0);   // same kernel symbol: it is part of the trailing update
-            prof_end(stream, pa, N - kend, la_end - kend, (kend - k0) * batch);
-            if (!rc && tail_split(kend)) rc = tail_update(k0, kend, kend, la_end);
-        }
+        if (trail_done) { GPAR_HIP_TRY(hipStreamWaitEvent(stream, trail_done, 0)); trail_done = nullptr; }
+        hipEvent_t panel_done = nullptr;
+        if (ahead) { panel_done = la_event(); GPAR_HIP_TRY(hipEventRecord(panel_done, stream)); }
+        rc = st.slice_small ? potrf_la_update_small(A, N, lda, k0, kend, st.next_end - kend, stream, batch, batch_a)
+                            : potrf_slice_update(c, nf, k0, kend, st.next_end, st.slice_tail ? nf : N, stream);
         if (rc) return rc;
-        // (2) everything to the right of the next step's columns, on the side stream
-        GPAR_HIP_TRY(hipStreamWaitEvent(side, panel_done, 0));
-        {
-            const int rows = N - next_end, cols = N - next_end;
-            if (rows > 0) {
-                prof_begin(side, pa, rows);
-                rc = rest_update(k0, kend, next_end, side);
-                prof_end(side, pa, rows, cols, (kend - k0) * batch);
-                if (rc) return rc;
-            }
-        }
-        trail_done = la_event();
-        GPAR_HIP_TRY(hipEventRecord(trail_done, side));
-    }
-    if (tail_pend.on) {   // (cannot happen: a rest update with rows of the factor left is followed by another step)
-        const int rc = tail_update(tail_pend.k0, tail_pend.kend, tail_pend.from, N);
+        if (ahead) GPAR_HIP_TRY(hipStreamWaitEvent(side, panel_done, 0));
+        if (st.update == POTRF_UPDATE_SLICE_REST) rc = potrf_rest_update(c, k0, kend, st.next_end, st.rest_tail ? nf : N, ahead ? side : stream);
         if (rc) return rc;
+        if (ahead) { trail_done = la_event(); GPAR_HIP_TRY(hipEventRecord(trail_done, side)); }
     }
     if (trail_done) GPAR_HIP_TRY(hipStreamWaitEvent(stream, trail_done, 0));   // join
     GPAR_LAUNCH_CHECK();
     return 0;
 }
 
-// `batch` factorisations of the same shape in lock-step (matrix b at A + b * batch_a, its words logdet[b] / info[b]): potrf_run
+static int potrf_run(double* A, int N, int nf, int lda, double* logdet, int* info, hipStream_t stream, int flags = 0) {
+    if (nf > N) return GPAR_ARG_ERROR(1);
+    const PotrfShape sh{N, nf, lda, 1, gpar_aligned16(A), true};
+    const PotrfPolicy pol = potrf_policy(sh, flags);
+    return potrf_exec(pol, sh, A, 0, logdet, info, stream);
+}
+
+// `batch` factorisations of the same shape in lock-step (matrix b at A + b * batch_a, its words logdet[b] / info[b]): potrf_exec
 // with ONE panel launch (gridDim.y = batch) and ONE batched trailing update where a single factorisation has a launch of its own.
 // Independent factorisations on separate streams contend for compute-unit slots - a panel workgroup of one finds every unit
 // holding two update workgroups of another, and its whole team waits; in lock-step every launch carries `batch` times the parallel
@@ -945,10 +724,9 @@ static int potrf_run_batch(double* A, int batch, long long batch_a, int N, int n
                            int flags = 0) {
     if (batch <= 0) return 0;
     if (nf > N) return GPAR_ARG_ERROR(1);
-    const PotrfPolicy pol = potrf_policy(N);
-    const bool lockstep = batch > 1 && pol.fused && !(flags & GPAR_POTRF_UNFUSED) && pol.nbo % 64 == 0 &&
-                          (lda % 2 == 0) && (batch_a % 2 == 0) && gpar_aligned16(A) && nf >= env_int("GPAR_POTRF_LOCKSTEP_MIN", 1);
-    if (lockstep) return potrf_run(A, N, nf, lda, logdet, info, stream, flags, batch, batch_a);
+    const PotrfShape sh{N, nf, lda, batch, gpar_aligned16(A), batch_a % 2 == 0};
+    const PotrfPolicy pol = potrf_policy(sh, flags);
+    if (pol.lockstep) return potrf_exec(pol, sh, A, batch_a, logdet, info, stream);
     for (int b = 0; b < batch; ++b) {
         const int rc = potrf_run(A + (size_t)b * batch_a, N, nf, lda, logdet + b, info + b, stream, flags);
         if (rc) return rc;

@@ -1,5 +1,5 @@
-"""The augmented rows of a partial factorisation (0 < N - nf <= 16) leave the matrix-core updates: potrf_run's tail split and its
-companion kernel (potrf_tail_update_kernel, csrc/potrf.h).
+"""The augmented rows of a partial factorisation (0 < N - nf <= 16) leave the matrix-core updates: the schedule's tail split
+(potrf_tail_split, csrc/potrf_schedule.h) and its companion kernel (potrf_tail_update_kernel, csrc/potrf.h).
 
 The split applies to lock-step batches only; a lone factorisation keeps every row in its updates and is covered as the unchanged path.
 
