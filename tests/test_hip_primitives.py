@@ -776,7 +776,9 @@ def test_lockstep_dense_logpdf_equals_layer_by_layer(env, n, batch):
 def test_gemm_triangular_aware_k_ranges(env, n):
     """K_FROM_ROW (upper-triangular op(A), zeros stored left of its diagonal) and K_TO_COL (upper-triangular op(B), zeros stored
     below its diagonal) only shorten the K loop: same numbers as the plain product; the two factors of the recursive
-    triangular inversion (gpar_chol_inverse) are this pair.  (1024: tile counts that take the per-XCD column grouping.)"""
+    triangular inversion (gpar_chol_inverse) are this pair.  (All three sizes run as half tiles - at most 256 tiles, k >= 64 - and so
+    through the round-robin tile map; the per-XCD column grouping of K_TO_COL needs whole tiles and is run by
+    tests/test_exact_arithmetic_gpu.py, case "whole-nn-k-to-col-column-grouping".)"""
     torch, hip, dev, to_dev = env
     rng = np.random.default_rng(n)
     U = np.triu(rng.standard_normal((n, n)))
