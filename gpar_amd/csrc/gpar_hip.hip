@@ -83,11 +83,8 @@ __global__ __launch_bounds__(256) void trmv_lower_kernel(const double* __restric
 // one wave per row, lanes stride the row, wave reduce.  alpha = (L L^T)^-1 y = L^-T (L^-1 y) = X z with X = L^-T, which the
 // inverse of the gradient pass has just formed: n^2 / 2 multiply-adds at memory speed instead of a backward substitution's chain of
 // n / 512 block kernels with an update each (n = 4096: 8 x 31 + 7 x 8 us -> ~15 us).
-__global__ __launch_bounds__(256) void trmv_upper_kernel(const double* __restrict__ U, int n, int ldu, const double* __restrict__ x,
-                                                         int incx, double* __restrict__ y, int incy) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
+__device__ __forceinline__ double trmv_upper_row(const double* __restrict__ U, int n, int ldu, const double* __restrict__ x, int incx, int row,
+                                                 int lane) {
     const double* Ur = U + (size_t)row * ldu;
     double a0 = 0.0, a1 = 0.0;
     int j = row + lane;
@@ -99,6 +96,14 @@ __global__ __launch_bounds__(256) void trmv_upper_kernel(const double* __restric
     double s = a0 + a1;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    return s;
+}
+__global__ __launch_bounds__(256) void trmv_upper_kernel(const double* __restrict__ U, int n, int ldu, const double* __restrict__ x,
+                                                         int incx, double* __restrict__ y, int incy) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const double s = trmv_upper_row(U, n, ldu, x, incx, row, lane);
     if (lane == 0) y[(size_t)row * incy] = s;
 }
 
@@ -901,6 +906,241 @@ int gpar_logpdf_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks
     return logpdf_grad_finish_run(fs, ks, x, n, ldx, z, zd, ldz, A, lda, logdet, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream);
 }
 
+// ---- leave-one-out cross-validation of one dense layer (ABI v8; Rasmussen & Williams 5.4.2, Sundararajan & Keerthi 2001) -----------
+// With Kinv = (K + D + eps I)^-1, alpha = Kinv y and d = diag Kinv:  mean_-i = y_i - alpha_i / d_i,  var_-i = 1 / d_i,
+//     L = sum_i [1/2 log d_i - alpha_i^2 / (2 d_i)] - n/2 log 2 pi,        dL/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta,
+//     W = alpha u^T + u alpha^T - 2 S S^T,   b = alpha / d,  c = 1/2 (1 / d + b^2),  S = Kinv diag(sqrt c),  u = Kinv b
+// - the shape of weights the weighted-sum pass of the marginal likelihood consumes.  Behind the inverse an evaluation adds three
+// launches to that one's chain (rows, {u, S}, the rank-2 term; the product S S^T takes the place of the rank-1 update).
+// `vec`: the four n-vectors b, sqrt c, value terms, u (gpar_workspace_doubles(GPAR_WS_LOO, n, 1, 0)).
+__device__ __forceinline__ void loo_row_write(int i, double a, double d, double yi, double* __restrict__ mean, double* __restrict__ var,
+                                              double* __restrict__ bvec, double* __restrict__ sc, double* __restrict__ term) {
+    const double v = 1.0 / d, b = a / d;
+    mean[i] = yi - b;
+    var[i] = v;
+    term[i] = 0.5 * log(d) - 0.5 * (a * b);
+    if (bvec) bvec[i] = b;
+    if (sc) sc[i] = sqrt(0.5 * (v + b * b));
+}
+
+// one wave per row: alpha_i as trmv_upper_kernel forms it (same bits), then the row's leave-one-out quantities from Kinv_ii
+__global__ __launch_bounds__(256) void loo_rows_kernel(const double* __restrict__ X, int n, int ldx, const double* __restrict__ zrow,
+                                                       const double* __restrict__ Kinv, int ldk, const double* __restrict__ y, long incy,
+                                                       double* __restrict__ alpha, double* __restrict__ mean, double* __restrict__ var,
+                                                       double* __restrict__ vec) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const double a = trmv_upper_row(X, n, ldx, zrow, 1, row, lane);
+    if (lane != 0) return;
+    alpha[row] = a;
+    loo_row_write(row, a, Kinv[(size_t)row * ldk + row], y[(size_t)row * incy], mean, var, vec, vec + n, vec + 2 * (size_t)n);
+}
+
+// the value-only form: alpha_i = sum_j X_ij z_j and d_i = sum_j X_ij^2 over the upper-triangular row i of X = L^-T in one pass
+__global__ __launch_bounds__(256) void loo_rows_from_x_kernel(const double* __restrict__ X, int n, int ldx, const double* __restrict__ zrow,
+                                                              const double* __restrict__ y, long incy, double* __restrict__ mean,
+                                                              double* __restrict__ var, double* __restrict__ term) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const double* Xr = X + (size_t)row * ldx;
+    double a0 = 0.0, a1 = 0.0, d0 = 0.0, d1 = 0.0;
+    int j = row + lane;
+    for (; j + 64 < n; j += 128) {
+        const double x0 = Xr[j], x1 = Xr[j + 64];
+        a0 = fma(x0, zrow[j], a0); d0 = fma(x0, x0, d0);
+        a1 = fma(x1, zrow[j + 64], a1); d1 = fma(x1, x1, d1);
+    }
+    if (j < n) { const double x0 = Xr[j]; a0 = fma(x0, zrow[j], a0); d0 = fma(x0, x0, d0); }
+    const double a = wave_sum(a0 + a1), d = wave_sum(d0 + d1);
+    if (lane == 0) loo_row_write(row, a, d, y[(size_t)row * incy], mean, var, nullptr, nullptr, term);
+}
+
+// blocks [0, nt^2), nt = ceil(n / 32): tile (bi, bj), bj <= bi, of the LOWER triangle of Kinv through LDS into S = Kinv diag(sqrt c) at
+// (bi, bj) and, transposed, at (bj, bi) - a full matrix for the product S S^T, both stores along rows;  the blocks behind them:
+// u = Kinv b from the lower triangle alone, one wave per row (its row up to the diagonal, its column below it), a fixed order.
+constexpr int LOO_T = 32;
+__global__ __launch_bounds__(256) void loo_weights_kernel(const double* __restrict__ Kinv, int ldk, int n, const double* __restrict__ bvec,
+                                                          const double* __restrict__ sc, double* __restrict__ u, double* __restrict__ S, int lds) {
+    __shared__ double tile[LOO_T][LOO_T + 1];
+    const int nt = (n + LOO_T - 1) / LOO_T;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= nt * nt) {
+        const int lane = t & 63;
+        const int row = (b - nt * nt) * 4 + (t >> 6);
+        if (row >= n) return;
+        const double* Kr = Kinv + (size_t)row * ldk;
+        double a0 = 0.0, a1 = 0.0;
+        for (int j = lane; j <= row; j += 64) a0 = fma(Kr[j], bvec[j], a0);
+        for (int j = row + 1 + lane; j < n; j += 64) a1 = fma(Kinv[(size_t)j * ldk + row], bvec[j], a1);
+        const double s = wave_sum(a0 + a1);
+        if (lane == 0) u[row] = s;
+        return;
+    }
+    const int bi = b / nt, bj = b - bi * nt;
+    if (bj > bi) return;
+    const int tx = t & 31, ty = t >> 5;
+    const int r0 = bi * LOO_T, c0 = bj * LOO_T;
+    for (int r = ty; r < LOO_T; r += 8) {
+        const int gr = r0 + r, gc = c0 + tx;
+        tile[r][tx] = (gr < n && gc <= gr) ? Kinv[(size_t)gr * ldk + gc] : 0.0;
+    }
+    __syncthreads();
+    for (int r = ty; r < LOO_T; r += 8) {
+        const int gr = r0 + r, gc = c0 + tx;
+        if (gr < n && gc < n) S[(size_t)gr * lds + gc] = ((bi == bj && tx > r) ? tile[tx][r] : tile[r][tx]) * sc[gc];
+        const int mr = c0 + r, mc = r0 + tx;
+        if (bi != bj && mr < n && mc < n) S[(size_t)mr * lds + mc] = tile[tx][r] * sc[mc];
+    }
+}
+
+// W_ij += alpha_i u_j + u_i alpha_j on the lower triangle
+__global__ __launch_bounds__(256) void loo_rank2_kernel(double* __restrict__ W, int ldw, int n, const double* __restrict__ alpha,
+                                                        const double* __restrict__ u) {
+    const int i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j <= i) W[(size_t)i * ldw + j] += alpha[i] * u[j] + u[i] * alpha[j];
+}
+
+// sum of the n value terms in a fixed order (256 strided partial sums, then a tree), by one workgroup
+__device__ __forceinline__ double loo_sum_terms(const double* __restrict__ term, int n, double* sm) {
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int i = t; i < n; i += 256) s += term[i];
+    sm[t] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) sm[t] += sm[t + off];
+        __syncthreads();
+    }
+    return sm[0];
+}
+__global__ __launch_bounds__(256) void loo_value_kernel(const double* __restrict__ term, int n, double half_n_log_2pi, double* __restrict__ out) {
+    __shared__ double sm[256];
+    const double s = loo_sum_terms(term, n, sm);
+    if (threadIdx.x == 0) out[0] = s - half_n_log_2pi;
+}
+
+// dense_grad_epilogue_kernel for the leave-one-out value: the partial sums of the gradient pass and 1/2 diag W as there; the last block
+// sums the value terms
+__global__ __launch_bounds__(256) void loo_grad_epilogue_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
+                                                                const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag,
+                                                                const double* __restrict__ term, double half_n_log_2pi) {
+    __shared__ double sm[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b < GRAD_NACC) {
+        if (t >= 64) return;
+        double s = 0.0;
+        for (int q = t; q < nblocks; q += 64) s += partial[(size_t)q * GRAD_NACC + b];
+        s = wave_sum(s);
+        if (t == 0) out[2 + b] = s;
+        return;
+    }
+    const int hb = b - GRAD_NACC, nh = (n + 255) / 256;
+    if (hb < nh) {
+        const int i = hb * 256 + t;
+        if (i < n) half_diag[i] = 0.5 * W[(size_t)i * ldw + i];
+        return;
+    }
+    const double s = loo_sum_terms(term, n, sm);
+    if (t == 0) out[0] = s - half_n_log_2pi;
+}
+
+// Everything of gpar_loo_dense_grad behind the factorisation (out[1] holds the log-determinant already)
+static int loo_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                               double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw, double* W, int ldw, double* alpha,
+                               double* vec, double* workspace, int nblocks, double* out, double* half_diag, double* loo_mean, double* loo_var,
+                               void* stream, bool dfreq = true) {
+    hipStream_t st = (hipStream_t)stream;
+    if (dfreq && zd && fs->dz > 0) {
+        const long total = (long)n * fs->dz;
+        hipLaunchKernelGGL(featurize_dfreq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, zd, ldz);
+    }
+    int rc = chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
+    if (rc) return rc;
+    double *bvec = vec, *sc = vec + n, *term = vec + 2 * (size_t)n, *u = vec + 3 * (size_t)n;
+    hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
+                       (const double*)(A + (size_t)n * lda), (const double*)W, ldw, y, incy, alpha, loo_mean, loo_var, vec);
+    // u and S (into X: alpha exists, L^-T is no longer needed), then W <- -2 S S^T + alpha u^T + u alpha^T
+    const int nt = gpar_ceil_div(n, LOO_T);
+    hipLaunchKernelGGL(loo_weights_kernel, dim3((unsigned)(nt * nt + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n, (const double*)bvec,
+                       (const double*)sc, u, X, ldxw);
+    rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
+    rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_grad_epilogue_kernel, dim3((unsigned)(GRAD_NACC + (n + 255) / 256 + 1)), dim3(256), 0, st, (const double*)workspace,
+                       nblocks, out, (const double*)W, ldw, n, half_diag, (const double*)term, 0.5 * (double)n * 1.8378770664093453);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                        const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                        double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                        double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var || !info ||
+        n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    {   // the launches of gpar_logpdf_dense_grad up to the factor
+        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
+        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
+                           out + 1, info);
+    }
+    int rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
+    if (rc) return rc;
+    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
+    if (rc) return rc;
+    return loo_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
+                               loo_mean, loo_var, stream, false);
+}
+
+int gpar_loo_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                               double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                               double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                               double* loo_mean, double* loo_var, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !logdet || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var ||
+        n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    GPAR_HIP_TRY(hipMemcpyAsync(out + 1, logdet, sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (info && info_out) GPAR_HIP_TRY(hipMemcpyAsync(info_out, info, sizeof(int), hipMemcpyDeviceToDevice, st));
+    return loo_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
+                               loo_mean, loo_var, stream);
+}
+
+// Value, means and variances alone: no K^-1 is formed - alpha = X (L^-1 y) and d = the squared row norms of X = L^-T come out of one pass
+// over X (n^3 / 3 flops for X instead of the inverse's 2 n^3 / 3)
+int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                   double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !loo_mean || !loo_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    {
+        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
+        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, (double*)nullptr, ldz, y,
+                           incy, A, lda, out + 1, info);
+    }
+    int rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
+    if (rc) return rc;
+    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
+    if (rc) return rc;
+    rc = trinv_upper_run(A, n, lda, X, ldxw, T, ldt, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_rows_from_x_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
+                       (const double*)(A + (size_t)n * lda), y, incy, loo_mean, loo_var, vec);
+    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
 int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int ldz1, const double* z2, int n2, int ldz2, int dz,
                          const double* W, int ldw, int mode, int nsplit, double* workspace, double* out, int ldo, void* stream) {
     GPAR_API_GUARD;
@@ -1067,6 +1307,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_GRAM_GRAD: return (long long)(a > 0 ? a : 0) * GRAD_NACC;          /* nblocks */
         case GPAR_WS_CHOL_INVERSE: return (long long)a * b;                             /* n, ldx: the X matrix */
         case GPAR_WS_INPUT_GRAD: return (long long)a * b * (c > 1 ? c : 1);             /* n1, dz, nsplit */
+        case GPAR_WS_LOO: return (long long)(a > 0 ? a : 0) * (b ? 4 : 1);              /* n, with gradient */
         default: return -1;
     }
 }

@@ -855,13 +855,19 @@ __global__ __launch_bounds__(256) void set_block_identity_kernel(double* __restr
     if (c < n && c < (r / blk + 1) * blk) X[(size_t)r * ldx + c] = (r == c) ? 1.0 : 0.0;
 }
 
-static int chol_inverse_run(const double* L, int n, int ldl, double* X, int ldx, double* Kinv, int ldk, hipStream_t stream) {
-    if (n <= 0) return 0;
+// The first half of chol_inverse_run: X = L^-T in the upper triangle of X (T: an n x n scratch matrix, the later Kinv).  On its own it
+// serves callers that need only alpha = X (L^-1 y) and diag((L L^T)^-1) = the squared row norms of X (gpar_loo_dense).
+static int trinv_upper_run(const double* L, int n, int ldl, double* X, int ldx, double* T, int ldt, hipStream_t stream) {
     const bool recursive = env_int("GPAR_INVERSE_RECURSIVE", 1) && n >= 1024 && n % 512 == 0 && gpar_aligned16(L) &&
-                           gpar_aligned16(X) && gpar_aligned16(Kinv) && ldl % 2 == 0 && ldx % 2 == 0 && ldk % 2 == 0;
+                           gpar_aligned16(X) && gpar_aligned16(T) && ldl % 2 == 0 && ldx % 2 == 0 && ldt % 2 == 0;
     if (recursive) hipLaunchKernelGGL(set_block_identity_kernel, dim3(2, n), dim3(256), 0, stream, X, n, ldx, 512);
     else hipLaunchKernelGGL(set_identity_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, stream, X, n, ldx);
-    int rc = recursive ? trinv_recursive(L, n, ldl, X, ldx, Kinv, ldk, stream) : trsm_rlt_run2(L, n, ldl, X, n, ldx, 1, stream);
+    return recursive ? trinv_recursive(L, n, ldl, X, ldx, T, ldt, stream) : trsm_rlt_run2(L, n, ldl, X, n, ldx, 1, stream);
+}
+
+static int chol_inverse_run(const double* L, int n, int ldl, double* X, int ldx, double* Kinv, int ldk, hipStream_t stream) {
+    if (n <= 0) return 0;
+    int rc = trinv_upper_run(L, n, ldl, X, ldx, Kinv, ldk, stream);
     if (rc) return rc;
     return gemm_launch(0, 1, n, n, n, 1.0, X, ldx, X, ldx, 0.0, Kinv, ldk, GPAR_GEMM_C_LOWER | GPAR_GEMM_K_FROM_ROW, stream);
 }

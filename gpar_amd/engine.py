@@ -237,6 +237,28 @@ class HipEngine:
 
         return out[0], info, gradients, (A, out[1:2])
 
+    def loo_dense(self, ck, x, y, noise_diag, jitter):
+        """One dense layer's leave-one-out value, predictive means and variances in one library call: (value as a 0-d device
+        tensor, info word, means, variances)."""
+        safe = getattr(self._tls, "safe", False)
+        depth = getattr(self._tls, "pipe_depth", 0)
+        out, mean, var, info = hip.loo_dense(ck, self._mat(x), y, noise_diag, jitter, lookahead=not safe and depth < 3, fused=not safe)
+        return out[0], info, mean, var
+
+    def loo_dense_grad(self, ck, x, y, noise_diag, jitter):
+        """The leave-one-out counterpart of `logpdf_dense_grad`, same conventions: (value, info word, a function returning (1/2 diag(W)
+        on the device, kernel-parameter gradients), (factor buffer, log-determinant word)), then the predictive means and variances."""
+        safe = getattr(self._tls, "safe", False)
+        depth = getattr(self._tls, "pipe_depth", 0)
+        out, half_diag, mean, var, info, A, _ = hip.loo_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
+                                                                   lookahead=not safe and depth < 3, fused=not safe)
+
+        def gradients():
+            raw = out[2:].cpu().numpy()
+            return half_diag, self._grads_from_moments(ck, raw, 0.5)
+
+        return out[0], info, gradients, (A, out[1:2]), mean, var
+
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""
         safe = getattr(self._tls, "safe", False)

@@ -262,12 +262,18 @@ class LockstepFactor:
 
 
 class DenseLayerObjective:
-    """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` and its gradient with respect to the latent (unconstrained)
+    """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or, with `objective="loo"`, minus the leave-one-out predictive
+    log-density under the same covariance (gpar_loo_dense_grad) - and its gradient with respect to the latent (unconstrained)
     variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are device tensors that do
     not change during the optimisation."""
 
-    def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None):
+    def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll"):
+        if objective not in ("mll", "loo"):
+            raise ValueError('objective must be "mll" or "loo"')
         self.eng, self.vs, self.names = eng, vs, list(names)
+        self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
+        if objective == "loo":
+            group = lane = None      # (leave-one-out lanes take no part in the lock-step rendezvous)
         self.group, self.lane = group, lane   # a LockstepFactor and this objective's slot in it, or None
         self.kernel, self.noise, self.holders = kernel, noise_holder, holders
         self.general_fg = general_fg
@@ -309,7 +315,9 @@ class DenseLayerObjective:
         nt = (n + 63) // 64
         self.nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
         nacc = _lib.GRAD_NACC
-        self.work = torch.empty(self.nblocks * nacc + n, dtype=torch.float64, device=dev)
+        # gradient partials, alpha; for the leave-one-out objective its vectors, the predictive means and variances behind them
+        nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_LOO, n, 1, 0)) + 2 * n if self.objective == "loo" else 0
+        self.work = torch.empty(self.nblocks * nacc + n + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
         self.res = torch.zeros(2 + nacc + n + 1, dtype=torch.float64, device=dev)
         self.res_host = torch.zeros(2 + nacc + n + 1, dtype=torch.float64).pin_memory()
@@ -326,10 +334,14 @@ class DenseLayerObjective:
             alpha=self.work[self.nblocks * nacc:].data_ptr(), work=self.work.data_ptr(), out=self.res.data_ptr(),
             half=self.res[2 + nacc:].data_ptr(), info=self.res[2 + nacc + n:].data_ptr(),
         )
+        if self.objective == "loo":
+            at = self.nblocks * nacc + n
+            self._ptrs.update(vec=self.work[at:].data_ptr(), loo_mean=self.work[at + nloo - 2 * n:].data_ptr(),
+                              loo_var=self.work[at + nloo - n:].data_ptr())
 
     def _device_eval(self, ck, noise):
-        """One library call + one device-to-host copy: (log marginal likelihood, kernel-parameter gradients of it, 1/2 diag W as
-        a host vector), or None when the factorisation reported a failure."""
+        """One library call + one device-to-host copy: (the objective - log marginal likelihood or leave-one-out value -, kernel-
+        parameter gradients of it, 1/2 diag W as a host vector), or None when the factorisation reported a failure."""
         dev = self.X.device
         stream = torch.cuda.current_stream(dev)
         if self.unit_weights:
@@ -338,7 +350,13 @@ class DenseLayerObjective:
             # the correctly rounded quotient of two tensors, as model.GPAR._noise_over forms it
             torch.true_divide(self.noise_num.fill_(noise), self.w, out=self.noise_vec)
         p = self._ptrs
-        if self.group is None:
+        if self.objective == "loo":
+            rc = self.lib.gpar_loo_dense_grad(
+                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
+                p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["vec"], p["work"], self.nblocks,
+                p["out"], p["half"], p["loo_mean"], p["loo_var"], p["info"], self.flags, stream.cuda_stream)
+            _lib.check(rc, "gpar_loo_dense_grad")
+        elif self.group is None:
             rc = self.lib.gpar_logpdf_dense_grad(
                 ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
                 p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["work"], self.nblocks, p["out"],
@@ -457,9 +475,10 @@ class DenseLayerObjective:
         return val
 
 
-def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None):
+def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll"):
     """The fast objective of layer `pi` of regressor `reg` with fixed design matrix `fixed_x`, or None when this route does not
-    apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised."""
+    apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised;
+    `objective`: "mll" (log marginal likelihood) or "loo" (leave-one-out predictive log-density)."""
     from .gp import one_call_grad_rows
     from .regression import _model_generator
 
@@ -495,7 +514,7 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     names = vs.match(names)   # (globs; resolved now that the layer's variables exist)
     if not names:
         return None
-    if group is not None and (group.n != n or not on_device):
+    if group is not None and (group.n != n or not on_device or objective == "loo"):
         group = None
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
-               lane=lane if group is not None else None)
+               lane=lane if group is not None else None, objective=objective)

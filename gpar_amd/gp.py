@@ -288,6 +288,30 @@ class _LogMarginal(torch.autograd.Function):
         return (None, out_noise, gX, gZ, *_param_grads(obs._params, ctx.shapes, grads, gval))
 
 
+class _LooValue(torch.autograd.Function):
+    """The leave-one-out predictive log-density sum_i log N(y_i; mean_-i, var_-i) of dense observations of a prior process as a
+    differentiable function of the kernel parameters and the noise vector (Rasmussen & Williams 5.4.2).  Forward: `Obs._loo_eval`.
+    Backward: the same weighted-sum pass as `_LogMarginal`, on other weights - d/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta with
+    W = alpha u^T + u alpha^T - 2 K^-1 C K^-1 (`Obs.loo_gradients`).  The inputs are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, obs, noise, *tensors):
+        ctx.obs = obs
+        ctx.noise_shape = None if noise is None else tuple(noise.shape)
+        ctx.shapes = [tuple(t.shape) for t in tensors]
+        return obs._loo_eval(want_grad=True)
+
+    @staticmethod
+    def backward(ctx, g):
+        obs = ctx.obs
+        noise_grad, grads = obs.loo_gradients()
+        gval = float(g)
+        out_noise = None
+        if ctx.noise_shape is not None:
+            out_noise = _shaped_noise_grad(noise_grad * gval, ctx.noise_shape, obs._noise_device)
+        return (None, out_noise, *_param_grads(obs._params, ctx.shapes, grads, gval))
+
+
 class _PosteriorMean(torch.autograd.Function):
     """Posterior mean of `f | obs` at x* as a differentiable function of the kernel parameters, the noise, the training
     inputs X, the inducing inputs Z and x* itself: the column `_update_inputs` feeds to the next layer
@@ -659,6 +683,81 @@ class Obs:
         ck, _ = self.fdd.features()
         grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
         self._W = W
+        return 0.5 * torch.diagonal(W).clone(), grads
+
+    # ---- leave-one-out cross-validation -------------------------------------------------------------------
+    def loo(self):
+        """(value, mean, var): the leave-one-out predictive means and variances of the observations - of y_i given all the others,
+        mean_-i = y_i - alpha_i / d_i and var_-i = 1 / d_i with alpha = S^-1 (y - m), d = diag S^-1, S = cov(f(X)) + D + eps I - and
+        value = sum_i log N(y_i; mean_-i, var_-i), a 0-d tensor that carries a gradient with respect to the kernel parameters and the
+        noise where they require one (observations of a prior process; Rasmussen & Williams 5.4.2)."""
+        if torch.is_grad_enabled():
+            params = kernel_parameters(self.base.kernel)
+            noise = self.fdd.noise_arg if _needs_grad(self.fdd.noise_arg) else None
+            if params or noise is not None:
+                if self.base.is_posterior or self.fdd.x.requires_grad:
+                    raise NotImplementedError("the leave-one-out gradient covers kernel parameters and noise of a prior process")
+                self._params = params
+                self._noise_device = None if noise is None else noise.device
+                value = _LooValue.apply(self, noise, *[p[3] for p in params])
+                return value, self._loo_mean, self._loo_var
+        value = self._loo_eval()
+        return value, self._loo_mean, self._loo_var
+
+    def _loo_eval(self, want_grad=False):
+        """The value (detached; the means and variances are left in `_loo_mean` / `_loo_var`).  One library call where the engine has
+        one and `_value_only` / `_fusable_grad` would let `logpdf` take it; otherwise composed of engine primitives: the factor, K^-1."""
+        eng, n = self.eng, self.fdd.n
+        dev = self.y.device
+        if n == 0:
+            self._loo_mean = self._loo_var = torch.zeros(0, dtype=torch.float64, device=dev)
+            self._loo_parts = None
+            return torch.zeros((), dtype=torch.float64, device=dev)
+        if want_grad and hasattr(eng, "loo_dense_grad") and self._fusable_grad():
+            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
+            value, info, self._fused_loo_gradients, (A, logdet), self._loo_mean, self._loo_var = eng.loo_dense_grad(
+                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon)
+            eng.check_info(info)
+            self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
+            return value.detach()
+        if not want_grad and hasattr(eng, "loo_dense") and self._value_only():
+            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
+            value, info, self._loo_mean, self._loo_var = eng.loo_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon)
+            eng.check_info(info)
+            return value.detach()
+        fac = self.factor()
+        low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
+        Kinv = low + torch.tril(low, -1).T
+        alpha = fac.alpha().reshape(-1).detach()
+        d = torch.diagonal(Kinv)
+        b = alpha / d
+        y = self.y.reshape(-1).detach()
+        self._loo_mean, self._loo_var = y - b, 1.0 / d
+        self._loo_parts = (Kinv, alpha, d, b) if want_grad else None
+        value = torch.sum(0.5 * torch.log(d) - 0.5 * alpha * b) - 0.5 * n * _LOG_2PI
+        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+
+    def loo_gradients(self):
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the leave-one-out value, with
+        W = alpha u^T + u alpha^T - 2 K^-1 C K^-1,  b = alpha / d,  C = diag(1/2 (1 / d + b^2)),  u = K^-1 b."""
+        fused = getattr(self, "_fused_loo_gradients", None)
+        if fused is not None:
+            self._fused_loo_gradients = None
+            return fused()
+        eng, n = self.eng, self.fdd.n
+        Kinv, alpha, d, b = self._loo_parts
+        self._loo_parts = None
+        u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
+        S = eng.new_matrix(n, n)
+        S.copy_(Kinv * torch.sqrt(0.5 * (1.0 / d + b * b))[None, :])
+        W = eng.new_matrix(n, n)
+        eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
+        left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
+        left.copy_(torch.stack([alpha, u]))
+        right.copy_(torch.stack([u, alpha]))
+        eng.gemm(left, right, ta=True, alpha=1.0, beta=1.0, out=W, c_lower=True)
+        ck, _ = self.fdd.features()
+        grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
         return 0.5 * torch.diagonal(W).clone(), grads
 
     def input_gradients(self, want_x, want_z):

@@ -154,6 +154,81 @@ def logpdf_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fu
     return out, half_diag, info, A
 
 
+def _dense_layer_args(x, y, noise_diag):
+    """(n, device, flat y, pointer of the noise diagonal or None) of one dense layer, checked (the noise vector is returned too: the
+    caller keeps it alive across the call)."""
+    _check_mat(x, "x")
+    n = x.shape[0]
+    y = y.reshape(-1)
+    if y.numel() != n or y.dtype != torch.float64 or not y.is_cuda:
+        raise ValueError("y must hold one fp64 device value per row of x")
+    if noise_diag is not None:
+        noise_diag = noise_diag.reshape(-1).contiguous()
+        if noise_diag.numel() != n:
+            raise ValueError("noise_diag must hold one value per row of x")
+    return n, x.device, y, noise_diag
+
+
+def loo_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
+    """Leave-one-out value, means and variances of one dense layer in one library call (gpar_loo_dense; no inverse is formed).
+    Returns (out, loo_mean, loo_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    z = alloc_matrix(n, max(ck.dz, 1), dev)
+    A = alloc_matrix(n + 1, n + 1, dev)
+    X = alloc_matrix(n, n, dev)
+    T = alloc_matrix(n, n, dev)
+    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_LOO, n, 0, 0)), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
+    _lib.check(
+        lib.gpar_loo_dense(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
+            T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), info.data_ptr(), flags,
+            stream_ptr(dev),
+        ),
+        "gpar_loo_dense",
+    )
+    return out, moments[0], moments[1], info
+
+
+def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
+    """One dense layer's leave-one-out value AND its gradient ingredients in one library call (gpar_loo_dense_grad).  Returns
+    (out, half_diag, loo_mean, loo_var, info, A, W): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W),
+    the n predictive means and variances, info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    dz = max(ck.dz, 1)
+    z = alloc_matrix(n, dz, dev)
+    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
+    A = alloc_matrix(n + 1, n + 1, dev)
+    X = alloc_matrix(n, n, dev)
+    W = alloc_matrix(n, n, dev)
+    nt = (n + 63) // 64
+    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
+    nacc = _lib.GRAD_NACC
+    nvec = int(lib.gpar_workspace_doubles(_lib.WS_LOO, n, 1, 0))
+    work = torch.empty(nblocks * nacc + n + nvec, dtype=torch.float64, device=dev)   # gradient partials, alpha, the LOO vectors
+    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
+    vectors = torch.empty(3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
+    _lib.check(
+        lib.gpar_loo_dense_grad(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
+            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(), work[nblocks * nacc + n:].data_ptr(),
+            work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), vectors[1].data_ptr(), vectors[2].data_ptr(), info.data_ptr(), flags,
+            stream_ptr(dev),
+        ),
+        "gpar_loo_dense_grad",
+    )
+    return out, vectors[0], vectors[1], vectors[2], info, A, W
+
+
 def factor_dense_batch(items, jitter, fused=True):
     """Augmented matrices [[k_b(x_b, x_b) + diag(noise_b) + jitter I, .], [y_b^T, 0]] of layers b that share their number of rows,
     built per layer (gpar_logpdf_dense_build) into one buffer and factored in lock-step (gpar_potrf_batch).

@@ -566,6 +566,47 @@ class GPAR:
             return x, x_ind
         return total.cpu() if total.is_cuda and not total.requires_grad else total
 
+    # ---- leave-one-out cross-validation -------------------------------------------------------------
+    def loo(self, x, y, w, outputs=None):
+        """Layer-wise leave-one-out cross-validation: layer i's inputs [x, y_<i] are built and fixed exactly as `logpdf` builds them
+        (observed, imputed or replaced), and its observed entries of output i are left out one at a time, under the noise diagonal
+        noise_i / w_i.  Returns (total, pieces): the sum over the visited layers of sum_j log N(y_ij; mean_-j, var_-j) - it carries a
+        gradient with respect to kernel parameters and noise where they require one - and per visited layer (rows, mean, var, logpdf):
+        the rows of the x handed in that are observed at output i, and the leave-one-out predictive mean, variance and log-density
+        of each.  `outputs` restricts the layers visited, as for `logpdf` (x is then the design matrix reached before the first of
+        them).  Inducing points have no dense K^-1 to leave a point out of: ValueError."""
+        if self.sparse:
+            raise ValueError("leave-one-out cross-validation needs dense observations (no inducing points)")
+        return _retry_unfused(lambda: self._loo(x, y, w, outputs), self.layers, (x, y, w))
+
+    def _loo(self, x, y, w, outputs):
+        x, y, w = self._prep(x, y, w)
+        items = list(per_output(y, w, keep=self.impute))
+        eng = get_engine()
+        rows = torch.arange(int(x.shape[0]), device=x.device)
+        total, pieces = torch.zeros((), dtype=torch.float64), []
+        with eng.defer_checks():
+            for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
+                complete = isinstance(mask, slice)
+                x, rows = x[mask], rows[mask]
+                f, noise = model()
+                n_missing, keep = getattr(yi, "_n_missing", None), getattr(yi, "_obs_idx", None)   # (the host's plan: per_output)
+                obs = self._obs(x, None, yi, wi, f, noise, complete=complete)
+                obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
+                value, mean, var = obs.loo()
+                if complete or n_missing == 0:
+                    seen = rows
+                elif n_missing is not None:
+                    seen = rows.index_select(0, keep)
+                else:
+                    seen = rows[~torch.isnan(yi[:, 0])]
+                resid = obs.y.reshape(-1) - mean
+                pieces.append((seen, mean, var, -0.5 * (torch.log(2.0 * np.pi * var) + resid * resid / var)))
+                total = value if len(pieces) == 1 else total + value   # (0-d tensors: a host and a device scalar add)
+                if not is_last:
+                    x, _ = self._next_inputs(ALL_LAYERS, i, x, None, yi, f, obs, complete)
+        return (total.cpu() if total.is_cuda and not total.requires_grad else total), pieces
+
     def _independent(self, items):
         """No layer needs anything a previous layer computes: no `replace`, no inducing points, and nothing to impute - complete
         data (slice masks), or rows dropped per layer with every kept row observed (`impute=False` with missing data; known

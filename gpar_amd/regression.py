@@ -203,6 +203,16 @@ def _run_on_streams(eng, streams, shares, fn, on_exit=None):
         raise errors[0]
 
 
+def _check_objective(objective, sparse, fix):
+    """The training objectives `fit` knows, and what the leave-one-out one needs."""
+    if objective not in ("mll", "loo"):
+        raise ValueError('objective must be "mll" or "loo"')
+    if objective == "loo" and sparse:
+        raise ValueError('objective="loo" needs dense layers: not available with inducing points (x_ind)')
+    if objective == "loo" and not fix:
+        raise NotImplementedError('objective="loo" trains layers with fixed inputs (fix=True) only')
+
+
 class GPARRegressor:
     """GPAR regressor.  See the reference docstring (regression.py:200-262) for the meaning of every keyword;
     signature and defaults are identical."""
@@ -288,13 +298,18 @@ class GPARRegressor:
             self.y = torch.from_numpy((y_np - means) / stds)
         self.is_conditioned = True
 
-    def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, **kw_args):
+    def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
+
+        `objective` (an addition): "mll", the log marginal likelihood, or "loo", the layer-wise leave-one-out predictive log-density
+        (`loo`; Rasmussen & Williams 5.4.2) - more robust where the kernel family is misspecified.  "loo" needs dense layers with
+        fixed inputs: ValueError with inducing points, NotImplementedError with `fix=False`.
 
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
+        _check_objective(objective, self.sparse, fix)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -302,11 +317,13 @@ class GPARRegressor:
             raise NotImplementedError("Greedy search is not implemented yet.")
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
-        self._train(range(self.p), fix, optimise_x_ind, **kw_args)
+        self._train(range(self.p), fix, optimise_x_ind, objective=objective, **kw_args)
 
-    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, **kw_args):
+    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
+        _check_objective(objective, self.sparse, fix)
+        loo = objective == "loo"
         self._x_ind_trainable = bool(optimise_x_ind) or getattr(self, "_x_ind_trainable", False)
         layers = list(layers)
         finals = {}
@@ -328,12 +345,14 @@ class GPARRegressor:
                     x_dev, y_cached, None, only_last_layer=True, outputs=list(range(pi)), return_inputs=True
                 )
 
-            def objective(vs):
+            def neg_value(vs):
                 gpar = _construct_gpar(self, vs, self.m, pi + 1)
                 if fix:
                     x_ind_pi = fixed_x_ind
                     if optimise_x_ind:  # the m base columns are the variable; the columns appended by earlier layers stay fixed
                         x_ind_pi = torch.cat([eng.tensor(vs["x_ind"]), fixed_x_ind[:, self.m :]], dim=1)
+                    if loo:
+                        return -gpar.loo(fixed_x, y_cached, None, outputs=[pi])[0]
                     return -gpar.logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi], x_ind=x_ind_pi)
                 return -gpar.logpdf(x_dev, y_cached, None, only_last_layer=False)
 
@@ -351,17 +370,17 @@ class GPARRegressor:
 
                 def general_fg(x):   # (a failed factorisation goes through the general route's evaluation: unfused retry, NaN)
                     if not general:
-                        general.append(objective_and_gradient(objective, self.vs, names, trace=kw_args.get("trace", False))[0])
+                        general.append(objective_and_gradient(neg_value, self.vs, names, trace=kw_args.get("trace", False))[0])
                     return general[0](x)
 
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
-                                     group=group, lane=lane)
+                                     group=group, lane=lane, objective=objective)
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
             if fast is not None:
                 finals[pi] = fast.minimise(**kw_args)
             else:
-                finals[pi] = minimise_l_bfgs_b(objective, self.vs, names=names, **kw_args)
+                finals[pi] = minimise_l_bfgs_b(neg_value, self.vs, names=names, **kw_args)
             if optimise_x_ind and "x_ind" in self.vs:
                 self.x_ind = self.vs["x_ind"].detach().clone()
 
@@ -387,7 +406,7 @@ class GPARRegressor:
             lanes = min(len(streams), len(layers))
             shares = [layers[k::lanes] for k in range(lanes)]
             group = None
-            if prepared and lanes > 1 and all(isinstance(item[2], slice) for item in y_cached[bool(self.impute)]):
+            if prepared and not loo and lanes > 1 and all(isinstance(item[2], slice) for item in y_cached[bool(self.impute)]):
                 # every layer goes through the prepared objective on the same number of rows: from ~1000 rows on their
                 # factorisations are taken in lock-step, one gpar_potrf_batch per round of evaluations (fastfit.LockstepFactor)
                 from . import fastfit
@@ -418,7 +437,8 @@ class GPARRegressor:
         engine's worker streams where layers do not feed one another (complete data, no `replace`, no inducing points).
 
         Returns (order, values): `order[i]` is the column of y placed at position i, `values[i]` the log marginal likelihood of
-        that layer after training (of the normalised outputs, as `fit` sees them).  The trained hyper-parameters of the chosen
+        that layer after training (of the normalised outputs, as `fit` sees them).  With `objective="loo"` among the keyword arguments
+        the candidates are trained on, and ranked by, the layer's leave-one-out value instead (`fit`).  The trained hyper-parameters of the chosen
         chain are kept in `self.greedy_vs_` (layer i there belongs to output `order[i]`): `reg.vs = reg.greedy_vs_.copy();
         reg.fit(x, y[:, order], ...)` continues from them.  `self` is conditioned on (x, y, w) in the GIVEN order, as after
         `condition`."""
@@ -466,6 +486,31 @@ class GPARRegressor:
         self.greedy_vs_ = chain_vs
         self.greedy_order_ = list(order)
         return order, values
+
+    def loo(self, x, y, w=None):
+        """Layer-wise leave-one-out cross-validation under the prior model (`GPAR.loo`): `(value, mean, var)`.  `value` is the sum
+        over outputs and observed entries of log N(y_ij; mean_ij, var_ij), with the data handling of `logpdf(x, y, w)` (same
+        transform and normalisation calls; a numpy scalar unless x or y was a torch tensor); `mean` and `var` are n x p numpy arrays
+        of the predictive mean and variance of every observed y_ij given all other observations of output j (and the layer's inputs
+        [x, y_<j] as `logpdf` builds them), in the space the model sees the outputs in, NaN where y is missing.  With inducing points
+        there is no dense K^-1 to leave a point out of: ValueError."""
+        if self.sparse:
+            raise ValueError("leave-one-out cross-validation needs dense layers: not available with inducing points (x_ind)")
+        any_torch = isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor)
+        x = _uprank(_to_engine(x))
+        y = self._unnormalise_y(self._transform_y(_uprank(_to_engine(y))))  # (as logpdf)
+        w = _init_weights(w, y)
+        m, p = x.shape[1], y.shape[1]
+        self._prepare_kernels(m, p, int(x.shape[0]))
+        with torch.no_grad():
+            value, pieces = _construct_gpar(self, self.vs, m, p).loo(x, y, w)
+        mean = np.full((int(x.shape[0]), p), np.nan)
+        var = np.full((int(x.shape[0]), p), np.nan)
+        for i, (rows, mean_i, var_i, _) in enumerate(pieces):
+            rows = rows.cpu().numpy()
+            mean[rows, i], var[rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
+        value = value.detach() if any_torch else value.detach().cpu().numpy()
+        return value, mean, var
 
     def _prepare_kernels(self, m, p, rows, training=False, inputs=False):
         """Have the engine compile the layers' run-time specialised device kernels up front and concurrently (HipEngine.prepare);

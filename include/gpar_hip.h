@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 7
+#define GPAR_ABI_VERSION 8
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -216,6 +216,34 @@ int gpar_logpdf_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const
 int gpar_logpdf_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, double* z, double* zd,
                                   int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw, double* W, int ldw,
                                   double* alpha, double* workspace, int nblocks, double* out, double* half_diag, int* info_out, void* stream);
+
+/* Leave-one-out cross-validation of one dense layer (ABI v8).  With S = k(x, x) + diag(noise_diag) + jitter I, alpha = S^-1 y and
+ * d = diag(S^-1):  loo_mean[i] = y_i - alpha_i / d_i and loo_var[i] = 1 / d_i are the predictive mean and variance of observation i given
+ * all the others, and  out[0] = sum_i log N(y_i; loo_mean[i], loo_var[i]) = sum_i [1/2 log d_i - alpha_i^2 / (2 d_i)] - n/2 log 2 pi.
+ * gpar_loo_dense_grad mirrors gpar_logpdf_dense_grad argument for argument: out[1] = log det S, out[2 .. 2 + GPAR_GRAD_NACC) = the moment
+ * sums of 1/2 sum_ab W_ab dS_ab/dtheta (as gpar_gram_grad) and half_diag[a] = 1/2 W_aa (the derivative with respect to noise_diag[a]) for
+ *   W = alpha u^T + u alpha^T - 2 S^-1 C S^-1,   b = alpha / d,   C = diag(1/2 (1 / d + b^2)),   u = S^-1 b
+ * (Sundararajan & Keerthi 2001, eq. 10-12, collected into one weight matrix).  The launches of gpar_logpdf_dense_grad up to alpha (prep,
+ * Gram, augmented factorisation, gpar_chol_inverse; alpha by gpar_trmv_upper's sum, in one launch with the per-row quantities), then
+ * {u from the lower triangle of S^-1, S^-1 diag(sqrt c) as a full matrix into X}, W <- -2 (.)(.)^T by gpar_gemm (GPAR_GEMM_C_LOWER), the
+ * rank-2 term, gpar_gram_grad's pass, one epilogue (moment partials, 1/2 diag W, the value terms summed in a fixed order).  Workspaces as
+ * gpar_logpdf_dense_grad, plus vec: gpar_workspace_doubles(GPAR_WS_LOO, n, 1, 0) doubles; loo_mean / loo_var: n doubles each (device).
+ * gpar_loo_dense_grad_finish is the second half for a factor that already exists, as gpar_logpdf_dense_grad_finish (same bits as the one-
+ * call form for the same factor); y is read again (the factor's row n holds L^-1 y).  A failed factorisation (info != 0) leaves garbage.
+ * gpar_loo_dense: value (out[0]), log det (out[1]), means and variances only - no S^-1 is formed: alpha and d come from one pass over
+ * X = L^-T (d_i = |row i of X|^2), half the inverse's flops.  X, T: n x n workspaces; vec: gpar_workspace_doubles(GPAR_WS_LOO, n, 0, 0).
+ * [no reference counterpart: the reference scores and trains by f.measure.logpdf alone, gpar/model.py:226, gpar/regression.py:434-459] */
+int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                        const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                        double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                        double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream);
+int gpar_loo_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                               double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                               double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                               double* loo_mean, double* loo_var, int* info_out, void* stream);
+int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                   double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream);
 
 /* The same moment sums of  sum W dK/dtheta  for the other weight shapes the inducing-point (VFE) bound needs
  * [gradient of the PseudoObs elbo, gpar/model.py:226,286-287 under varz's optimiser]:
@@ -384,12 +412,14 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_GEMM_SPLITK  (m, n, splits)   gpar_gemm_splitk
  *   GPAR_WS_GEMV_T       (rows, cols, -)  gpar_gemv_t
  *   GPAR_WS_GRAM_GRAD    (nblocks, -, -)  gpar_gram_grad / gpar_gram_grad_cross
- *   GPAR_WS_CHOL_INVERSE (n, ldx, -)      the X matrix of gpar_chol_inverse */
+ *   GPAR_WS_CHOL_INVERSE (n, ldx, -)      the X matrix of gpar_chol_inverse
+ *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
 #define GPAR_WS_CHOL_INVERSE 4
 #define GPAR_WS_INPUT_GRAD 5   /* (n1, dz, nsplit)  gpar_gram_input_grad */
+#define GPAR_WS_LOO 6
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
