@@ -22,10 +22,11 @@ GEMM_K_FROM_ROW = 4
 GEMM_K_TO_COL = 8
 POTRF_NO_LOOKAHEAD = 1
 POTRF_UNFUSED = 2
-WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO = 1, 2, 3, 4, 5, 6
+WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO, WS_CV = 1, 2, 3, 4, 5, 6, 7
+CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -145,6 +146,21 @@ SIGNATURES = {
         _c_int,
         [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _c_int, _ptr, _c_int,
          _ptr, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
+    ),
+    "gpar_cv_dense_grad": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _ptr, _c_int, _ptr, _c_int,
+         _ptr, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr],
+    ),
+    "gpar_cv_dense_grad_finish": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr,
+         _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr],
+    ),
+    "gpar_cv_dense": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _c_int, _ptr, _c_int,
+         _ptr, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr],
     ),
     "gpar_logpdf_dense_build": (
         _c_int,

@@ -400,6 +400,16 @@ size_t gpar_sizeof_fspec(void) { return sizeof(gpar_fspec_t); }
 size_t gpar_sizeof_kspec(void) { return sizeof(gpar_kspec_t); }
 size_t gpar_sizeof_layer(void) { return sizeof(gpar_layer_t); }
 
+// The fold kernel of the blocked cross-validation (defined with its entry points below) and its dynamic LDS: two max_fold x CV_LD tiles
+// and two vectors.
+constexpr int CV_LD = GPAR_CV_MAX_FOLD + 1;   // (odd leading dimension: columns of a tile fall into distinct LDS banks)
+constexpr int cv_lds_bytes(int max_fold) { return (2 * max_fold * CV_LD + 2 * GPAR_CV_MAX_FOLD) * (int)sizeof(double); }
+constexpr int CV_LDS_BYTES = cv_lds_bytes(GPAR_CV_MAX_FOLD);   // 67,584 B of the 160 KiB a workgroup may claim on gfx950
+__global__ void cv_folds_kernel(const double* __restrict__ P, int ldp, int n, const double* __restrict__ X, int ldx, const double* __restrict__ zrow,
+                                const double* __restrict__ y, long incy, const int* __restrict__ fold_start, int nfolds, int max_fold,
+                                double* __restrict__ alpha, double* __restrict__ mean, double* __restrict__ var, double* __restrict__ bvec,
+                                double* __restrict__ term, double* __restrict__ Rm, int* __restrict__ info);
+
 // Everything the library creates lazily, created now: the look-ahead side stream paired with `stream`, the event ring and
 // every kernel's dynamic-LDS attribute on the device that owns `stream`.  After it, entry points called
 // on `stream` make no HIP object-creation call - the precondition of capturing them into a hipGraph (the run-time compiled
@@ -418,6 +428,7 @@ int gpar_init(void* stream) {
     const void* p2[] = {reinterpret_cast<const void*>(&potrf_panel2_kernel), reinterpret_cast<const void*>(&trsm_block2_kernel),
                         reinterpret_cast<const void*>(&trsm_block2_back_kernel), reinterpret_cast<const void*>(&trinv_blocks2_kernel)};
     for (const void* fn : p2) GPAR_HIP_TRY(gpar_set_max_lds(fn, P2_LDS_BYTES));
+    GPAR_HIP_TRY(gpar_set_max_lds(reinterpret_cast<const void*>(&cv_folds_kernel), CV_LDS_BYTES));
     return 0;
 }
 
@@ -1141,6 +1152,310 @@ int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double*
     return 0;
 }
 
+// ---- blocked (leave-fold-out) cross-validation of one dense layer (ABI v9) ------------------------------------------------------------
+// The folds F partition the rows into contiguous blocks (fold_start: nfolds + 1 ascending offsets, 0 ... n).  With P = (K + D + eps I)^-1
+// and alpha = P y, per fold  D_F = P[F, F],  b_F = D_F^-1 alpha_F:  y_F | the other rows ~ N(y_F - b_F, D_F^-1), and
+//     L = sum_F [1/2 log|D_F| - 1/2 alpha_F^T b_F] - n/2 log 2 pi,        dL/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta,
+//     W = alpha u^T + u alpha^T - 2 S S^T,   C = blockdiag(1/2 (D_F^-1 + b_F b_F^T)) = blockdiag(R_F R_F^T),  S = P blockdiag(R_F),  u = P b
+// - leave-one-out's weights with a block-diagonal C in place of the diagonal one, so everything behind S is that chain's.
+// `vec`: b, value terms, u (n each), then R_F compactly, row i of its fold in the max_fold doubles at 3 n + i max_fold
+// (gpar_workspace_doubles(GPAR_WS_CV, n, 1, max_fold)); the value-only form keeps the n value terms alone.
+
+// T (m x m, lower triangle, leading dimension CV_LD, in LDS) <- its Cholesky factor, in place, by the whole workgroup; 0 or the 1-based
+// index of the first non-positive pivot (the same verdict in every thread).  Entered and left behind a barrier.
+__device__ __forceinline__ int cv_chol_lower(double* T, int m, int t) {
+    for (int k = 0; k < m; ++k) {
+        const double d = T[k * CV_LD + k];
+        if (!(d > 0.0)) return k + 1;
+        const double sd = sqrt(d), rinv = 1.0 / sd;
+        __syncthreads();
+        if (t == k) T[k * CV_LD + k] = sd;
+        else if (t > k && t < m) T[t * CV_LD + k] *= rinv;
+        __syncthreads();
+        const int w = m - k - 1;
+        for (int idx = t; idx < w * w; idx += 256) {
+            const int i = k + 1 + idx / w, j = k + 1 + idx % w;
+            if (j <= i) T[i * CV_LD + j] = fma(-T[i * CV_LD + k], T[j * CV_LD + k], T[i * CV_LD + j]);
+        }
+        __syncthreads();
+    }
+    return 0;
+}
+
+// fold f's extent (start, size m) when it is well-formed - inside [0, n), 1 <= m <= max_fold <= GPAR_CV_MAX_FOLD, the first fold starting at
+// 0 and the last ending at n - and m = 0 otherwise
+__device__ __forceinline__ int cv_fold_extent(const int* __restrict__ fold_start, int nfolds, int max_fold, int n, int f, int& start) {
+    start = fold_start[f];
+    const int end = fold_start[f + 1], m = end - start;
+    const bool ok = start >= 0 && end <= n && m >= 1 && m <= max_fold && max_fold <= GPAR_CV_MAX_FOLD && (f > 0 || start == 0) &&
+                    (f < nfolds - 1 || end == n);
+    return ok ? m : 0;
+}
+
+// One workgroup per fold, everything in LDS (two max_fold x CV_LD tiles and two vectors).  alpha_F as trmv_upper_kernel forms it (one wave per
+// row); D_F = G G^T in place; G^-1 column by column into the second tile; D_F^-1 = G^-T G^-1 over the first; b_F, the means, the marginal
+// variances, the fold's value term (wave 0, a fixed butterfly) at the fold's first row of `term` and zeros behind it; with Rm, C_F in place
+// of D_F^-1, factored in place, its factor stored.  A non-positive pivot of either factorisation: its 1-based row into info (the first
+// to report stays, as for the factorisation of K); a malformed fold: n + 1 + fold, with nothing else touched.
+__global__ __launch_bounds__(256) void cv_folds_kernel(const double* __restrict__ P, int ldp, int n, const double* __restrict__ X, int ldx,
+                                                       const double* __restrict__ zrow, const double* __restrict__ y, long incy,
+                                                       const int* __restrict__ fold_start, int nfolds, int max_fold, double* __restrict__ alpha,
+                                                       double* __restrict__ mean, double* __restrict__ var, double* __restrict__ bvec,
+                                                       double* __restrict__ term, double* __restrict__ Rm, int* __restrict__ info) {
+    extern __shared__ double cv_sm[];
+    const int f = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    int s;
+    const int m = cv_fold_extent(fold_start, nfolds, max_fold, n, f, s);
+    if (m == 0) {
+        if (t == 0) atomicCAS(info, 0, n + 1 + f);
+        return;
+    }
+    double* TA = cv_sm;
+    double* TB = TA + max_fold * CV_LD;
+    double* al = TB + max_fold * CV_LD;
+    double* bv = al + GPAR_CV_MAX_FOLD;
+    for (int i = t >> 6; i < m; i += 4) {
+        const double a = trmv_upper_row(X, n, ldx, zrow, 1, s + i, lane);
+        if (lane == 0) {
+            al[i] = a;
+            if (alpha) alpha[s + i] = a;
+        }
+    }
+    for (int idx = t; idx < m * m; idx += 256) {
+        const int i = idx / m, j = idx - i * m;
+        if (j <= i) TA[i * CV_LD + j] = P[(size_t)(s + i) * ldp + s + j];
+    }
+    if (t < m) term[s + t] = 0.0;
+    __syncthreads();
+    int bad = cv_chol_lower(TA, m, t);
+    if (bad) {
+        if (t == 0) atomicCAS(info, 0, s + bad);
+        return;
+    }
+    const double log_g = t < m ? log(TA[t * CV_LD + t]) : 0.0;   // 1/2 log|D_F| = sum_i log G_ii
+    if (t < m) {   // column t of G^-1 by forward substitution (below the diagonal; nothing above it is read)
+        for (int i = t; i < m; ++i) {
+            double acc = i == t ? 1.0 : 0.0;
+            for (int k = t; k < i; ++k) acc = fma(-TA[i * CV_LD + k], TB[k * CV_LD + t], acc);
+            TB[i * CV_LD + t] = acc / TA[i * CV_LD + i];
+        }
+    }
+    __syncthreads();
+    for (int idx = t; idx < m * m; idx += 256) {   // D_F^-1 = G^-T G^-1, lower triangle
+        const int i = idx / m, j = idx - i * m;
+        if (j > i) continue;
+        double acc = 0.0;
+        for (int k = i; k < m; ++k) acc = fma(TB[k * CV_LD + i], TB[k * CV_LD + j], acc);
+        TA[i * CV_LD + j] = acc;
+    }
+    __syncthreads();
+    double ab = 0.0;
+    if (t < m) {
+        double acc = 0.0;
+        for (int j = 0; j <= t; ++j) acc = fma(TA[t * CV_LD + j], al[j], acc);
+        for (int j = t + 1; j < m; ++j) acc = fma(TA[j * CV_LD + t], al[j], acc);
+        bv[t] = acc;
+        ab = al[t] * acc;
+        mean[s + t] = y[(size_t)(s + t) * incy] - acc;
+        var[s + t] = TA[t * CV_LD + t];
+        if (bvec) bvec[s + t] = acc;
+    }
+    if (t < 64) {
+        const double v = wave_sum(log_g - 0.5 * ab);
+        if (t == 0) term[s] = v;
+    }
+    if (!Rm) return;
+    __syncthreads();
+    for (int idx = t; idx < m * m; idx += 256) {   // C_F = 1/2 (D_F^-1 + b_F b_F^T)
+        const int i = idx / m, j = idx - i * m;
+        if (j <= i) TA[i * CV_LD + j] = 0.5 * fma(bv[i], bv[j], TA[i * CV_LD + j]);
+    }
+    __syncthreads();
+    bad = cv_chol_lower(TA, m, t);
+    if (bad) {
+        if (t == 0) atomicCAS(info, 0, s + bad);
+        return;
+    }
+    for (int idx = t; idx < m * m; idx += 256) {
+        const int i = idx / m, j = idx - i * m;
+        Rm[(size_t)(s + i) * max_fold + j] = j <= i ? TA[i * CV_LD + j] : 0.0;
+    }
+}
+
+// blocks [0, nrb * nfolds), nrb = ceil(n / 32): S[rows of block rb, F] = P[rows, F] R_F for fold F = b / nrb, a full matrix for the product
+// S S^T.  P is read from its lower triangle alone: element (i, j) with j > i as (j, i), in a second pass whose threads run along row j, so
+// both passes read along rows; the tile and R_F meet in LDS.  The blocks behind them: u = P b as loo_weights_kernel's tail forms it.
+constexpr int CV_T = 32;
+__global__ __launch_bounds__(256) void cv_weights_kernel(const double* __restrict__ P, int ldp, int n, const int* __restrict__ fold_start, int nfolds,
+                                                         int max_fold, const double* __restrict__ Rm, const double* __restrict__ bvec,
+                                                         double* __restrict__ u, double* __restrict__ S, int lds) {
+    __shared__ double Pt[CV_T][CV_LD];
+    __shared__ double Rt[GPAR_CV_MAX_FOLD][CV_LD];
+    const int nrb = (n + CV_T - 1) / CV_T;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (b >= nrb * nfolds) {
+        const int lane = t & 63;
+        const int row = (b - nrb * nfolds) * 4 + (t >> 6);
+        if (row >= n) return;
+        const double* Pr = P + (size_t)row * ldp;
+        double a0 = 0.0, a1 = 0.0;
+        for (int j = lane; j <= row; j += 64) a0 = fma(Pr[j], bvec[j], a0);
+        for (int j = row + 1 + lane; j < n; j += 64) a1 = fma(P[(size_t)j * ldp + row], bvec[j], a1);
+        const double sum = wave_sum(a0 + a1);
+        if (lane == 0) u[row] = sum;
+        return;
+    }
+    const int f = b / nrb, r0 = (b - f * nrb) * CV_T;
+    int s;
+    const int m = cv_fold_extent(fold_start, nfolds, max_fold, n, f, s);
+    if (m == 0) return;   // (cv_folds_kernel has reported it)
+    for (int idx = t; idx < m * m; idx += 256) {
+        const int i = idx / m, j = idx - i * m;
+        Rt[i][j] = Rm[(size_t)(s + i) * max_fold + j];
+    }
+    for (int idx = t; idx < CV_T * m; idx += 256) {
+        const int r = idx / m, c = idx - r * m;
+        const int gr = r0 + r, gc = s + c;
+        if (gr < n && gc <= gr) Pt[r][c] = P[(size_t)gr * ldp + gc];
+    }
+    for (int idx = t; idx < CV_T * m; idx += 256) {
+        const int c = idx / CV_T, r = idx - c * CV_T;
+        const int gr = r0 + r, gc = s + c;
+        if (gr < n && gc > gr) Pt[r][c] = P[(size_t)gc * ldp + gr];
+    }
+    __syncthreads();
+    for (int idx = t; idx < CV_T * m; idx += 256) {
+        const int r = idx / m, j = idx - r * m;
+        const int gr = r0 + r;
+        if (gr >= n) continue;
+        double acc = 0.0;
+        for (int k = j; k < m; ++k) acc = fma(Pt[r][k], Rt[k][j], acc);
+        S[(size_t)gr * lds + s + j] = acc;
+    }
+}
+
+static int cv_check_folds(const int* fold_start, int n, int nfolds, int max_fold) {
+    if (!fold_start) return GPAR_ARG_ERROR(1);
+    if (max_fold < 1 || max_fold > GPAR_CV_MAX_FOLD) return GPAR_ARG_ERROR(3);
+    if (nfolds < 1 || nfolds > n) return GPAR_ARG_ERROR(4);
+    return 0;
+}
+
+static int cv_folds_launch(const double* P, int ldp, int n, const double* X, int ldx, const double* zrow, const double* y, long incy,
+                           const int* fold_start, int nfolds, int max_fold, double* alpha, double* mean, double* var, double* bvec, double* term,
+                           double* Rm, int* info, hipStream_t st) {
+    GPAR_HIP_TRY(gpar_set_max_lds(reinterpret_cast<const void*>(&cv_folds_kernel), CV_LDS_BYTES));
+    hipLaunchKernelGGL(cv_folds_kernel, dim3((unsigned)nfolds), dim3(256), (size_t)cv_lds_bytes(max_fold), st, P, ldp, n, X, ldx, zrow, y, incy,
+                       fold_start, nfolds, max_fold, alpha, mean, var, bvec, term, Rm, info);
+    return 0;
+}
+
+// Everything of gpar_cv_dense_grad behind the factorisation: loo_grad_finish_run with the two fold kernels in the places of its row and
+// weight kernels
+static int cv_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                              double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw, double* W, int ldw, double* alpha,
+                              double* vec, double* workspace, int nblocks, double* out, double* half_diag, double* cv_mean, double* cv_var,
+                              const int* fold_start, int nfolds, int max_fold, int* info, void* stream, bool dfreq = true) {
+    hipStream_t st = (hipStream_t)stream;
+    if (dfreq && zd && fs->dz > 0) {
+        const long total = (long)n * fs->dz;
+        hipLaunchKernelGGL(featurize_dfreq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, zd, ldz);
+    }
+    int rc = chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
+    if (rc) return rc;
+    double *bvec = vec, *term = vec + n, *u = vec + 2 * (size_t)n, *Rm = vec + 3 * (size_t)n;
+    rc = cv_folds_launch(W, ldw, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, max_fold, alpha, cv_mean, cv_var, bvec, term, Rm,
+                         info, st);
+    if (rc) return rc;
+    // u and S (into X: alpha exists, L^-T is no longer needed), then W <- -2 S S^T + alpha u^T + u alpha^T
+    const int nrb = gpar_ceil_div(n, CV_T);
+    hipLaunchKernelGGL(cv_weights_kernel, dim3((unsigned)(nrb * nfolds + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n, fold_start,
+                       nfolds, max_fold, (const double*)Rm, (const double*)bvec, u, X, ldxw);
+    rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
+    rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_grad_epilogue_kernel, dim3((unsigned)(GRAD_NACC + (n + 255) / 256 + 1)), dim3(256), 0, st, (const double*)workspace,
+                       nblocks, out, (const double*)W, ldw, n, half_diag, (const double*)term, 0.5 * (double)n * 1.8378770664093453);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+int gpar_cv_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                       const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                       double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                       double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info, int potrf_flags,
+                       void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !cv_mean || !cv_var || !info ||
+        n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    int rc = cv_check_folds(fold_start, n, nfolds, max_fold);
+    if (rc) return rc;
+    {   // the launches of gpar_logpdf_dense_grad up to the factor
+        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
+        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
+                           out + 1, info);
+    }
+    rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
+    if (rc) return rc;
+    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
+    if (rc) return rc;
+    return cv_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
+                              cv_mean, cv_var, fold_start, nfolds, max_fold, info, stream, false);
+}
+
+int gpar_cv_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                              double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                              double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                              double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !logdet || !info || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !cv_mean ||
+        !cv_var || !info_out || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = cv_check_folds(fold_start, n, nfolds, max_fold);
+    if (rc) return rc;
+    GPAR_HIP_TRY(hipMemcpyAsync(out + 1, logdet, sizeof(double), hipMemcpyDeviceToDevice, st));
+    GPAR_HIP_TRY(hipMemcpyAsync(info_out, info, sizeof(int), hipMemcpyDeviceToDevice, st));   // (the fold kernel reports into it)
+    return cv_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
+                              cv_mean, cv_var, fold_start, nfolds, max_fold, info_out, stream);
+}
+
+// Value, means and variances alone.  K^-1 is formed whole (gpar_chol_inverse) and the fold kernel shared; D_F = X_F X_F^T from the row
+// slabs of X = L^-T would halve the flops, as gpar_loo_dense does for single rows - a later optimisation.
+int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                  const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                  double* vec, double* out, double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info,
+                  int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !cv_mean || !cv_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    int rc = cv_check_folds(fold_start, n, nfolds, max_fold);
+    if (rc) return rc;
+    {
+        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
+        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, (double*)nullptr, ldz, y,
+                           incy, A, lda, out + 1, info);
+    }
+    rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
+    if (rc) return rc;
+    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
+    if (rc) return rc;
+    rc = chol_inverse_run(A, n, lda, X, ldxw, T, ldt, st);
+    if (rc) return rc;
+    rc = cv_folds_launch(T, ldt, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, max_fold, nullptr, cv_mean, cv_var, nullptr, vec,
+                         nullptr, info, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
 int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int ldz1, const double* z2, int n2, int ldz2, int dz,
                          const double* W, int ldw, int mode, int nsplit, double* workspace, double* out, int ldo, void* stream) {
     GPAR_API_GUARD;
@@ -1308,6 +1623,9 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_CHOL_INVERSE: return (long long)a * b;                             /* n, ldx: the X matrix */
         case GPAR_WS_INPUT_GRAD: return (long long)a * b * (c > 1 ? c : 1);             /* n1, dz, nsplit */
         case GPAR_WS_LOO: return (long long)(a > 0 ? a : 0) * (b ? 4 : 1);              /* n, with gradient */
+        case GPAR_WS_CV:                                                                /* n, with gradient, max_fold */
+            if (c < 1 || c > GPAR_CV_MAX_FOLD) return -1;
+            return (long long)(a > 0 ? a : 0) * (b ? 3 + c : 1);
         default: return -1;
     }
 }

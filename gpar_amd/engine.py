@@ -259,6 +259,28 @@ class HipEngine:
 
         return out[0], info, gradients, (A, out[1:2]), mean, var
 
+    def cv_dense(self, ck, x, y, noise_diag, jitter, fold_start):
+        """One dense layer's blocked cross-validation value, predictive means and marginal variances in one library call, for contiguous
+        folds of at most `_lib.CV_MAX_FOLD` rows given by their nfolds + 1 row offsets: (value as a 0-d device tensor, info word, means,
+        variances)."""
+        safe = getattr(self._tls, "safe", False)
+        depth = getattr(self._tls, "pipe_depth", 0)
+        out, mean, var, info = hip.cv_dense(ck, self._mat(x), y, noise_diag, jitter, fold_start, lookahead=not safe and depth < 3, fused=not safe)
+        return out[0], info, mean, var
+
+    def cv_dense_grad(self, ck, x, y, noise_diag, jitter, fold_start):
+        """The blocked cross-validation counterpart of `loo_dense_grad`, same conventions and return values."""
+        safe = getattr(self._tls, "safe", False)
+        depth = getattr(self._tls, "pipe_depth", 0)
+        out, half_diag, mean, var, info, A, _ = hip.cv_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), fold_start,
+                                                                  lookahead=not safe and depth < 3, fused=not safe)
+
+        def gradients():
+            raw = out[2:].cpu().numpy()
+            return half_diag, self._grads_from_moments(ck, raw, 0.5)
+
+        return out[0], info, gradients, (A, out[1:2]), mean, var
+
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""
         safe = getattr(self._tls, "safe", False)

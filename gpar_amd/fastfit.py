@@ -263,17 +263,23 @@ class LockstepFactor:
 
 class DenseLayerObjective:
     """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or, with `objective="loo"`, minus the leave-one-out predictive
-    log-density under the same covariance (gpar_loo_dense_grad) - and its gradient with respect to the latent (unconstrained)
-    variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are device tensors that do
-    not change during the optimisation."""
+    log-density under the same covariance (gpar_loo_dense_grad), or, with `objective="cv"`, minus the blocked cross-validation value
+    over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad) - and its gradient with respect to
+    the latent (unconstrained) variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are
+    device tensors that do not change during the optimisation."""
 
-    def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll"):
-        if objective not in ("mll", "loo"):
-            raise ValueError('objective must be "mll" or "loo"')
+    def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
+                 fold_start=None):
+        if objective not in ("mll", "loo", "cv"):
+            raise ValueError('objective must be "mll", "loo" or "cv"')
+        if (objective == "cv") != (fold_start is not None):
+            raise ValueError('fold_start belongs to objective="cv"')
         self.eng, self.vs, self.names = eng, vs, list(names)
         self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
-        if objective == "loo":
-            group = lane = None      # (leave-one-out lanes take no part in the lock-step rendezvous)
+        # (host offsets of the folds; their device copy is made once, with the other buffers)
+        self.fold_start = None if fold_start is None else np.asarray(fold_start, dtype=np.int64).reshape(-1)
+        if objective != "mll":
+            group = lane = None      # (cross-validation lanes take no part in the lock-step rendezvous)
         self.group, self.lane = group, lane   # a LockstepFactor and this objective's slot in it, or None
         self.kernel, self.noise, self.holders = kernel, noise_holder, holders
         self.general_fg = general_fg
@@ -316,7 +322,12 @@ class DenseLayerObjective:
         self.nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
         nacc = _lib.GRAD_NACC
         # gradient partials, alpha; for the leave-one-out objective its vectors, the predictive means and variances behind them
-        nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_LOO, n, 1, 0)) + 2 * n if self.objective == "loo" else 0
+        nloo = 0
+        if self.objective == "loo":
+            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_LOO, n, 1, 0)) + 2 * n
+        elif self.objective == "cv":
+            self.folds = hip.upload_folds(self.fold_start, n, dev)   # (device offsets, number of folds, largest fold)
+            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_CV, n, 1, self.folds[2])) + 2 * n
         self.work = torch.empty(self.nblocks * nacc + n + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
         self.res = torch.zeros(2 + nacc + n + 1, dtype=torch.float64, device=dev)
@@ -334,14 +345,14 @@ class DenseLayerObjective:
             alpha=self.work[self.nblocks * nacc:].data_ptr(), work=self.work.data_ptr(), out=self.res.data_ptr(),
             half=self.res[2 + nacc:].data_ptr(), info=self.res[2 + nacc + n:].data_ptr(),
         )
-        if self.objective == "loo":
+        if self.objective != "mll":
             at = self.nblocks * nacc + n
             self._ptrs.update(vec=self.work[at:].data_ptr(), loo_mean=self.work[at + nloo - 2 * n:].data_ptr(),
                               loo_var=self.work[at + nloo - n:].data_ptr())
 
     def _device_eval(self, ck, noise):
-        """One library call + one device-to-host copy: (the objective - log marginal likelihood or leave-one-out value -, kernel-
-        parameter gradients of it, 1/2 diag W as a host vector), or None when the factorisation reported a failure."""
+        """One library call + one device-to-host copy: (the objective - log marginal likelihood, leave-one-out or blocked cross-
+        validation value -, kernel-parameter gradients of it, 1/2 diag W as a host vector), or None when the factorisation reported a failure."""
         dev = self.X.device
         stream = torch.cuda.current_stream(dev)
         if self.unit_weights:
@@ -356,6 +367,13 @@ class DenseLayerObjective:
                 p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["vec"], p["work"], self.nblocks,
                 p["out"], p["half"], p["loo_mean"], p["loo_var"], p["info"], self.flags, stream.cuda_stream)
             _lib.check(rc, "gpar_loo_dense_grad")
+        elif self.objective == "cv":
+            starts, nfolds, max_fold = self.folds
+            rc = self.lib.gpar_cv_dense_grad(
+                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
+                p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["vec"], p["work"], self.nblocks,
+                p["out"], p["half"], p["loo_mean"], p["loo_var"], starts.data_ptr(), nfolds, max_fold, p["info"], self.flags, stream.cuda_stream)
+            _lib.check(rc, "gpar_cv_dense_grad")
         elif self.group is None:
             rc = self.lib.gpar_logpdf_dense_grad(
                 ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
@@ -475,11 +493,14 @@ class DenseLayerObjective:
         return val
 
 
-def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll"):
+def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None):
     """The fast objective of layer `pi` of regressor `reg` with fixed design matrix `fixed_x`, or None when this route does not
     apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised;
-    `objective`: "mll" (log marginal likelihood) or "loo" (leave-one-out predictive log-density)."""
+    `objective`: "mll" (log marginal likelihood), "loo" (leave-one-out predictive log-density) or "cv" (blocked cross-validation over
+    `folds`, one integer label per row of `fixed_x`: the layer's rows are sorted by label here, once; None when its largest fold
+    exceeds what the library call takes - the general route trains it)."""
     from .gp import one_call_grad_rows
+    from .model import contiguous_folds, host_index
     from .regression import _model_generator
 
     on_device = cls is None   # (the CPU tests of the host logic hand in a class with its own device side)
@@ -504,6 +525,17 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     n = int(X.shape[0])
     if not 0 < n <= one_call_grad_rows():
         return None
+    fold_start = None
+    if objective == "cv":
+        labels = np.asarray(folds).reshape(-1)[host_index(mask)]
+        if not isinstance(mask, slice) and n_missing:
+            labels = labels[host_index(keep)]
+        perm, fold_start = contiguous_folds(labels)
+        if int(np.diff(fold_start).max()) > _lib.CV_MAX_FOLD:
+            return None
+        if perm is not None:
+            at = torch.as_tensor(perm, dtype=torch.long, device=X.device)
+            X, yi, wi = X.index_select(0, at), yi.index_select(0, at), wi.index_select(0, at)
     tracer = _TracingVars(vs)
     f, noise = _model_generator(tracer, reg.m, pi, **reg.model_config)()
     kernel = f.kernel
@@ -514,7 +546,7 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     names = vs.match(names)   # (globs; resolved now that the layer's variables exist)
     if not names:
         return None
-    if group is not None and (group.n != n or not on_device or objective == "loo"):
+    if group is not None and (group.n != n or not on_device or objective != "mll"):
         group = None
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
-               lane=lane if group is not None else None, objective=objective)
+               lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}))

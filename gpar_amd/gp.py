@@ -37,7 +37,9 @@ import math
 import numpy as np
 import torch
 
+from ._lib import CV_MAX_FOLD
 from .engine import get_engine, joining
+from .hip import fold_offsets
 from .kernels import Kernel
 
 __all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs"]
@@ -310,6 +312,36 @@ class _LooValue(torch.autograd.Function):
         if ctx.noise_shape is not None:
             out_noise = _shaped_noise_grad(noise_grad * gval, ctx.noise_shape, obs._noise_device)
         return (None, out_noise, *_param_grads(obs._params, ctx.shapes, grads, gval))
+
+
+class _CvValue(torch.autograd.Function):
+    """The blocked cross-validation value sum_F log N(y_F; mean_-F, cov_-F) over contiguous folds F of dense observations of a prior
+    process as a differentiable function of the kernel parameters and the noise vector.  Forward: `Obs._cv_eval`.  Backward: the
+    weighted-sum pass of `_LooValue` with a block-diagonal C (`Obs.cv_gradients`).  The inputs are not differentiated."""
+
+    @staticmethod
+    def forward(ctx, obs, starts, noise, *tensors):
+        ctx.obs = obs
+        ctx.noise_shape = None if noise is None else tuple(noise.shape)
+        ctx.shapes = [tuple(t.shape) for t in tensors]
+        return obs._cv_eval(starts, want_grad=True)
+
+    @staticmethod
+    def backward(ctx, g):
+        obs = ctx.obs
+        noise_grad, grads = obs.cv_gradients()
+        gval = float(g)
+        out_noise = None
+        if ctx.noise_shape is not None:
+            out_noise = _shaped_noise_grad(noise_grad * gval, ctx.noise_shape, obs._noise_device)
+        return (None, None, out_noise, *_param_grads(obs._params, ctx.shapes, grads, gval))
+
+
+def _fold_groups(starts, device):
+    """Folds of equal size share batched block algebra: [(size m, k x m index tensor of the rows of the k folds of that size)]."""
+    sizes, first = np.diff(starts), starts[:-1]
+    return [(int(m), torch.as_tensor(first[sizes == m][:, None] + np.arange(m)[None, :], dtype=torch.long, device=device))
+            for m in np.unique(sizes)]
 
 
 class _PosteriorMean(torch.autograd.Function):
@@ -750,6 +782,100 @@ class Obs:
         u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
         S = eng.new_matrix(n, n)
         S.copy_(Kinv * torch.sqrt(0.5 * (1.0 / d + b * b))[None, :])
+        W = eng.new_matrix(n, n)
+        eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
+        left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
+        left.copy_(torch.stack([alpha, u]))
+        right.copy_(torch.stack([u, alpha]))
+        eng.gemm(left, right, ta=True, alpha=1.0, beta=1.0, out=W, c_lower=True)
+        ck, _ = self.fdd.features()
+        grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
+        return 0.5 * torch.diagonal(W).clone(), grads
+
+    # ---- blocked cross-validation ---------------------------------------------------------------------------
+    def cv(self, fold_start):
+        """(value, mean, var) of blocked (leave-fold-out) cross-validation over contiguous folds of the observations, given by their
+        nfolds + 1 ascending row offsets (0 ... n).  With P = S^-1, alpha = P (y - m) and per fold D_F = P[F, F], b_F = D_F^-1 alpha_F:
+        y_F given all other observations ~ N(y_F - b_F, D_F^-1); mean and var hold y_F - b_F and the marginal variances diag D_F^-1, and
+        value = sum_F log N(y_F; y_F - b_F, D_F^-1), the JOINT fold densities - a 0-d tensor that carries a gradient with respect to
+        the kernel parameters and the noise where they require one (observations of a prior process).  Folds of one row give `loo`;
+        one fold of every row gives `logpdf`."""
+        starts = fold_offsets(fold_start, self.fdd.n)
+        if torch.is_grad_enabled():
+            params = kernel_parameters(self.base.kernel)
+            noise = self.fdd.noise_arg if _needs_grad(self.fdd.noise_arg) else None
+            if params or noise is not None:
+                if self.base.is_posterior or self.fdd.x.requires_grad:
+                    raise NotImplementedError("the cross-validation gradient covers kernel parameters and noise of a prior process")
+                self._params = params
+                self._noise_device = None if noise is None else noise.device
+                value = _CvValue.apply(self, starts, noise, *[p[3] for p in params])
+                return value, self._cv_mean, self._cv_var
+        value = self._cv_eval(starts)
+        return value, self._cv_mean, self._cv_var
+
+    def _cv_eval(self, starts, want_grad=False):
+        """The value (detached; the means and variances are left in `_cv_mean` / `_cv_var`).  One library call where the engine has one,
+        `_value_only` / `_fusable_grad` would let `logpdf` take it and no fold exceeds the call's limit; otherwise composed of engine
+        primitives (the factor, K^-1) and batched torch algebra on the fold blocks, for folds of any size."""
+        eng, n = self.eng, self.fdd.n
+        dev = self.y.device
+        if n == 0:
+            self._cv_mean = self._cv_var = torch.zeros(0, dtype=torch.float64, device=dev)
+            self._cv_parts = None
+            return torch.zeros((), dtype=torch.float64, device=dev)
+        fits = int(np.diff(starts).max()) <= CV_MAX_FOLD
+        if want_grad and fits and hasattr(eng, "cv_dense_grad") and self._fusable_grad():
+            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
+            value, info, self._fused_cv_gradients, (A, logdet), self._cv_mean, self._cv_var = eng.cv_dense_grad(
+                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, starts)
+            eng.check_info(info)
+            self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
+            return value.detach()
+        if not want_grad and fits and hasattr(eng, "cv_dense") and self._value_only():
+            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
+            value, info, self._cv_mean, self._cv_var = eng.cv_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, starts)
+            eng.check_info(info)
+            return value.detach()
+        fac = self.factor()
+        low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
+        Kinv = low + torch.tril(low, -1).T
+        alpha = fac.alpha().reshape(-1).detach()
+        b, var = torch.empty_like(alpha), torch.empty_like(alpha)
+        value = torch.zeros((), dtype=torch.float64, device=alpha.device)
+        blocks = []
+        for m, idx in _fold_groups(starts, alpha.device):
+            D = Kinv[idx[:, :, None], idx[:, None, :]]   # k x m x m
+            G, info = torch.linalg.cholesky_ex(D)
+            eng.check_info(info.max().reshape(1).to(torch.int32))   # (one word: the largest failing pivot of the group, 0 if none)
+            Dinv = torch.cholesky_inverse(G)
+            a_f = alpha[idx]
+            b_f = torch.matmul(Dinv, a_f[:, :, None])[:, :, 0]
+            b[idx], var[idx] = b_f, torch.diagonal(Dinv, dim1=1, dim2=2)
+            value = value + torch.sum(torch.log(torch.diagonal(G, dim1=1, dim2=2))) - 0.5 * torch.sum(a_f * b_f)
+            blocks.append((idx, Dinv, b_f))
+        y = self.y.reshape(-1).detach()
+        self._cv_mean, self._cv_var = y - b, var
+        self._cv_parts = (Kinv, alpha, b, blocks) if want_grad else None
+        value = value - 0.5 * n * _LOG_2PI
+        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+
+    def cv_gradients(self):
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the blocked cross-validation value, with
+        W = alpha u^T + u alpha^T - 2 K^-1 C K^-1,  C = blockdiag(1/2 (D_F^-1 + b_F b_F^T)) = blockdiag(R_F R_F^T),  u = K^-1 b."""
+        fused = getattr(self, "_fused_cv_gradients", None)
+        if fused is not None:
+            self._fused_cv_gradients = None
+            return fused()
+        eng, n = self.eng, self.fdd.n
+        Kinv, alpha, b, blocks = self._cv_parts
+        self._cv_parts = None
+        u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
+        S = eng.new_matrix(n, n)
+        for idx, Dinv, b_f in blocks:   # S[:, F] = K^-1[:, F] R_F
+            R = torch.linalg.cholesky(0.5 * (Dinv + b_f[:, :, None] * b_f[:, None, :]))
+            cols = torch.matmul(Kinv[:, idx].permute(1, 0, 2), R)   # k x n x m
+            S[:, idx.reshape(-1)] = cols.permute(1, 0, 2).reshape(n, -1)
         W = eng.new_matrix(n, n)
         eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
         left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)

@@ -8,6 +8,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -225,6 +226,89 @@ def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused
             stream_ptr(dev),
         ),
         "gpar_loo_dense_grad",
+    )
+    return out, vectors[0], vectors[1], vectors[2], info, A, W
+
+
+def fold_offsets(fold_start, n):
+    """The nfolds + 1 row offsets of contiguous folds over n rows as a checked host array (int64): ascending strictly from 0 to n
+    (no rows: the single offset 0).  The one check of fold offsets: `gp.Obs.cv` and `upload_folds` both go through it."""
+    starts = np.asarray(fold_start.cpu() if isinstance(fold_start, torch.Tensor) else fold_start, dtype=np.int64).reshape(-1)
+    if n == 0 and starts.size <= 1:
+        return np.zeros(1, dtype=np.int64)
+    if starts.size < 2 or starts[0] != 0 or starts[-1] != n or np.any(np.diff(starts) < 1):
+        raise ValueError("fold_start must ascend strictly from 0 to the number of rows")
+    return starts
+
+
+def upload_folds(fold_start, n, device):
+    """(device int32 array of the nfolds + 1 row offsets, nfolds, largest fold): what the fused cross-validation entries take, from
+    offsets checked by `fold_offsets`; a fold larger than GPAR_CV_MAX_FOLD is a ValueError."""
+    starts = fold_offsets(fold_start, n)
+    sizes = np.diff(starts)
+    if sizes.size == 0 or int(sizes.max()) > _lib.CV_MAX_FOLD:
+        raise ValueError(f"the fused cross-validation takes 1 to {_lib.CV_MAX_FOLD} rows per fold")
+    return torch.tensor(starts, dtype=torch.int32, device=device), int(sizes.size), int(sizes.max())
+
+
+def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=True):
+    """Blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_dense).
+    `fold_start`: the nfolds + 1 row offsets of the contiguous folds (host sequence, or the triple `upload_folds` returns).
+    Returns (out, cv_mean, cv_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    starts, nfolds, max_fold = fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
+    z = alloc_matrix(n, max(ck.dz, 1), dev)
+    A = alloc_matrix(n + 1, n + 1, dev)
+    X = alloc_matrix(n, n, dev)
+    T = alloc_matrix(n, n, dev)
+    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_CV, n, 0, max_fold)), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
+    _lib.check(
+        lib.gpar_cv_dense(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
+            T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), starts.data_ptr(), nfolds, max_fold,
+            info.data_ptr(), flags, stream_ptr(dev),
+        ),
+        "gpar_cv_dense",
+    )
+    return out, moments[0], moments[1], info
+
+
+def cv_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead=True, fused=True):
+    """One dense layer's blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_dense_grad).
+    `fold_start` as for `cv_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    starts, nfolds, max_fold = fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
+    dz = max(ck.dz, 1)
+    z = alloc_matrix(n, dz, dev)
+    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
+    A = alloc_matrix(n + 1, n + 1, dev)
+    X = alloc_matrix(n, n, dev)
+    W = alloc_matrix(n, n, dev)
+    nt = (n + 63) // 64
+    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
+    nacc = _lib.GRAD_NACC
+    nvec = int(lib.gpar_workspace_doubles(_lib.WS_CV, n, 1, max_fold))
+    work = torch.empty(nblocks * nacc + n + nvec, dtype=torch.float64, device=dev)   # gradient partials, alpha, the fold workspace
+    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
+    vectors = torch.empty(3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
+    _lib.check(
+        lib.gpar_cv_dense_grad(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
+            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(), work[nblocks * nacc + n:].data_ptr(),
+            work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), vectors[1].data_ptr(), vectors[2].data_ptr(), starts.data_ptr(), nfolds,
+            max_fold, info.data_ptr(), flags, stream_ptr(dev),
+        ),
+        "gpar_cv_dense_grad",
     )
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 

@@ -201,6 +201,32 @@ def _differentiable(f, noise):
     return (_is_torch(noise) and noise.requires_grad) or bool(kernel_parameters(f.kernel))
 
 
+def host_index(sel):
+    """A row selection (slice, index tensor or boolean tensor) for a numpy array.  The host copy of a tensor is kept on the tensor
+    (as per_output's plan is): the masks of a cached per_output serve every evaluation of a training run, and only the first one
+    waits for the device."""
+    if isinstance(sel, slice):
+        return sel
+    host = getattr(sel, "_host_index", None)
+    if host is None:
+        host = sel._host_index = sel.cpu().numpy()
+    return host
+
+
+def contiguous_folds(labels):
+    """(perm, starts) for one integer fold label per row: the stable permutation that sorts the rows by label - None where they
+    already ascend, the blocked time-series case - and the nfolds + 1 row offsets of the folds in that order."""
+    labels = np.asarray(labels).reshape(-1)
+    if labels.size == 0:
+        return None, np.zeros(1, dtype=np.int64)
+    perm = None
+    if np.any(np.diff(labels) < 0):
+        perm = np.argsort(labels, kind="stable")
+        labels = labels[perm]
+    starts = np.concatenate([[0], np.nonzero(np.diff(labels))[0] + 1, [labels.size]]).astype(np.int64)
+    return perm, starts
+
+
 def per_output(y, w=None, keep=False):
     """Per layer: `(y_i (n_i x 1), w_i (n_i,), mask_i)` where `mask_i` selects, among the rows that survived
     layer i-1, those observed at output i (or, with `keep`, at any later output: rows needed to keep the data
@@ -602,6 +628,64 @@ class GPAR:
                     seen = rows[~torch.isnan(yi[:, 0])]
                 resid = obs.y.reshape(-1) - mean
                 pieces.append((seen, mean, var, -0.5 * (torch.log(2.0 * np.pi * var) + resid * resid / var)))
+                total = value if len(pieces) == 1 else total + value   # (0-d tensors: a host and a device scalar add)
+                if not is_last:
+                    x, _ = self._next_inputs(ALL_LAYERS, i, x, None, yi, f, obs, complete)
+        return (total.cpu() if total.is_cuda and not total.requires_grad else total), pieces
+
+    # ---- blocked cross-validation ---------------------------------------------------------------------
+    def cv(self, x, y, w, folds, outputs=None):
+        """Layer-wise blocked (leave-fold-out) cross-validation: `loo` with whole folds held out and scored by their joint predictive
+        density.  `folds`: one integer label per row of the x handed in; per layer the labels are restricted to the rows observed at
+        that output (folds left empty vanish) and each fold's observed entries are left out together.  Returns (total, pieces): the
+        sum over the visited layers and folds of log N(y_F; mean_-F, cov_-F) - it carries a gradient with respect to kernel parameters
+        and noise where they require one - and per visited layer (rows, mean, var): the rows of the x handed in that are observed at
+        output i, in their order there, with the predictive mean and marginal variance of each given every fold but its own.  Rows
+        are sorted by label (stably; not at all where the labels already ascend) for the evaluation alone: the inputs forwarded to the
+        next layer keep their order.  `outputs` as for `loo`.  Inducing points: ValueError."""
+        if self.sparse:
+            raise ValueError("cross-validation needs dense observations (no inducing points)")
+        labels = np.asarray(folds.cpu() if _is_torch(folds) else folds).reshape(-1)
+        if labels.size != int(x.shape[0]) or not np.issubdtype(labels.dtype, np.integer):
+            raise ValueError("folds must hold one integer label per row of x")
+        return _retry_unfused(lambda: self._cv(x, y, w, labels, outputs), self.layers, (x, y, w))
+
+    def _cv(self, x, y, w, labels, outputs):
+        x, y, w = self._prep(x, y, w)
+        items = list(per_output(y, w, keep=self.impute))
+        eng = get_engine()
+        rows = torch.arange(int(x.shape[0]), device=x.device)
+        rows_host = np.arange(int(x.shape[0]))   # (the same rows on the host: the labels live there)
+        total, pieces = torch.zeros((), dtype=torch.float64), []
+        with eng.defer_checks():
+            for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
+                complete = isinstance(mask, slice)
+                x, rows, rows_host = x[mask], rows[mask], rows_host[host_index(mask)]
+                f, noise = model()
+                n_missing, keep = getattr(yi, "_n_missing", None), getattr(yi, "_obs_idx", None)   # (the host's plan: per_output)
+                obs = self._obs(x, None, yi, wi, f, noise, complete=complete)
+                if complete or n_missing == 0:
+                    seen, seen_host = rows, rows_host
+                elif n_missing is not None:
+                    seen, seen_host = rows.index_select(0, keep), rows_host[host_index(keep)]
+                else:
+                    observed = ~torch.isnan(yi[:, 0])
+                    seen, seen_host = rows[observed], rows_host[host_index(observed)]
+                perm, starts = contiguous_folds(labels[seen_host])
+                if perm is None:
+                    obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
+                    value, mean, var = obs.cv(starts)
+                else:
+                    # the evaluation's own observations, rows sorted by fold; `obs` keeps the order the next layer reads
+                    at = torch.as_tensor(perm, dtype=torch.long, device=obs.y.device)
+                    noise_arg = obs.fdd.noise_arg
+                    if _is_torch(noise_arg) and noise_arg.numel() > 1:
+                        noise_arg = noise_arg.reshape(-1).index_select(0, at)
+                    sorted_obs = Obs(f(obs.fdd.x.index_select(0, at), noise_arg), obs.y.index_select(0, at))
+                    sorted_obs.transient = True
+                    value, mean, var = sorted_obs.cv(starts)
+                    mean, var = torch.empty_like(mean).index_copy_(0, at, mean), torch.empty_like(var).index_copy_(0, at, var)
+                pieces.append((seen, mean, var))
                 total = value if len(pieces) == 1 else total + value   # (0-d tensors: a host and a device scalar add)
                 if not is_last:
                     x, _ = self._next_inputs(ALL_LAYERS, i, x, None, yi, f, obs, complete)

@@ -16,7 +16,7 @@ import torch
 from .engine import get_engine
 from .gp import GP, Measure
 from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
-from .model import GPAR, host_masks, per_output
+from .model import GPAR, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
 from .vars import Vars
 
@@ -203,14 +203,40 @@ def _run_on_streams(eng, streams, shares, fn, on_exit=None):
         raise errors[0]
 
 
-def _check_objective(objective, sparse, fix):
-    """The training objectives `fit` knows, and what the leave-one-out one needs."""
-    if objective not in ("mll", "loo"):
-        raise ValueError('objective must be "mll" or "loo"')
-    if objective == "loo" and sparse:
-        raise ValueError('objective="loo" needs dense layers: not available with inducing points (x_ind)')
-    if objective == "loo" and not fix:
-        raise NotImplementedError('objective="loo" trains layers with fixed inputs (fix=True) only')
+def _check_objective(objective, sparse, fix, folds=None):
+    """The training objectives `fit` knows, and what the cross-validation ones need."""
+    if objective not in ("mll", "loo", "cv"):
+        raise ValueError('objective must be "mll", "loo" or "cv"')
+    if objective == "cv" and folds is None:
+        raise ValueError('objective="cv" needs folds: a number of contiguous blocks or one integer label per row')
+    if objective != "cv" and folds is not None:
+        raise ValueError('folds belong to objective="cv"')
+    if objective != "mll" and sparse:
+        raise ValueError(f'objective="{objective}" needs dense layers: not available with inducing points (x_ind)')
+    if objective != "mll" and not fix:
+        raise NotImplementedError(f'objective="{objective}" trains layers with fixed inputs (fix=True) only')
+
+
+def _fold_labels(folds, n):
+    """`folds` of `cv` / `fit(objective="cv")` as one integer label per row: an int k stands for k contiguous blocks of the rows as
+    given, split as `np.array_split` splits them; a 1-D integer array of n labels is taken as it is."""
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
+        k = int(folds)
+        if not 1 <= k <= n:
+            raise ValueError(f"folds={k}: the number of blocks must lie between 1 and the number of rows ({n})")
+        return np.concatenate([np.full(len(part), j, dtype=np.int64) for j, part in enumerate(np.array_split(np.arange(n), k))])
+    labels = np.asarray(folds.cpu() if isinstance(folds, torch.Tensor) else folds)
+    if labels.ndim != 1 or labels.size != n or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"folds must be a number of blocks or a 1-D array of {n} integer labels, one per row")
+    return labels.astype(np.int64)
+
+
+def _surviving_rows(items, pi, n):
+    """The rows of the conditioned data that reach layer `pi`: those the masks of the earlier layers (`model.per_output`) keep."""
+    rows = np.arange(n)
+    for _, _, mask in items[:pi]:
+        rows = rows[host_index(mask)]
+    return rows
 
 
 class GPARRegressor:
@@ -298,18 +324,20 @@ class GPARRegressor:
             self.y = torch.from_numpy((y_np - means) / stds)
         self.is_conditioned = True
 
-    def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", **kw_args):
+    def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
 
         `objective` (an addition): "mll", the log marginal likelihood, or "loo", the layer-wise leave-one-out predictive log-density
         (`loo`; Rasmussen & Williams 5.4.2) - more robust where the kernel family is misspecified.  "loo" needs dense layers with
-        fixed inputs: ValueError with inducing points, NotImplementedError with `fix=False`.
+        fixed inputs: ValueError with inducing points, NotImplementedError with `fix=False`.  "cv" is the blocked form for ordered data
+        (`cv`): whole folds are held out and scored by their joint predictive density; it needs `folds` (as `cv` takes them), which
+        no other objective accepts, and has the restrictions of "loo".
 
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
-        _check_objective(objective, self.sparse, fix)
+        _check_objective(objective, self.sparse, fix, folds)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -317,13 +345,14 @@ class GPARRegressor:
             raise NotImplementedError("Greedy search is not implemented yet.")
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
-        self._train(range(self.p), fix, optimise_x_ind, objective=objective, **kw_args)
+        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, **kw_args)
 
-    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", **kw_args):
+    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
-        _check_objective(objective, self.sparse, fix)
-        loo = objective == "loo"
+        _check_objective(objective, self.sparse, fix, folds)
+        loo, cv = objective == "loo", objective == "cv"
+        labels = _fold_labels(folds, self.n) if cv else None
         self._x_ind_trainable = bool(optimise_x_ind) or getattr(self, "_x_ind_trainable", False)
         layers = list(layers)
         finals = {}
@@ -344,6 +373,8 @@ class GPARRegressor:
                 fixed_x, fixed_x_ind = gpar.logpdf(
                     x_dev, y_cached, None, only_last_layer=True, outputs=list(range(pi)), return_inputs=True
                 )
+            # (the fold labels of the rows that reach this layer: earlier layers' masks have dropped the others from fixed_x)
+            layer_labels = labels[_surviving_rows(y_cached[bool(self.impute)], pi, self.n)] if cv else None
 
             def neg_value(vs):
                 gpar = _construct_gpar(self, vs, self.m, pi + 1)
@@ -353,6 +384,8 @@ class GPARRegressor:
                         x_ind_pi = torch.cat([eng.tensor(vs["x_ind"]), fixed_x_ind[:, self.m :]], dim=1)
                     if loo:
                         return -gpar.loo(fixed_x, y_cached, None, outputs=[pi])[0]
+                    if cv:
+                        return -gpar.cv(fixed_x, y_cached, None, layer_labels, outputs=[pi])[0]
                     return -gpar.logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi], x_ind=x_ind_pi)
                 return -gpar.logpdf(x_dev, y_cached, None, only_last_layer=False)
 
@@ -374,7 +407,7 @@ class GPARRegressor:
                     return general[0](x)
 
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
-                                     group=group, lane=lane, objective=objective)
+                                     group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv else {}))
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
             if fast is not None:
@@ -406,7 +439,7 @@ class GPARRegressor:
             lanes = min(len(streams), len(layers))
             shares = [layers[k::lanes] for k in range(lanes)]
             group = None
-            if prepared and not loo and lanes > 1 and all(isinstance(item[2], slice) for item in y_cached[bool(self.impute)]):
+            if prepared and not loo and not cv and lanes > 1 and all(isinstance(item[2], slice) for item in y_cached[bool(self.impute)]):
                 # every layer goes through the prepared objective on the same number of rows: from ~1000 rows on their
                 # factorisations are taken in lock-step, one gpar_potrf_batch per round of evaluations (fastfit.LockstepFactor)
                 from . import fastfit
@@ -438,7 +471,8 @@ class GPARRegressor:
 
         Returns (order, values): `order[i]` is the column of y placed at position i, `values[i]` the log marginal likelihood of
         that layer after training (of the normalised outputs, as `fit` sees them).  With `objective="loo"` among the keyword arguments
-        the candidates are trained on, and ranked by, the layer's leave-one-out value instead (`fit`).  The trained hyper-parameters of the chosen
+        the candidates are trained on, and ranked by, the layer's leave-one-out value instead (`fit`); with `objective="cv", folds=...` by its
+        blocked cross-validation value.  The trained hyper-parameters of the chosen
         chain are kept in `self.greedy_vs_` (layer i there belongs to output `order[i]`): `reg.vs = reg.greedy_vs_.copy();
         reg.fit(x, y[:, order], ...)` continues from them.  `self` is conditioned on (x, y, w) in the GIVEN order, as after
         `condition`."""
@@ -507,6 +541,36 @@ class GPARRegressor:
         mean = np.full((int(x.shape[0]), p), np.nan)
         var = np.full((int(x.shape[0]), p), np.nan)
         for i, (rows, mean_i, var_i, _) in enumerate(pieces):
+            rows = rows.cpu().numpy()
+            mean[rows, i], var[rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
+        value = value.detach() if any_torch else value.detach().cpu().numpy()
+        return value, mean, var
+
+    def cv(self, x, y, w=None, folds=None):
+        """Layer-wise blocked (leave-fold-out) cross-validation under the prior model (`GPAR.cv`): `(value, mean, var)` with the
+        conventions of `loo`.  `folds`: an int k - k contiguous blocks of the rows as given, split as `np.array_split` splits them, the
+        estimator for time series and other ordered data, where a single left-out point is predicted almost for free from its
+        neighbours - or a 1-D integer array of n labels (any order; per output the labels are restricted to its observed rows, and a
+        fold left empty vanishes).  `value` is the sum over outputs and folds of the JOINT log-density of the fold's observed entries
+        given every other fold's; `mean` and `var` are n x p numpy arrays of the predictive means and marginal variances (the diagonals
+        of the folds' predictive covariances), NaN where y is missing.  Folds of one row give `loo`; one fold gives `logpdf` for one
+        output.  Dense layers only: ValueError with inducing points."""
+        if self.sparse:
+            raise ValueError("cross-validation needs dense layers: not available with inducing points (x_ind)")
+        if folds is None:
+            raise ValueError("cv needs folds: a number of contiguous blocks or one integer label per row")
+        any_torch = isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor)
+        x = _uprank(_to_engine(x))
+        y = self._unnormalise_y(self._transform_y(_uprank(_to_engine(y))))  # (as logpdf)
+        w = _init_weights(w, y)
+        m, p = x.shape[1], y.shape[1]
+        labels = _fold_labels(folds, int(x.shape[0]))
+        self._prepare_kernels(m, p, int(x.shape[0]))
+        with torch.no_grad():
+            value, pieces = _construct_gpar(self, self.vs, m, p).cv(x, y, w, labels)
+        mean = np.full((int(x.shape[0]), p), np.nan)
+        var = np.full((int(x.shape[0]), p), np.nan)
+        for i, (rows, mean_i, var_i) in enumerate(pieces):
             rows = rows.cpu().numpy()
             mean[rows, i], var[rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
         value = value.detach() if any_torch else value.detach().cpu().numpy()

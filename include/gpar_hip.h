@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 8
+#define GPAR_ABI_VERSION 9
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -245,6 +245,43 @@ int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double*
                    const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
                    double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream);
 
+/* Blocked (leave-fold-out) cross-validation of one dense layer (ABI v9): leave-one-out with whole contiguous blocks of rows held out and
+ * scored by their JOINT predictive density - the estimator for ordered data, where a single left-out point is predicted almost for free
+ * from its neighbours.  fold_start: a DEVICE array of nfolds + 1 ascending row offsets, fold_start[0] = 0, fold_start[nfolds] = n; fold f
+ * holds the rows [fold_start[f], fold_start[f + 1]) in the order handed in.  max_fold: the host's bound on the largest fold,
+ * 1 <= max_fold <= GPAR_CV_MAX_FOLD (otherwise an argument error: nothing is launched).  With S = k(x, x) + diag(noise_diag) + jitter I,
+ * P = S^-1, alpha = P y and per fold D_F = P[F, F], b_F = D_F^-1 alpha_F:  y_F given all other rows ~ N(y_F - b_F, D_F^-1), so
+ *   cv_mean[F] = y_F - b_F,  cv_var[F] = diag(D_F^-1) (the marginal variances),
+ *   out[0] = sum_F [1/2 log|D_F| - 1/2 alpha_F^T b_F] - n/2 log 2 pi   (the joint fold densities).
+ * Folds of size 1 give gpar_loo_dense*; one fold of all rows gives the log marginal likelihood.
+ * gpar_cv_dense_grad mirrors gpar_loo_dense_grad argument for argument (fold_start, nfolds, max_fold before info): out[1] = log det S,
+ * out[2 .. 2 + GPAR_GRAD_NACC) and half_diag as there, for the weights
+ *   W = alpha u^T + u alpha^T - 2 P C P,   C = blockdiag(1/2 (D_F^-1 + b_F b_F^T)),   u = P b.
+ * Its launches: those of gpar_loo_dense_grad with the fold kernel (one workgroup per fold, in LDS: alpha_F, D_F = G G^T, D_F^-1, b_F, the
+ * moments, the fold's value term, C_F = R_F R_F^T) in the place of the row kernel and {u, P blockdiag(R_F) as a full matrix into X} in the
+ * place of {u, P diag(sqrt c)}.  vec: gpar_workspace_doubles(GPAR_WS_CV, n, 1, max_fold) doubles.  gpar_cv_dense_grad_finish is the second
+ * half for a factor that already exists (same bits); info and info_out are both required (the fold kernel reports into info_out).
+ * gpar_cv_dense: value, log det, means and variances; it forms P whole (X, T: n x n workspaces, T receives P) and shares the fold kernel;
+ * vec: gpar_workspace_doubles(GPAR_WS_CV, n, 0, max_fold).
+ * info, besides the factorisation's own codes: the 1-based row of a non-positive pivot in a fold's D_F or C_F; n + 1 + f for a fold f
+ * whose extent in fold_start is not positive, exceeds max_fold or leaves [0, n) (that fold is then skipped).  Results are garbage then.
+ * Limits: dense layers; folds of at most GPAR_CV_MAX_FOLD rows (larger folds: compose gpar_chol_inverse with host-side block algebra).
+ * [no reference counterpart] */
+#define GPAR_CV_MAX_FOLD 64
+int gpar_cv_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                       const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                       double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                       double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info, int potrf_flags,
+                       void* stream);
+int gpar_cv_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                              double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                              double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                              double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info_out, void* stream);
+int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                  const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                  double* vec, double* out, double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info,
+                  int potrf_flags, void* stream);
+
 /* The same moment sums of  sum W dK/dtheta  for the other weight shapes the inducing-point (VFE) bound needs
  * [gradient of the PseudoObs elbo, gpar/model.py:226,286-287 under varz's optimiser]:
  *   GPAR_GRAD_SYM   z2 == z1: W symmetric n1 x n1, lower triangle read, sum over all pairs (what gpar_gram_grad does);
@@ -413,13 +450,15 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_GEMV_T       (rows, cols, -)  gpar_gemv_t
  *   GPAR_WS_GRAM_GRAD    (nblocks, -, -)  gpar_gram_grad / gpar_gram_grad_cross
  *   GPAR_WS_CHOL_INVERSE (n, ldx, -)      the X matrix of gpar_chol_inverse
- *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1) */
+ *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1)
+ *   GPAR_WS_CV           (n, grad, max_fold)  the `vec` of gpar_cv_dense (grad = 0) / gpar_cv_dense_grad[_finish] (grad = 1) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
 #define GPAR_WS_CHOL_INVERSE 4
 #define GPAR_WS_INPUT_GRAD 5   /* (n1, dz, nsplit)  gpar_gram_input_grad */
 #define GPAR_WS_LOO 6
+#define GPAR_WS_CV 7
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
