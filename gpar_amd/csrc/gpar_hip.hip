@@ -831,90 +831,36 @@ __global__ __launch_bounds__(256) void dense_grad_prep_kernel(gpar_fspec_t fs, c
     }
 }
 
-// blocks [0, GRAD_NACC): the gradient pass's partial sums in their fixed order (lanes 0-63, as gram_grad_reduce_kernel); blocks
-// [GRAD_NACC, GRAD_NACC + ceil(n / 256)): 1/2 diag W; the last block: the value from the corner of the factor and its log-determinant.
-__global__ __launch_bounds__(256) void dense_grad_epilogue_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
-                                                                  const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag,
-                                                                  const double* __restrict__ A, int lda, double n_log_2pi,
-                                                                  const double* __restrict__ logdet) {
+// What the epilogues of every objective share.  Blocks [0, GRAD_NACC): the gradient pass's partial sums in their fixed order (lanes 0-63,
+// as gram_grad_reduce_kernel); blocks [GRAD_NACC, GRAD_NACC + ceil(n / 256)): 1/2 diag W.  False for the one block behind them, which
+// forms the objective's value.
+__device__ __forceinline__ bool grad_epilogue_sums(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
+                                                   const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (b < GRAD_NACC) {
-        if (t >= 64) return;
+        if (t >= 64) return true;
         double s = 0.0;
         for (int q = t; q < nblocks; q += 64) s += partial[(size_t)q * GRAD_NACC + b];
         s = wave_sum(s);
         if (t == 0) out[2 + b] = s;
-        return;
+        return true;
     }
     const int hb = b - GRAD_NACC, nh = (n + 255) / 256;
     if (hb < nh) {
         const int i = hb * 256 + t;
         if (i < n) half_diag[i] = 0.5 * W[(size_t)i * ldw + i];
-        return;
+        return true;
     }
-    if (t == 0) out[0] = -0.5 * ((logdet[0] + n_log_2pi) - A[(size_t)n * lda + n]);
+    return false;
 }
 
-// Everything of gpar_logpdf_dense_grad behind the factorisation: value, K^-1 from L, alpha^T = (L^-1 y)^T L^-1, W = alpha alpha^T - K^-1,
-// the fused weighted-sum pass, 1/2 diag W.  `logdet`: the word the factorisation left (out + 1 itself in the one-call form).
-static int logpdf_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, double* z, double* zd,
-                                  int ldz, double* A, int lda, const double* logdet, double* X, int ldxw, double* W, int ldw, double* alpha,
-                                  double* workspace, int nblocks, double* out, double* half_diag, void* stream, bool dfreq = true) {
-    hipStream_t st = (hipStream_t)stream;
-    if (dfreq && zd && fs->dz > 0) {
-        const long total = (long)n * fs->dz;
-        hipLaunchKernelGGL(featurize_dfreq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, zd, ldz);
-    }
-    int rc = chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
-    if (rc) return rc;
-    // alpha = (K + D)^-1 y = X (L^-1 y): X = L^-T is what the inverse has just left in its workspace, L^-1 y is row n of the factor
-    hipLaunchKernelGGL(trmv_upper_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
-                       (const double*)(A + (size_t)n * lda), 1, alpha, 1);
-    rc = gemm_launch(1, 0, n, n, 1, 1.0, alpha, n, alpha, n, -1.0, W, ldw, GPAR_GEMM_C_LOWER, st);
-    if (!rc) rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
-    if (rc) return rc;
-    // the partial sums of the gradient pass, 1/2 diag W and the value (from the corner of the factor, untouched since the factorisation)
-    hipLaunchKernelGGL(dense_grad_epilogue_kernel, dim3((unsigned)(GRAD_NACC + (n + 255) / 256 + 1)), dim3(256), 0, st, (const double*)workspace,
-                       nblocks, out, (const double*)W, ldw, n, half_diag, (const double*)A, lda, (double)n * 1.8378770664093453, logdet);
-    GPAR_LAUNCH_CHECK();
-    return 0;
-}
-
-int gpar_logpdf_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                           const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
-                           double* W, int ldw, double* alpha, double* workspace, int nblocks, double* out, double* half_diag, int* info,
-                           int potrf_flags, void* stream) {
-    GPAR_API_GUARD;
-    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !workspace || !out || !half_diag || !info || n <= 0 || nblocks <= 0)
-        return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    // ---- what gpar_logpdf_dense does up to the factor: features (+ their frequency derivatives) and observations in ONE launch, Gram,
-    // the augmented factorisation
-    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
-    {
-        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
-        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
-                           out + 1, info);
-    }
-    int rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
-    if (rc) return rc;
-    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
-    if (rc) return rc;
-    // ---- value and gradient ingredients from the factor
-    return logpdf_grad_finish_run(fs, ks, x, n, ldx, z, zd, ldz, A, lda, out + 1, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream,
-                                  false);
-}
-
-int gpar_logpdf_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, double* z, double* zd,
-                                  int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw, double* W, int ldw,
-                                  double* alpha, double* workspace, int nblocks, double* out, double* half_diag, int* info_out, void* stream) {
-    GPAR_API_GUARD;
-    if (!fs || !ks || !x || !z || !A || !logdet || !X || !W || !alpha || !workspace || !out || !half_diag || n <= 0 || nblocks <= 0)
-        return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    GPAR_HIP_TRY(hipMemcpyAsync(out + 1, logdet, sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (info && info_out) GPAR_HIP_TRY(hipMemcpyAsync(info_out, info, sizeof(int), hipMemcpyDeviceToDevice, st));
-    return logpdf_grad_finish_run(fs, ks, x, n, ldx, z, zd, ldz, A, lda, logdet, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream);
+// the last block: the value from the corner of the factor and its log-determinant
+__global__ __launch_bounds__(256) void dense_grad_epilogue_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
+                                                                  const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag,
+                                                                  const double* __restrict__ A, int lda, double n_log_2pi,
+                                                                  const double* __restrict__ logdet) {
+    if (grad_epilogue_sums(partial, nblocks, out, W, ldw, n, half_diag)) return;
+    if (threadIdx.x == 0) out[0] = -0.5 * ((logdet[0] + n_log_2pi) - A[(size_t)n * lda + n]);
 }
 
 // ---- leave-one-out cross-validation of one dense layer (ABI v8; Rasmussen & Williams 5.4.2, Sundararajan & Keerthi 2001) -----------
@@ -968,9 +914,24 @@ __global__ __launch_bounds__(256) void loo_rows_from_x_kernel(const double* __re
     if (lane == 0) loo_row_write(row, a, d, y[(size_t)row * incy], mean, var, nullptr, nullptr, term);
 }
 
+// u = P b for a symmetric P stored in its lower triangle: one wave per row (its row up to the diagonal, its column below it), a fixed
+// order.  The tail blocks of loo_weights_kernel and cv_weights_kernel: `blk` counts from the first of them.
+__device__ __forceinline__ void sym_lower_matvec_rows(const double* __restrict__ P, int ldp, int n, const double* __restrict__ bvec,
+                                                      double* __restrict__ u, int blk, int t) {
+    const int lane = t & 63;
+    const int row = blk * 4 + (t >> 6);
+    if (row >= n) return;
+    const double* Pr = P + (size_t)row * ldp;
+    double a0 = 0.0, a1 = 0.0;
+    for (int j = lane; j <= row; j += 64) a0 = fma(Pr[j], bvec[j], a0);
+    for (int j = row + 1 + lane; j < n; j += 64) a1 = fma(P[(size_t)j * ldp + row], bvec[j], a1);
+    const double s = wave_sum(a0 + a1);
+    if (lane == 0) u[row] = s;
+}
+
 // blocks [0, nt^2), nt = ceil(n / 32): tile (bi, bj), bj <= bi, of the LOWER triangle of Kinv through LDS into S = Kinv diag(sqrt c) at
 // (bi, bj) and, transposed, at (bj, bi) - a full matrix for the product S S^T, both stores along rows;  the blocks behind them:
-// u = Kinv b from the lower triangle alone, one wave per row (its row up to the diagonal, its column below it), a fixed order.
+// u = Kinv b (sym_lower_matvec_rows).
 constexpr int LOO_T = 32;
 __global__ __launch_bounds__(256) void loo_weights_kernel(const double* __restrict__ Kinv, int ldk, int n, const double* __restrict__ bvec,
                                                           const double* __restrict__ sc, double* __restrict__ u, double* __restrict__ S, int lds) {
@@ -978,15 +939,7 @@ __global__ __launch_bounds__(256) void loo_weights_kernel(const double* __restri
     const int nt = (n + LOO_T - 1) / LOO_T;
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= nt * nt) {
-        const int lane = t & 63;
-        const int row = (b - nt * nt) * 4 + (t >> 6);
-        if (row >= n) return;
-        const double* Kr = Kinv + (size_t)row * ldk;
-        double a0 = 0.0, a1 = 0.0;
-        for (int j = lane; j <= row; j += 64) a0 = fma(Kr[j], bvec[j], a0);
-        for (int j = row + 1 + lane; j < n; j += 64) a1 = fma(Kinv[(size_t)j * ldk + row], bvec[j], a1);
-        const double s = wave_sum(a0 + a1);
-        if (lane == 0) u[row] = s;
+        sym_lower_matvec_rows(Kinv, ldk, n, bvec, u, b - nt * nt, t);
         return;
     }
     const int bi = b / nt, bj = b - bi * nt;
@@ -1032,124 +985,15 @@ __global__ __launch_bounds__(256) void loo_value_kernel(const double* __restrict
     if (threadIdx.x == 0) out[0] = s - half_n_log_2pi;
 }
 
-// dense_grad_epilogue_kernel for the leave-one-out value: the partial sums of the gradient pass and 1/2 diag W as there; the last block
-// sums the value terms
+// dense_grad_epilogue_kernel for both cross-validation objectives, leave-one-out (whose name it keeps) and blocked: the last block sums
+// the value terms
 __global__ __launch_bounds__(256) void loo_grad_epilogue_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
                                                                 const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag,
                                                                 const double* __restrict__ term, double half_n_log_2pi) {
     __shared__ double sm[256];
-    const int b = blockIdx.x, t = threadIdx.x;
-    if (b < GRAD_NACC) {
-        if (t >= 64) return;
-        double s = 0.0;
-        for (int q = t; q < nblocks; q += 64) s += partial[(size_t)q * GRAD_NACC + b];
-        s = wave_sum(s);
-        if (t == 0) out[2 + b] = s;
-        return;
-    }
-    const int hb = b - GRAD_NACC, nh = (n + 255) / 256;
-    if (hb < nh) {
-        const int i = hb * 256 + t;
-        if (i < n) half_diag[i] = 0.5 * W[(size_t)i * ldw + i];
-        return;
-    }
+    if (grad_epilogue_sums(partial, nblocks, out, W, ldw, n, half_diag)) return;
     const double s = loo_sum_terms(term, n, sm);
-    if (t == 0) out[0] = s - half_n_log_2pi;
-}
-
-// Everything of gpar_loo_dense_grad behind the factorisation (out[1] holds the log-determinant already)
-static int loo_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                               double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw, double* W, int ldw, double* alpha,
-                               double* vec, double* workspace, int nblocks, double* out, double* half_diag, double* loo_mean, double* loo_var,
-                               void* stream, bool dfreq = true) {
-    hipStream_t st = (hipStream_t)stream;
-    if (dfreq && zd && fs->dz > 0) {
-        const long total = (long)n * fs->dz;
-        hipLaunchKernelGGL(featurize_dfreq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, zd, ldz);
-    }
-    int rc = chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
-    if (rc) return rc;
-    double *bvec = vec, *sc = vec + n, *term = vec + 2 * (size_t)n, *u = vec + 3 * (size_t)n;
-    hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
-                       (const double*)(A + (size_t)n * lda), (const double*)W, ldw, y, incy, alpha, loo_mean, loo_var, vec);
-    // u and S (into X: alpha exists, L^-T is no longer needed), then W <- -2 S S^T + alpha u^T + u alpha^T
-    const int nt = gpar_ceil_div(n, LOO_T);
-    hipLaunchKernelGGL(loo_weights_kernel, dim3((unsigned)(nt * nt + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n, (const double*)bvec,
-                       (const double*)sc, u, X, ldxw);
-    rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
-    rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
-    if (rc) return rc;
-    hipLaunchKernelGGL(loo_grad_epilogue_kernel, dim3((unsigned)(GRAD_NACC + (n + 255) / 256 + 1)), dim3(256), 0, st, (const double*)workspace,
-                       nblocks, out, (const double*)W, ldw, n, half_diag, (const double*)term, 0.5 * (double)n * 1.8378770664093453);
-    GPAR_LAUNCH_CHECK();
-    return 0;
-}
-
-int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                        const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
-                        double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
-                        double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
-    GPAR_API_GUARD;
-    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var || !info ||
-        n <= 0 || nblocks <= 0)
-        return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
-    {   // the launches of gpar_logpdf_dense_grad up to the factor
-        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
-        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
-                           out + 1, info);
-    }
-    int rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
-    if (rc) return rc;
-    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
-    if (rc) return rc;
-    return loo_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
-                               loo_mean, loo_var, stream, false);
-}
-
-int gpar_loo_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                               double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
-                               double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
-                               double* loo_mean, double* loo_var, int* info_out, void* stream) {
-    GPAR_API_GUARD;
-    if (!fs || !ks || !x || !y || !z || !A || !logdet || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var ||
-        n <= 0 || nblocks <= 0)
-        return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    GPAR_HIP_TRY(hipMemcpyAsync(out + 1, logdet, sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (info && info_out) GPAR_HIP_TRY(hipMemcpyAsync(info_out, info, sizeof(int), hipMemcpyDeviceToDevice, st));
-    return loo_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
-                               loo_mean, loo_var, stream);
-}
-
-// Value, means and variances alone: no K^-1 is formed - alpha = X (L^-1 y) and d = the squared row norms of X = L^-T come out of one pass
-// over X (n^3 / 3 flops for X instead of the inverse's 2 n^3 / 3)
-int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
-                   double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
-    GPAR_API_GUARD;
-    if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !loo_mean || !loo_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
-    {
-        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
-        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, (double*)nullptr, ldz, y,
-                           incy, A, lda, out + 1, info);
-    }
-    int rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
-    if (rc) return rc;
-    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
-    if (rc) return rc;
-    rc = trinv_upper_run(A, n, lda, X, ldxw, T, ldt, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(loo_rows_from_x_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
-                       (const double*)(A + (size_t)n * lda), y, incy, loo_mean, loo_var, vec);
-    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
-    GPAR_LAUNCH_CHECK();
-    return 0;
+    if (threadIdx.x == 0) out[0] = s - half_n_log_2pi;
 }
 
 // ---- blocked (leave-fold-out) cross-validation of one dense layer (ABI v9) ------------------------------------------------------------
@@ -1284,7 +1128,7 @@ __global__ __launch_bounds__(256) void cv_folds_kernel(const double* __restrict_
 
 // blocks [0, nrb * nfolds), nrb = ceil(n / 32): S[rows of block rb, F] = P[rows, F] R_F for fold F = b / nrb, a full matrix for the product
 // S S^T.  P is read from its lower triangle alone: element (i, j) with j > i as (j, i), in a second pass whose threads run along row j, so
-// both passes read along rows; the tile and R_F meet in LDS.  The blocks behind them: u = P b as loo_weights_kernel's tail forms it.
+// both passes read along rows; the tile and R_F meet in LDS.  The blocks behind them: u = P b (sym_lower_matvec_rows).
 constexpr int CV_T = 32;
 __global__ __launch_bounds__(256) void cv_weights_kernel(const double* __restrict__ P, int ldp, int n, const int* __restrict__ fold_start, int nfolds,
                                                          int max_fold, const double* __restrict__ Rm, const double* __restrict__ bvec,
@@ -1294,15 +1138,7 @@ __global__ __launch_bounds__(256) void cv_weights_kernel(const double* __restric
     const int nrb = (n + CV_T - 1) / CV_T;
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= nrb * nfolds) {
-        const int lane = t & 63;
-        const int row = (b - nrb * nfolds) * 4 + (t >> 6);
-        if (row >= n) return;
-        const double* Pr = P + (size_t)row * ldp;
-        double a0 = 0.0, a1 = 0.0;
-        for (int j = lane; j <= row; j += 64) a0 = fma(Pr[j], bvec[j], a0);
-        for (int j = row + 1 + lane; j < n; j += 64) a1 = fma(P[(size_t)j * ldp + row], bvec[j], a1);
-        const double sum = wave_sum(a0 + a1);
-        if (lane == 0) u[row] = sum;
+        sym_lower_matvec_rows(P, ldp, n, bvec, u, b - nrb * nfolds, t);
         return;
     }
     const int f = b / nrb, r0 = (b - f * nrb) * CV_T;
@@ -1334,10 +1170,14 @@ __global__ __launch_bounds__(256) void cv_weights_kernel(const double* __restric
     }
 }
 
-static int cv_check_folds(const int* fold_start, int n, int nfolds, int max_fold) {
-    if (!fold_start) return GPAR_ARG_ERROR(1);
-    if (max_fold < 1 || max_fold > GPAR_CV_MAX_FOLD) return GPAR_ARG_ERROR(3);
-    if (nfolds < 1 || nfolds > n) return GPAR_ARG_ERROR(4);
+struct CvFolds {
+    const int* start;   // nfolds + 1 ascending row offsets (device)
+    int nfolds, max_fold;
+};
+static int cv_check_folds(const CvFolds& f, int n) {
+    if (!f.start) return GPAR_ARG_ERROR(1);
+    if (f.max_fold < 1 || f.max_fold > GPAR_CV_MAX_FOLD) return GPAR_ARG_ERROR(3);
+    if (f.nfolds < 1 || f.nfolds > n) return GPAR_ARG_ERROR(4);
     return 0;
 }
 
@@ -1350,12 +1190,42 @@ static int cv_folds_launch(const double* P, int ldp, int n, const double* X, int
     return 0;
 }
 
-// Everything of gpar_cv_dense_grad behind the factorisation: loo_grad_finish_run with the two fold kernels in the places of its row and
-// weight kernels
-static int cv_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                              double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw, double* W, int ldw, double* alpha,
-                              double* vec, double* workspace, int nblocks, double* out, double* half_diag, double* cv_mean, double* cv_var,
-                              const int* fold_start, int nfolds, int max_fold, int* info, void* stream, bool dfreq = true) {
+// ---- one chain for the dense objectives: marginal likelihood, leave-one-out, blocked cross-validation ---------------------------------
+// Every one-call entry is  prologue (features, Gram, factor) -> inverse -> the objective's weights W -> weighted-sum pass -> epilogue;
+// the objectives differ in the weight stage and in the last block of the epilogue alone.
+enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV };
+struct DenseObjective {
+    DenseObjectiveKind kind;
+    const double* y;            // the observations (the finish form of OBJ_MLL has none: row n of the factor holds all it needs)
+    long incy;
+    double *vec, *mean, *var;   // OBJ_LOO, OBJ_CV: the vector workspace, held-out means and variances
+    CvFolds folds;              // OBJ_CV
+};
+
+// What gpar_logpdf_dense does up to the factor: features (+ their frequency derivatives when zd is given; the value-only forms pass null)
+// and observations in ONE launch, Gram, the augmented factorisation.  `logdet`: out + 1 of the caller.  `folds`: the blocked entries' folds,
+// checked here - between the check of the feature map and the first launch, the order of their error codes -, null for the others.
+static int dense_factor_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                            const CvFolds* folds, const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda,
+                            double* logdet, int* info, int potrf_flags, hipStream_t st) {
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    int rc = folds ? cv_check_folds(*folds, n) : 0;
+    if (rc) return rc;
+    const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
+    hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
+                       logdet, info);
+    rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
+    if (rc) return rc;
+    return potrf_run(A, n + 1, n, lda, logdet, info, st, potrf_flags);
+}
+
+// Everything of the one-call gradient entries behind the factorisation: K^-1 from L (with X = L^-T), the objective's W on the lower
+// triangle, the fused weighted-sum pass, then its partial sums, 1/2 diag W and the value in one epilogue.  `logdet`: the word the
+// factorisation left (OBJ_MLL reads it; out[1] holds it in every form).  `info`: where OBJ_CV's fold kernel reports.  `dfreq`: the
+// frequency derivatives are still to be formed (the finish forms; the one-call forms' prologue has written them).
+static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const DenseObjective& ob, double* z,
+                                 double* zd, int ldz, double* A, int lda, const double* logdet, int* info, double* X, int ldxw, double* W, int ldw,
+                                 double* alpha, double* workspace, int nblocks, double* out, double* half_diag, void* stream, bool dfreq) {
     hipStream_t st = (hipStream_t)stream;
     if (dfreq && zd && fs->dz > 0) {
         const long total = (long)n * fs->dz;
@@ -1363,21 +1233,133 @@ static int cv_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, co
     }
     int rc = chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
     if (rc) return rc;
-    double *bvec = vec, *term = vec + n, *u = vec + 2 * (size_t)n, *Rm = vec + 3 * (size_t)n;
-    rc = cv_folds_launch(W, ldw, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, max_fold, alpha, cv_mean, cv_var, bvec, term, Rm,
-                         info, st);
+    const double* zrow = A + (size_t)n * lda;   // L^-1 y
+    double *bvec = ob.vec, *term = nullptr, *u = nullptr;
+    switch (ob.kind) {
+        case OBJ_MLL:   // alpha = (K + D)^-1 y = X (L^-1 y), then W = alpha alpha^T - K^-1
+            hipLaunchKernelGGL(trmv_upper_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw, zrow, 1, alpha, 1);
+            rc = gemm_launch(1, 0, n, n, 1, 1.0, alpha, n, alpha, n, -1.0, W, ldw, GPAR_GEMM_C_LOWER, st);
+            break;
+        case OBJ_LOO: {   // `vec`: b, sqrt c, value terms, u
+            term = ob.vec + 2 * (size_t)n, u = ob.vec + 3 * (size_t)n;
+            hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw, zrow, (const double*)W, ldw,
+                               ob.y, ob.incy, alpha, ob.mean, ob.var, ob.vec);
+            const int nt = gpar_ceil_div(n, LOO_T);
+            hipLaunchKernelGGL(loo_weights_kernel, dim3((unsigned)(nt * nt + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n,
+                               (const double*)bvec, (const double*)(ob.vec + n), u, X, ldxw);
+            break;
+        }
+        case OBJ_CV: {   // `vec`: b, value terms, u, then R_F compactly
+            double* Rm = ob.vec + 3 * (size_t)n;
+            term = ob.vec + n, u = ob.vec + 2 * (size_t)n;
+            rc = cv_folds_launch(W, ldw, n, X, ldxw, zrow, ob.y, ob.incy, ob.folds.start, ob.folds.nfolds, ob.folds.max_fold, alpha, ob.mean, ob.var, bvec, term, Rm,
+                                 info, st);
+            if (rc) return rc;
+            const int nrb = gpar_ceil_div(n, CV_T);
+            hipLaunchKernelGGL(cv_weights_kernel, dim3((unsigned)(nrb * ob.folds.nfolds + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n,
+                               ob.folds.start, ob.folds.nfolds, ob.folds.max_fold, (const double*)Rm, (const double*)bvec, u, X, ldxw);
+            break;
+        }
+    }
+    if (ob.kind != OBJ_MLL) {   // u and S (in X: alpha exists, L^-T is no longer needed) are formed: W <- -2 S S^T + alpha u^T + u alpha^T
+        rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
+    }
+    if (!rc) rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
     if (rc) return rc;
-    // u and S (into X: alpha exists, L^-T is no longer needed), then W <- -2 S S^T + alpha u^T + u alpha^T
-    const int nrb = gpar_ceil_div(n, CV_T);
-    hipLaunchKernelGGL(cv_weights_kernel, dim3((unsigned)(nrb * nfolds + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n, fold_start,
-                       nfolds, max_fold, (const double*)Rm, (const double*)bvec, u, X, ldxw);
-    rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
+    const dim3 grid((unsigned)(GRAD_NACC + (n + 255) / 256 + 1));
+    const double n_log_2pi = (double)n * 1.8378770664093453;
+    if (ob.kind == OBJ_MLL)   // (the corner of the factor is untouched since the factorisation)
+        hipLaunchKernelGGL(dense_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
+                           half_diag, (const double*)A, lda, n_log_2pi, logdet);
+    else
+        hipLaunchKernelGGL(loo_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
+                           half_diag, (const double*)term, 0.5 * n_log_2pi);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+// The finish forms take the words an earlier (batched) factorisation left: the log-determinant into out[1], the info word into info_out.
+// The three entries differ in which of `info` / `info_out` may be null, and are kept so (ABI 9): the marginal-likelihood and leave-one-out
+// forms accept either as null and then skip the copy; the blocked form requires both, because its fold kernel reports into info_out.
+static int finish_carry_words(const double* logdet, const int* info, double* out, int* info_out, hipStream_t st) {
+    GPAR_HIP_TRY(hipMemcpyAsync(out + 1, logdet, sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (info && info_out) GPAR_HIP_TRY(hipMemcpyAsync(info_out, info, sizeof(int), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int gpar_logpdf_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                           double* W, int ldw, double* alpha, double* workspace, int nblocks, double* out, double* half_diag, int* info,
+                           int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !workspace || !out || !half_diag || !info || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const DenseObjective ob{OBJ_MLL, y, incy};
+    const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
+                                    (hipStream_t)stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
-    rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, out + 1, info, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag,
+                                 stream, false);
+}
+
+int gpar_logpdf_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, double* z, double* zd,
+                                  int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw, double* W, int ldw,
+                                  double* alpha, double* workspace, int nblocks, double* out, double* half_diag, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !z || !A || !logdet || !X || !W || !alpha || !workspace || !out || !half_diag || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const int rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(loo_grad_epilogue_kernel, dim3((unsigned)(GRAD_NACC + (n + 255) / 256 + 1)), dim3(256), 0, st, (const double*)workspace,
-                       nblocks, out, (const double*)W, ldw, n, half_diag, (const double*)term, 0.5 * (double)n * 1.8378770664093453);
+    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_MLL}, z, zd, ldz, A, lda, logdet, info_out, X, ldxw, W, ldw, alpha, workspace,
+                                 nblocks, out, half_diag, stream, true);
+}
+
+int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                        const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                        double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                        double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var || !info ||
+        n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const DenseObjective ob{OBJ_LOO, y, incy, vec, loo_mean, loo_var};
+    const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
+                                    (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, out + 1, info, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag,
+                                 stream, false);
+}
+
+int gpar_loo_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                               double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                               double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                               double* loo_mean, double* loo_var, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !logdet || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var ||
+        n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const int rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_LOO, y, incy, vec, loo_mean, loo_var}, z, zd, ldz, A, lda, logdet, info_out, X,
+                                 ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream, true);
+}
+
+// Value, means and variances alone: no K^-1 is formed - alpha = X (L^-1 y) and d = the squared row norms of X = L^-T come out of one pass
+// over X (n^3 / 3 flops for X instead of the inverse's 2 n^3 / 3)
+int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                   double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !loo_mean || !loo_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
+    if (!rc) rc = trinv_upper_run(A, n, lda, X, ldxw, T, ldt, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_rows_from_x_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
+                       (const double*)(A + (size_t)n * lda), y, incy, loo_mean, loo_var, vec);
+    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
     GPAR_LAUNCH_CHECK();
     return 0;
 }
@@ -1391,21 +1373,12 @@ int gpar_cv_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const dou
     if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !cv_mean || !cv_var || !info ||
         n <= 0 || nblocks <= 0)
         return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
-    int rc = cv_check_folds(fold_start, n, nfolds, max_fold);
+    const DenseObjective ob{OBJ_CV, y, incy, vec, cv_mean, cv_var, {fold_start, nfolds, max_fold}};
+    const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, &ob.folds, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
+                                    (hipStream_t)stream);
     if (rc) return rc;
-    {   // the launches of gpar_logpdf_dense_grad up to the factor
-        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
-        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
-                           out + 1, info);
-    }
-    rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
-    if (rc) return rc;
-    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
-    if (rc) return rc;
-    return cv_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
-                              cv_mean, cv_var, fold_start, nfolds, max_fold, info, stream, false);
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, out + 1, info, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag,
+                                 stream, false);
 }
 
 int gpar_cv_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
@@ -1416,13 +1389,12 @@ int gpar_cv_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, co
     if (!fs || !ks || !x || !y || !z || !A || !logdet || !info || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !cv_mean ||
         !cv_var || !info_out || n <= 0 || nblocks <= 0)
         return GPAR_ARG_ERROR(1);
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = cv_check_folds(fold_start, n, nfolds, max_fold);
+    const DenseObjective ob{OBJ_CV, y, incy, vec, cv_mean, cv_var, {fold_start, nfolds, max_fold}};
+    int rc = cv_check_folds(ob.folds, n);
+    if (!rc) rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
     if (rc) return rc;
-    GPAR_HIP_TRY(hipMemcpyAsync(out + 1, logdet, sizeof(double), hipMemcpyDeviceToDevice, st));
-    GPAR_HIP_TRY(hipMemcpyAsync(info_out, info, sizeof(int), hipMemcpyDeviceToDevice, st));   // (the fold kernel reports into it)
-    return cv_grad_finish_run(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks, out, half_diag,
-                              cv_mean, cv_var, fold_start, nfolds, max_fold, info_out, stream);
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, logdet, info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out,
+                                 half_diag, stream, true);
 }
 
 // Value, means and variances alone.  K^-1 is formed whole (gpar_chol_inverse) and the fold kernel shared; D_F = X_F X_F^T from the row
@@ -1434,22 +1406,11 @@ int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* 
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !cv_mean || !cv_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
     hipStream_t st = (hipStream_t)stream;
-    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
-    int rc = cv_check_folds(fold_start, n, nfolds, max_fold);
-    if (rc) return rc;
-    {
-        const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
-        hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, (double*)nullptr, ldz, y,
-                           incy, A, lda, out + 1, info);
-    }
-    rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
-    if (rc) return rc;
-    rc = potrf_run(A, n + 1, n, lda, out + 1, info, st, potrf_flags);
-    if (rc) return rc;
-    rc = chol_inverse_run(A, n, lda, X, ldxw, T, ldt, st);
-    if (rc) return rc;
-    rc = cv_folds_launch(T, ldt, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, max_fold, nullptr, cv_mean, cv_var, nullptr, vec,
-                         nullptr, info, st);
+    const CvFolds folds{fold_start, nfolds, max_fold};
+    int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, &folds, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
+    if (!rc) rc = chol_inverse_run(A, n, lda, X, ldxw, T, ldt, st);
+    if (!rc) rc = cv_folds_launch(T, ldt, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, max_fold, nullptr, cv_mean, cv_var, nullptr,
+                                  vec, nullptr, info, st);
     if (rc) return rc;
     hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
     GPAR_LAUNCH_CHECK();

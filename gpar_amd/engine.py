@@ -192,9 +192,7 @@ class HipEngine:
         return hip.gram_diag(ck, z)
 
     def potrf_(self, A, nf=None):
-        # inside a layer pipeline of three or more streams the factorisations overlap one another: no look-ahead stream each
-        safe = getattr(self._tls, "safe", False)
-        return hip.potrf_(A, nf=nf, lookahead=not safe and getattr(self._tls, "pipe_depth", 0) < 3, fused=not safe)
+        return hip.potrf_(A, nf=nf, **self._factor_flags())
 
     def potrf_batch_(self, A, batch):
         """`batch` square matrices stacked by rows in A, factored in lock-step (logdets, info words)."""
@@ -209,11 +207,23 @@ class HipEngine:
     def gemm_batch_(self, A, B, out, batch, ta=False, tb=False, alpha=1.0, beta=0.0, c_lower=False):
         return hip.gemm_batch_(A, B, out, batch, ta=ta, tb=tb, alpha=alpha, beta=beta, c_lower=c_lower)
 
+    def _factor_flags(self):
+        """lookahead / fused of a factorisation started now: the safe mode has neither, and inside a layer pipeline of three or more
+        streams the factorisations overlap one another: no look-ahead stream each."""
+        safe = getattr(self._tls, "safe", False)
+        return {"lookahead": not safe and getattr(self._tls, "pipe_depth", 0) < 3, "fused": not safe}
+
+    def _gradients_of(self, ck, out, half_diag):
+        """A function returning (1/2 diag(W) on the device, kernel-parameter gradients) once the host needs them."""
+        def gradients():
+            raw = out[2:].cpu().numpy()   # (the one device-to-host copy of the backward pass)
+            return half_diag, self._grads_from_moments(ck, raw, 0.5)
+
+        return gradients
+
     def logpdf_dense(self, ck, x, y, noise_diag, jitter):
         """One dense layer's log marginal likelihood in one library call (value as a 0-d device tensor, info word)."""
-        safe = getattr(self._tls, "safe", False)
-        depth = getattr(self._tls, "pipe_depth", 0)
-        value, _, info, _ = hip.logpdf_dense(ck, self._mat(x), y, noise_diag, jitter, lookahead=not safe and depth < 3, fused=not safe)
+        value, _, info, _ = hip.logpdf_dense(ck, self._mat(x), y, noise_diag, jitter, **self._factor_flags())
         return value, info
 
     def logpdf_dense_batch(self, items, jitter):
@@ -226,60 +236,34 @@ class HipEngine:
         info word, a function returning (1/2 diag(W) on the device, kernel-parameter gradients) once the host needs them, the
         (n + 1) x (n + 1) factor buffer with its log-determinant word - the factor a later posterior mean or conditioning on the
         same observations would otherwise compute a second time)."""
-        safe = getattr(self._tls, "safe", False)
-        depth = getattr(self._tls, "pipe_depth", 0)
-        out, half_diag, info, A = hip.logpdf_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
-                                                        lookahead=not safe and depth < 3, fused=not safe)
-
-        def gradients():
-            raw = out[2:].cpu().numpy()   # (the one device-to-host copy of the backward pass)
-            return half_diag, self._grads_from_moments(ck, raw, 0.5)
-
-        return out[0], info, gradients, (A, out[1:2])
+        out, half_diag, info, A = hip.logpdf_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), **self._factor_flags())
+        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2])
 
     def loo_dense(self, ck, x, y, noise_diag, jitter):
         """One dense layer's leave-one-out value, predictive means and variances in one library call: (value as a 0-d device
         tensor, info word, means, variances)."""
-        safe = getattr(self._tls, "safe", False)
-        depth = getattr(self._tls, "pipe_depth", 0)
-        out, mean, var, info = hip.loo_dense(ck, self._mat(x), y, noise_diag, jitter, lookahead=not safe and depth < 3, fused=not safe)
+        out, mean, var, info = hip.loo_dense(ck, self._mat(x), y, noise_diag, jitter, **self._factor_flags())
         return out[0], info, mean, var
 
     def loo_dense_grad(self, ck, x, y, noise_diag, jitter):
         """The leave-one-out counterpart of `logpdf_dense_grad`, same conventions: (value, info word, a function returning (1/2 diag(W)
         on the device, kernel-parameter gradients), (factor buffer, log-determinant word)), then the predictive means and variances."""
-        safe = getattr(self._tls, "safe", False)
-        depth = getattr(self._tls, "pipe_depth", 0)
         out, half_diag, mean, var, info, A, _ = hip.loo_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
-                                                                   lookahead=not safe and depth < 3, fused=not safe)
-
-        def gradients():
-            raw = out[2:].cpu().numpy()
-            return half_diag, self._grads_from_moments(ck, raw, 0.5)
-
-        return out[0], info, gradients, (A, out[1:2]), mean, var
+                                                                   **self._factor_flags())
+        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
     def cv_dense(self, ck, x, y, noise_diag, jitter, fold_start):
         """One dense layer's blocked cross-validation value, predictive means and marginal variances in one library call, for contiguous
         folds of at most `_lib.CV_MAX_FOLD` rows given by their nfolds + 1 row offsets: (value as a 0-d device tensor, info word, means,
         variances)."""
-        safe = getattr(self._tls, "safe", False)
-        depth = getattr(self._tls, "pipe_depth", 0)
-        out, mean, var, info = hip.cv_dense(ck, self._mat(x), y, noise_diag, jitter, fold_start, lookahead=not safe and depth < 3, fused=not safe)
+        out, mean, var, info = hip.cv_dense(ck, self._mat(x), y, noise_diag, jitter, fold_start, **self._factor_flags())
         return out[0], info, mean, var
 
     def cv_dense_grad(self, ck, x, y, noise_diag, jitter, fold_start):
         """The blocked cross-validation counterpart of `loo_dense_grad`, same conventions and return values."""
-        safe = getattr(self._tls, "safe", False)
-        depth = getattr(self._tls, "pipe_depth", 0)
         out, half_diag, mean, var, info, A, _ = hip.cv_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), fold_start,
-                                                                  lookahead=not safe and depth < 3, fused=not safe)
-
-        def gradients():
-            raw = out[2:].cpu().numpy()
-            return half_diag, self._grads_from_moments(ck, raw, 0.5)
-
-        return out[0], info, gradients, (A, out[1:2]), mean, var
+                                                                  **self._factor_flags())
+        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""
@@ -320,8 +304,7 @@ class HipEngine:
 
     def vfe_factor(self, G, c, ys, kdiag, d, with_trace):
         """chol of A = I + G with the row c appended and the inducing-point bound, the scalar side in two launches (hip.vfe_factor)."""
-        safe = getattr(self._tls, "safe", False)
-        return hip.vfe_factor(G, c, ys, kdiag, d, 1.0, with_trace, lookahead=not safe and getattr(self._tls, "pipe_depth", 0) < 3, fused=not safe)
+        return hip.vfe_factor(G, c, ys, kdiag, d, 1.0, with_trace, **self._factor_flags())
 
     def chol_spread(self, L, limit):
         return hip.chol_spread(L, limit)

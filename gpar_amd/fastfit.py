@@ -321,13 +321,9 @@ class DenseLayerObjective:
         nt = (n + 63) // 64
         self.nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
         nacc = _lib.GRAD_NACC
-        # gradient partials, alpha; for the leave-one-out objective its vectors, the predictive means and variances behind them
-        nloo = 0
-        if self.objective == "loo":
-            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_LOO, n, 1, 0)) + 2 * n
-        elif self.objective == "cv":
-            self.folds = hip.upload_folds(self.fold_start, n, dev)   # (device offsets, number of folds, largest fold)
-            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_CV, n, 1, self.folds[2])) + 2 * n
+        # gradient partials, alpha; for the cross-validation objectives their vectors, the predictive means and variances behind them
+        self.folds = hip.upload_folds(self.fold_start, n, dev) if self.objective == "cv" else ()   # (device offsets, number of folds, largest fold)
+        nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.objective, n, 1, self.folds) + 2 * n
         self.work = torch.empty(self.nblocks * nacc + n + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
         self.res = torch.zeros(2 + nacc + n + 1, dtype=torch.float64, device=dev)
@@ -361,37 +357,30 @@ class DenseLayerObjective:
             # the correctly rounded quotient of two tensors, as model.GPAR._noise_over forms it
             torch.true_divide(self.noise_num.fill_(noise), self.w, out=self.noise_vec)
         p = self._ptrs
-        if self.objective == "loo":
-            rc = self.lib.gpar_loo_dense_grad(
-                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
-                p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["vec"], p["work"], self.nblocks,
-                p["out"], p["half"], p["loo_mean"], p["loo_var"], p["info"], self.flags, stream.cuda_stream)
-            _lib.check(rc, "gpar_loo_dense_grad")
-        elif self.objective == "cv":
-            starts, nfolds, max_fold = self.folds
-            rc = self.lib.gpar_cv_dense_grad(
-                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
-                p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["vec"], p["work"], self.nblocks,
-                p["out"], p["half"], p["loo_mean"], p["loo_var"], starts.data_ptr(), nfolds, max_fold, p["info"], self.flags, stream.cuda_stream)
-            _lib.check(rc, "gpar_cv_dense_grad")
+        fs, ks, eps = ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), float(self.eng.epsilon)
+        # what every one-call entry takes ahead of its own arguments, and behind them
+        head = (fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"],
+                p["W"], p["ldw"], p["alpha"])
+        tail = (p["info"], self.flags, stream.cuda_stream)
+        if self.objective != "mll":
+            name = "gpar_cv_dense_grad" if self.objective == "cv" else "gpar_loo_dense_grad"
+            fold_args = (self.folds[0].data_ptr(), *self.folds[1:]) if self.objective == "cv" else ()
+            rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *tail)
+            _lib.check(rc, name)
         elif self.group is None:
-            rc = self.lib.gpar_logpdf_dense_grad(
-                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
-                p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["work"], self.nblocks, p["out"],
-                p["half"], p["info"], self.flags, stream.cuda_stream)
+            rc = self.lib.gpar_logpdf_dense_grad(*head, p["work"], self.nblocks, p["out"], p["half"], *tail)
             _lib.check(rc, "gpar_logpdf_dense_grad")
         else:
             # build into this lane's slot, factor with the round, finish on this stream (LockstepFactor)
             g = self.group
             a, ld, info = g.slot(self.lane)
-            rc = self.lib.gpar_logpdf_dense_build(
-                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], float(self.eng.epsilon),
-                p["z"], p["ldz"], a, g.lda, ld, info, stream.cuda_stream)
+            rc = self.lib.gpar_logpdf_dense_build(fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["ldz"], a, g.lda, ld,
+                                                  info, stream.cuda_stream)
             _lib.check(rc, "gpar_logpdf_dense_build")
             g.factor(self.lane)
-            rc = self.lib.gpar_logpdf_dense_grad_finish(
-                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], self.n, p["ldx"], p["z"], p["zd"], p["ldz"], a, g.lda, ld, info,
-                p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"], p["work"], self.nblocks, p["out"], p["half"], p["info"], stream.cuda_stream)
+            rc = self.lib.gpar_logpdf_dense_grad_finish(fs, ks, p["x"], self.n, p["ldx"], p["z"], p["zd"], p["ldz"], a, g.lda, ld, info, p["X"], p["ldxw"],
+                                                        p["W"], p["ldw"], p["alpha"], p["work"], self.nblocks, p["out"], p["half"], p["info"],
+                                                        stream.cuda_stream)
             _lib.check(rc, "gpar_logpdf_dense_grad_finish")
         self.res_host.copy_(self.res, non_blocking=True)
         stream.synchronize()

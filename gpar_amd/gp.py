@@ -290,46 +290,25 @@ class _LogMarginal(torch.autograd.Function):
         return (None, out_noise, gX, gZ, *_param_grads(obs._params, ctx.shapes, grads, gval))
 
 
-class _LooValue(torch.autograd.Function):
-    """The leave-one-out predictive log-density sum_i log N(y_i; mean_-i, var_-i) of dense observations of a prior process as a
-    differentiable function of the kernel parameters and the noise vector (Rasmussen & Williams 5.4.2).  Forward: `Obs._loo_eval`.
-    Backward: the same weighted-sum pass as `_LogMarginal`, on other weights - d/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta with
-    W = alpha u^T + u alpha^T - 2 K^-1 C K^-1 (`Obs.loo_gradients`).  The inputs are not differentiated."""
-
-    @staticmethod
-    def forward(ctx, obs, noise, *tensors):
-        ctx.obs = obs
-        ctx.noise_shape = None if noise is None else tuple(noise.shape)
-        ctx.shapes = [tuple(t.shape) for t in tensors]
-        return obs._loo_eval(want_grad=True)
-
-    @staticmethod
-    def backward(ctx, g):
-        obs = ctx.obs
-        noise_grad, grads = obs.loo_gradients()
-        gval = float(g)
-        out_noise = None
-        if ctx.noise_shape is not None:
-            out_noise = _shaped_noise_grad(noise_grad * gval, ctx.noise_shape, obs._noise_device)
-        return (None, out_noise, *_param_grads(obs._params, ctx.shapes, grads, gval))
-
-
-class _CvValue(torch.autograd.Function):
-    """The blocked cross-validation value sum_F log N(y_F; mean_-F, cov_-F) over contiguous folds F of dense observations of a prior
-    process as a differentiable function of the kernel parameters and the noise vector.  Forward: `Obs._cv_eval`.  Backward: the
-    weighted-sum pass of `_LooValue` with a block-diagonal C (`Obs.cv_gradients`).  The inputs are not differentiated."""
+class _HeldOutValue(torch.autograd.Function):
+    """A cross-validation value of dense observations of a prior process as a differentiable function of the kernel parameters and the
+    noise vector: with `starts` None the leave-one-out predictive log-density sum_i log N(y_i; mean_-i, var_-i) (Rasmussen & Williams
+    5.4.2), otherwise the blocked value sum_F log N(y_F; mean_-F, cov_-F) over the contiguous folds F with those row offsets.  Forward:
+    `Obs._held_out_eval`.  Backward: the same weighted-sum pass as `_LogMarginal`, on other weights - d/dtheta = 1/2 sum_ab W_ab
+    dK_ab/dtheta with W = alpha u^T + u alpha^T - 2 K^-1 C K^-1, C diagonal or block-diagonal (`Obs._held_out_gradients`).  The inputs are
+    not differentiated."""
 
     @staticmethod
     def forward(ctx, obs, starts, noise, *tensors):
         ctx.obs = obs
         ctx.noise_shape = None if noise is None else tuple(noise.shape)
         ctx.shapes = [tuple(t.shape) for t in tensors]
-        return obs._cv_eval(starts, want_grad=True)
+        return obs._held_out_eval(starts, want_grad=True)
 
     @staticmethod
     def backward(ctx, g):
         obs = ctx.obs
-        noise_grad, grads = obs.cv_gradients()
+        noise_grad, grads = obs._held_out_gradients()
         gval = float(g)
         out_noise = None
         if ctx.noise_shape is not None:
@@ -342,6 +321,45 @@ def _fold_groups(starts, device):
     sizes, first = np.diff(starts), starts[:-1]
     return [(int(m), torch.as_tensor(first[sizes == m][:, None] + np.arange(m)[None, :], dtype=torch.long, device=device))
             for m in np.unique(sizes)]
+
+
+# The block algebra of the two cross-validation values from K^-1 and alpha, where no library call takes the evaluation: (value without
+# its -n/2 log 2 pi, b, variances, a function filling S with K^-1 R for the gradient's product S S^T = K^-1 C K^-1, C = R R^T).
+def _loo_algebra(Kinv, alpha):
+    """Leave-one-out: the diagonal, in closed form.  b = alpha / d, C = diag(1/2 (1 / d + b^2))."""
+    d = torch.diagonal(Kinv)
+    b = alpha / d
+
+    def fill(S):
+        S.copy_(Kinv * torch.sqrt(0.5 * (1.0 / d + b * b))[None, :])
+
+    return torch.sum(0.5 * torch.log(d) - 0.5 * alpha * b), b, 1.0 / d, fill
+
+
+def _cv_algebra(eng, Kinv, alpha, starts):
+    """Folds of any size: batched Cholesky over the folds of equal size.  b_F = D_F^-1 alpha_F, C = blockdiag(1/2 (D_F^-1 + b_F b_F^T))."""
+    n = alpha.numel()
+    b, var = torch.empty_like(alpha), torch.empty_like(alpha)
+    value = torch.zeros((), dtype=torch.float64, device=alpha.device)
+    blocks = []
+    for m, idx in _fold_groups(starts, alpha.device):
+        D = Kinv[idx[:, :, None], idx[:, None, :]]   # k x m x m
+        G, info = torch.linalg.cholesky_ex(D)
+        eng.check_info(info.max().reshape(1).to(torch.int32))   # (one word: the largest failing pivot of the group, 0 if none)
+        Dinv = torch.cholesky_inverse(G)
+        a_f = alpha[idx]
+        b_f = torch.matmul(Dinv, a_f[:, :, None])[:, :, 0]
+        b[idx], var[idx] = b_f, torch.diagonal(Dinv, dim1=1, dim2=2)
+        value = value + torch.sum(torch.log(torch.diagonal(G, dim1=1, dim2=2))) - 0.5 * torch.sum(a_f * b_f)
+        blocks.append((idx, Dinv, b_f))
+
+    def fill(S):
+        for idx, Dinv, b_f in blocks:   # S[:, F] = K^-1[:, F] R_F
+            R = torch.linalg.cholesky(0.5 * (Dinv + b_f[:, :, None] * b_f[:, None, :]))
+            cols = torch.matmul(Kinv[:, idx].permute(1, 0, 2), R)   # k x n x m
+            S[:, idx.reshape(-1)] = cols.permute(1, 0, 2).reshape(n, -1)
+
+    return value, b, var, fill
 
 
 class _PosteriorMean(torch.autograd.Function):
@@ -717,82 +735,14 @@ class Obs:
         self._W = W
         return 0.5 * torch.diagonal(W).clone(), grads
 
-    # ---- leave-one-out cross-validation -------------------------------------------------------------------
+    # ---- leave-one-out and blocked cross-validation ----------------------------------------------------------
     def loo(self):
         """(value, mean, var): the leave-one-out predictive means and variances of the observations - of y_i given all the others,
         mean_-i = y_i - alpha_i / d_i and var_-i = 1 / d_i with alpha = S^-1 (y - m), d = diag S^-1, S = cov(f(X)) + D + eps I - and
         value = sum_i log N(y_i; mean_-i, var_-i), a 0-d tensor that carries a gradient with respect to the kernel parameters and the
         noise where they require one (observations of a prior process; Rasmussen & Williams 5.4.2)."""
-        if torch.is_grad_enabled():
-            params = kernel_parameters(self.base.kernel)
-            noise = self.fdd.noise_arg if _needs_grad(self.fdd.noise_arg) else None
-            if params or noise is not None:
-                if self.base.is_posterior or self.fdd.x.requires_grad:
-                    raise NotImplementedError("the leave-one-out gradient covers kernel parameters and noise of a prior process")
-                self._params = params
-                self._noise_device = None if noise is None else noise.device
-                value = _LooValue.apply(self, noise, *[p[3] for p in params])
-                return value, self._loo_mean, self._loo_var
-        value = self._loo_eval()
-        return value, self._loo_mean, self._loo_var
+        return self._held_out(None, "leave-one-out")
 
-    def _loo_eval(self, want_grad=False):
-        """The value (detached; the means and variances are left in `_loo_mean` / `_loo_var`).  One library call where the engine has
-        one and `_value_only` / `_fusable_grad` would let `logpdf` take it; otherwise composed of engine primitives: the factor, K^-1."""
-        eng, n = self.eng, self.fdd.n
-        dev = self.y.device
-        if n == 0:
-            self._loo_mean = self._loo_var = torch.zeros(0, dtype=torch.float64, device=dev)
-            self._loo_parts = None
-            return torch.zeros((), dtype=torch.float64, device=dev)
-        if want_grad and hasattr(eng, "loo_dense_grad") and self._fusable_grad():
-            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._fused_loo_gradients, (A, logdet), self._loo_mean, self._loo_var = eng.loo_dense_grad(
-                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon)
-            eng.check_info(info)
-            self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
-            return value.detach()
-        if not want_grad and hasattr(eng, "loo_dense") and self._value_only():
-            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._loo_mean, self._loo_var = eng.loo_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon)
-            eng.check_info(info)
-            return value.detach()
-        fac = self.factor()
-        low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
-        Kinv = low + torch.tril(low, -1).T
-        alpha = fac.alpha().reshape(-1).detach()
-        d = torch.diagonal(Kinv)
-        b = alpha / d
-        y = self.y.reshape(-1).detach()
-        self._loo_mean, self._loo_var = y - b, 1.0 / d
-        self._loo_parts = (Kinv, alpha, d, b) if want_grad else None
-        value = torch.sum(0.5 * torch.log(d) - 0.5 * alpha * b) - 0.5 * n * _LOG_2PI
-        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
-
-    def loo_gradients(self):
-        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the leave-one-out value, with
-        W = alpha u^T + u alpha^T - 2 K^-1 C K^-1,  b = alpha / d,  C = diag(1/2 (1 / d + b^2)),  u = K^-1 b."""
-        fused = getattr(self, "_fused_loo_gradients", None)
-        if fused is not None:
-            self._fused_loo_gradients = None
-            return fused()
-        eng, n = self.eng, self.fdd.n
-        Kinv, alpha, d, b = self._loo_parts
-        self._loo_parts = None
-        u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
-        S = eng.new_matrix(n, n)
-        S.copy_(Kinv * torch.sqrt(0.5 * (1.0 / d + b * b))[None, :])
-        W = eng.new_matrix(n, n)
-        eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
-        left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
-        left.copy_(torch.stack([alpha, u]))
-        right.copy_(torch.stack([u, alpha]))
-        eng.gemm(left, right, ta=True, alpha=1.0, beta=1.0, out=W, c_lower=True)
-        ck, _ = self.fdd.features()
-        grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
-        return 0.5 * torch.diagonal(W).clone(), grads
-
-    # ---- blocked cross-validation ---------------------------------------------------------------------------
     def cv(self, fold_start):
         """(value, mean, var) of blocked (leave-fold-out) cross-validation over contiguous folds of the observations, given by their
         nfolds + 1 ascending row offsets (0 ... n).  With P = S^-1, alpha = P (y - m) and per fold D_F = P[F, F], b_F = D_F^-1 alpha_F:
@@ -800,82 +750,74 @@ class Obs:
         value = sum_F log N(y_F; y_F - b_F, D_F^-1), the JOINT fold densities - a 0-d tensor that carries a gradient with respect to
         the kernel parameters and the noise where they require one (observations of a prior process).  Folds of one row give `loo`;
         one fold of every row gives `logpdf`."""
-        starts = fold_offsets(fold_start, self.fdd.n)
+        return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
+
+    def _held_out(self, starts, what):
+        """`loo` (`starts` None) and `cv`: through `_HeldOutValue` where a kernel parameter or the noise needs a gradient.  The two share
+        one set of pending-gradient state on the observations (`_fused_held_out_gradients`, `_held_out_parts`): a second `loo()` or `cv()`
+        with gradients on the same `Obs` replaces what the first left, so run each value's backward pass before evaluating the next."""
         if torch.is_grad_enabled():
             params = kernel_parameters(self.base.kernel)
             noise = self.fdd.noise_arg if _needs_grad(self.fdd.noise_arg) else None
             if params or noise is not None:
                 if self.base.is_posterior or self.fdd.x.requires_grad:
-                    raise NotImplementedError("the cross-validation gradient covers kernel parameters and noise of a prior process")
+                    raise NotImplementedError(f"the {what} gradient covers kernel parameters and noise of a prior process")
                 self._params = params
                 self._noise_device = None if noise is None else noise.device
-                value = _CvValue.apply(self, starts, noise, *[p[3] for p in params])
-                return value, self._cv_mean, self._cv_var
-        value = self._cv_eval(starts)
-        return value, self._cv_mean, self._cv_var
+                value = _HeldOutValue.apply(self, starts, noise, *[p[3] for p in params])
+                return value, self._held_out_mean, self._held_out_var
+        value = self._held_out_eval(starts)
+        return value, self._held_out_mean, self._held_out_var
 
-    def _cv_eval(self, starts, want_grad=False):
-        """The value (detached; the means and variances are left in `_cv_mean` / `_cv_var`).  One library call where the engine has one,
-        `_value_only` / `_fusable_grad` would let `logpdf` take it and no fold exceeds the call's limit; otherwise composed of engine
-        primitives (the factor, K^-1) and batched torch algebra on the fold blocks, for folds of any size."""
+    def _held_out_eval(self, starts, want_grad=False):
+        """The value (detached; the means and variances are left in `_held_out_mean` / `_held_out_var`).  One library call where the
+        engine has one, `_value_only` / `_fusable_grad` would let `logpdf` take it and no fold exceeds the call's limit; otherwise composed
+        of engine primitives (the factor, K^-1) and the objective's block algebra (`_loo_algebra`, `_cv_algebra`: folds of any size)."""
         eng, n = self.eng, self.fdd.n
         dev = self.y.device
         if n == 0:
-            self._cv_mean = self._cv_var = torch.zeros(0, dtype=torch.float64, device=dev)
-            self._cv_parts = None
+            self._held_out_mean = self._held_out_var = torch.zeros(0, dtype=torch.float64, device=dev)
+            self._held_out_parts = None
             return torch.zeros((), dtype=torch.float64, device=dev)
-        fits = int(np.diff(starts).max()) <= CV_MAX_FOLD
-        if want_grad and fits and hasattr(eng, "cv_dense_grad") and self._fusable_grad():
+        call = "loo_dense" if starts is None else "cv_dense"
+        folds = () if starts is None else (starts,)
+        fits = starts is None or int(np.diff(starts).max()) <= CV_MAX_FOLD
+        if want_grad and fits and hasattr(eng, call + "_grad") and self._fusable_grad():
             ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._fused_cv_gradients, (A, logdet), self._cv_mean, self._cv_var = eng.cv_dense_grad(
-                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, starts)
+            value, info, self._fused_held_out_gradients, (A, logdet), self._held_out_mean, self._held_out_var = getattr(eng, call + "_grad")(
+                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, *folds)
             eng.check_info(info)
             self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
             return value.detach()
-        if not want_grad and fits and hasattr(eng, "cv_dense") and self._value_only():
+        if not want_grad and fits and hasattr(eng, call) and self._value_only():
             ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._cv_mean, self._cv_var = eng.cv_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, starts)
+            value, info, self._held_out_mean, self._held_out_var = getattr(eng, call)(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, *folds)
             eng.check_info(info)
             return value.detach()
         fac = self.factor()
         low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
         Kinv = low + torch.tril(low, -1).T
         alpha = fac.alpha().reshape(-1).detach()
-        b, var = torch.empty_like(alpha), torch.empty_like(alpha)
-        value = torch.zeros((), dtype=torch.float64, device=alpha.device)
-        blocks = []
-        for m, idx in _fold_groups(starts, alpha.device):
-            D = Kinv[idx[:, :, None], idx[:, None, :]]   # k x m x m
-            G, info = torch.linalg.cholesky_ex(D)
-            eng.check_info(info.max().reshape(1).to(torch.int32))   # (one word: the largest failing pivot of the group, 0 if none)
-            Dinv = torch.cholesky_inverse(G)
-            a_f = alpha[idx]
-            b_f = torch.matmul(Dinv, a_f[:, :, None])[:, :, 0]
-            b[idx], var[idx] = b_f, torch.diagonal(Dinv, dim1=1, dim2=2)
-            value = value + torch.sum(torch.log(torch.diagonal(G, dim1=1, dim2=2))) - 0.5 * torch.sum(a_f * b_f)
-            blocks.append((idx, Dinv, b_f))
+        value, b, var, fill = _loo_algebra(Kinv, alpha) if starts is None else _cv_algebra(eng, Kinv, alpha, starts)
         y = self.y.reshape(-1).detach()
-        self._cv_mean, self._cv_var = y - b, var
-        self._cv_parts = (Kinv, alpha, b, blocks) if want_grad else None
+        self._held_out_mean, self._held_out_var = y - b, var
+        self._held_out_parts = (Kinv, alpha, b, fill) if want_grad else None
         value = value - 0.5 * n * _LOG_2PI
         return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
 
-    def cv_gradients(self):
-        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the blocked cross-validation value, with
-        W = alpha u^T + u alpha^T - 2 K^-1 C K^-1,  C = blockdiag(1/2 (D_F^-1 + b_F b_F^T)) = blockdiag(R_F R_F^T),  u = K^-1 b."""
-        fused = getattr(self, "_fused_cv_gradients", None)
+    def _held_out_gradients(self):
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the value `_held_out_eval(want_grad=True)` has just formed, with
+        W = alpha u^T + u alpha^T - 2 S S^T,  u = K^-1 b,  S from the objective's block algebra."""
+        fused = getattr(self, "_fused_held_out_gradients", None)
         if fused is not None:
-            self._fused_cv_gradients = None
+            self._fused_held_out_gradients = None
             return fused()
         eng, n = self.eng, self.fdd.n
-        Kinv, alpha, b, blocks = self._cv_parts
-        self._cv_parts = None
+        Kinv, alpha, b, fill = self._held_out_parts
+        self._held_out_parts = None
         u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
         S = eng.new_matrix(n, n)
-        for idx, Dinv, b_f in blocks:   # S[:, F] = K^-1[:, F] R_F
-            R = torch.linalg.cholesky(0.5 * (Dinv + b_f[:, :, None] * b_f[:, None, :]))
-            cols = torch.matmul(Kinv[:, idx].permute(1, 0, 2), R)   # k x n x m
-            S[:, idx.reshape(-1)] = cols.permute(1, 0, 2).reshape(n, -1)
+        fill(S)
         W = eng.new_matrix(n, n)
         eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
         left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
@@ -885,6 +827,16 @@ class Obs:
         ck, _ = self.fdd.features()
         grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
         return 0.5 * torch.diagonal(W).clone(), grads
+
+    def loo_gradients(self):
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the leave-one-out value, with
+        W = alpha u^T + u alpha^T - 2 K^-1 C K^-1,  b = alpha / d,  C = diag(1/2 (1 / d + b^2)),  u = K^-1 b."""
+        return self._held_out_gradients()
+
+    def cv_gradients(self):
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the blocked cross-validation value, with
+        W = alpha u^T + u alpha^T - 2 K^-1 C K^-1,  C = blockdiag(1/2 (D_F^-1 + b_F b_F^T)) = blockdiag(R_F R_F^T),  u = K^-1 b."""
+        return self._held_out_gradients()
 
     def input_gradients(self, want_x, want_z):
         """d logpdf / d X = 1/2 d/dX sum_ab W_ab k(x_a, x_b) (both arguments of k move)."""

@@ -83,78 +83,6 @@ def featurize(ck, x):
     return z
 
 
-def logpdf_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
-    """log N(y; 0, k(x, x) + diag(noise_diag) + jitter I) in one library call (gpar_logpdf_dense): returns
-    (value, logdet, info) as one-element device tensors and the (n + 1) x (n + 1) factor buffer."""
-    lib = _lib.load()
-    _check_mat(x, "x")
-    n = x.shape[0]
-    y = y.reshape(-1)
-    if y.numel() != n or y.dtype != torch.float64 or not y.is_cuda:
-        raise ValueError("y must hold one fp64 device value per row of x")
-    nptr = None
-    if noise_diag is not None:
-        noise_diag = noise_diag.reshape(-1).contiguous()
-        if noise_diag.numel() != n:
-            raise ValueError("noise_diag must hold one value per row of x")
-        nptr = noise_diag.data_ptr()
-    z = alloc_matrix(n, max(ck.dz, 1), x.device)
-    A = alloc_matrix(n + 1, n + 1, x.device)
-    words = torch.empty(2, dtype=torch.float64, device=x.device)   # value, logdet
-    info = torch.empty(1, dtype=torch.int32, device=x.device)
-    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
-    _lib.check(
-        lib.gpar_logpdf_dense(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)), nptr, float(jitter),
-            z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), words[1:].data_ptr(), info.data_ptr(), words.data_ptr(), flags,
-            stream_ptr(x.device),
-        ),
-        "gpar_logpdf_dense",
-    )
-    return words[0], words[1:], info, A
-
-
-def logpdf_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
-    """One dense layer's log marginal likelihood AND its gradient ingredients in one library call (gpar_logpdf_dense_grad).
-    Returns (out, half_diag, info, A): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W) (device, n),
-    info word, the (n + 1) x (n + 1) factor buffer."""
-    lib = _lib.load()
-    _check_mat(x, "x")
-    n, dev = x.shape[0], x.device
-    y = y.reshape(-1)
-    if y.numel() != n or y.dtype != torch.float64 or not y.is_cuda:
-        raise ValueError("y must hold one fp64 device value per row of x")
-    nptr = None
-    if noise_diag is not None:
-        noise_diag = noise_diag.reshape(-1).contiguous()
-        if noise_diag.numel() != n:
-            raise ValueError("noise_diag must hold one value per row of x")
-        nptr = noise_diag.data_ptr()
-    dz = max(ck.dz, 1)
-    z = alloc_matrix(n, dz, dev)
-    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
-    A = alloc_matrix(n + 1, n + 1, dev)
-    X = alloc_matrix(n, n, dev)
-    W = alloc_matrix(n, n, dev)
-    nt = (n + 63) // 64
-    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
-    work = torch.empty(nblocks * _lib.GRAD_NACC + n, dtype=torch.float64, device=dev)   # gradient partials, then alpha
-    out = torch.empty(2 + _lib.GRAD_NACC, dtype=torch.float64, device=dev)
-    half_diag = torch.empty(n, dtype=torch.float64, device=dev)
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
-    _lib.check(
-        lib.gpar_logpdf_dense_grad(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)), nptr, float(jitter),
-            z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W),
-            work[nblocks * _lib.GRAD_NACC:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), half_diag.data_ptr(), info.data_ptr(), flags,
-            stream_ptr(dev),
-        ),
-        "gpar_logpdf_dense_grad",
-    )
-    return out, half_diag, info, A
-
-
 def _dense_layer_args(x, y, noise_diag):
     """(n, device, flat y, pointer of the noise diagonal or None) of one dense layer, checked (the noise vector is returned too: the
     caller keeps it alive across the call)."""
@@ -170,38 +98,52 @@ def _dense_layer_args(x, y, noise_diag):
     return n, x.device, y, noise_diag
 
 
-def loo_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
-    """Leave-one-out value, means and variances of one dense layer in one library call (gpar_loo_dense; no inverse is formed).
-    Returns (out, loo_mean, loo_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+def _potrf_flags(lookahead, fused):
+    return (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
+
+
+def logpdf_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
+    """log N(y; 0, k(x, x) + diag(noise_diag) + jitter I) in one library call (gpar_logpdf_dense): returns
+    (value, logdet, info) as one-element device tensors and the (n + 1) x (n + 1) factor buffer."""
     lib = _lib.load()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
     z = alloc_matrix(n, max(ck.dz, 1), dev)
     A = alloc_matrix(n + 1, n + 1, dev)
-    X = alloc_matrix(n, n, dev)
-    T = alloc_matrix(n, n, dev)
-    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_LOO, n, 0, 0)), dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+    words = torch.empty(2, dtype=torch.float64, device=dev)   # value, logdet
     info = torch.empty(1, dtype=torch.int32, device=dev)
-    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
     _lib.check(
-        lib.gpar_loo_dense(
+        lib.gpar_logpdf_dense(
             ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
-            T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), info.data_ptr(), flags,
-            stream_ptr(dev),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A),
+            words[1:].data_ptr(), info.data_ptr(), words.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
         ),
-        "gpar_loo_dense",
+        "gpar_logpdf_dense",
     )
-    return out, moments[0], moments[1], info
+    return words[0], words[1:], info, A
 
 
-def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
-    """One dense layer's leave-one-out value AND its gradient ingredients in one library call (gpar_loo_dense_grad).  Returns
-    (out, half_diag, loo_mean, loo_var, info, A, W): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W),
-    the n predictive means and variances, info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
+def _folds_of(objective, fold_start, n, dev):
+    """() for "mll" and "loo"; for "cv" the (device offsets, nfolds, largest fold) triple, uploaded unless it is one already."""
+    if objective != "cv":
+        return ()
+    return fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
+
+
+def objective_vec_doubles(lib, objective, n, grad, folds):
+    """Doubles of the objective's vector workspace ("mll" has none)."""
+    if objective == "mll":
+        return 0
+    return int(lib.gpar_workspace_doubles(_lib.WS_CV, n, grad, folds[2]) if objective == "cv" else lib.gpar_workspace_doubles(_lib.WS_LOO, n, grad, 0))
+
+
+def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused):
+    """One dense layer's objective ("mll", "loo" or "cv") AND its gradient ingredients in one library call (gpar_logpdf_dense_grad,
+    gpar_loo_dense_grad, gpar_cv_dense_grad): allocation and marshalling for the three.  Returns (out, vectors, info, A, W): out = [value,
+    logdet, GRAD_NACC moment sums], vectors = 1/2 diag(W) and - but for "mll" - the held-out means and variances in its rows."""
     lib = _lib.load()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    folds = _folds_of(objective, fold_start, n, dev)
+    fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
     dz = max(ck.dz, 1)
     z = alloc_matrix(n, dz, dev)
     zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
@@ -211,22 +153,72 @@ def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused
     nt = (n + 63) // 64
     nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
     nacc = _lib.GRAD_NACC
-    nvec = int(lib.gpar_workspace_doubles(_lib.WS_LOO, n, 1, 0))
-    work = torch.empty(nblocks * nacc + n + nvec, dtype=torch.float64, device=dev)   # gradient partials, alpha, the LOO vectors
+    # gradient partials, alpha, the objective's vector workspace
+    work = torch.empty(nblocks * nacc + n + objective_vec_doubles(lib, objective, n, 1, folds), dtype=torch.float64, device=dev)
     out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
-    vectors = torch.empty(3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
+    vectors = torch.empty(1 if objective == "mll" else 3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
     info = torch.empty(1, dtype=torch.int32, device=dev)
-    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
-    _lib.check(
-        lib.gpar_loo_dense_grad(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+    head = (ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
             None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
-            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(), work[nblocks * nacc + n:].data_ptr(),
-            work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), vectors[1].data_ptr(), vectors[2].data_ptr(), info.data_ptr(), flags,
-            stream_ptr(dev),
+            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr())
+    tail = (info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev))
+    if objective == "mll":
+        rc = lib.gpar_logpdf_dense_grad(*head, work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), *tail)
+    else:
+        entry = lib.gpar_cv_dense_grad if objective == "cv" else lib.gpar_loo_dense_grad
+        rc = entry(*head, work[nblocks * nacc + n:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(),
+                   vectors[1].data_ptr(), vectors[2].data_ptr(), *fold_args, *tail)
+    _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad", "cv": "gpar_cv_dense_grad"}[objective])
+    return out, vectors, info, A, W
+
+
+def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead, fused):
+    """Value, held-out means and variances of one dense layer for "loo" or "cv" in one library call (gpar_loo_dense, gpar_cv_dense).
+    Returns (out, mean, var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    folds = _folds_of(objective, fold_start, n, dev)
+    fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
+    z = alloc_matrix(n, max(ck.dz, 1), dev)
+    A = alloc_matrix(n + 1, n + 1, dev)
+    X = alloc_matrix(n, n, dev)
+    T = alloc_matrix(n, n, dev)
+    vec = torch.empty(objective_vec_doubles(lib, objective, n, 0, folds), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    entry = lib.gpar_cv_dense if objective == "cv" else lib.gpar_loo_dense
+    _lib.check(
+        entry(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
+            T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(),
+            *fold_args, info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
         ),
-        "gpar_loo_dense_grad",
+        "gpar_cv_dense" if objective == "cv" else "gpar_loo_dense",
     )
+    return out, moments[0], moments[1], info
+
+
+def logpdf_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
+    """One dense layer's log marginal likelihood AND its gradient ingredients in one library call (gpar_logpdf_dense_grad).
+    Returns (out, half_diag, info, A): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W) (device, n),
+    info word, the (n + 1) x (n + 1) factor buffer."""
+    out, vectors, info, A, _ = _dense_grad("mll", ck, x, y, noise_diag, jitter, periodic, None, lookahead, fused)
+    return out, vectors[0], info, A
+
+
+def loo_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
+    """Leave-one-out value, means and variances of one dense layer in one library call (gpar_loo_dense; no inverse is formed).
+    Returns (out, loo_mean, loo_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+    return _dense_value("loo", ck, x, y, noise_diag, jitter, None, lookahead, fused)
+
+
+def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
+    """One dense layer's leave-one-out value AND its gradient ingredients in one library call (gpar_loo_dense_grad).  Returns
+    (out, half_diag, loo_mean, loo_var, info, A, W): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W),
+    the n predictive means and variances, info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
+    out, vectors, info, A, W = _dense_grad("loo", ck, x, y, noise_diag, jitter, periodic, None, lookahead, fused)
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 
@@ -255,61 +247,13 @@ def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=Tru
     """Blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_dense).
     `fold_start`: the nfolds + 1 row offsets of the contiguous folds (host sequence, or the triple `upload_folds` returns).
     Returns (out, cv_mean, cv_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
-    lib = _lib.load()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    starts, nfolds, max_fold = fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
-    z = alloc_matrix(n, max(ck.dz, 1), dev)
-    A = alloc_matrix(n + 1, n + 1, dev)
-    X = alloc_matrix(n, n, dev)
-    T = alloc_matrix(n, n, dev)
-    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_CV, n, 0, max_fold)), dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
-    _lib.check(
-        lib.gpar_cv_dense(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
-            T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), starts.data_ptr(), nfolds, max_fold,
-            info.data_ptr(), flags, stream_ptr(dev),
-        ),
-        "gpar_cv_dense",
-    )
-    return out, moments[0], moments[1], info
+    return _dense_value("cv", ck, x, y, noise_diag, jitter, fold_start, lookahead, fused)
 
 
 def cv_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead=True, fused=True):
     """One dense layer's blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_dense_grad).
     `fold_start` as for `cv_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
-    lib = _lib.load()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    starts, nfolds, max_fold = fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
-    dz = max(ck.dz, 1)
-    z = alloc_matrix(n, dz, dev)
-    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
-    A = alloc_matrix(n + 1, n + 1, dev)
-    X = alloc_matrix(n, n, dev)
-    W = alloc_matrix(n, n, dev)
-    nt = (n + 63) // 64
-    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
-    nacc = _lib.GRAD_NACC
-    nvec = int(lib.gpar_workspace_doubles(_lib.WS_CV, n, 1, max_fold))
-    work = torch.empty(nblocks * nacc + n + nvec, dtype=torch.float64, device=dev)   # gradient partials, alpha, the fold workspace
-    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
-    vectors = torch.empty(3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    flags = (0 if lookahead else _lib.POTRF_NO_LOOKAHEAD) | (0 if fused else _lib.POTRF_UNFUSED)
-    _lib.check(
-        lib.gpar_cv_dense_grad(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
-            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(), work[nblocks * nacc + n:].data_ptr(),
-            work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), vectors[1].data_ptr(), vectors[2].data_ptr(), starts.data_ptr(), nfolds,
-            max_fold, info.data_ptr(), flags, stream_ptr(dev),
-        ),
-        "gpar_cv_dense_grad",
-    )
+    out, vectors, info, A, W = _dense_grad("cv", ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused)
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 

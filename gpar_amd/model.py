@@ -603,35 +603,7 @@ class GPAR:
         them).  Inducing points have no dense K^-1 to leave a point out of: ValueError."""
         if self.sparse:
             raise ValueError("leave-one-out cross-validation needs dense observations (no inducing points)")
-        return _retry_unfused(lambda: self._loo(x, y, w, outputs), self.layers, (x, y, w))
-
-    def _loo(self, x, y, w, outputs):
-        x, y, w = self._prep(x, y, w)
-        items = list(per_output(y, w, keep=self.impute))
-        eng = get_engine()
-        rows = torch.arange(int(x.shape[0]), device=x.device)
-        total, pieces = torch.zeros((), dtype=torch.float64), []
-        with eng.defer_checks():
-            for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
-                complete = isinstance(mask, slice)
-                x, rows = x[mask], rows[mask]
-                f, noise = model()
-                n_missing, keep = getattr(yi, "_n_missing", None), getattr(yi, "_obs_idx", None)   # (the host's plan: per_output)
-                obs = self._obs(x, None, yi, wi, f, noise, complete=complete)
-                obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
-                value, mean, var = obs.loo()
-                if complete or n_missing == 0:
-                    seen = rows
-                elif n_missing is not None:
-                    seen = rows.index_select(0, keep)
-                else:
-                    seen = rows[~torch.isnan(yi[:, 0])]
-                resid = obs.y.reshape(-1) - mean
-                pieces.append((seen, mean, var, -0.5 * (torch.log(2.0 * np.pi * var) + resid * resid / var)))
-                total = value if len(pieces) == 1 else total + value   # (0-d tensors: a host and a device scalar add)
-                if not is_last:
-                    x, _ = self._next_inputs(ALL_LAYERS, i, x, None, yi, f, obs, complete)
-        return (total.cpu() if total.is_cuda and not total.requires_grad else total), pieces
+        return _retry_unfused(lambda: self._held_out(x, y, w, None, outputs), self.layers, (x, y, w))
 
     # ---- blocked cross-validation ---------------------------------------------------------------------
     def cv(self, x, y, w, folds, outputs=None):
@@ -648,33 +620,38 @@ class GPAR:
         labels = np.asarray(folds.cpu() if _is_torch(folds) else folds).reshape(-1)
         if labels.size != int(x.shape[0]) or not np.issubdtype(labels.dtype, np.integer):
             raise ValueError("folds must hold one integer label per row of x")
-        return _retry_unfused(lambda: self._cv(x, y, w, labels, outputs), self.layers, (x, y, w))
+        return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs), self.layers, (x, y, w))
 
-    def _cv(self, x, y, w, labels, outputs):
+    def _held_out(self, x, y, w, labels, outputs):
+        """The layer loop of `loo` (`labels` None: pieces carry the per-row log-density, and nothing is kept on the host) and `cv`."""
         x, y, w = self._prep(x, y, w)
         items = list(per_output(y, w, keep=self.impute))
         eng = get_engine()
+        blocked = labels is not None
         rows = torch.arange(int(x.shape[0]), device=x.device)
-        rows_host = np.arange(int(x.shape[0]))   # (the same rows on the host: the labels live there)
+        rows_host = np.arange(int(x.shape[0])) if blocked else None   # (the same rows on the host: the labels live there)
         total, pieces = torch.zeros((), dtype=torch.float64), []
         with eng.defer_checks():
             for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
                 complete = isinstance(mask, slice)
-                x, rows, rows_host = x[mask], rows[mask], rows_host[host_index(mask)]
+                x, rows = x[mask], rows[mask]
                 f, noise = model()
                 n_missing, keep = getattr(yi, "_n_missing", None), getattr(yi, "_obs_idx", None)   # (the host's plan: per_output)
                 obs = self._obs(x, None, yi, wi, f, noise, complete=complete)
-                if complete or n_missing == 0:
-                    seen, seen_host = rows, rows_host
+                if complete or n_missing == 0:   # (`sel`: the observed among this layer's rows; None: all of them)
+                    seen, sel = rows, None
                 elif n_missing is not None:
-                    seen, seen_host = rows.index_select(0, keep), rows_host[host_index(keep)]
+                    seen, sel = rows.index_select(0, keep), keep
                 else:
-                    observed = ~torch.isnan(yi[:, 0])
-                    seen, seen_host = rows[observed], rows_host[host_index(observed)]
-                perm, starts = contiguous_folds(labels[seen_host])
+                    sel = ~torch.isnan(yi[:, 0])
+                    seen = rows[sel]
+                perm = None
+                if blocked:
+                    rows_host = rows_host[host_index(mask)]
+                    perm, starts = contiguous_folds(labels[rows_host if sel is None else rows_host[host_index(sel)]])
                 if perm is None:
                     obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
-                    value, mean, var = obs.cv(starts)
+                    value, mean, var = obs.cv(starts) if blocked else obs.loo()
                 else:
                     # the evaluation's own observations, rows sorted by fold; `obs` keeps the order the next layer reads
                     at = torch.as_tensor(perm, dtype=torch.long, device=obs.y.device)
@@ -685,7 +662,11 @@ class GPAR:
                     sorted_obs.transient = True
                     value, mean, var = sorted_obs.cv(starts)
                     mean, var = torch.empty_like(mean).index_copy_(0, at, mean), torch.empty_like(var).index_copy_(0, at, var)
-                pieces.append((seen, mean, var))
+                if blocked:
+                    pieces.append((seen, mean, var))
+                else:
+                    resid = obs.y.reshape(-1) - mean
+                    pieces.append((seen, mean, var, -0.5 * (torch.log(2.0 * np.pi * var) + resid * resid / var)))
                 total = value if len(pieces) == 1 else total + value   # (0-d tensors: a host and a device scalar add)
                 if not is_last:
                     x, _ = self._next_inputs(ALL_LAYERS, i, x, None, yi, f, obs, complete)
