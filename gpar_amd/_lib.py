@@ -22,11 +22,12 @@ GEMM_K_FROM_ROW = 4
 GEMM_K_TO_COL = 8
 POTRF_NO_LOOKAHEAD = 1
 POTRF_UNFUSED = 2
-WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO, WS_CV = 1, 2, 3, 4, 5, 6, 7
+WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO, WS_CV, WS_PIVOTED_CHOL = 1, 2, 3, 4, 5, 6, 7, 8
+PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -102,6 +103,7 @@ SIGNATURES = {
          _ptr],
     ),
     "gpar_gram_diag": (_c_int, [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    "gpar_pivoted_chol": (_c_int, [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "gpar_featurize_dfreq": (_c_int, [ctypes.POINTER(FSpec), _ptr, _c_int, _c_int, _ptr, _c_int, _ptr]),
     "gpar_grad_nacc": (_c_int, []),
     "gpar_gram_grad": (

@@ -11,6 +11,7 @@
 #include "gram_jit.h"
 #include "grad_jit.h"
 #include "blas1.h"
+#include "pivchol.h"
 
 namespace gpar {
 
@@ -747,6 +748,12 @@ int gpar_gram_diag(const gpar_kspec_t* ks, const double* z, int n, int ldz, int 
     hipLaunchKernelGGL(gram_diag_kernel, dim3(gpar_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, *ks, z, n, ldz, out);
     GPAR_LAUNCH_CHECK();
     return 0;
+}
+
+int gpar_pivoted_chol(const gpar_kspec_t* ks, const double* z, int n, int ldz, int dz, int max_rank, double tol_trace, double floor, double* Lt,
+                      int ldl, int* piv, double* trace, int* rank, int* info, double* ws, void* stream) {
+    GPAR_API_GUARD;
+    return pivoted_chol_run(ks, z, n, ldz, dz, max_rank, tol_trace, floor, Lt, ldl, piv, trace, rank, info, ws, (hipStream_t)stream);
 }
 
 int gpar_featurize_dfreq(const gpar_fspec_t* fs, const double* x, int n, int ldx, double* zd, int ldz, void* stream) {
@@ -1587,6 +1594,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_CV:                                                                /* n, with gradient, max_fold */
             if (c < 1 || c > GPAR_CV_MAX_FOLD) return -1;
             return (long long)(a > 0 ? a : 0) * (b ? 3 + c : 1);
+        case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         default: return -1;
     }
 }

@@ -303,10 +303,8 @@ __global__ __launch_bounds__(256) void lockstep_build_kernel(LockstepSpecs sp, c
     }
 }
 
-__global__ __launch_bounds__(256) void gram_diag_kernel(gpar_kspec_t ks, const double* __restrict__ z, int n, int ldz,
-                                                        double* __restrict__ out) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
+// k(z, z) of one feature row: the scalar interpreter loop (shared with the pivoted Cholesky's start, pivchol.h)
+__device__ __forceinline__ double gram_diag_value(const gpar_kspec_t& ks, const double* __restrict__ zr) {
     double total = 0.0;
     int f = 0;
     for (int term = 0; term < ks.nterms; ++term) {
@@ -315,7 +313,7 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(gpar_kspec_t ks, const d
             double s = 0.0;
             if (ks.factor[f].type == GPAR_K_LINEAR) {
                 for (int d = ks.factor[f].off; d < ks.factor[f].off + ks.factor[f].nd; ++d) {
-                    const double v = z[(size_t)r * ldz + d];
+                    const double v = zr[d];
                     s = fma(v, v, s);
                 }
             }
@@ -324,7 +322,14 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(gpar_kspec_t ks, const d
         }
         total += prod;
     }
-    out[r] = total;
+    return total;
+}
+
+__global__ __launch_bounds__(256) void gram_diag_kernel(gpar_kspec_t ks, const double* __restrict__ z, int n, int ldz,
+                                                        double* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    out[r] = gram_diag_value(ks, z + (size_t)r * ldz);
 }
 
 

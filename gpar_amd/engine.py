@@ -14,6 +14,7 @@ Primitive set (all tensors float64, row-major, lower triangles authoritative):
     features(ck, x)                   z = stretch(periodic(select(x)))
     gram(ck, z1, z2=None, ...)        fused Gram (+ noise diagonal + jitter), optionally lower-only
     gram_diag(ck, z)                  k(x_i, x_i)
+    pivoted_cholesky(ck, z, r, ...)   greedy pivoted Cholesky of k(z, z) (HipEngine only: gp.greedy_inducing composes it elsewhere)
     new_matrix(r, c, zero=False)      workspace with aligned, padded rows
     potrf_(A, nf=None)                (partial) Cholesky -> (logdet, info) device scalars
     trsm_rlt_(L, B) / trsm_rln_(L, B) B L^-T / B L^-1
@@ -190,6 +191,16 @@ class HipEngine:
 
     def gram_diag(self, ck, z):
         return hip.gram_diag(ck, z)
+
+    def pivoted_cholesky(self, ck, z, max_rank, tol=0.0, floor=None):
+        """Greedy (partially pivoted) Cholesky of k(z, z) on the features z in one library call (gpar_pivoted_chol): (Lt, piv, trace, rank)
+        as device tensors - the factor transposed (max_rank x n, zero rows from the rank on), the pivots (-1 beyond the rank), the
+        residual traces (max_rank + 1) and the rank as a one-element tensor.  Nothing synchronises; a non-finite pivot is reported like
+        a failed factorisation (check_info: deferred inside defer_checks()).  `floor` None: the engine's jitter - what the inducing-
+        point path adds to K_zz anyway; a pivot whose residual variance lies below it adds nothing K_zz + epsilon I can resolve."""
+        Lt, piv, trace, rank, info, _ = hip.pivoted_chol(ck, z, max_rank, tol, self.epsilon if floor is None else floor)
+        self.check_info(info)
+        return Lt, piv, trace, rank
 
     def potrf_(self, A, nf=None):
         return hip.potrf_(A, nf=nf, **self._factor_flags())

@@ -42,7 +42,7 @@ from .engine import get_engine, joining
 from .hip import fold_offsets
 from .kernels import Kernel
 
-__all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs"]
+__all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs", "greedy_inducing"]
 
 _LOG_2PI = math.log(2.0 * math.pi)
 
@@ -1620,3 +1620,61 @@ class PseudoObsDTC(PseudoObs):
 
 PseudoObsVFE = PseudoObs
 SparseObs = PseudoObs
+
+
+def _pivoted_cholesky_composed(eng, ck, z, max_rank, tol, floor):
+    """The greedy pivoted Cholesky of k(z, z) from primitives every engine has - `gram_diag`, `gram` against the pivot's single row,
+    torch for the update and the argmax, ONE device-to-host read per pivot (the row, its residual and the trace together) - with the
+    semantics of gpar_pivoted_chol (include/gpar_hip.h): ties go to the smallest row, a NaN ranks above every number (+inf included),
+    the same three stop rules, zero rows and -1 pivots beyond the rank.  The route of engines without `pivoted_cholesky`, and the
+    yardstick of the fused call."""
+    n = int(z.shape[0])
+    d = eng.gram_diag(ck, z).reshape(-1).clone()
+    dev = d.device
+    Lt = torch.zeros(max_rank, n, dtype=torch.float64, device=dev)
+    rows = torch.arange(n, device=dev)
+    piv, trace = [-1] * max_rank, [0.0] * (max_rank + 1)
+    rank, info = max_rank, 0
+    for j in range(max_rank + 1):
+        nan = torch.isnan(d)
+        top = torch.where(nan, torch.full_like(d, -math.inf), d).max()
+        p = torch.where(torch.where(nan.any(), nan, d == top), rows, n).min()
+        p, dp, tr = torch.stack([p.to(torch.float64), d[p], d.sum()]).tolist()   # (the step's one synchronisation)
+        p = int(p)
+        trace[j] = tr
+        if j == max_rank:
+            break
+        if dp <= floor or tr <= tol * trace[0] or not math.isfinite(dp):
+            rank, info = j, (0 if math.isfinite(dp) else p + 1)
+            break
+        c = eng.gram(ck, z, z[p:p + 1]).reshape(-1) - Lt[:j, p] @ Lt[:j]
+        root = math.sqrt(dp)
+        col = c / root
+        col[p] = root
+        Lt[j] = col
+        d = d - col * col
+        d[p] = 0.0
+        piv[j] = p
+    eng.check_info(torch.tensor([info], dtype=torch.int32))
+    return (Lt, torch.tensor(piv, dtype=torch.int32, device=dev), torch.tensor(trace, dtype=torch.float64, device=dev),
+            torch.tensor([rank], dtype=torch.int32, device=dev))
+
+
+def greedy_inducing(eng, ck, x, num, tol=0.0, floor=None):
+    """Greedy selection of up to `num` inducing points among the rows of the design matrix `x` under the compiled kernel `ck`: the
+    partially pivoted Cholesky factorisation of k(x, x) that always takes the row of largest conditional variance next (Fine &
+    Scheinberg 2001; the initialisation Burt et al. 2019 recommend for sparse variational GPs).  O(n num^2), deterministic, and it stops
+    early when the largest residual variance is at most `floor` (None: the engine's jitter, which K_zz receives anyway) or the
+    residual trace tr(K - Q) - the quantity the VFE bound penalises - has fallen to `tol` times its start.
+    Returns engine tensors (Lt, piv, trace, rank): the factor transposed (num x n, K ~ Lt^T Lt, zero rows from the rank on), the chosen
+    rows in order (int32, -1 beyond the rank), the residual trace before every step (num + 1 values; trace[rank] is the final one)
+    and the rank as a one-element tensor.  Engines with `pivoted_cholesky` take it (one library call, no synchronisation); others run
+    the same algorithm composed of their primitives."""
+    z = eng.features(ck, _as_matrix(eng, x))
+    num = int(num)
+    if not 1 <= num <= int(z.shape[0]):
+        raise ValueError(f"num={num}: between 1 and the number of rows ({int(z.shape[0])}) inducing points can be selected")
+    floor = eng.epsilon if floor is None else float(floor)
+    if hasattr(eng, "pivoted_cholesky"):
+        return eng.pivoted_cholesky(ck, z, num, tol=tol, floor=floor)
+    return _pivoted_cholesky_composed(eng, ck, z, num, float(tol), floor)

@@ -19,6 +19,7 @@ __all__ = [
     "featurize",
     "gram",
     "gram_diag",
+    "pivoted_chol",
     "potrf_",
     "trsm_rlt_",
     "trsm_rln_",
@@ -422,6 +423,28 @@ def gram_diag(ck, z):
         "gpar_gram_diag",
     )
     return out
+
+
+def pivoted_chol(ck, z, max_rank, tol_trace, floor):
+    """Greedy (partially pivoted) Cholesky of k(z, z) on the features z (gpar_pivoted_chol; semantics: include/gpar_hip.h).  Returns
+    device tensors and never synchronises: (Lt max_rank x n - the factor transposed, rows from the rank on zero -, piv int32 max_rank
+    with -1 beyond the rank, trace max_rank + 1, rank and info as one-element int32 tensors, the final residual diagonal d)."""
+    lib = _lib.load()
+    _check_mat(z, "z")
+    n, dev, max_rank = z.shape[0], z.device, int(max_rank)
+    if n < 1 or not 1 <= max_rank <= _lib.PIVCHOL_MAX_RANK:
+        raise ValueError(f"pivoted_chol takes at least one row and 1 to {_lib.PIVCHOL_MAX_RANK} steps")
+    Lt = alloc_matrix(max_rank, n, dev)
+    piv = torch.empty(max_rank, dtype=torch.int32, device=dev)
+    trace = torch.empty(max_rank + 1, dtype=torch.float64, device=dev)
+    words = torch.empty(2, dtype=torch.int32, device=dev)   # rank, info
+    ws = torch.empty(lib.gpar_workspace_doubles(_lib.WS_PIVOTED_CHOL, n, 0, 0), dtype=torch.float64, device=dev)
+    _lib.check(
+        lib.gpar_pivoted_chol(ctypes.byref(ck.kspec), z.data_ptr(), n, _ld(z), ck.dz, max_rank, float(tol_trace), float(floor), Lt.data_ptr(),
+                              _ld(Lt), piv.data_ptr(), trace.data_ptr(), words.data_ptr(), words[1:].data_ptr(), ws.data_ptr(), stream_ptr(dev)),
+        "gpar_pivoted_chol",
+    )
+    return Lt, piv, trace, words[0:1], words[1:2], ws[:n]
 
 
 def potrf_(A, nf=None, logdet=None, info=None, lookahead=True, fused=True):

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .engine import get_engine
-from .gp import GP, Measure
+from .gp import GP, Measure, greedy_inducing
 from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
 from .model import GPAR, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
@@ -520,6 +520,48 @@ class GPARRegressor:
         self.greedy_vs_ = chain_vs
         self.greedy_order_ = list(order)
         return order, values
+
+    def select_inducing(self, x, num, tol=0.0, assign=False):
+        """Greedy selection of inducing points among the rows of x (n x m) - an addition; the reference's constructor takes an array and
+        nothing else.  The rows are picked by largest conditional variance under the first layer's kernel over the inputs, as the
+        model builds it for output 0 at the current values of `self.vs` (variables that do not exist yet are created with their
+        usual names, initial values and bounds, as `fit` would create them; after `fit`: the trained length scales): a partially
+        pivoted Cholesky factorisation of k(x, x) (`gp.greedy_inducing`), O(n num^2) and deterministic.  It stops before `num` rows
+        when the residual trace tr(K - K_xz K_zz^-1 K_zx) - what the VFE bound penalises - has fallen to `tol` times tr K, or when no
+        remaining row has a conditional variance above the engine's jitter.
+        Returns numpy arrays (x_ind, index, trace): the rank <= num selected rows of x in selection order, their row indices, and the
+        residual trace before each step and after the last (rank + 1 values).  `assign=True` installs the rows as `self.x_ind` and
+        makes the regressor sparse, as the constructor would have, dropping any conditioned state; otherwise nothing changes."""
+        x_np = np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
+        if x_np.ndim < 2:
+            x_np = x_np.reshape(-1, 1)
+        n, m = x_np.shape
+        num = int(num)
+        if num < 1 or num > n:
+            raise ValueError(f"num={num}: between 1 and the number of rows ({n}) inducing points can be selected")
+        if self.m is not None and m != self.m:
+            raise ValueError(f"x has {m} columns, the model has {self.m} inputs")
+        eng = get_engine()
+        with torch.no_grad():
+            kernel = _model_generator(self.vs, m, 0, **self.model_config)()[0].kernel
+            with eng.defer_checks():
+                _, piv, trace, rank = greedy_inducing(eng, eng.compile(kernel, m), eng.tensor(x_np), num, tol=tol)
+        rank = int(rank.item())
+        index = piv[:rank].cpu().numpy().astype(np.int64)
+        x_ind = x_np[index]
+        if assign:
+            self.x_ind = _uprank(_to_torch(x_ind.copy()))
+            self.sparse = True
+            # (inducing inputs trained earlier - fit(optimise_x_ind=True) - live on as the variable "x_ind", which the model would
+            # prefer to the attribute: the constructor's state has neither the variable nor the flag)
+            self._x_ind_trainable = False
+            if "x_ind" in self.vs:
+                self.vs.remove("x_ind")
+            self.is_conditioned = False
+            self.x = self.y = self.w = None
+            self.n = self.m = self.p = None
+            self._unnormalise_y, self._normalise_y = (lambda x: x), (lambda x: x)
+        return x_ind, index, trace[: rank + 1].cpu().numpy()
 
     def loo(self, x, y, w=None):
         """Layer-wise leave-one-out cross-validation under the prior model (`GPAR.loo`): `(value, mean, var)`.  `value` is the sum

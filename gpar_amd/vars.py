@@ -155,6 +155,11 @@ class Vars:
         with torch.no_grad():
             var.latent.copy_(torch.tensor(latent, dtype=self.dtype).reshape(var.latent.shape))
 
+    def remove(self, name):
+        """Forget a variable (and what was memoised from the store): the next `get` / `pos` / `bnd` of that name creates it anew."""
+        del self._vars[name]
+        self._memo.clear()
+
     def match(self, patterns):
         """Names matching any of the glob patterns (e.g. "0/*"), in creation order."""
         if isinstance(patterns, str):

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 9
+#define GPAR_ABI_VERSION 10
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -175,6 +175,28 @@ int gpar_gram_batch(const gpar_kspec_t* ks, const double* z, int n, int ldz, lon
 
 /* out[a] = k(z[a], z[a])   [kernel diagonal; VFE trace term, posterior marginal variances] */
 int gpar_gram_diag(const gpar_kspec_t* ks, const double* z, int n, int ldz, int dz, double* out, void* stream);
+
+/* Greedy (partially pivoted) Cholesky of k(Z, Z) (ABI v10): the selection of inducing points by largest conditional variance (Fine &
+ * Scheinberg 2001; the initialisation Burt et al. 2019 recommend for sparse variational GPs).  z: n x dz features as gpar_featurize
+ * writes them (ldz).  d starts as diag k(Z, Z) - no noise, no jitter, the arithmetic of gpar_gram_diag - and step j = 0, 1, ... does, in
+ * this order:
+ *   1. p = argmax_i d_i; ties go to the smallest i, a NaN ranks above every number;
+ *   2. stop if d_p <= floor, or trace_j = sum_i d_i <= tol_trace * trace_0, or d_p is not finite (then info[0] = p + 1; 0 otherwise);
+ *   3. c_i = k(z_i, z_p) - sum_{t<j} Lt[t][i] Lt[t][p]  (c <- fma(-Lt[t][i], Lt[t][p], c), t ascending, starting from the kernel entry);
+ *   4. Lt[j][i] = c_i / sqrt(d_p), and Lt[j][p] = sqrt(d_p) itself;
+ *   5. d_i <- fma(-Lt[j][i], Lt[j][i], d_i), and d_p <- 0 exactly (with floor >= 0 a picked row is never picked again).
+ * Lt: max_rank x n row-major (ldl >= n), the factor TRANSPOSED: Lt[t][i] = L[i][t], so K ~ Lt^T Lt and K[:, piv] = Lt^T Lt[:, piv].
+ * On return (all device memory, written by the kernels): rank[0] = steps taken; piv[0 .. rank) the pivots in order, -1 beyond; rows rank ..
+ * of Lt zero; trace[j] = the residual trace before step j for j <= rank (trace[rank]: after the last step), 0 beyond: max_rank + 1 values.
+ * ws: gpar_workspace_doubles(GPAR_WS_PIVOTED_CHOL, n, 0, 0) doubles; its first n hold the final residual diagonal d.
+ * Limits: 1 <= max_rank <= GPAR_PIVCHOL_MAX_RANK (the pivot's row of the factor is staged in LDS), floor >= 0, tol_trace >= 0.
+ * max_rank + 2 plain launches on `stream` and nothing else: no host synchronisation, no atomics, no waiting inside a launch; once a step
+ * has stopped, the remaining launches only clear their row.  The result is a function of the inputs alone: two runs give the same bits.
+ * Traffic: 8 n max_rank^2 / 2 bytes of Lt read; the kernel entries use libm's exp (gpar_gram uses tables: agreement to rounding).
+ * [no reference counterpart: GPAR(x_ind=...) takes an array and nothing else, gpar/model.py:286-287] */
+#define GPAR_PIVCHOL_MAX_RANK 4096
+int gpar_pivoted_chol(const gpar_kspec_t* ks, const double* z, int n, int ldz, int dz, int max_rank, double tol_trace, double floor,
+                      double* Lt, int ldl, int* piv, double* trace, int* rank, int* info, double* ws, void* stream);
 
 /* zd[q] = d z[q] / d freq[q] (zero for non-periodic features): the feature derivative the period gradients need. */
 int gpar_featurize_dfreq(const gpar_fspec_t* fs, const double* x, int n, int ldx, double* zd, int ldz, void* stream);
@@ -451,7 +473,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_GRAM_GRAD    (nblocks, -, -)  gpar_gram_grad / gpar_gram_grad_cross
  *   GPAR_WS_CHOL_INVERSE (n, ldx, -)      the X matrix of gpar_chol_inverse
  *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1)
- *   GPAR_WS_CV           (n, grad, max_fold)  the `vec` of gpar_cv_dense (grad = 0) / gpar_cv_dense_grad[_finish] (grad = 1) */
+ *   GPAR_WS_CV           (n, grad, max_fold)  the `vec` of gpar_cv_dense (grad = 0) / gpar_cv_dense_grad[_finish] (grad = 1)
+ *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -459,6 +482,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_INPUT_GRAD 5   /* (n1, dz, nsplit)  gpar_gram_input_grad */
 #define GPAR_WS_LOO 6
 #define GPAR_WS_CV 7
+#define GPAR_WS_PIVOTED_CHOL 8
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */

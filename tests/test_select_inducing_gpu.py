@@ -1,0 +1,191 @@
+"""The fused greedy pivoted Cholesky (gpar_pivoted_chol through `HipEngine.pivoted_cholesky`) on the GPU: against the route composed of
+the engine's own primitives (`gp._pivoted_cholesky_composed`: gpar_gram_diag, gpar_gram against the pivot's row, torch), by invariants
+that need no pivot order, and from `GPARRegressor.select_inducing` to a trained sparse model.
+
+The comparisons carry the assertions of tests/test_select_inducing.py on the numpy reference first (gap between the two largest
+residuals above 1e-9 at every step, pivots above `PIVOT_MIN`), and its tolerance:
+
+    bound(k, kmax) = 8 ((k + 1) 2^-53 kmax + 1e-13 kmax + 1e-14)
+
+(backward error of a rank-k Cholesky with |L||L^T| <= max diag K = kmax, plus the tolerance tests/test_hip_primitives.py holds gpar_gram
+to against the oracle - the fused column kernel uses libm's exp, gpar_gram its tables - taken 8 times).  Evaluated for the cases here:
+k = 40, kmax = 1.3 (EQ): 1.2e-12;  k = 64, kmax = 1.60 (EQ + linear, n = 600): 1.4e-12;  k = 96, kmax = 1: 9.7e-13.  `Lt` and the traces
+of the two routes are held to it; only where a trace is RECOMPUTED here as a sum of n residuals, each of them held to the bound (the
+invariants test), is it held to n times the bound.
+"""
+import numpy as np
+import pytest
+import torch
+
+from gpar_amd import greedy_inducing
+from gpar_amd.engine import NotPositiveDefiniteError
+from gpar_amd.gp import _pivoted_cholesky_composed
+from gpar_amd.kernels import EQ, Linear
+from gpar_amd.regression import GPARRegressor
+
+from .conftest import make_engine, to_np
+from .test_select_inducing import (FLOOR, GAP, PIVOT_MIN, _reference, assert_rank3, assert_same, bound, dense_gram, kernels2d, linear_rank3,
+                                   points, regression_data)
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from gpar_amd.engine import set_engine
+
+    engine = make_engine("hip")
+    previous = set_engine(engine)
+    yield engine
+    set_engine(previous)
+
+
+def _wide():
+    """A structure of 20 feature dims (more than the 16 up to which Gram kernels are generated): EQ over 16 columns + linear over 4."""
+    cols = list(range(20))
+    kernel = (1.1 * EQ().stretch(np.full(16, 3.0))).select(cols[:16]) + Linear().stretch(np.full(4, 2.0)).select(cols[16:])
+    return kernel, np.random.default_rng(5).uniform(0.0, 1.0, (300, 20))
+
+
+def _both_routes(eng, kernel, x, num, tol=0.0):
+    ck = eng.compile(kernel, x.shape[1])
+    z = eng.features(ck, eng.tensor(x))
+    fused = eng.pivoted_cholesky(ck, z, num, tol=tol)
+    composed = _pivoted_cholesky_composed(eng, ck, z, num, tol, eng.epsilon)
+    return fused, composed
+
+
+def _compare(eng, kernel, x, num):
+    K = dense_gram(None, kernel, x)
+    ref = _reference(K, num)
+    assert ref[4] > GAP, f"the pivot order is not comparable between two roundings: smallest gap {ref[4]:.3g}"
+    assert ref[3] == num and ref[5] > PIVOT_MIN
+    fused, composed = _both_routes(eng, kernel, x, num)
+    cLt, cpiv, ctrace, crank = (to_np(t) for t in composed)
+    np.testing.assert_array_equal(cpiv, ref[1])
+    assert_same(fused, (cLt, cpiv, ctrace, int(crank[0])), np.max(np.diag(K)))
+
+
+@pytest.mark.parametrize("name", list(kernels2d()))
+@pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 600])
+def test_fused_matches_composed(eng, n, name):
+    _compare(eng, kernels2d()[name], points(n), min(n, 40))
+
+
+def test_fused_matches_composed_on_a_wide_structure(eng):
+    kernel, x = _wide()
+    assert eng.compile(kernel, 20).dz == 20
+    _compare(eng, kernel, x, 40)
+
+
+@pytest.mark.parametrize("name", list(kernels2d()))
+def test_invariants_of_the_fused_result(eng, name):
+    """What must hold whatever the pivot order, at n = 600 (three workgroups), 64 steps; K is the engine's own Gram matrix."""
+    from gpar_amd import hip
+
+    n, num = 600, 64
+    kernel, x = kernels2d()[name], points(n)
+    ck = eng.compile(kernel, 2)
+    z = eng.features(ck, eng.tensor(x))
+    Lt, piv, trace, rank, info, d = (to_np(t) for t in hip.pivoted_chol(ck, z, num, 0.0, eng.epsilon))
+    K = to_np(eng.gram(ck, z))
+    k = int(rank[0])
+    assert int(info[0]) == 0 and 1 <= k <= num
+    piv = piv[:k]
+    b = bound(k, np.max(np.diag(K)))
+    assert len(set(piv.tolist())) == k and np.all((piv >= 0) & (piv < n))
+    # Lt[:k, piv] transposed is lower triangular with a positive diagonal: above it stand residual covariances of rows picked earlier,
+    # zero up to the bound before the division by the pivot's root Lt[t, piv[t]]
+    T = Lt[:k][:, piv].T
+    assert np.all(np.diag(T) > 0.0)
+    assert np.max(np.abs(np.triu(T, 1)) * np.diag(T)[None, :]) <= b
+    # the columns of K at the pivots are reproduced
+    err = np.max(np.abs(Lt[:k].T @ Lt[:k][:, piv] - K[:, piv]))
+    # the residual diagonal, and the traces recomputed from the factor
+    resid = np.diag(K)[None, :] - np.concatenate([np.zeros((1, n)), np.cumsum(Lt[:k] ** 2, axis=0)])   # row j: before step j
+    err_d = np.max(np.abs(resid[k] - d))
+    err_t = np.max(np.abs(resid.sum(axis=1) - trace[: k + 1]))
+    short = np.max([resid[j].max() - resid[j, piv[j]] for j in range(k)])
+    print(f"{name}: rank {k}, bound {b:.3g}: columns {err:.3g}, residual {err_d:.3g}, min residual {d.min():.3g}, trace {err_t:.3g} "
+          f"(n bound {n * b:.3g}), pivot below the maximum by {short:.3g}")
+    assert err <= b and err_d <= b and d.min() >= -b and resid[k].min() >= -b
+    assert err_t <= n * b
+    assert short <= b
+
+
+def test_full_rank_reproduces_the_matrix(eng):
+    kernel, x = (1.0 * EQ().stretch(np.array([0.15, 0.15]))).select([0, 1]), points(96)
+    K = dense_gram(None, kernel, x)
+    ref = _reference(K, 96)
+    assert ref[3] == 96 and ref[5] > 1e3 * FLOOR   # the residual stays above the floor for all 96 steps
+    Lt, piv, trace, rank = (to_np(t) for t in greedy_inducing(eng, eng.compile(kernel, 2), x, 96))
+    assert int(rank[0]) == 96 and sorted(piv.tolist()) == list(range(96))
+    err = np.max(np.abs(Lt.T @ Lt - K))
+    print(f"full rank: |Lt^T Lt - K| {err:.3g} (bound {bound(96, 1.0):.3g}), final trace {trace[96]:.3g}")
+    assert err <= bound(96, 1.0) and abs(trace[96]) <= bound(96, 1.0)
+
+
+def test_two_runs_give_the_same_bits(eng):
+    from gpar_amd import hip
+
+    kernel, x = kernels2d()["eq+linear"], points(600)
+    ck = eng.compile(kernel, 2)
+    z = eng.features(ck, eng.tensor(x))
+    first = [to_np(t).copy() for t in eng.pivoted_cholesky(ck, z, 40)]
+    second = [to_np(t).copy() for t in eng.pivoted_cholesky(ck, z, 40)]
+    # ... and a third while another stream factors a matrix
+    A = eng.new_matrix(1536, 1536)
+    A.copy_(torch.eye(1536, dtype=torch.float64, device=A.device) * 4.0 + 1e-3)
+    side = torch.cuda.Stream(device=eng.device)
+    side.wait_stream(torch.cuda.current_stream(eng.device))
+    with torch.cuda.stream(side):
+        _, info = hip.potrf_(A)
+    third = [to_np(t).copy() for t in eng.pivoted_cholesky(ck, z, 40)]
+    torch.cuda.current_stream(eng.device).wait_stream(side)
+    assert int(info.item()) == 0
+    for a, b, c in zip(first, second, third):
+        assert a.tobytes() == b.tobytes() == c.tobytes()
+
+
+def test_stops_on_the_device(eng):
+    kernel, x = linear_rank3()
+    assert_rank3(greedy_inducing(eng, eng.compile(kernel, 3), x, 10))
+    kernel, x = kernels2d()["eq"], points(200)
+    ref = _reference(dense_gram(None, kernel, x), 40)
+    first = int(np.argmax(ref[2] <= 0.5 * ref[2][0]))
+    assert 0 < first < 40 and abs(ref[2][first] - 0.5 * ref[2][0]) > 1e-6
+    Lt, piv, trace, rank = (to_np(t) for t in greedy_inducing(eng, eng.compile(kernel, 2), x, 40, tol=0.5))
+    assert int(rank[0]) == first and np.all(piv[first:] == -1) and np.all(Lt[first:] == 0.0) and np.all(trace[first + 1:] == 0.0)
+    np.testing.assert_array_equal(piv[:first], ref[1][:first])
+
+
+def test_a_nan_row_is_reported_through_the_deferred_check(eng):
+    # (EQ + linear: the prior variance of a row depends on its features, so the NaN is in d from the start and ranks first)
+    kernel, x = kernels2d()["eq+linear"], points(300)
+    x[37, 1] = np.nan
+    with pytest.raises(NotPositiveDefiniteError) as caught:
+        with eng.defer_checks():
+            Lt, piv, trace, rank = greedy_inducing(eng, eng.compile(kernel, 2), x, 20)
+    assert caught.value.info == 38
+    assert int(rank.item()) == 0 and np.all(to_np(piv) == -1) and np.all(to_np(Lt) == 0.0)
+    # a NaN ranks above every number, +inf at a smaller row included
+    x[5, 0] = np.inf
+    with pytest.raises(NotPositiveDefiniteError) as caught:
+        greedy_inducing(eng, eng.compile(kernel, 2), x, 20)
+    assert caught.value.info == 38
+
+
+def test_select_inducing_to_a_trained_sparse_model(eng):
+    x, y = regression_data(500)
+    kw = dict(replace=True, scale=0.3, linear=True, nonlinear=True, noise=0.1)
+    reg = GPARRegressor(**kw)
+    x_ind, index, trace = reg.select_inducing(x, 32, assign=True)
+    assert x_ind.shape == (32, 2) and reg.sparse and np.all(np.diff(trace) < 0.0)
+    np.testing.assert_array_equal(x_ind, x[index])
+    built = GPARRegressor(x_ind=x_ind, **kw)
+    value = float(reg.logpdf(x, y))
+    np.testing.assert_allclose(value, float(built.logpdf(x, y)), rtol=1e-8)   # (the sparse parity tolerance of tests/test_parity_gpu.py)
+    reg.fit(x, y, iters=3)
+    assert np.isfinite(float(reg.logpdf(x, y)))
+    mean, var = reg.predict_moments(x[:50])
+    assert mean.shape == (50, 2) and np.all(np.isfinite(mean)) and np.all(var > 0.0)
