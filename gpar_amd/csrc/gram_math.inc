@@ -211,9 +211,12 @@ __device__ __forceinline__ void gram_exp8(double (&x)[8], const double* __restri
 //   w = fl(1 + u), c = u - (w - 1) (the exact rounding error),  w = m 2^e,  j = top 7 mantissa bits of m,  r = m v_j - 1, |r| < 2^-8:
 //   log1p(u) = (e - 1) ln2 + log(2 / v_j) + log1p(r) + c / w,      log1p(r) = r + r^2 (-1/2 + r (1/3 + r (-1/4 + r (1/5 - r/6))))
 // with v_j, log(2 / v_j) from the LDS table and c / w ~ c v_j 2^-e (a correction of at most 1e-16: 1 % accuracy is plenty).
-// Relative error ~2e-16 down to u ~ 1e-3 and absolute error < 1e-18 below (the table value and log1p(r) cancel there), which is
-// more than the exponent -alpha log1p(u) needs; u == 0 gives exactly 0, so that the diagonal of an RQ Gram matrix is exactly its
-// coefficient.  ~20 vector instructions per value where the library's
+// Relative error at most 8.1 * 2^-53 = 9.0e-16 for u >= 2^-7 and absolute error at most 17 * 2^-62 = 3.7e-18 below (the table value
+// and log1p(r) cancel there; the degree-6 truncation r^7 / 7 = 1.9e-18 at the interval ends is half of it) - a rounding analysis, written
+// out in tests/test_gram_math.py, whose sweep of an operation-by-operation emulation measures 1.9 * 2^-53 and 2.6e-18; below u ~ 1e-17 the
+// result is 1.7e-18 whatever u is, so only the absolute bound holds there.  That is what the exponent -alpha log1p(u) needs (alpha L times
+// the relative bound stays inside 1e-13 at exponents of 100); u == 0 gives exactly 0, so that the diagonal of an RQ Gram matrix is exactly
+// its coefficient.  ~20 vector instructions per value where the library's
 // log1p (double-double arithmetic, every special case) takes ~130 - it was 60 % of the C5 kernel's instructions.
 __device__ __forceinline__ double gram_log1p_pos(double u, const double* __restrict__ tab) {
     _Pragma("clang fp contract(off)")   // (1 + s h would otherwise be fused in one compilation and not in the other)
