@@ -12,6 +12,7 @@
 #include "grad_jit.h"
 #include "blas1.h"
 #include "pivchol.h"
+#include "chol_update.h"
 
 namespace gpar {
 
@@ -1523,6 +1524,28 @@ int gpar_chol_inverse(const double* L, int n, int ldl, double* X, int ldx, doubl
     return chol_inverse_run(L, n, ldl, X, ldx, Kinv, ldk, (hipStream_t)stream);
 }
 
+int gpar_chol_drop_leading(const double* A, int n, int k, int lda, double* out, int ldo, double* ws, double* logdet, int* info, void* stream) {
+    GPAR_API_GUARD;
+    return chol_drop_leading_run(A, n, k, lda, out, ldo, ws, logdet, info, (hipStream_t)stream);
+}
+
+int gpar_chol_append(double* A, int n0, int k, int lda, double* logdet, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (n0 < 0 || k < 1 || lda < n0 + k + 1) return GPAR_ARG_ERROR(1);
+    if (!A) return GPAR_ARG_ERROR(2);
+    hipStream_t st = (hipStream_t)stream;
+    const int N = n0 + k + 1;
+    double* bottom = A + (size_t)n0 * lda;   // the k + 1 bottom rows; their trailing block starts at column n0
+    GPAR_HIP_TRY(hipMemsetAsync(A + (size_t)(N - 1) * lda + (N - 1), 0, sizeof(double), st));
+    if (n0 > 0) {
+        int rc = trsm_rlt_run(A, n0, lda, bottom, k, lda, st);
+        if (rc) return rc;
+        rc = gemm_launch(0, 1, k + 1, k + 1, n0, -1.0, bottom, lda, bottom, lda, 1.0, bottom + n0, lda, GPAR_GEMM_C_LOWER, st);
+        if (rc) return rc;
+    }
+    return potrf_run(bottom + n0, k + 1, k, lda, logdet, info, st, potrf_flags);
+}
+
 int gpar_gemm(int ta, int tb, int m, int n, int k, double alpha, const double* A, int lda, const double* B, int ldb,
               double beta, double* C, int ldc, int flags, void* stream) {
     GPAR_API_GUARD;
@@ -1595,6 +1618,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
             if (c < 1 || c > GPAR_CV_MAX_FOLD) return -1;
             return (long long)(a > 0 ? a : 0) * (b ? 3 + c : 1);
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
+        case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         default: return -1;
     }
 }

@@ -17,6 +17,8 @@ Primitive set (all tensors float64, row-major, lower triangles authoritative):
     pivoted_cholesky(ck, z, r, ...)   greedy pivoted Cholesky of k(z, z) (HipEngine only: gp.greedy_inducing composes it elsewhere)
     new_matrix(r, c, zero=False)      workspace with aligned, padded rows
     potrf_(A, nf=None)                (partial) Cholesky -> (logdet, info) device scalars
+    chol_drop_leading(A, k)           augmented factor without its k leading observations (HipEngine only: gp.chol_drop_leading composes it elsewhere)
+    chol_append_(A, n0, k, logdet)    augmented factor extended by k observations laid out in A (HipEngine only: gp.chol_append_ composes it)
     trsm_rlt_(L, B) / trsm_rln_(L, B) B L^-T / B L^-1
     gemm(A, B, ta, tb, alpha, beta, out, c_lower, a_lower)
     gemv_t(A, v) / rownorm2(A)        A^T v for a tall A / squared row norms (HBM-bound passes)
@@ -204,6 +206,16 @@ class HipEngine:
 
     def potrf_(self, A, nf=None):
         return hip.potrf_(A, nf=nf, **self._factor_flags())
+
+    def chol_drop_leading(self, A, k):
+        """The augmented factor of the observations k .. n - 1 from the augmented factor `A` of all n, in one library call
+        (gpar_chol_drop_leading: a rank-k Cholesky update, out of place): (out, logdet, info word)."""
+        return hip.chol_drop_leading(A, k)
+
+    def chol_append_(self, A, n0, k, logdet):
+        """`A` - the old factor, the raw Gram rows of k new observations and the row [z_old, y_new, .] (include/gpar_hip.h:
+        gpar_chol_append) - becomes the augmented factor of all n0 + k in place; `logdet` is accumulated: (logdet, info word)."""
+        return hip.chol_append_(A, n0, k, logdet, **self._factor_flags())
 
     def potrf_batch_(self, A, batch):
         """`batch` square matrices stacked by rows in A, factored in lock-step (logdets, info words)."""

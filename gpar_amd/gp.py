@@ -37,7 +37,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import CV_MAX_FOLD
+from ._lib import CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
 from .engine import get_engine, joining
 from .hip import fold_offsets
 from .kernels import Kernel
@@ -877,6 +877,69 @@ class Obs:
         self._fac = _Factor.placeholder(self.eng, self.fdd.n)
         return self._fac
 
+    def _streamable(self, what):
+        if self.base.is_posterior or self.fdd.n == 0:
+            raise ValueError(f"{what} needs dense observations of a prior process")
+        if getattr(self.eng, "cholesky_retry_factor", 1.0) > 1.0:
+            raise ValueError(f"{what} keeps the jitter of the factor it extends: not available with a Cholesky retry ladder")
+
+    def extended(self, x_new, y_new, noise_new=None):
+        """Observations of the same prior process with k more rows appended - a new `Obs` over [x; x_new], [y; y_new] whose factor
+        is this one's, extended: only the k x (n + k) new rows of the Gram matrix are built (one rectangular `gram`), solved against
+        L and factored (`chol_append_`: gpar_chol_append, O(k n^2)); nothing the factor already encodes is computed again.
+        [(f | obs) built again on more data, reference gpar/model.py:286-301]"""
+        self._streamable("extended")
+        eng, fac, n0 = self.eng, self.factor(), self.fdd.n
+        x_new, y_new = _as_matrix(eng, x_new), _as_matrix(eng, y_new)
+        k = int(x_new.shape[0])
+        if y_new.shape[0] != k or x_new.shape[1] != self.fdd.x.shape[1]:
+            raise ValueError("x_new and y_new must hold the same number of rows, x_new as wide as the observed inputs")
+        if k == 0:
+            return self
+        nv_new = _noise_vector(eng, noise_new, k)
+        old = self.fdd.noise
+        if old is None and nv_new is None:
+            noise = None
+        else:
+            dev = self.fdd.x.device
+            noise = torch.cat([old if old is not None else torch.zeros(n0, dtype=torch.float64, device=dev),
+                               nv_new if nv_new is not None else torch.zeros(k, dtype=torch.float64, device=dev)])
+        fdd = FDD(self.base, torch.cat([self.fdd.x, x_new], dim=0), noise)
+        out = Obs(fdd, torch.cat([self.y, y_new], dim=0))
+        ck, z = fdd.features()
+        n = n0 + k
+        A = eng.new_matrix(n + 1, n + 1)
+        A[:n0, :n0] = fac.L
+        eng.gram(ck, z[n0:], z, out=A[n0:n, :n])
+        shift = torch.full((k,), eng.epsilon, dtype=torch.float64, device=A.device)
+        torch.diagonal(A[n0:n, n0:n]).add_(shift if nv_new is None else shift + nv_new)
+        A[n, :n0] = fac.zrow.reshape(-1)
+        A[n, n0:n] = y_new.reshape(-1)
+        logdet, info = chol_append_(eng, A, n0, k, fac.logdet.clone())
+        eng.check_info(info)
+        out._fac = _Factor.from_batch(eng, n, A, logdet)
+        return out
+
+    def without_leading(self, k):
+        """Observations of the same prior process without their k leading rows - a new `Obs` over x[k:], y[k:] whose factor is this
+        one's, updated: L22' L22'^T = L22 L22^T + L21 L21^T, a rank-k Cholesky UPDATE (`chol_drop_leading`: gpar_chol_drop_leading,
+        O(k n^2), unconditionally stable), with L^-1 y carried along as one more row.
+        [(f | obs) built again on less data, reference gpar/model.py:286-301]"""
+        self._streamable("without_leading")
+        k = int(k)
+        n = self.fdd.n
+        if not 0 <= k < n:
+            raise ValueError(f"k={k}: between 0 and n - 1 = {n - 1} leading observations can be forgotten")
+        if k == 0:
+            return self
+        eng, fac = self.eng, self.factor()
+        noise = None if self.fdd.noise is None else self.fdd.noise[k:]
+        out = Obs(FDD(self.base, self.fdd.x[k:], noise), self.y[k:])
+        A, logdet, info = chol_drop_leading(eng, fac.A, k)
+        eng.check_info(info)
+        out._fac = _Factor.from_batch(eng, n - k, A, logdet)
+        return out
+
     def _batchable(self):
         """This observation's factor may come out of a lock-step batch: a prior process (zero mean: the right-hand side is y
         itself), nothing factored yet, checks deferred, no retry ladder to climb."""
@@ -1620,6 +1683,55 @@ class PseudoObsDTC(PseudoObs):
 
 PseudoObsVFE = PseudoObs
 SparseObs = PseudoObs
+
+
+def fused_updates():
+    """GPAR_CHOL_UPDATE=0 (read at every call): `chol_drop_leading` / `chol_append_` take the route composed of the engine's primitives
+    on every engine - the yardstick of the library calls."""
+    return os.environ.get("GPAR_CHOL_UPDATE", "1") != "0"
+
+
+def _chol_drop_leading_composed(eng, A, k):
+    """The augmented factor of the observations k .. n - 1 from that of all n, from primitives every engine has: with B = [L21, L22] (the
+    rows k .. n - 1 of L), S22 = B B^T = L21 L21^T + L22 L22^T and y2 = B z by `gemm`, then the partial factorisation of the augmented
+    [[S22, .], [y2^T, 0]] by `potrf_` - O(n^3 / 3), where the library's rank-k update costs O(k n^2)."""
+    n = int(A.shape[0]) - 1
+    m = n - k
+    B = eng.new_matrix(m, n)
+    B.copy_(torch.tril(A[k:n, :n], diagonal=k))   # (the strict upper triangle of a factor buffer is scratch)
+    out = eng.new_matrix(m + 1, m + 1)
+    eng.gemm(B, B, tb=True, out=out[:m, :m], c_lower=True)
+    out[m:m + 1, :m] = eng.gemm(A[n:n + 1, :n], B, tb=True)
+    out[m, m].zero_()
+    logdet, info = eng.potrf_(out, nf=m)
+    return out, logdet, info
+
+
+def chol_drop_leading(eng, A, k):
+    """(out, logdet, info): `HipEngine.chol_drop_leading` where the engine has it (and `fused_updates()`), otherwise composed."""
+    if hasattr(eng, "chol_drop_leading") and fused_updates() and k <= CHOL_UPDATE_MAX_RANK:
+        return eng.chol_drop_leading(A, k)
+    return _chol_drop_leading_composed(eng, A, k)
+
+
+def _chol_append_composed(eng, A, n0, k, logdet):
+    """gpar_chol_append from primitives every engine has, on the same layout: the k new rows solved against L (`trsm_rlt_`), the trailing
+    (k + 1) x (k + 1) block downdated by the k + 1 bottom rows (`gemm`), and factored (`potrf_`, nf = k)."""
+    A[n0 + k, n0 + k].zero_()
+    tail = A[n0:, n0:]
+    if n0 > 0:
+        eng.trsm_rlt_(A[:n0, :n0], A[n0:n0 + k, :n0])
+        bottom = A[n0:, :n0]
+        eng.gemm(bottom, bottom, tb=True, alpha=-1.0, beta=1.0, out=tail, c_lower=True)
+    more, info = eng.potrf_(tail, nf=k)
+    return logdet + more, info
+
+
+def chol_append_(eng, A, n0, k, logdet):
+    """(logdet, info) with A factored in place: `HipEngine.chol_append_` where the engine has it (and `fused_updates()`), otherwise composed."""
+    if hasattr(eng, "chol_append_") and fused_updates():
+        return eng.chol_append_(A, n0, k, logdet)
+    return _chol_append_composed(eng, A, n0, k, logdet)
 
 
 def _pivoted_cholesky_composed(eng, ck, z, max_rank, tol, floor):

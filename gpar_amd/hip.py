@@ -20,6 +20,8 @@ __all__ = [
     "gram",
     "gram_diag",
     "pivoted_chol",
+    "chol_drop_leading",
+    "chol_append_",
     "potrf_",
     "trsm_rlt_",
     "trsm_rln_",
@@ -445,6 +447,44 @@ def pivoted_chol(ck, z, max_rank, tol_trace, floor):
         "gpar_pivoted_chol",
     )
     return Lt, piv, trace, words[0:1], words[1:2], ws[:n]
+
+
+def chol_drop_leading(A, k):
+    """The augmented factor of the trailing n - k observations from the (n + 1) x (n + 1) augmented factor `A` of all n, by a rank-k
+    Cholesky update (gpar_chol_drop_leading; semantics: include/gpar_hip.h).  Out of place; returns (out (n - k + 1) x (n - k + 1),
+    logdet, info) - device tensors, nothing synchronises."""
+    lib = _lib.load()
+    _check_mat(A, "A")
+    n, k, dev = A.shape[0] - 1, int(k), A.device
+    if A.shape[1] != n + 1 or not 1 <= k < n or k > _lib.CHOL_UPDATE_MAX_RANK:
+        raise ValueError(f"chol_drop_leading takes a square augmented factor and 1 <= k < n, k <= {_lib.CHOL_UPDATE_MAX_RANK}")
+    out = alloc_matrix(n - k + 1, n - k + 1, dev)
+    ws = torch.empty(lib.gpar_workspace_doubles(_lib.WS_CHOL_UPDATE, n, k, 0), dtype=torch.float64, device=dev)
+    logdet = torch.empty(1, dtype=torch.float64, device=dev)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(
+        lib.gpar_chol_drop_leading(A.data_ptr(), n, k, _ld(A), out.data_ptr(), _ld(out), ws.data_ptr(), logdet.data_ptr(), info.data_ptr(),
+                                   stream_ptr(dev)),
+        "gpar_chol_drop_leading",
+    )
+    return out, logdet, info
+
+
+def chol_append_(A, n0, k, logdet, lookahead=True, fused=True):
+    """In place: the (n0 + k + 1) x (n0 + k + 1) matrix A, laid out as gpar_chol_append wants it (the old factor, the raw new Gram rows,
+    the row [z_old, y_new, .]), becomes the augmented factor of the n0 + k observations; `logdet` (one device word holding the old
+    log-determinant) is accumulated.  Returns (logdet, info)."""
+    lib = _lib.load()
+    _check_mat(A, "A")
+    if A.shape[0] != n0 + k + 1 or A.shape[1] != n0 + k + 1 or k < 1:
+        raise ValueError("A must be (n0 + k + 1) x (n0 + k + 1) with k >= 1")
+    info = torch.zeros(1, dtype=torch.int32, device=A.device)
+    _lib.check(
+        lib.gpar_chol_append(A.data_ptr(), int(n0), int(k), _ld(A), logdet.data_ptr(), info.data_ptr(), _potrf_flags(lookahead, fused),
+                             stream_ptr(A.device)),
+        "gpar_chol_append",
+    )
+    return logdet, info
 
 
 def potrf_(A, nf=None, logdet=None, info=None, lookahead=True, fused=True):

@@ -492,6 +492,37 @@ class GPAR:
             _lockstep_factors(eng, pending)
         return post
 
+    # ---- streaming -------------------------------------------------------------------------------
+    def update(self, x_new=None, y_new=None, w_new=None, drop=0):
+        """A conditioned GPAR (the result of `gpar | (x, y, w)`) whose data lose their `drop` leading rows and gain the rows
+        (x_new, y_new, w_new): what `prior | (concat(x[drop:], x_new), ...)` gives, without factoring any layer again - per layer a
+        rank-`drop` update of the factor (`Obs.without_leading`) and a bordered extension by the new rows (`Obs.extended`), O((drop + k)
+        n^2) against O(n^3 / 3).  For models whose layers' design matrices are the data's own - dense layers, no `replace`, complete
+        data (no NaN in what was conditioned on or in y_new): layer i sees [x, y_<i] - and ValueError otherwise.
+        [gpar | (x, y, w) on the moved window, reference gpar/model.py:158-176]"""
+        if self.sparse or self.replace:
+            raise ValueError("update needs dense layers that are fed observations: no inducing points, no replace")
+        eng = get_engine()
+        drop = int(drop)
+        k = 0
+        if x_new is not None:
+            x_new = eng.tensor(x_new)
+            x_new = x_new[:, None] if x_new.dim() == 1 else x_new
+            y_new, w_new = eng.tensor(y_new), eng.tensor(w_new)
+            k = int(x_new.shape[0])
+        post = self.copy()
+        with eng.defer_checks():
+            for i, model in enumerate(self.layers):
+                f, noise = model()
+                obs = f._obs if f.is_posterior else None
+                if not isinstance(obs, Obs) or not obs.fast_dense:
+                    raise ValueError("update needs a conditioned model with dense observations in every layer")
+                obs = obs.without_leading(drop)
+                if k:
+                    obs = obs.extended(torch.cat([x_new, y_new[:, :i]], dim=1), y_new[:, i:i + 1], self._noise_over(noise, w_new[:, i]))
+                post.layers.append(construct_model(obs.base | obs, noise))
+        return post
+
     # ---- log marginal likelihood -------------------------------------------------------------------
     def logpdf(self, x, y, w, only_last_layer=False, sample_missing=False, return_inputs=False, x_ind=None, outputs=None):
         """Sum over layers of log N(y_i; 0, K_i([x, y_<i]) + noise_i / w_i) (the VFE bound with inducing points).

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import torch
 
+from ._lib import CHOL_UPDATE_MAX_RANK
 from .engine import get_engine
 from .gp import GP, Measure, greedy_inducing
 from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
@@ -140,6 +141,17 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
         return f, noise_variance
 
     return model
+
+
+def update_drop_fraction():
+    """`GPARRegressor.update` forgets up to this fraction of its rows by a rank-k update of the layers' factors and conditions again
+    above it (GPAR_UPDATE_DROP_FRACTION, read at every call).  By flop count the update costs ~3 k n^2 vector flops against n^3 / 3 on
+    the matrix cores, which predicts a crossover near k = n / 16.  MEASURED (tools/time_update.py, profiles/update_times.txt) the
+    update loses at every size tried, k = 1 included - n = 1024 / 4096 / 16384, one row forgotten and one appended, then `predict`:
+    2.5 / 8.8 / 38.3 ms against 1.2 / 3.6 / 35.0 ms for conditioning again - because its diagonal kernel is a chain of n k dependent
+    sqrt / divide steps on one wave.  So the default is 0: rows are only forgotten by conditioning again (the kept factors still
+    spare `predict` its own conditioning), rows are appended incrementally, and the rank-k route is opt-in through this switch."""
+    return float(os.environ.get("GPAR_UPDATE_DROP_FRACTION", "0"))
 
 
 def _construct_gpar(reg, vs, m, p):
@@ -286,6 +298,8 @@ class GPARRegressor:
         self.normalise_y = normalise_y
         self._unnormalise_y, self._normalise_y = (lambda x: x), (lambda x: x)
         self._transform_y, self._untransform_y = transform_y
+        self._stream_cache = None            # (key, conditioned GPAR) kept by `update`
+        self.last_update_incremental_ = None  # did the last `update` take the incremental route?
 
     def get_variables(self):
         """Dictionary name -> value of every hyper-parameter instantiated so far."""
@@ -298,6 +312,7 @@ class GPARRegressor:
         # more elements opens an OpenMP region whose workers (one per core) spin afterwards, which in a container with a CPU
         # quota throttles the evaluations that follow (fit(iters=3) at n = 8192: 0.68 -> 0.60 s) - and changing torch's
         # global thread count around the call instead would be visible to other threads of the process.
+        self._stream_cache = None
         self.x = _uprank(_to_torch(x)).detach().cpu()
         self.y = self._transform_y(_uprank(_to_torch(y))).detach().cpu()
         self.w = _init_weights(w, self.y, attribute=True)
@@ -558,10 +573,93 @@ class GPARRegressor:
             if "x_ind" in self.vs:
                 self.vs.remove("x_ind")
             self.is_conditioned = False
+            self._stream_cache = None
             self.x = self.y = self.w = None
             self.n = self.m = self.p = None
             self._unnormalise_y, self._normalise_y = (lambda x: x), (lambda x: x)
         return x_ind, index, trace[: rank + 1].cpu().numpy()
+
+    # ---- streaming conditioning ------------------------------------------------------------------------
+    def _stream_key(self):
+        """What the kept factors are a function of, besides the data: the store, its variables' names and a COPY of their values, and
+        the inducing inputs."""
+        names = self.vs.names
+        return self.vs, tuple(names), self.vs.get_vector(names).copy(), (None if self.x_ind is None else self.x_ind.detach().clone())
+
+    def _stream_posterior(self):
+        """The conditioned model `update` keeps, if it still belongs to the current hyper-parameters and inducing inputs; otherwise the
+        cache is dropped and None returned (the caller conditions as if `update` had never been called)."""
+        cache = self._stream_cache
+        if cache is None:
+            return None
+        (vs, names, vector, x_ind), gpar = cache
+        now = self._stream_key()
+        same = (vs is now[0] and names == now[1] and np.array_equal(vector, now[2])
+                and ((x_ind is None and now[3] is None) or (x_ind is not None and now[3] is not None and x_ind.shape == now[3].shape
+                                                            and torch.equal(x_ind, now[3]))))
+        if not same:
+            self._stream_cache = None
+            return None
+        return gpar
+
+    def update(self, x_new=None, y_new=None, w=None, drop=0):
+        """Move the window of data a conditioned regressor holds - an addition; the reference conditions again (regression.py:339-389).
+        Forget the `drop` leading rows and append the rows (x_new, y_new, w): afterwards the regressor is exactly what
+        `condition(concat(x[drop:], x_new), concat(y[drop:], y_new), concat(w[drop:], w))` would make it, EXCEPT that the output
+        normalisation constants of the last `condition` / `fit` are kept: the new outputs are normalised with the means and standard
+        deviations computed then (a stream must not re-standardise under a trained model).  `self.x / y / w / n` are updated.
+
+        The first `update` conditions every layer once in the ordinary way and keeps the p conditioned layers - p factors of n^2
+        doubles, held until the next `fit`, `condition`, `select_inducing(assign=True)` or change of a hyper-parameter.  `predict`,
+        `sample(posterior=True)`, `predict_moments` and `logpdf(posterior=True)` use them instead of conditioning again, and later
+        updates move them incrementally: per layer a rank-`drop` Cholesky update and a bordered extension by the new rows, O((drop + k)
+        n^2) instead of the O(n^3 / 3) of a factorisation.  That route applies where every layer's design matrix is the data's own -
+        dense layers, `replace=False`, no NaN among the stored or the new outputs - and while `drop` is at most
+        `update_drop_fraction()` of n (0 by default: as measured, forgetting rows is cheaper by conditioning again); anything else is conditioned in full on the new window inside this call (same result, same
+        frozen normalisation).  `last_update_incremental_` says which route ran.
+
+        ValueError: `drop` outside 0 .. n, `drop == n` with nothing appended, x_new / y_new / w of the wrong width or without one
+        another; RuntimeError: not conditioned."""
+        if not self.is_conditioned:
+            raise RuntimeError("Must condition or fit model before updating it.")
+        drop = int(drop)
+        k = 0
+        if (x_new is None) != (y_new is None):
+            raise ValueError("x_new and y_new come together")
+        if x_new is not None:
+            x_new = _uprank(_to_torch(x_new)).detach().cpu().to(torch.float64)
+            y_new = _uprank(_to_torch(y_new)).detach().cpu().to(torch.float64)
+            k = int(x_new.shape[0])
+            if x_new.shape[1] != self.m or y_new.shape[1] != self.p or y_new.shape[0] != k:
+                raise ValueError(f"x_new must be k x {self.m} and y_new k x {self.p}")
+            w_new = _init_weights(w, y_new, attribute=True).detach().cpu().to(torch.float64)
+            if tuple(w_new.shape) != tuple(y_new.shape):
+                raise ValueError("w must have the shape of y_new")
+            y_new = self._normalise_y(self._transform_y(y_new))   # the constants of the last condition / fit
+        elif w is not None:
+            raise ValueError("w belongs to the appended rows")
+        if drop < 0 or drop > self.n or (drop == self.n and k == 0):
+            raise ValueError(f"drop={drop}: between 0 and n = {self.n} leading rows can be forgotten, all of them only when rows are appended")
+        if drop == 0 and k == 0:
+            self.last_update_incremental_ = self._stream_posterior() is not None
+            return self
+        incremental = (not self.sparse and not self.replace and drop < self.n and drop <= update_drop_fraction() * self.n
+                       and drop <= CHOL_UPDATE_MAX_RANK and not bool(torch.isnan(self.y).any())
+                       and (k == 0 or not bool(torch.isnan(y_new).any())))
+        gpar = None
+        if incremental:
+            gpar = self._stream_posterior()
+            if gpar is None:   # the first update: an ordinary full conditioning on the data held so far
+                gpar = _construct_gpar(self, self.vs, self.m, self.p) | (self.x, self.y, self.w)
+            gpar = gpar.update(x_new, y_new, w_new if k else None, drop=drop)
+        parts = lambda old, new: torch.cat([old[drop:], new], dim=0) if k else old[drop:].clone()
+        self.x, self.y, self.w = parts(self.x, x_new), parts(self.y, y_new), parts(self.w, w_new if k else None)
+        self.n = int(self.x.shape[0])
+        if gpar is None:
+            gpar = _construct_gpar(self, self.vs, self.m, self.p) | (self.x, self.y, self.w)
+        self._stream_cache = (self._stream_key(), gpar)
+        self.last_update_incremental_ = bool(incremental)
+        return self
 
     def loo(self, x, y, w=None):
         """Layer-wise leave-one-out cross-validation under the prior model (`GPAR.loo`): `(value, mean, var)`.  `value` is the sum
@@ -660,7 +758,8 @@ class GPARRegressor:
         self._prepare_kernels(m, p, int(x.shape[0]))
         gpar = _construct_gpar(self, self.vs, m, p)
         if posterior:
-            gpar = gpar | (self.x, self.y, self.w)
+            cached = self._stream_posterior() if getattr(self, "_stream_cache", None) is not None else None
+            gpar = cached if cached is not None else gpar | (self.x, self.y, self.w)
         value = gpar.logpdf(x, y, w, only_last_layer=False, sample_missing=sample_missing)
         if not any_torch:
             value = value.detach().cpu().numpy()
@@ -677,6 +776,8 @@ class GPARRegressor:
             w = _default_weights(x.shape[0], self.p if posterior else p)
         else:
             w = _uprank(_to_torch(w))
+        if posterior and conditioned is None and getattr(self, "_stream_cache", None) is not None:
+            conditioned = self._stream_posterior()   # the factors `update` keeps, while they are valid
         if posterior and conditioned is not None:
             gpar = conditioned  # parallel.sharded_condition: factors computed across ranks
         elif posterior:
@@ -703,6 +804,8 @@ class GPARRegressor:
         x = _uprank(_to_engine(x))
         w = _default_weights(x.shape[0], self.p) if w is None else _uprank(_to_torch(w))
         gpar = _conditioned
+        if gpar is None and getattr(self, "_stream_cache", None) is not None:
+            gpar = self._stream_posterior()
         if gpar is None:
             gpar = _construct_gpar(self, self.vs, self.m, self.p) | (self.x, self.y, self.w)
         with torch.no_grad():

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 10
+#define GPAR_ABI_VERSION 11
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -432,6 +432,38 @@ int gpar_trsm_rln(const double* L, int n, int ldl, double* B, int nrows, int ldb
  * 1/2 tr((aa^T - K^-1) dK) needs; replaces autograd through cholesky / solve_triangular, gpar/regression.py:459] */
 int gpar_chol_inverse(const double* L, int n, int ldl, double* X, int ldx, double* Kinv, int ldk, void* stream);
 
+/* Streaming conditioning (ABI v11): moving a conditioned layer's window of observations without factoring it again.
+ * gpar_chol_drop_leading forgets the k LEADING observations.  A: the augmented (n + 1) x (n + 1) factor as gpar_potrf (nf = n) leaves it
+ * - L in the lower triangle, z^T = (L^-1 y)^T in row n, -|z|^2 in the corner.  With L = [[L11, 0], [L21, L22]] and z = [z1; z2] it writes,
+ * OUT OF PLACE into out ((n - k + 1) x (n - k + 1), ldo; must not overlap A; the strict upper triangle is left alone), L22' with
+ * L22' L22'^T = L22 L22^T + L21 L21^T, z2' with L22' z2' = y2 in its last row and -|z2'|^2 in the corner: the augmented factor of the
+ * trailing n - k observations.  logdet[0] <- 2 sum log L22'_jj (written, not accumulated; may be NULL).  A positive rank-k update (never a
+ * downdate): LINPACK's dchud, blocked.  For column j ascending and update vector t = 0 .. k-1 ascending (v_t = column t of L21, with the
+ * augmented row as one more row of it: v_t[n - k] = z1[t]), a = L_jj and b = v_t[j] as the earlier operations left them:
+ *   r = sqrt(fma(a, a, b * b)), c = a / r, s = b / r, L_jj <- r; for every row i > j, the augmented row like any other:
+ *   L_ij' = fma(c, L_ij, s * v_t[i]), v_t[i]' = fma(c, v_t[i], -(s * L_ij));  corner = -(fma chain of z2'_j^2 over j ascending from 0).
+ * A non-finite r is reported as info[0] = its 1-based column of `out` (first one wins; untouched on success: zero it first; may be NULL).
+ * Launches: two plain launches per 64 columns - the diagonal block by one workgroup, which also leaves the panel's (c, s) table in the
+ * workspace, then all rows below it and the augmented row, one thread per row - and nothing else: no waiting inside a launch, no atomics,
+ * no host synchronisation, vector stores only.  The result is a function of the inputs alone: two runs give the same bits.
+ * ws: gpar_workspace_doubles(GPAR_WS_CHOL_UPDATE, n, k, 0) doubles.  Limits: 1 <= k < n, k <= GPAR_CHOL_UPDATE_MAX_RANK - the workspace
+ * holds the (n - k + 1) x k update vectors and a 64 x k table of (c, s) pairs, as much as the factor itself once k nears n, and the
+ * 3 k n^2 flops of the update pass the n^3 / 3 of a fresh factorisation long before that.  Traffic: 8 n^2 bytes of L read and written.
+ * [replaces (f | obs) built again on the moved window: Obs construction and conditioning at gpar/model.py:286-301]
+ *
+ * gpar_chol_append takes k NEW observations in.  A: (n0 + k + 1) x (n0 + k + 1) (lda).  On entry its leading n0 x n0 block holds L; rows
+ * n0 .. n0 + k - 1 hold the raw entries [K_new,old, K_new,new + noise + jitter] (lower triangle); the last row holds
+ * [z_old^T, y_new^T, .] - the caller moves the old augmented row below the new rows; the corner is ignored.  logdet[0] holds the
+ * log-determinant of L on entry.  On exit A is the augmented factor of the n0 + k observations and logdet[0] their log-determinant.
+ * It composes existing kernels, in this order: the corner zeroed (a memset node); gpar_trsm_rlt of rows n0 .. n0 + k - 1 against L (the
+ * last row's first n0 entries ARE already solved: z_old); gpar_gemm (GPAR_GEMM_C_LOWER) C <- C - B B^T on the trailing
+ * (k + 1) x (k + 1) block with B the n0 leading columns of the k + 1 bottom rows; gpar_potrf_ex of that block with nf = k.
+ * info: as gpar_potrf_ex reports it for the trailing block (1-based among the k new rows).  n0 >= 0, k >= 1.
+ * [replaces (f | obs) built again on the longer data: gpar/model.py:286-301] */
+#define GPAR_CHOL_UPDATE_MAX_RANK 1024
+int gpar_chol_drop_leading(const double* A, int n, int k, int lda, double* out, int ldo, double* ws, double* logdet, int* info, void* stream);
+int gpar_chol_append(double* A, int n0, int k, int lda, double* logdet, int* info, int potrf_flags, void* stream);
+
 /* C <- alpha * op(A) op(B) + beta * C with op(A) m x k, op(B) k x n.  ta: A is stored k x m (transposed);
  * tb: B is stored n x k (transposed).  fp64 on the matrix cores (v_mfma_f64_16x16x4).
  * [B.matmul in lab: K_*x alpha, V^T V, chol(var) z] */
@@ -474,7 +506,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_CHOL_INVERSE (n, ldx, -)      the X matrix of gpar_chol_inverse
  *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_CV           (n, grad, max_fold)  the `vec` of gpar_cv_dense (grad = 0) / gpar_cv_dense_grad[_finish] (grad = 1)
- *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol */
+ *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol
+ *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -483,6 +516,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_LOO 6
 #define GPAR_WS_CV 7
 #define GPAR_WS_PIVOTED_CHOL 8
+#define GPAR_WS_CHOL_UPDATE 9
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
