@@ -50,6 +50,37 @@ POTRF_CASES = [
     # 64 x 64 block with such pivots is exact only while the chains of couplings inside the block are short: a thinner block)
     _pc("1601-lone-refinement-pivots-1-and-64", 1601, 1600, diag=(1.0, 64.0), in_block=0.03125),
 ]
+# Lock-step batches at the COUNTS where the batch code branches (the count is the number of layers of a GPAR, or of samples): the
+# smallest matrices at which the named predicate is live, every member with data of its own (seed SEED0 + b), so that a wrong matrix
+# index is an integer-sized error.  BATCH_CROSSES holds the value of each predicate; tests/test_exact_cases.py checks it against the
+# schedule printer and the restatements below.
+# (up to 257 seeds reach further into the tail of the block inverses' sizes than three do - one 64 x 64 block of seed 100 + b at 129 rows has an
+# inverse entry of 19.2 at in_block = 0.125, above the premise's bound of 16: thinner blocks, largest entry 3.7 over all members)
+def _bc(id, N, nf, batch, env=()):
+    return _pc(id, N, nf, batch=batch, env=env, in_block=0.0625)
+
+
+# 128-column steps: a slice that ends on a tile row - the tail split - at 257 rows; with the default 512 columns it takes 641
+_NBO128 = {"GPAR_POTRF_NBO": "128"}
+BATCH_CASES = [
+    _bc("1089-batch5-fused-group-split-team-on-waiting-475", 1089, 1088, batch=5),
+    _bc("1105-batch5-tail17-fused-group-split-team-on", 1105, 1088, batch=5),
+    _bc("1089-batch6-fused-group-split-team-off-waiting-570", 1089, 1088, batch=6),
+    _bc("1105-batch6-tail17-fused-group-split-team-off", 1105, 1088, batch=6),
+    _bc("1105-batch7-fused-group-split-team-off-tail17", 1105, 1088, batch=7),
+    _bc("1089-batch17-fuse2-rows-970-below-N-single-panels", 1089, 1088, batch=17),
+    _bc("1105-batch17-tail17-single-panels", 1105, 1088, batch=17),
+    _bc("577-batch65-two-panels-small-slice", 577, 576, batch=65),
+    _bc("593-batch65-tail17-half-tile-update", 593, 576, batch=65),
+    _bc("257-batch65-small-slice-325-tiles-no-tail", 257, 256, batch=65, env=_NBO128),
+    _bc("321-batch130-one-panel", 321, 320, batch=130),
+    _bc("337-batch130-tail17-half-tile-update", 337, 320, batch=130),
+    _bc("272-batch130-gemm-slice-650-tiles-tail16-gmax1", 272, 256, batch=130, env=_NBO128),
+    _bc("129-batch257-one-panel", 129, 128, batch=257),
+    _bc("257-batch257-gemm-slice-tail1-gmax1-from-256-on", 257, 256, batch=257, env=_NBO128),
+    _bc("145-batch257-tail17-whole-tile-update", 145, 128, batch=257),
+]
+POTRF_CASES += BATCH_CASES
 POTRF_BY_ID = {c.id: c for c in POTRF_CASES}
 LONE_TWIN = _pc("1601-lone", 1601, 1600)   # member 0 of "1601-batch3-fused-group-lockstep" on its own
 
@@ -60,7 +91,56 @@ ZERO_PIVOT_CASES = [
     ("2113-lone-fused-group4-small-slice", 0, 612, "second panel of a fused-group launch"),
     ("1100-lone-odd-lda-leaf", 0, 1030, "ragged leaf panel"),
     ("1601-batch3-fused-group-lockstep", 1, 700, "one member of a lock-step batch"),
+    # one indefinite member of a wide batch: the first, the ones on either side of index 64, the last
+    ("577-batch65-two-panels-small-slice", 0, 0, "batch 65 member 0 first column"),
+    ("577-batch65-two-panels-small-slice", 63, 511, "batch 65 member 63 last column of the first panel"),
+    ("577-batch65-two-panels-small-slice", 64, 575, "batch 65 last member last column"),
+    ("321-batch130-one-panel", 0, 319, "batch 130 member 0 last column"),
+    ("321-batch130-one-panel", 63, 64, "batch 130 member 63 second row block"),
+    ("321-batch130-one-panel", 64, 200, "batch 130 member 64"),
+    ("321-batch130-one-panel", 129, 0, "batch 130 last member first column"),
 ]
+
+
+# (group_waiting and tail_grid RESTATE host code of panel2.h / potrf.h - the schedule printer shows neither the split team nor the
+# tail companion's grid -, slice_tiles restates what decides the printer's "small" / "gemm": a change of those rules has to be made here too)
+def group_waiting(case, k0=0, S=8):
+    """potrf_group_fused (gpar_amd/csrc/panel2.h): the workgroups of a fused launch that mostly wait, over the whole batch; above 512
+    the split team (and with it the next team's rows by tile) is switched off."""
+    R0 = (case.N - k0 + 63) // 64
+    return case.batch * (S + (S - 1) * (S - 2) // 2 + S * S + max(R0 - 2 * S, 0))
+
+
+def tail_grid(batch, ncols):
+    """potrf_tail_update (gpar_amd/csrc/potrf.h): (workgroups per matrix the panel's columns ask for, the clamp gmax)."""
+    return -(-ncols // 64), 1 if batch >= 256 else 256 // batch
+
+
+def slice_tiles(case, kend, next_end):
+    """potrf_slice_small (gpar_amd/csrc/potrf_schedule.h): the 64 x 64 tiles of the slice [kend, next_end), counted over the batch."""
+    nc, tr = (next_end - kend) // 64, (case.N - kend + 63) // 64
+    return (nc * (nc + 1) // 2 + (tr - nc) * nc) * case.batch
+
+
+# the value of every batch-dependent predicate a case of BATCH_CASES is there for
+BATCH_CROSSES = {
+    "1089-batch5-fused-group-split-team-on-waiting-475": dict(fuse2_rows=3300, waiting=475),
+    "1105-batch5-tail17-fused-group-split-team-on": dict(fuse2_rows=3300, waiting=475, tail_split=0, update_kernel="half-NT"),
+    "1089-batch6-fused-group-split-team-off-waiting-570": dict(fuse2_rows=2750, waiting=570),
+    "1105-batch6-tail17-fused-group-split-team-off": dict(fuse2_rows=2750, waiting=570, tail_split=0, update_kernel="half-NT"),
+    "1105-batch7-fused-group-split-team-off-tail17": dict(fuse2_rows=2357, waiting=665, tail_split=0, update_kernel="half-NT"),
+    "1089-batch17-fuse2-rows-970-below-N-single-panels": dict(fuse2_rows=970, tail_split=1),
+    "1105-batch17-tail17-single-panels": dict(fuse2_rows=970, tail_split=0, slice=(1024, 1088, 34), update_kernel="half-NT"),
+    "577-batch65-two-panels-small-slice": dict(fuse2_rows=253, slice=(512, 576, 130)),
+    "593-batch65-tail17-half-tile-update": dict(tail_split=0, slice=(512, 576, 130), update_kernel="half-NT"),
+    "257-batch65-small-slice-325-tiles-no-tail": dict(slice=(128, 256, 325)),
+    "321-batch130-one-panel": dict(fuse2_rows=126),
+    "337-batch130-tail17-half-tile-update": dict(fuse2_rows=126, tail_split=0, update_kernel="half-NT"),
+    "272-batch130-gemm-slice-650-tiles-tail16-gmax1": dict(slice=(128, 256, 650), tail_grid=(2, 1), tail_split=1),
+    "129-batch257-one-panel": dict(fuse2_rows=64),
+    "257-batch257-gemm-slice-tail1-gmax1-from-256-on": dict(slice=(128, 256, 1285), tail_grid=(2, 1), tail_split=1),
+    "145-batch257-tail17-whole-tile-update": dict(tail_split=0, update_kernel="whole-NT"),
+}
 
 
 def padded_ld(cols):
@@ -73,7 +153,12 @@ def potrf_lda(case):
 
 def potrf_problems():
     """Every (n, seed, diag, in_block, nf) the factorisation tests generate."""
-    return sorted({(c.N, SEED0 + b, c.diag, c.in_block, c.nf) for c in POTRF_CASES + [LONE_TWIN] for b in range(c.batch)})
+    return sorted({(c.N, SEED0 + b, c.diag, c.in_block, c.nf) for c in POTRF_CASES + [LONE_TWIN] if c not in BATCH_CASES for b in range(c.batch)})
+
+
+def batch_case_problems(case):
+    """The same for a case of BATCH_CASES (tests/test_exact_cases.py checks their members case by case, not one test per member)."""
+    return [(case.N, SEED0 + b, case.diag, case.in_block, case.nf) for b in range(case.batch)]
 
 
 @functools.lru_cache(maxsize=4)
@@ -361,7 +446,13 @@ def _check_member(case, b, got):
 @pytest.mark.parametrize("case", POTRF_CASES, ids=[c.id for c in POTRF_CASES])
 def test_factorisation_is_exact_on_exact_inputs(env, monkeypatch, case, lookahead):
     """tril(got[:nf, :nf]) == L, got[nf:, :nf] == L[nf:, :nf], the lower triangle of got[nf:, nf:] == L22 L22^T, info == 0, the
-    NaN-filled strict upper triangle still NaN; logdet == 2 sum log diag L at rtol 1e-12 (its atomicAdd order is not fixed)."""
+    NaN-filled strict upper triangle still NaN; logdet == 2 sum log diag L at rtol 1e-12 (its atomicAdd order is not fixed).
+    The cases of BATCH_CASES - batches of 5 .. 257 - each cross one batch-dependent predicate, named in the id and held in
+    BATCH_CROSSES: fuse2_rows = 16500 / batch against N, the fused launch's waiting workgroups against 512 (split team on / off), the
+    slice's tiles over the batch against 512 (small tile kernel / GEMM), potrf_tail_update's grid clamp 256 / batch (1 from batch 129
+    on, a branch of its own from 256 on), tail_split, the GEMM's half-tile rule ntiles * batch <= 256.  Every batch count has a case with
+    17 rows below the factored part (tail_split off; those rows through the GEMM: a half tile per matrix up to batch 256, whole at 257),
+    batch 130 one with 16 (the tail companion in launches of 4 rows)."""
     got, logdet, info = _run_potrf(env, monkeypatch, case, lookahead)
     assert info == [0] * case.batch
     for b in range(case.batch):

@@ -26,6 +26,24 @@ def test_cholesky_of_an_exact_matrix_is_exact_on_the_cpu(n, seed, diag, in_block
     assert np.array_equal(R[nf:, nf:], np.tril(L[nf:, nf:] @ L[nf:, nf:].T))
 
 
+@pytest.mark.parametrize("case", gpu.BATCH_CASES, ids=[c.id for c in gpu.BATCH_CASES])
+def test_every_member_of_a_wide_batch_is_exact_on_the_cpu(case):
+    """The premises above for ALL members of the batch-count cases (up to 257 seeds of small matrices: one test per case, not per
+    member), and no two members of a batch hold the same matrix."""
+    seen = set()
+    for n, seed, diag, in_block, nf in gpu.batch_case_problems(case):
+        L, A = gpu.factor_problem(n, seed, diag, in_block)
+        assert np.array_equal(A, np.rint(A)) and np.abs(A).max() < 2.0 ** 53
+        assert np.array_equal(np.linalg.cholesky(A), L)
+        R, pairs = exact.blocked_cholesky(A, nf)
+        for D, Dinv in pairs:
+            assert np.array_equal(Dinv @ D, np.eye(len(D))) and np.abs(Dinv).max() <= 16.0
+        assert np.array_equal(R[:, :nf], L[:, :nf])
+        assert np.array_equal(R[nf:, nf:], np.tril(L[nf:, nf:] @ L[nf:, nf:].T))
+        seen.add(A.tobytes())
+    assert len(seen) == case.batch
+
+
 def test_the_refinement_case_has_blocks_above_the_refinement_ratio():
     case = gpu.POTRF_BY_ID["1601-lone-refinement-pivots-1-and-64"]
     d = np.diag(gpu.factor_problem(case.N, gpu.SEED0, case.diag, case.in_block)[0])[:case.nf].reshape(-1, 16)
@@ -92,6 +110,23 @@ POTRF_REACHES = {
     "5121-lone-mixed-last-round": {("lone", "lookahead=1"), ("lone", "update", "slice+rest")},
     "1024-lone-no-update": {("lone", "update", "none")},
     "1601-lone-refinement-pivots-1-and-64": {("lone", "panel", "fused-group")},
+    # the batch-count cases (their predicates: test_batch_count_cases_cross_the_predicates_they_name)
+    "1089-batch5-fused-group-split-team-on-waiting-475": {("lockstep", "fused-group G=2"), ("lockstep", "slice", "small")},
+    "1105-batch5-tail17-fused-group-split-team-on": {("lockstep", "fused-group G=2"), ("lockstep", "tail_split=0"), ("lockstep", "update", "one")},
+    "1089-batch6-fused-group-split-team-off-waiting-570": {("lockstep", "fused-group G=2")},
+    "1105-batch6-tail17-fused-group-split-team-off": {("lockstep", "fused-group G=2"), ("lockstep", "tail_split=0")},
+    "1105-batch7-fused-group-split-team-off-tail17": {("lockstep", "fused-group G=2"), ("lockstep", "tail_split=0")},
+    "1089-batch17-fuse2-rows-970-below-N-single-panels": {("lockstep", "panel", "fused"), ("lockstep", "slice", "gemm"), ("lockstep", "slice", "small")},
+    "1105-batch17-tail17-single-panels": {("lockstep", "panel", "fused"), ("lockstep", "slice", "gemm"), ("lockstep", "slice", "small"), ("lockstep", "tail_split=0")},
+    "577-batch65-two-panels-small-slice": {("lockstep", "panel", "fused"), ("lockstep", "slice", "small")},
+    "593-batch65-tail17-half-tile-update": {("lockstep", "panel", "fused"), ("lockstep", "slice", "small"), ("lockstep", "tail_split=0")},
+    "257-batch65-small-slice-325-tiles-no-tail": {("lockstep", "slice", "small"), ("lockstep", "tail_split=1")},
+    "321-batch130-one-panel": {("lockstep", "panel", "fused"), ("lockstep", "update", "one")},
+    "337-batch130-tail17-half-tile-update": {("lockstep", "panel", "fused"), ("lockstep", "update", "one"), ("lockstep", "tail_split=0")},
+    "272-batch130-gemm-slice-650-tiles-tail16-gmax1": {("lockstep", "slice", "gemm+tail")},
+    "129-batch257-one-panel": {("lockstep", "panel", "fused"), ("lockstep", "update", "one")},
+    "257-batch257-gemm-slice-tail1-gmax1-from-256-on": {("lockstep", "slice", "gemm+tail")},
+    "145-batch257-tail17-whole-tile-update": {("lockstep", "tail_split=0"), ("lockstep", "update", "one")},
 }
 
 
@@ -115,6 +150,59 @@ def test_factorisation_cases_reach_the_forms_they_name(printer):  # noqa: F811
         assert piece in union
     # the tails of the lock-step cases: 1, 16 and 17 rows (and the 62 appended rows of the ragged case)
     assert {c.N - c.nf for c in gpu.POTRF_CASES if c.batch > 1} == {1, 16, 17, 62}
+
+
+def test_batch_count_cases_cross_the_predicates_they_name(printer):  # noqa: F811
+    """Every case of BATCH_CASES sits on the side of the batch-dependent predicate its id names - fuse2_rows = 16500 / batch against N
+    (potrf_policy), the waiting workgroups of a fused launch against 512 (potrf_group_fused), the tiles of a slice over the whole batch
+    against GPAR_POTRF_LA_SMALL_TILES = 512 (potrf_slice_small), the grid clamp 256 / batch of potrf_tail_update (1 from batch 129 on,
+    and by the branch of its own from 256 on), tail_split (batches only, 1 .. 16 rows), the half-tile rule ntiles * batch <= 256 of the
+    update's GEMM - and a neighbour in the list sits on the other side.  The schedules are printed (pytest -s).
+    The forms, fuse2_rows, tail_split and small / gemm are READ from the printer; the waiting count and the tail companion's grid are
+    restatements (gpu.group_waiting, gpu.tail_grid) of host code the printer does not show, checked against the figures in BATCH_CROSSES."""
+    assert [c.id for c in gpu.BATCH_CASES] == list(gpu.BATCH_CROSSES)
+    assert {c.batch for c in gpu.BATCH_CASES} == {5, 6, 7, 17, 65, 130, 257}
+    seen = {}
+    for case in gpu.BATCH_CASES:
+        shape, policy, steps = _schedule(printer, case, True)
+        print(case.id, policy, *[" ".join(str(f) for f in s if f is not None) for s in steps], sep="\n    ")
+        want = gpu.BATCH_CROSSES[case.id]
+        assert shape["batch"] == case.batch and policy["lockstep"] == 1
+        nbo = int(dict(case.env).get("GPAR_POTRF_NBO", 512))
+        assert policy["nbo"] == nbo and policy["fuse2_rows"] == 16500 // case.batch
+        forms = {s[2] for s in steps}
+        # fuse2_rows against N: a fused launch of several panels exactly where the matrix has at most fuse2_rows rows
+        assert ("fused-group" in forms) == (nbo == 512 and case.nf >= 1024 and case.N <= policy["fuse2_rows"]), case.id
+        if "fuse2_rows" in want:
+            assert policy["fuse2_rows"] == want["fuse2_rows"]
+        if "waiting" in want:
+            assert steps[0][2] == "fused-group" and int(steps[0][0]) == 0 and gpu.group_waiting(case) == want["waiting"]
+            seen.setdefault("split", set()).add(want["waiting"] > 512)
+        if "tail_split" in want:
+            assert policy["tail_split"] == want["tail_split"] == int(0 < case.N - case.nf <= 16)
+        if "slice" in want:
+            kend, next_end, tiles = want["slice"]
+            (step,) = [s for s in steps if s[5] is not None and (int(s[5]), int(s[6])) == (kend, next_end)]
+            assert gpu.slice_tiles(case, kend, next_end) == tiles and step[7] == ("small" if tiles <= 512 else "gemm"), case.id
+            seen.setdefault("slice", set()).add(step[7])
+            if "tail_grid" in want:
+                assert step[8] == "+tail" and gpu.tail_grid(case.batch, next_end - kend) == want["tail_grid"]
+                seen.setdefault("gmax", set()).add("branch" if case.batch >= 256 else "quotient")
+        if "update_kernel" in want:   # the 17 rows below the last step: one tile of the GEMM per matrix, a half tile while batch <= 256
+            step = steps[-1]
+            rows, K = case.N - int(step[1]), int(step[1]) - int(step[0])
+            assert step[4] == "one" and rows == 17 and K >= 64   # (not the one-wave kernel, which takes up to 16 rows)
+            kernels = {p[0] for p in gpu.gemm_paths(gpu._gc("rest", "NT", rows, rows, K, c_lower=True, batch=case.batch), -1.0, 1.0, role=1,
+                                                    fast=(True, True, True))}
+            assert kernels == {want["update_kernel"]} == {"half-NT" if case.batch <= 256 else "whole-NT"}, case.id
+            seen.setdefault("tail17", {})[case.batch] = want["update_kernel"]
+    # every batch count has a case with a 17-row tail (tail_split off, the rows below the last step through the GEMM), one has 16 rows
+    assert seen.pop("tail17") == {5: "half-NT", 6: "half-NT", 7: "half-NT", 17: "half-NT", 65: "half-NT", 130: "half-NT", 257: "whole-NT"}
+    assert sorted(c.batch for c in gpu.BATCH_CASES if c.N - c.nf == 17) == [5, 6, 7, 17, 65, 130, 257]
+    assert [c.batch for c in gpu.BATCH_CASES if c.N - c.nf == 16] == [130]
+    assert seen == {"split": {False, True}, "slice": {"small", "gemm"}, "gmax": {"branch", "quotient"}}
+    # 257 / 256 rows with 128-column steps: the same shape is a small slice without a companion at batch 65 and a GEMM slice with one at 257
+    assert {(c.N, c.nf, c.env) for c in gpu.BATCH_CASES if c.id.startswith("257-")} == {(257, 256, (("GPAR_POTRF_NBO", "128"),))}
 
 
 def test_the_5121_case_ends_its_first_trailing_update_on_a_mixed_round(printer):  # noqa: F811
@@ -155,6 +243,11 @@ def test_zero_pivot_columns_sit_where_their_names_say(printer):  # noqa: F811
     form, off, width, _, _ = where["ragged leaf panel"]
     assert form == "leaf" and width % 64 != 0
     assert where["one member of a lock-step batch"][4] > 1
+    wide = [(case_id, member, j) for case_id, member, j, what in gpu.ZERO_PIVOT_CASES if what.startswith("batch ")]
+    for batch in (65, 130):
+        members = {member for case_id, member, j in wide if gpu.POTRF_BY_ID[case_id].batch == batch}
+        assert {0, 63, 64, batch - 1} <= members
+    assert len({j for _, _, j in wide}) >= 5   # (first, last and interior columns)
 
 
 # ---- the product cases reach the GEMM paths they name -------------------------------------------------------------------

@@ -772,6 +772,230 @@ def test_lockstep_dense_logpdf_equals_layer_by_layer(env, n, batch):
             assert abs(v - ref[b]) <= 1e-11 * max(1.0, abs(ref[b]))
 
 
+# ---- gpar_logpdf_lockstep at the layer counts where it branches ----------------------------------------------------------------------
+# LS_CHUNK = 4 layers per launch of the fused build (gram.h), LOCKSTEP_CHUNK = 64 per launch of the preparing kernel (gpar_hip.hip),
+# 64 threads looping over the layers in lockstep_finish_kernel
+_LOCKSTEP_COUNTS = [1, 4, 5, 7, 8, 9, 64, 65, 67]
+_LOCKSTEP_ZOO = [(1, []), (2, [2]), (3, [3, 4, 5]), (4, [6, 7])]   # (inputs, output columns) of _kernels: 8 columns in all
+_LOCKSTEP_NAMES = ["eq", "gpar-layer", "rq", "matern32", "zero-width-outputs", "matern52+lin+const", "matern12-gpar-layer"]
+_LOCKSTEP_WIDTH = 8
+_LOCKSTEP_JITTER = 1e-8
+_lockstep_cache = {}
+
+
+def _lockstep_layers(batch):
+    """Kernel, noise variance and observed column of `batch` layers that differ in every field: the structure cycles through seven
+    entries of the zoo and four (inputs, output columns) selections of the widest x (7 and 4 coprime: 28 combinations), the noise
+    is 0.05 + 0.003 b, the observed column a fixed permutation of the layers (not the identity)."""
+    from gpar_amd.kernels import compile_kernel
+
+    zoos = [_kernels(m, p_cols) for m, p_cols in _LOCKSTEP_ZOO]
+    cols = np.random.default_rng(batch).permutation(batch)
+    out, last_dz = [], None
+    for b in range(batch):
+        zoo = zoos[b % len(zoos)]
+        for step in range(len(_LOCKSTEP_NAMES)):   # (the next structure of the cycle where the neighbour has the same feature width)
+            name = _LOCKSTEP_NAMES[(b + step) % len(_LOCKSTEP_NAMES)]
+            kernel = zoo.get(name, zoo["eq+lin+const"])
+            dz = compile_kernel(kernel, _LOCKSTEP_WIDTH).dz
+            if dz != last_dz:
+                break
+        last_dz = dz
+        out.append((kernel, 0.05 + 0.003 * b, int(cols[b])))
+    return out
+
+
+def _lockstep_problem(n, batch):
+    """(x, y, w) on the host, drawn once per (n, batch); the oracle's value of every layer with and without weights."""
+    from oracle import gp_ref
+    from oracle import kernels as ok
+
+    if (n, batch) not in _lockstep_cache:
+        rng = np.random.default_rng(1000 * n + batch)
+        x = rng.uniform(0, 1, (n, _LOCKSTEP_WIDTH))
+        y = rng.standard_normal((n, batch))
+        w = rng.uniform(0.5, 2.0, (n, batch))
+        oracle = {True: [], False: []}
+        for kernel, noise, col in _lockstep_layers(batch):
+            spec = ok.spec_to_dict(kernel.resolve(_LOCKSTEP_WIDTH))
+            oracle[True].append(gp_ref.logpdf(spec, x, y[:, col], noise / w[:, col], eps=_LOCKSTEP_JITTER))
+            oracle[False].append(gp_ref.logpdf(spec, x, y[:, col], noise, eps=_LOCKSTEP_JITTER))
+        _lockstep_cache[(n, batch)] = (x, y, w, oracle)
+    return _lockstep_cache[(n, batch)]
+
+
+def _lockstep_call(env, layers, x, y, w):
+    """hip.logpdf_lockstep, keeping the buffer of factored matrices: (values, total, info, lower triangles incl. row n)."""
+    import ctypes
+
+    from gpar_amd import _lib
+
+    torch, hip, dev, to_dev = env
+    lib = _lib.load()
+    batch, n = len(layers), x.shape[0]
+    arr = (_lib.Layer * batch)()
+    for b, (ck, noise, col) in enumerate(layers):
+        arr[b].fs, arr[b].ks, arr[b].noise, arr[b].y_col = ctypes.pointer(ck.fspec), ctypes.pointer(ck.kspec), float(noise), int(col)
+    A = hip.alloc_matrix(batch * (n + 1), n + 1, dev)
+    A.fill_(float("nan"))
+    z = hip.alloc_matrix(batch * n, max(max(ck.dz for ck, _, _ in layers), 1), dev)
+    nd = torch.empty(batch * n, dtype=torch.float64, device=dev) if w is not None else None
+    words = torch.full((2 * batch + 1,), float("nan"), dtype=torch.float64, device=dev)
+    info = torch.full((batch,), -5, dtype=torch.int32, device=dev)
+    ld = lambda t: int(t.stride(0))   # noqa: E731
+    _lib.check(lib.gpar_logpdf_lockstep(
+        arr, batch, x.data_ptr(), n, ld(x), y.data_ptr(), ld(y), None if w is None else w.data_ptr(), 0 if w is None else ld(w),
+        _LOCKSTEP_JITTER, z.data_ptr(), ld(z), None if nd is None else nd.data_ptr(), A.data_ptr(), ld(A), (n + 1) * ld(A), words.data_ptr(),
+        info.data_ptr(), words[batch:].data_ptr(), words[2 * batch:].data_ptr(), 0, hip.stream_ptr(dev)), "gpar_logpdf_lockstep")
+    return (words[batch:2 * batch].cpu().numpy(), float(words[2 * batch]), info.cpu().tolist(),
+            np.tril(A.cpu().numpy().reshape(batch, n + 1, n + 1)))
+
+
+@pytest.mark.parametrize("batch", _LOCKSTEP_COUNTS)
+@pytest.mark.parametrize("n", [77, 130])
+def test_lockstep_logpdf_across_both_chunk_sizes(env, monkeypatch, n, batch):
+    """gpar_logpdf_lockstep with 1 .. 67 layers that differ in kernel structure, feature width, selected columns, noise and observed
+    column, by its three routes: the fused build (weights: LS_CHUNK = 4 layers per launch - 5, 7, 9, 65 and 67 leave a ragged last
+    chunk, every chunk holds layers of different dz), unit weights (the 64-layer preparing launch: 65 and 67 need a second one, at
+    offsets logdet + 64, info + 64), and weights with GPAR_LOCKSTEP_FUSED_BUILD_ROWS=0 (the preparing launch with the noise diagonals nd + 64 n).
+    More than 64 layers also take lockstep_finish_kernel's threads round their loop.
+    (a) value[b] is gpar_logpdf_dense's of layer b alone, under the rule of test_lockstep_dense_logpdf_equals_layer_by_layer
+        (1e-11 max(1, |ref|)); the fused and the separate build leave the same bits: factored matrices, values and total.  (The
+        library has no entry point that stops after the fused build, so the BUILT matrices are compared through what the one
+        deterministic factorisation makes of them - lower triangle, solved row of observations, corner -, not before it: a
+        difference in a built entry that the factorisation maps to the same bits would pass.)
+    (b) value[b] is the oracle's (oracle.gp_ref.logpdf: slogdet + solve) at the suite's rtol 1e-10 (tests/test_parity_gpu.py);
+    (c) total == ((0 + value[0]) + value[1]) + ..., bit for bit."""
+    from gpar_amd.kernels import compile_kernel
+
+    torch, hip, dev, to_dev = env
+    x, y, w, oracle = _lockstep_problem(n, batch)
+    dx, dy, dw = to_dev(x), to_dev(y), to_dev(w)
+    layers = [(compile_kernel(k, _LOCKSTEP_WIDTH), noise, col) for k, noise, col in _lockstep_layers(batch)]
+    dzs = [ck.dz for ck, _, _ in layers]
+    assert all(0 <= dz <= 24 for dz in dzs) and n <= 4096   # the fused build's own conditions (gpar_logpdf_lockstep)
+    assert all(dzs[b] != dzs[b + 1] for b in range(batch - 1))   # neighbours differ in dz
+    assert batch == 1 or sorted(col for _, _, col in layers) == list(range(batch)) and [col for _, _, col in layers] != list(range(batch))
+
+    runs = {}
+    runs["fused"] = _lockstep_call(env, layers, dx, dy, dw)
+    runs["unit"] = _lockstep_call(env, layers, dx, dy, None)
+    monkeypatch.setenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS", "0")
+    runs["separate"] = _lockstep_call(env, layers, dx, dy, dw)
+    monkeypatch.delenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS")
+    for route, (values, total, info, _) in runs.items():
+        assert info == [0] * batch, route
+        ref = oracle[route != "unit"]
+        for b, (ck, noise, col) in enumerate(layers):
+            nd = noise / dw[:, col] if route != "unit" else None
+            one, _, info1, _ = hip.logpdf_dense(ck, dx, dy[:, col], nd, _LOCKSTEP_JITTER if nd is not None else noise + _LOCKSTEP_JITTER)
+            assert int(info1.item()) == 0
+            assert abs(values[b] - float(one)) <= 1e-11 * max(1.0, abs(float(one))), (route, b, values[b], float(one))      # (a)
+            assert abs(values[b] - ref[b]) <= 1e-10 * abs(ref[b]), (route, b, values[b], ref[b])                            # (b)
+        acc = 0.0
+        for v in values:
+            acc = acc + float(v)
+        assert total == acc, route                                                                                        # (c)
+    fused, separate = runs["fused"], runs["separate"]
+    for b in range(batch):
+        assert np.array_equal(fused[3][b], separate[3][b]), "factored matrix of layer %d: fused against separate build" % b
+    assert np.array_equal(fused[0], separate[0]) and fused[1] == separate[1]
+
+
+@pytest.mark.parametrize("where", [0, 3, 4, 63, 64, 66])
+def test_lockstep_logpdf_reports_a_bad_layer_in_its_own_words(env, monkeypatch, where):
+    """67 layers of 77 rows, one of them spoilt - the first, the ones on either side of the fused build's first chunk boundary (3, 4)
+    and of the preparing launch's (63, 64), the last - by each of the three routes:
+    * NaN for its noise variance: every pivot of ITS matrix is NaN, so info[where] == 1 (column 0, LAPACK style) and every other
+      info word is 0;
+    * a NaN in ITS column of y: the observations sit in the augmented row, which no pivot reads - the ABI reports a pivot in info and
+      nothing else -, so info stays 0 everywhere and value[where], and only it, is NaN.
+    Either way the values of all other layers keep their bits."""
+    from gpar_amd.kernels import compile_kernel
+
+    torch, hip, dev, to_dev = env
+    n, batch = 77, 67
+    x, y, w, _ = _lockstep_problem(n, batch)
+    dx, dy, dw = to_dev(x), to_dev(y), to_dev(w)
+    layers = [(compile_kernel(k, _LOCKSTEP_WIDTH), noise, col) for k, noise, col in _lockstep_layers(batch)]
+    others = [b for b in range(batch) if b != where]
+    bad_noise = [(ck, float("nan") if b == where else noise, col) for b, (ck, noise, col) in enumerate(layers)]
+    bad_y = y.copy()
+    bad_y[n // 2, layers[where][2]] = np.nan
+    dbad = to_dev(bad_y)
+    for route in ("fused", "unit", "separate"):
+        if route == "separate":
+            monkeypatch.setenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS", "0")
+        wr = None if route == "unit" else dw
+        clean = _lockstep_call(env, layers, dx, dy, wr)
+        values, total, info, _ = _lockstep_call(env, bad_noise, dx, dy, wr)
+        assert info[where] == 1 and [info[b] for b in others] == [0] * len(others), (route, info)
+        assert np.array_equal(values[others], clean[0][others]), route
+        values, total, info, _ = _lockstep_call(env, layers, dx, dbad, wr)
+        assert info == [0] * batch, (route, info)
+        assert np.isnan(values[where]) and np.isnan(total) and np.array_equal(values[others], clean[0][others]), route
+
+
+@pytest.mark.parametrize("ns,n,batch", [(65, 10, 257), (33, 70, 65), (20, 130, 64)])
+def test_batched_helpers_at_sample_sized_batches(env, ns, n, batch):
+    """gpar_gemm_batch, gpar_gram_batch (gridDim.z = batch) and gpar_trmv_lower_batch (gridDim.y = batch) with as many members as a
+    layer draws samples - 64, 65 and 257 -, every member with data of its own: the references and tolerances of
+    test_batched_downdate_and_draws (the per-member launches bit for bit; numpy at rtol = atol = 1e-12; the Gram matrices against the
+    oracle at test_gram_matches_oracle's rtol 1e-13, atol 1e-14).  Member 64 (where there is one) and the last are compared first."""
+    from gpar_amd.kernels import EQ, Linear, Matern32, compile_kernel
+    from oracle import kernels as ok
+
+    torch, hip, dev, to_dev = env
+    rng = np.random.default_rng(ns + n + batch)
+    order = [b for b in (batch - 1, 64) if b < batch]
+    order += [b for b in range(batch) if b not in order]
+    blk = lambda t, b: t[b * ns:(b + 1) * ns]   # noqa: E731
+    V = rng.standard_normal((batch * ns, n)) / np.sqrt(n)
+    C = rng.standard_normal((batch * ns, ns))
+    assert len({blk(V, b).tobytes() for b in range(batch)}) == batch
+    dV, dC = to_dev(V), to_dev(C)
+    ref = {}
+    for b in order:
+        one = blk(dC, b).clone()
+        hip.gemm(blk(dV, b), blk(dV, b), tb=True, alpha=-1.0, beta=1.0, out=one, c_lower=True)
+        ref[b] = np.tril(one.cpu().numpy())
+    hip.gemm_batch_(dV, dV, dC, batch, tb=True, alpha=-1.0, beta=1.0, c_lower=True)
+    got = dC.cpu().numpy()
+    for b in order:
+        assert np.array_equal(np.tril(blk(got, b)), ref[b]), b
+        assert np.allclose(ref[b], np.tril(blk(C, b) - blk(V, b) @ blk(V, b).T), rtol=1e-12, atol=1e-12), b
+    xs_host = rng.uniform(0, 1, (batch * ns, 3))
+    xs = to_dev(xs_host)
+    noise_host = rng.uniform(0.1, 0.2, ns)
+    noise = to_dev(noise_host[:, None])[:, 0]
+    il = np.tril_indices(ns)
+    for kernel in (0.7 * EQ().stretch(np.array([0.5, 0.8])).select([0, 1]) + Linear().stretch(np.array([3.0])).select([2]),
+                   0.7 * Matern32().stretch(np.array([0.5, 0.8])).select([0, 1]) + Linear().stretch(np.array([3.0])).select([2])):
+        ck = compile_kernel(kernel, 3)
+        spec = ok.spec_to_dict(kernel.resolve(3))
+        z_all = hip.featurize(ck, xs)
+        Ks = hip.alloc_matrix(batch * ns, ns, dev)
+        hip.gram_batch_(ck, z_all, batch, Ks, lower=True, diag_add=noise, diag_const=1e-9)
+        for b in order:
+            one = hip.gram(ck, blk(z_all, b), lower=True, diag_add=noise, diag_const=1e-9)
+            assert torch.equal(torch.tril(blk(Ks, b)), torch.tril(one)), b
+            want = ok.gram(spec, blk(xs_host, b), None, noise_diag=noise_host, jitter=1e-9)
+            assert np.allclose(blk(Ks, b).cpu().numpy()[il], want[il], rtol=1e-13, atol=1e-14), b
+    Ls = np.tril(rng.standard_normal((batch * ns, ns)))
+    Z = rng.standard_normal((ns, batch))
+    M = rng.standard_normal((batch * ns, 1))
+    dL, dZ, dM = to_dev(Ls), to_dev(Z), to_dev(M)
+    out = torch.empty(ns, batch, dtype=torch.float64, device=dev)
+    hip.trmv_lower_batch_(dL, batch, dZ, out, add=dM)
+    plain = torch.empty(ns, batch, dtype=torch.float64, device=dev)
+    hip.trmv_lower_batch_(dL, batch, dZ, plain)
+    for b in order:
+        single = hip.trmv_lower(blk(dL, b), dZ[:, b:b + 1])
+        assert torch.equal(plain[:, b:b + 1], single), b
+        assert torch.equal(out[:, b:b + 1], single + blk(dM, b)), b
+        assert np.allclose(single.cpu().numpy()[:, 0], np.tril(blk(Ls, b)) @ Z[:, b], rtol=1e-12, atol=1e-12), b
+
+
 @pytest.mark.parametrize("n", [384, 1024, 1300])
 def test_gemm_triangular_aware_k_ranges(env, n):
     """K_FROM_ROW (upper-triangular op(A), zeros stored left of its diagonal) and K_TO_COL (upper-triangular op(B), zeros stored

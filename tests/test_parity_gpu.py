@@ -379,6 +379,99 @@ def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, w
         assert abs(got["1"] - ref) <= 1e-9 * abs(ref), (got, ref)
 
 
+def _many_outputs(n, p, weights):
+    x, y = _problem(n, 2, 6, seed=n + p)
+    y = np.concatenate([y] * (p // y.shape[1] + 1), axis=1)[:, :p] + 0.05 * np.random.default_rng(p).standard_normal((n, p))
+    w = np.random.default_rng(p + 1).uniform(0.5, 2.0, y.shape) if weights else None
+    return x, y, w
+
+
+_MANY_OUTPUTS_KW = dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3, normalise_y=False)
+
+
+def _cuts(p, cap):
+    """Sizes of the calls that `p` layers are cut into when at most `cap` fit the workspace budget."""
+    return [p] if cap is None else [min(cap, p - s0) for s0 in range(0, p, cap)]
+
+
+@pytest.mark.parametrize("weights", [True, False], ids=["weights", "no-weights-argument"])
+@pytest.mark.parametrize("p", [9, 66])
+def test_logpdf_with_many_outputs_matches_the_oracle_however_the_layers_are_cut(monkeypatch, p, weights):
+    """GPARRegressor.logpdf with 9 and with 66 outputs at n = 60 against the oracle engine at the suite's rtol 1e-10
+    (test_logpdf_condition_predict_match_oracle):
+    * in one call (GPAR_ONE_CALL=1, model._lockstep_total) and with GPAR_LAYER_BATCH_BYTES cutting the layers into calls of at most 4,
+      5 and p - 1: several calls, a ragged last one, a lone last layer, the list of values in place of the device-side sum.  The
+      regressor hands the library a weight matrix in every case (ones when `w` is None), so at this size gpar_logpdf_lockstep takes
+      the fused build - three and seventeen launches of LS_CHUNK = 4 layers, ragged last ones;
+    * the same with GPAR_LOCKSTEP_FUSED_BUILD_ROWS=0: the separate build, for 66 outputs two launches of the 64-layer preparing kernel;
+    * through the per-layer build calls (GPAR_ONE_CALL=0, model._lockstep_values -> logpdf_dense_batch): a lone last layer takes the
+      one-layer route.
+    The routes are not taken on trust: the engine's logpdf_lockstep and logpdf_dense_batch are wrapped, and the sizes of their calls
+    must be the cuts - a silent fall-back to the layer-by-layer evaluation would return the same value."""
+    from gpar_amd.engine import get_engine
+    from gpar_amd.regression import GPARRegressor
+
+    n = 60
+    x, y, w = _many_outputs(n, p, weights)
+    # (a pivot reported by a wrongly built matrix must fail here, not be repeated layer by layer in the engine's safe mode)
+    monkeypatch.setenv("GPAR_NOTPD_RETRY", "0")
+
+    def run():
+        eng = get_engine()
+        calls = {"lockstep": [], "batch": []}
+        inner_lockstep, inner_batch = eng.logpdf_lockstep, eng.logpdf_dense_batch
+        monkeypatch.setattr(eng, "logpdf_lockstep", lambda layers, *a, **k: (calls["lockstep"].append(len(layers)), inner_lockstep(layers, *a, **k))[1], raising=False)
+        monkeypatch.setattr(eng, "logpdf_dense_batch", lambda items, *a, **k: (calls["batch"].append(len(items)), inner_batch(items, *a, **k))[1], raising=False)
+        out = {}
+        for mode, rows in (("1", None), ("1", "0"), ("0", None)):
+            monkeypatch.setenv("GPAR_ONE_CALL", mode)
+            if rows is not None:
+                monkeypatch.setenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS", rows)
+            for cap in (None, 4, 5, p - 1):
+                if cap is None:
+                    monkeypatch.delenv("GPAR_LAYER_BATCH_BYTES", raising=False)
+                else:
+                    monkeypatch.setenv("GPAR_LAYER_BATCH_BYTES", str(8 * (n + 1) * (n + 17) * cap))
+                calls["lockstep"].clear(), calls["batch"].clear()
+                out[mode, rows, cap] = float(GPARRegressor(**_MANY_OUTPUTS_KW).logpdf(x, y, w))
+                if mode == "1":
+                    assert (calls["lockstep"], calls["batch"]) == (_cuts(p, cap), []), (mode, rows, cap, calls)
+                else:   # (a lone last layer is not a batch)
+                    assert (calls["lockstep"], calls["batch"]) == ([], [c for c in _cuts(p, cap) if c >= 2]), (mode, cap, calls)
+            monkeypatch.delenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS", raising=False)
+        monkeypatch.delenv("GPAR_LAYER_BATCH_BYTES")
+        monkeypatch.delenv("GPAR_ONE_CALL")
+        return out
+
+    got = _on("hip", run)
+    ref = _on("oracle", lambda: float(GPARRegressor(**_MANY_OUTPUTS_KW).logpdf(x, y, w)))
+    for key, value in got.items():
+        print(f"[many outputs] p={p} weights={weights} one_call={key[0]} fused_build_rows={key[1]} cap={key[2]}: "
+              f"error / tolerance = {abs(value - ref) / (1e-10 * abs(ref)):.3g}")
+    for key, value in got.items():
+        assert abs(value - ref) <= 1e-10 * abs(ref), (key, value, ref)
+
+
+def test_gradient_with_nine_outputs_matches_oracle(hip):
+    """The `backward` gradient of the 9-output model above, at test_gradient_matches_oracle's tolerance (rtol 1e-8, atol 1e-9 max |ref|).
+    Under autograd `_differentiable` keeps every layer on the one-layer route: this runs NO lock-step or batch code - nine layers of
+    60 rows through the per-layer objective and its analytic gradient, which no other test evaluates with more than five outputs."""
+    from gpar_amd.regression import GPARRegressor
+
+    x, y, _ = _many_outputs(60, 9, False)
+
+    def grads():
+        reg = GPARRegressor(**dict(_MANY_OUTPUTS_KW, impute=False))
+        with torch.no_grad():
+            reg.logpdf(x, y)
+        reg.vs.requires_grad(True)
+        reg.logpdf(torch.tensor(x), torch.tensor(y)).backward()
+        return np.concatenate([v.grad.numpy().reshape(-1) for v in reg.vs.get_vars()])
+
+    ref, got = _on("oracle", grads), _on("hip", grads)
+    np.testing.assert_allclose(got, ref, rtol=1e-8, atol=1e-9 * np.max(np.abs(ref)))
+
+
 @pytest.mark.parametrize("n,p", [(1500, 4), (300, 3)])
 def test_lockstep_conditioning_equals_layer_by_layer(monkeypatch, n, p):
     """Conditioning on complete data factors the (independent) layers in lock-step (HipEngine.factor_dense_batch): the posterior
