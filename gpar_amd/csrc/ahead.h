@@ -1,0 +1,239 @@
+// Rolling-origin forecast scoring of one dense layer (ABI v12): the kernels between the factorisation and the two products with X = L^-T.
+// With K + D + eps I = L L^T, a = L^-1 y (row n of the augmented factor) and the rows in the order given, the prediction of row r from rows
+// 0 ... o_r - 1 (o_r = origin[r]; -1: the row is not scored) has
+//     e_r = y_r - mean_r = sum_{c = o_r .. r} L_rc a_c,      v_r = var_r = sum_{c = o_r .. r} L_rc^2
+// - the factor of a leading block is the leading block of the factor -, and
+//     value = sum_scored -1/2 [log 2 pi + log v_r + e_r^2 / v_r],      dvalue/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta,
+//     q_r = e_r / v_r,  s_r = 1/2 (1 / v_r - q_r^2)   (zero on unscored rows),
+//     B_rc = -q_r a_c - 2 s_r L_rc  (o_r <= c <= r),      abar_c = -sum_{r >= c, o_r <= c} q_r L_rc,
+//     P = Phi(L^T B - abar a^T),      W = X (P + P^T) X^T.
+// Four launches: ahead_check_kernel (the origins' range, the smallest origin of every 32 rows), ahead_rows_kernel (e, v, q, s, the value
+// terms), ahead_abar_kernel, ahead_band_kernel (P + P^T as a full matrix).  Every kernel behind the check returns at once when the info
+// word is set - by the factorisation, by the check, by a non-positive v_r -, so a failed call leaves the value, the means, the variances
+// and the gradient outputs as they were.  No workgroup waits on another one; every sum has a fixed order.
+#pragma once
+
+namespace gpar {
+
+constexpr int AH_T = 32;                 // tile edge of ahead_abar_kernel and ahead_band_kernel, rows per entry of `cmin`
+constexpr int AH_NONE = 0x7fffffff;      // "no origin": an unscored row, a chunk without scored rows
+
+// `vec` of the gradient forms: q, s, value terms, abar (n each), cmin (ceil(n / AH_T) ints in n doubles), then the n x ah_ldt(n) matrix of
+// the first product at an even offset; of the value-only form: the n value terms.
+inline int ah_ldt(int n) { return n + (n & 1); }
+inline long long ah_off_t(int n) { return 5LL * n + (n & 1); }
+inline long long ah_workspace_doubles(int n, int grad) {
+    if (n <= 0) return 0;
+    return grad ? ah_off_t(n) + (long long)n * ah_ldt(n) : n;
+}
+
+// One workgroup.  An origin outside -1 ... r: n + 1 + r of the first such row into info (the first to report stays) and nothing else;
+// otherwise cmin[k] = the smallest origin among the scored rows of chunk k (AH_NONE when it has none).
+__global__ __launch_bounds__(256) void ahead_check_kernel(const int* __restrict__ origin, int n, int* __restrict__ cmin, int* __restrict__ info) {
+    __shared__ int sm[256];
+    const int t = threadIdx.x;
+    int bad = AH_NONE;
+    for (int r = t; r < n; r += 256) {
+        const int o = origin[r];
+        if ((o < -1 || o > r) && bad == AH_NONE) bad = r;
+    }
+    sm[t] = bad;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) sm[t] = min(sm[t], sm[t + off]);
+        __syncthreads();
+    }
+    if (sm[0] != AH_NONE) {
+        if (t == 0) atomicCAS(info, 0, n + 1 + sm[0]);
+        return;
+    }
+    if (!cmin) return;
+    const int nchunks = (n + AH_T - 1) / AH_T;
+    for (int k = t; k < nchunks; k += 256) {
+        int m = AH_NONE;
+        for (int r = k * AH_T; r < min(n, (k + 1) * AH_T); ++r) {
+            const int o = origin[r];
+            if (o >= 0) m = min(m, o);
+        }
+        cmin[k] = m;
+    }
+}
+
+// One wave per row: lanes stride the row of L from o_r to r, two wave sums.  q, s null: the value-only form.  A non-positive v_r: the
+// 1-based row into info, nothing written for it.
+__global__ __launch_bounds__(256) void ahead_rows_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ a,
+                                                         const double* __restrict__ y, long incy, const int* __restrict__ origin,
+                                                         double* __restrict__ mean, double* __restrict__ var, double* __restrict__ q,
+                                                         double* __restrict__ s, double* __restrict__ term, int* __restrict__ info) {
+    if (info[0] != 0) return;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const int o = origin[row];
+    if (o < 0) {
+        if (lane == 0) {
+            mean[row] = var[row] = __builtin_nan("");
+            term[row] = 0.0;
+            if (q) q[row] = s[row] = 0.0;
+        }
+        return;
+    }
+    const double* Lr = L + (size_t)row * ldl;
+    double e0 = 0.0, e1 = 0.0, v0 = 0.0, v1 = 0.0;
+    int j = o + lane;
+    for (; j + 64 <= row; j += 128) {
+        const double l0 = Lr[j], l1 = Lr[j + 64];
+        e0 = fma(l0, a[j], e0); v0 = fma(l0, l0, v0);
+        e1 = fma(l1, a[j + 64], e1); v1 = fma(l1, l1, v1);
+    }
+    if (j <= row) { const double l0 = Lr[j]; e0 = fma(l0, a[j], e0); v0 = fma(l0, l0, v0); }
+    const double e = wave_sum(e0 + e1), v = wave_sum(v0 + v1);
+    if (lane != 0) return;
+    if (!(v > 0.0)) {
+        atomicCAS(info, 0, row + 1);
+        return;
+    }
+    const double qr = e / v;
+    mean[row] = y[(size_t)row * incy] - e;
+    var[row] = v;
+    term[row] = -0.5 * (1.8378770664093453 + log(v) + e * qr);
+    if (q) {
+        q[row] = qr;
+        s[row] = 0.5 * (1.0 / v - qr * qr);
+    }
+}
+
+// abar_c = -sum_{r >= c, o_r <= c} q_r L_rc for the AH_T columns of one workgroup: thread (ty, tx) takes rows c0 + ty, c0 + ty + 8, ... of
+// column c0 + tx - the 32 threads of a row group read along a row of L - and the 8 partial sums of a column meet in LDS, summed in order.
+// LDS: 8 x 33 doubles (2112 bytes).
+__global__ __launch_bounds__(256) void ahead_abar_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ q,
+                                                         const int* __restrict__ origin, double* __restrict__ abar,
+                                                         const int* __restrict__ info) {
+    __shared__ double part[8][AH_T + 1];
+    if (info[0] != 0) return;
+    const int tx = threadIdx.x & (AH_T - 1), ty = threadIdx.x / AH_T;
+    const int c0 = blockIdx.x * AH_T, c = c0 + tx;
+    double acc = 0.0;
+    if (c < n) {
+#pragma unroll 4
+        for (int r = c0 + ty; r < n; r += 8) {
+            const int o = origin[r];
+            if (r >= c && o >= 0 && o <= c) acc = fma(q[r], L[(size_t)r * ldl + c], acc);
+        }
+    }
+    part[ty][tx] = acc;
+    __syncthreads();
+    if (ty == 0 && c < n) {
+        double sum = 0.0;
+        for (int k = 0; k < 8; ++k) sum += part[k][tx];
+        abar[c] = -sum;
+    }
+}
+
+// Tile (bj, bc), bc <= bj, of  P + P^T  (its lower triangle:  (L^T B)_jc - abar_j a_c,  (L^T B)_jc = -sum_{r >= j, o_r <= c} L_rj (q_r a_c +
+// 2 s_r L_rc)),  written at (bj, bc) and, transposed, at (bc, bj): a full symmetric matrix for the product with X, both stores along rows.
+// The rows r come through LDS in chunks of AH_T (both column slabs of L read along rows; L_rj stored as zero for r < j, the origin of an
+// unscored row as AH_NONE); a chunk whose smallest origin lies right of the tile's columns is skipped, which makes the cost follow the
+// band (sum_j sum_{i >= j} #{r >= i: o_r <= j} multiply-adds up to the tile granularity).  Thread (ty, tx): column c0 + tx, rows j0 + ty + 8 k.
+// LDS: two 32 x 33 tiles of doubles, q, s and the origins of a chunk: 2 * 8448 + 2 * 256 + 128 = 17536 bytes.
+__global__ __launch_bounds__(256) void ahead_band_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ a,
+                                                         const double* __restrict__ q, const double* __restrict__ s,
+                                                         const double* __restrict__ abar, const int* __restrict__ origin,
+                                                         const int* __restrict__ cmin, double* __restrict__ S, int lds,
+                                                         const int* __restrict__ info) {
+    __shared__ double Lj[AH_T][AH_T + 1];
+    __shared__ double Lc[AH_T][AH_T + 1];
+    __shared__ double qs[AH_T], ss[AH_T];
+    __shared__ int os[AH_T];
+    const int bc = blockIdx.x, bj = blockIdx.y;
+    if (bc > bj || info[0] != 0) return;
+    const int t = threadIdx.x, tx = t & (AH_T - 1), ty = t / AH_T;
+    const int j0 = bj * AH_T, c0 = bc * AH_T, gc = c0 + tx;
+    const int nchunks = (n + AH_T - 1) / AH_T;
+    const double ac = gc < n ? a[gc] : 0.0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = bj; k < nchunks; ++k) {
+        if (cmin[k] > c0 + AH_T - 1) continue;   // (the same verdict in every thread)
+        const int r0 = k * AH_T;
+        __syncthreads();
+        for (int rr = ty; rr < AH_T; rr += 8) {
+            const int gr = r0 + rr;
+            Lj[rr][tx] = (gr < n && j0 + tx <= gr) ? L[(size_t)gr * ldl + j0 + tx] : 0.0;
+            Lc[rr][tx] = (gr < n && gc <= gr) ? L[(size_t)gr * ldl + gc] : 0.0;
+        }
+        if (t < AH_T) {
+            const int gr = r0 + t;
+            const int o = gr < n ? origin[gr] : -1;
+            qs[t] = o >= 0 ? q[gr] : 0.0;
+            ss[t] = o >= 0 ? s[gr] : 0.0;
+            os[t] = o >= 0 ? o : AH_NONE;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int rr = 0; rr < AH_T; ++rr) {
+            const double wv = os[rr] <= gc ? fma(2.0 * ss[rr], Lc[rr][tx], qs[rr] * ac) : 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = fma(Lj[rr][ty + 8 * i], wv, acc[i]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int gj = j0 + ty + 8 * i;
+        Lj[ty + 8 * i][tx] = gj < n ? -acc[i] - abar[gj] * ac : 0.0;
+    }
+    __syncthreads();
+    const bool diag = bj == bc;
+    for (int r = ty; r < AH_T; r += 8) {
+        const int gr = j0 + r;
+        if (gr < n && gc < n) S[(size_t)gr * lds + gc] = (diag && tx > r) ? Lj[tx][r] : Lj[r][tx];
+        const int mr = c0 + r, mc = j0 + tx;
+        if (!diag && mr < n && mc < n) S[(size_t)mr * lds + mc] = Lj[tx][r];
+    }
+}
+
+// the value-only form's last launch, and the last block of the gradient forms' epilogue: the sum of the value terms in loo_sum_terms' order
+__global__ __launch_bounds__(256) void ahead_value_kernel(const double* __restrict__ term, int n, double* __restrict__ out,
+                                                          const int* __restrict__ info) {
+    __shared__ double sm[256];
+    if (info[0] != 0) return;
+    const double v = loo_sum_terms(term, n, sm);
+    if (threadIdx.x == 0) out[0] = v;
+}
+
+__global__ __launch_bounds__(256) void ahead_grad_epilogue_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
+                                                                  const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag,
+                                                                  const double* __restrict__ term, const int* __restrict__ info) {
+    __shared__ double sm[256];
+    if (info[0] != 0) return;
+    if (grad_epilogue_sums(partial, nblocks, out, W, ldw, n, half_diag)) return;
+    const double v = loo_sum_terms(term, n, sm);
+    if (threadIdx.x == 0) out[0] = v;
+}
+
+// check + rows: everything of the value-only form behind the factor, the head of the weight stage.  q, s, cmin null: value only.
+static void ahead_rows_run(const double* A, int lda, int n, const double* y, long incy, const int* origin, double* mean, double* var, double* q,
+                           double* s, double* term, int* cmin, int* info, hipStream_t st) {
+    hipLaunchKernelGGL(ahead_check_kernel, dim3(1), dim3(256), 0, st, origin, n, cmin, info);
+    hipLaunchKernelGGL(ahead_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, lda, n, A + (size_t)n * lda, y, incy, origin, mean, var,
+                       q, s, term, info);
+}
+
+// The weight stage of the gradient forms: W <- X (P + P^T) X^T on its lower triangle (X = L^-T in its upper triangle, whatever lies below
+// its diagonal blocks unread: both products start their K range at the tile's first row).
+static int ahead_weights_run(const double* A, int lda, int n, const double* y, long incy, const int* origin, double* mean, double* var, double* vec,
+                             const double* X, int ldx, double* W, int ldw, int* info, hipStream_t st) {
+    double *q = vec, *s = vec + n, *term = vec + 2 * (size_t)n, *abar = vec + 3 * (size_t)n, *T = vec + ah_off_t(n);
+    int* cmin = reinterpret_cast<int*>(vec + 4 * (size_t)n);
+    const int ldt = ah_ldt(n), nt = gpar_ceil_div(n, AH_T);
+    const double* a = A + (size_t)n * lda;
+    ahead_rows_run(A, lda, n, y, incy, origin, mean, var, q, s, term, cmin, info, st);
+    hipLaunchKernelGGL(ahead_abar_kernel, dim3((unsigned)nt), dim3(256), 0, st, A, lda, n, (const double*)q, origin, abar, (const int*)info);
+    hipLaunchKernelGGL(ahead_band_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(256), 0, st, A, lda, n, a, (const double*)q, (const double*)s,
+                       (const double*)abar, origin, (const int*)cmin, W, ldw, (const int*)info);
+    int rc = gemm_launch(0, 1, n, n, n, 1.0, X, ldx, W, ldw, 0.0, T, ldt, GPAR_GEMM_K_FROM_ROW, st);
+    if (!rc) rc = gemm_launch(0, 1, n, n, n, 1.0, X, ldx, T, ldt, 0.0, W, ldw, GPAR_GEMM_C_LOWER | GPAR_GEMM_K_FROM_ROW, st);
+    return rc;
+}
+
+}  // namespace gpar

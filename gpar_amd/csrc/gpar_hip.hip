@@ -1198,16 +1198,19 @@ static int cv_folds_launch(const double* P, int ldp, int n, const double* X, int
     return 0;
 }
 
-// ---- one chain for the dense objectives: marginal likelihood, leave-one-out, blocked cross-validation ---------------------------------
+#include "ahead.h"   // rolling-origin forecast scoring: its kernels and weight stage (after loo_sum_terms and grad_epilogue_sums, which it uses)
+
+// ---- one chain for the dense objectives: marginal likelihood, leave-one-out, blocked cross-validation, rolling-origin forecasts --------
 // Every one-call entry is  prologue (features, Gram, factor) -> inverse -> the objective's weights W -> weighted-sum pass -> epilogue;
-// the objectives differ in the weight stage and in the last block of the epilogue alone.
-enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV };
+// the objectives differ in the weight stage and in the last block of the epilogue alone (OBJ_AHEAD also stops the inverse at X = L^-T).
+enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV, OBJ_AHEAD };
 struct DenseObjective {
     DenseObjectiveKind kind;
     const double* y;            // the observations (the finish form of OBJ_MLL has none: row n of the factor holds all it needs)
     long incy;
     double *vec, *mean, *var;   // OBJ_LOO, OBJ_CV: the vector workspace, held-out means and variances
     CvFolds folds;              // OBJ_CV
+    const int* origin;          // OBJ_AHEAD: n origins (device)
 };
 
 // What gpar_logpdf_dense does up to the factor: features (+ their frequency derivatives when zd is given; the value-only forms pass null)
@@ -1239,7 +1242,7 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
         const long total = (long)n * fs->dz;
         hipLaunchKernelGGL(featurize_dfreq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, zd, ldz);
     }
-    int rc = chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
+    int rc = ob.kind == OBJ_AHEAD ? trinv_upper_run(A, n, lda, X, ldxw, W, ldw, st) : chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
     if (rc) return rc;
     const double* zrow = A + (size_t)n * lda;   // L^-1 y
     double *bvec = ob.vec, *term = nullptr, *u = nullptr;
@@ -1268,8 +1271,12 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
                                ob.folds.start, ob.folds.nfolds, ob.folds.max_fold, (const double*)Rm, (const double*)bvec, u, X, ldxw);
             break;
         }
+        case OBJ_AHEAD:   // `vec`: q, s, value terms, abar, chunk origins, the first product;  W = X (P + P^T) X^T whole (no rank-2 tail)
+            term = ob.vec + 2 * (size_t)n;
+            rc = ahead_weights_run(A, lda, n, ob.y, ob.incy, ob.origin, ob.mean, ob.var, ob.vec, X, ldxw, W, ldw, info, st);
+            break;
     }
-    if (ob.kind != OBJ_MLL) {   // u and S (in X: alpha exists, L^-T is no longer needed) are formed: W <- -2 S S^T + alpha u^T + u alpha^T
+    if (ob.kind == OBJ_LOO || ob.kind == OBJ_CV) {   // u and S (in X: alpha exists, L^-T is no longer needed) are formed: W <- -2 S S^T + alpha u^T + u alpha^T
         rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
         if (rc) return rc;
         hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
@@ -1281,6 +1288,9 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
     if (ob.kind == OBJ_MLL)   // (the corner of the factor is untouched since the factorisation)
         hipLaunchKernelGGL(dense_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
                            half_diag, (const double*)A, lda, n_log_2pi, logdet);
+    else if (ob.kind == OBJ_AHEAD)
+        hipLaunchKernelGGL(ahead_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
+                           half_diag, (const double*)term, (const int*)info);
     else
         hipLaunchKernelGGL(loo_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
                            half_diag, (const double*)term, 0.5 * n_log_2pi);
@@ -1421,6 +1431,53 @@ int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* 
                                   vec, nullptr, info, st);
     if (rc) return rc;
     hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- rolling-origin forecast scoring (ABI v12; ahead.h) ----------------------------------------------------------------------------------
+int gpar_ahead_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                          const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                          double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                          double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !ahead_mean || !ahead_var ||
+        !origin || !info || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const DenseObjective ob{OBJ_AHEAD, y, incy, vec, ahead_mean, ahead_var, {}, origin};
+    const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
+                                    (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, out + 1, info, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag,
+                                 stream, false);
+}
+
+// (both info words are required, as for the blocked form: the kernels of the weight stage read and report into info_out)
+int gpar_ahead_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                 double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                                 double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                 double* ahead_mean, double* ahead_var, const int* origin, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !logdet || !info || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !ahead_mean ||
+        !ahead_var || !origin || !info_out || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const int rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_AHEAD, y, incy, vec, ahead_mean, ahead_var, {}, origin}, z, zd, ldz, A, lda, logdet,
+                                 info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream, true);
+}
+
+// Value, means and variances alone: the factor and its augmented row are all it reads - no X, no K^-1
+int gpar_ahead_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                     const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                     double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !vec || !out || !ahead_mean || !ahead_var || !origin || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
+    if (rc) return rc;
+    ahead_rows_run(A, lda, n, y, incy, origin, ahead_mean, ahead_var, nullptr, nullptr, vec, nullptr, info, st);
+    hipLaunchKernelGGL(ahead_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, out, (const int*)info);
     GPAR_LAUNCH_CHECK();
     return 0;
 }
@@ -1617,6 +1674,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_CV:                                                                /* n, with gradient, max_fold */
             if (c < 1 || c > GPAR_CV_MAX_FOLD) return -1;
             return (long long)(a > 0 ? a : 0) * (b ? 3 + c : 1);
+        case GPAR_WS_AHEAD: return ah_workspace_doubles(a, b);                          /* n, with gradient */
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         default: return -1;

@@ -288,6 +288,18 @@ class HipEngine:
                                                                   **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
+    def ahead_dense(self, ck, x, y, noise_diag, jitter, origin):
+        """One dense layer's rolling-origin forecast value, predictive means and variances in one library call, row r predicted from rows
+        0 ... origin[r] - 1 (-1: not scored, NaN in its mean and variance): (value as a 0-d device tensor, info word, means, variances)."""
+        out, mean, var, info = hip.ahead_dense(ck, self._mat(x), y, noise_diag, jitter, origin, **self._factor_flags())
+        return out[0], info, mean, var
+
+    def ahead_dense_grad(self, ck, x, y, noise_diag, jitter, origin):
+        """The rolling-origin counterpart of `loo_dense_grad`, same conventions and return values."""
+        out, half_diag, mean, var, info, A, _ = hip.ahead_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), origin,
+                                                                     **self._factor_flags())
+        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
+
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""
         safe = getattr(self._tls, "safe", False)

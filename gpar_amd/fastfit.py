@@ -264,16 +264,21 @@ class LockstepFactor:
 class DenseLayerObjective:
     """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or, with `objective="loo"`, minus the leave-one-out predictive
     log-density under the same covariance (gpar_loo_dense_grad), or, with `objective="cv"`, minus the blocked cross-validation value
-    over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad) - and its gradient with respect to
+    over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad), or, with `objective="ahead"`, minus the
+    rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad) - and its gradient with respect to
     the latent (unconstrained) variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are
     device tensors that do not change during the optimisation."""
 
     def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
-                 fold_start=None):
-        if objective not in ("mll", "loo", "cv"):
-            raise ValueError('objective must be "mll", "loo" or "cv"')
+                 fold_start=None, origin=None):
+        if objective not in ("mll", "loo", "cv", "ahead"):
+            raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
         if (objective == "cv") != (fold_start is not None):
             raise ValueError('fold_start belongs to objective="cv"')
+        if (objective == "ahead") != (origin is not None):
+            raise ValueError('origin belongs to objective="ahead"')
+        # (host origins of the rows; their device copy is made once, with the other buffers)
+        self.origin = None if origin is None else np.asarray(origin, dtype=np.int64).reshape(-1)
         self.eng, self.vs, self.names = eng, vs, list(names)
         self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
         # (host offsets of the folds; their device copy is made once, with the other buffers)
@@ -323,8 +328,11 @@ class DenseLayerObjective:
         nacc = _lib.GRAD_NACC
         # gradient partials, alpha; for the cross-validation objectives their vectors, the predictive means and variances behind them
         self.folds = hip.upload_folds(self.fold_start, n, dev) if self.objective == "cv" else ()   # (device offsets, number of folds, largest fold)
+        if self.objective == "ahead":
+            self.folds = (hip.upload_origin(self.origin, n, dev),)   # (the one argument the entry takes in the folds' place)
         nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.objective, n, 1, self.folds) + 2 * n
-        self.work = torch.empty(self.nblocks * nacc + n + nloo, dtype=torch.float64, device=dev)
+        nalpha = n + (n & 1)   # (the vectors start at an even offset: "ahead" keeps a matrix among them)
+        self.work = torch.empty(self.nblocks * nacc + nalpha + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
         self.res = torch.zeros(2 + nacc + n + 1, dtype=torch.float64, device=dev)
         self.res_host = torch.zeros(2 + nacc + n + 1, dtype=torch.float64).pin_memory()
@@ -342,7 +350,7 @@ class DenseLayerObjective:
             half=self.res[2 + nacc:].data_ptr(), info=self.res[2 + nacc + n:].data_ptr(),
         )
         if self.objective != "mll":
-            at = self.nblocks * nacc + n
+            at = self.nblocks * nacc + nalpha
             self._ptrs.update(vec=self.work[at:].data_ptr(), loo_mean=self.work[at + nloo - 2 * n:].data_ptr(),
                               loo_var=self.work[at + nloo - n:].data_ptr())
 
@@ -363,8 +371,8 @@ class DenseLayerObjective:
                 p["W"], p["ldw"], p["alpha"])
         tail = (p["info"], self.flags, stream.cuda_stream)
         if self.objective != "mll":
-            name = "gpar_cv_dense_grad" if self.objective == "cv" else "gpar_loo_dense_grad"
-            fold_args = (self.folds[0].data_ptr(), *self.folds[1:]) if self.objective == "cv" else ()
+            name = {"loo": "gpar_loo_dense_grad", "cv": "gpar_cv_dense_grad", "ahead": "gpar_ahead_dense_grad"}[self.objective]
+            fold_args = (self.folds[0].data_ptr(), *self.folds[1:]) if self.folds else ()
             rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *tail)
             _lib.check(rc, name)
         elif self.group is None:
@@ -482,14 +490,16 @@ class DenseLayerObjective:
         return val
 
 
-def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None):
+def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None, ahead=None):
     """The fast objective of layer `pi` of regressor `reg` with fixed design matrix `fixed_x`, or None when this route does not
     apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised;
     `objective`: "mll" (log marginal likelihood), "loo" (leave-one-out predictive log-density) or "cv" (blocked cross-validation over
     `folds`, one integer label per row of `fixed_x`: the layer's rows are sorted by label here, once; None when its largest fold
-    exceeds what the library call takes - the general route trains it)."""
+    exceeds what the library call takes - the general route trains it) or "ahead" (rolling-origin forecast score; `ahead` = (horizon,
+    start, the indices in the data as given of the rows of `fixed_x`): the layer's origins are counted here, once, from the rows that
+    survive)."""
     from .gp import one_call_grad_rows
-    from .model import contiguous_folds, host_index
+    from .model import contiguous_folds, host_index, rolling_origins
     from .regression import _model_generator
 
     on_device = cls is None   # (the CPU tests of the host logic hand in a class with its own device side)
@@ -525,6 +535,13 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
         if perm is not None:
             at = torch.as_tensor(perm, dtype=torch.long, device=X.device)
             X, yi, wi = X.index_select(0, at), yi.index_select(0, at), wi.index_select(0, at)
+    origin = None
+    if objective == "ahead":
+        horizon, start, rows = ahead
+        observed = np.asarray(rows, dtype=np.int64).reshape(-1)[host_index(mask)]
+        if not isinstance(mask, slice) and n_missing:
+            observed = observed[host_index(keep)]
+        origin = rolling_origins(observed, horizon, start)
     tracer = _TracingVars(vs)
     f, noise = _model_generator(tracer, reg.m, pi, **reg.model_config)()
     kernel = f.kernel
@@ -538,4 +555,5 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     if group is not None and (group.n != n or not on_device or objective != "mll"):
         group = None
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
-               lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}))
+               lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}),
+               **({} if origin is None else {"origin": origin}))

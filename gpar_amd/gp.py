@@ -39,7 +39,7 @@ import torch
 
 from ._lib import CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
 from .engine import get_engine, joining
-from .hip import fold_offsets
+from .hip import fold_offsets, origin_array, upload_origin
 from .kernels import Kernel
 
 __all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs", "greedy_inducing"]
@@ -360,6 +360,49 @@ def _cv_algebra(eng, Kinv, alpha, starts):
             S[:, idx.reshape(-1)] = cols.permute(1, 0, 2).reshape(n, -1)
 
     return value, b, var, fill
+
+
+class _Origins:
+    """The third held-out scheme beside `None` (leave-one-out) and fold offsets: rolling origins, one per row (`Obs.ahead`)."""
+
+    def __init__(self, origin):
+        self.origin = origin   # checked host array (int64), -1: not scored
+        self.device = None     # the uploaded copy, made at the first fused call
+
+
+def _ahead_algebra(eng, L, a, origin):
+    """Rolling-origin forecasts from the factor L and a = L^-1 y, where no library call takes the evaluation: (value, e = y - mean, v with
+    NaN on unscored rows, a function returning the weights W on their lower triangle from K^-1).  Row r is predicted from rows
+    0 ... origin[r] - 1: e_r = sum_{c = origin[r] .. r} L_rc a_c, v_r = sum L_rc^2.  The weights follow the reverse mode of the Cholesky
+    factorisation: W = L^-T (P + P^T) L^-1 = K^-1 [L (P + P^T) L^T] K^-1, P = Phi(L^T B - abar a^T), in products both engines have."""
+    n, dev = a.numel(), a.device
+    o = torch.as_tensor(origin, device=dev)
+    scored = o >= 0
+    cols = torch.arange(n, device=dev)
+    band = scored[:, None] & (cols[None, :] >= o[:, None]) & (cols[None, :] <= cols[:, None])
+    Lb = torch.where(band, torch.tril(L), torch.zeros((), dtype=torch.float64, device=dev))
+    e = torch.sum(Lb * a[None, :], dim=1)
+    v = torch.where(scored, torch.sum(Lb * Lb, dim=1), torch.ones((), dtype=torch.float64, device=dev))
+    q = e / v
+    value = torch.sum(torch.where(scored, -0.5 * (_LOG_2PI + torch.log(v) + e * q), torch.zeros((), dtype=torch.float64, device=dev)))
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+
+    def weights(Kinv):
+        s = torch.where(scored, 0.5 * (1.0 / v - q * q), torch.zeros((), dtype=torch.float64, device=dev))
+        B = eng.new_matrix(n, n)
+        B.copy_(torch.where(band, -q[:, None] * a[None, :] - 2.0 * s[:, None] * Lb, torch.zeros((), dtype=torch.float64, device=dev)))
+        abar = -torch.sum(Lb * q[:, None], dim=0)
+        Lt = eng.new_matrix(n, n)
+        Lt.copy_(torch.tril(L))
+        raw = torch.tril(eng.gemm(Lt, B, ta=True) - abar[:, None] * a[None, :])
+        S = eng.new_matrix(n, n)
+        S.copy_(raw + torch.tril(raw, -1).T)            # P + P^T (Phi halves the diagonal, the sum restores it)
+        G = eng.gemm(eng.gemm(Lt, S), Lt, tb=True)       # L (P + P^T) L^T
+        W = eng.new_matrix(n, n)
+        eng.gemm(eng.gemm(Kinv, G), Kinv, out=W, c_lower=True)
+        return W
+
+    return value, e, torch.where(scored, v, nan), scored, weights
 
 
 class _PosteriorMean(torch.autograd.Function):
@@ -752,6 +795,21 @@ class Obs:
         one fold of every row gives `logpdf`."""
         return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
 
+    def ahead(self, origin):
+        """(value, mean, var) of rolling-origin forecasts, the observations in the order given (the time order): row r is predicted from
+        rows 0 ... origin[r] - 1 (origin[r] in 0 ... r; 0: from the prior), origin[r] = -1 leaves it unscored (NaN in mean and var).  mean
+        and var are the predictive moments of the noisy observation and value = sum_scored log N(y_r; mean_r, var_r) - a 0-d tensor that
+        carries a gradient with respect to the kernel parameters and the noise where they require one (observations of a prior process).
+        All of it comes from the ONE factorisation `logpdf` computes; origin[r] = r for every row gives `logpdf`."""
+        if self.base.is_posterior:
+            raise NotImplementedError("rolling-origin forecasts are those of a prior process")
+        return self._held_out(_Origins(origin_array(origin, self.fdd.n)), "rolling-origin forecast")
+
+    def ahead_gradients(self):
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the rolling-origin value, with W = L^-T (P + P^T) L^-1,
+        P = Phi(L^T B - abar a^T) (`_ahead_algebra`)."""
+        return self._held_out_gradients()
+
     def _held_out(self, starts, what):
         """`loo` (`starts` None) and `cv`: through `_HeldOutValue` where a kernel parameter or the noise needs a gradient.  The two share
         one set of pending-gradient state on the observations (`_fused_held_out_gradients`, `_held_out_parts`): a second `loo()` or `cv()`
@@ -779,9 +837,14 @@ class Obs:
             self._held_out_mean = self._held_out_var = torch.zeros(0, dtype=torch.float64, device=dev)
             self._held_out_parts = None
             return torch.zeros((), dtype=torch.float64, device=dev)
-        call = "loo_dense" if starts is None else "cv_dense"
+        ahead = isinstance(starts, _Origins)
+        call = "ahead_dense" if ahead else "loo_dense" if starts is None else "cv_dense"
         folds = () if starts is None else (starts,)
-        fits = starts is None or int(np.diff(starts).max()) <= CV_MAX_FOLD
+        fits = starts is None or ahead or int(np.diff(starts).max()) <= CV_MAX_FOLD
+        if ahead and fits and hasattr(eng, call) and (self._fusable_grad() if want_grad else self._value_only()):
+            if starts.device is None:
+                starts.device = upload_origin(starts.origin, n, dev)
+            folds = (starts.device,)
         if want_grad and fits and hasattr(eng, call + "_grad") and self._fusable_grad():
             ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
             value, info, self._fused_held_out_gradients, (A, logdet), self._held_out_mean, self._held_out_var = getattr(eng, call + "_grad")(
@@ -794,6 +857,13 @@ class Obs:
             value, info, self._held_out_mean, self._held_out_var = getattr(eng, call)(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, *folds)
             eng.check_info(info)
             return value.detach()
+        if ahead:
+            fac = self.factor()
+            value, e, var, scored, weights = _ahead_algebra(eng, fac.L.detach(), fac.zrow.reshape(-1).detach(), starts.origin)
+            self._held_out_mean = torch.where(scored, self.y.reshape(-1).detach() - e, var)
+            self._held_out_var = var
+            self._held_out_parts = (fac, weights) if want_grad else None
+            return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
         fac = self.factor()
         low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
         Kinv = low + torch.tril(low, -1).T
@@ -813,6 +883,16 @@ class Obs:
             self._fused_held_out_gradients = None
             return fused()
         eng, n = self.eng, self.fdd.n
+        if len(self._held_out_parts) == 2:   # rolling origins: W is not of the form below; its algebra returns it whole
+            fac, weights = self._held_out_parts
+            self._held_out_parts = None
+            low = torch.tril(eng.chol_inverse(fac.L))
+            Kinv = eng.new_matrix(n, n)
+            Kinv.copy_(low + torch.tril(low, -1).T)
+            W = weights(Kinv)
+            ck, _ = self.fdd.features()
+            grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
+            return 0.5 * torch.diagonal(W).clone(), grads
         Kinv, alpha, b, fill = self._held_out_parts
         self._held_out_parts = None
         u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)

@@ -126,7 +126,10 @@ def logpdf_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
 
 
 def _folds_of(objective, fold_start, n, dev):
-    """() for "mll" and "loo"; for "cv" the (device offsets, nfolds, largest fold) triple, uploaded unless it is one already."""
+    """() for "mll" and "loo"; for "cv" the (device offsets, nfolds, largest fold) triple, uploaded unless it is one already; for "ahead"
+    the one-element tuple of the device origins (`fold_start` holds them), uploaded unless they are a device tensor already."""
+    if objective == "ahead":
+        return (fold_start if isinstance(fold_start, torch.Tensor) and fold_start.is_cuda else upload_origin(fold_start, n, dev),)
     if objective != "cv":
         return ()
     return fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
@@ -136,12 +139,14 @@ def objective_vec_doubles(lib, objective, n, grad, folds):
     """Doubles of the objective's vector workspace ("mll" has none)."""
     if objective == "mll":
         return 0
+    if objective == "ahead":
+        return int(lib.gpar_workspace_doubles(_lib.WS_AHEAD, n, grad, 0))
     return int(lib.gpar_workspace_doubles(_lib.WS_CV, n, grad, folds[2]) if objective == "cv" else lib.gpar_workspace_doubles(_lib.WS_LOO, n, grad, 0))
 
 
 def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused):
-    """One dense layer's objective ("mll", "loo" or "cv") AND its gradient ingredients in one library call (gpar_logpdf_dense_grad,
-    gpar_loo_dense_grad, gpar_cv_dense_grad): allocation and marshalling for the three.  Returns (out, vectors, info, A, W): out = [value,
+    """One dense layer's objective ("mll", "loo", "cv" or "ahead") AND its gradient ingredients in one library call (gpar_logpdf_dense_grad,
+    gpar_loo_dense_grad, gpar_cv_dense_grad, gpar_ahead_dense_grad): allocation and marshalling for the four.  Returns (out, vectors, info, A, W): out = [value,
     logdet, GRAD_NACC moment sums], vectors = 1/2 diag(W) and - but for "mll" - the held-out means and variances in its rows."""
     lib = _lib.load()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
@@ -156,8 +161,9 @@ def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, l
     nt = (n + 63) // 64
     nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
     nacc = _lib.GRAD_NACC
-    # gradient partials, alpha, the objective's vector workspace
-    work = torch.empty(nblocks * nacc + n + objective_vec_doubles(lib, objective, n, 1, folds), dtype=torch.float64, device=dev)
+    # gradient partials, alpha, the objective's vector workspace (at an even offset: "ahead" keeps a matrix in it)
+    nalpha = n + (n & 1)
+    work = torch.empty(nblocks * nacc + nalpha + objective_vec_doubles(lib, objective, n, 1, folds), dtype=torch.float64, device=dev)
     out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
     vectors = torch.empty(1 if objective == "mll" else 3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
     info = torch.empty(1, dtype=torch.int32, device=dev)
@@ -168,22 +174,39 @@ def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, l
     if objective == "mll":
         rc = lib.gpar_logpdf_dense_grad(*head, work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), *tail)
     else:
-        entry = lib.gpar_cv_dense_grad if objective == "cv" else lib.gpar_loo_dense_grad
-        rc = entry(*head, work[nblocks * nacc + n:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(),
+        entry = {"loo": lib.gpar_loo_dense_grad, "cv": lib.gpar_cv_dense_grad, "ahead": lib.gpar_ahead_dense_grad}[objective]
+        rc = entry(*head, work[nblocks * nacc + nalpha:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(),
                    vectors[1].data_ptr(), vectors[2].data_ptr(), *fold_args, *tail)
-    _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad", "cv": "gpar_cv_dense_grad"}[objective])
+    _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad", "cv": "gpar_cv_dense_grad",
+                    "ahead": "gpar_ahead_dense_grad"}[objective])
     return out, vectors, info, A, W
 
 
 def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead, fused):
-    """Value, held-out means and variances of one dense layer for "loo" or "cv" in one library call (gpar_loo_dense, gpar_cv_dense).
-    Returns (out, mean, var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+    """Value, held-out means and variances of one dense layer for "loo", "cv" or "ahead" in one library call (gpar_loo_dense, gpar_cv_dense,
+    gpar_ahead_dense).  Returns (out, mean, var, info): out = [value, logdet] (device), the n predictive means and variances (device), info
+    word."""
     lib = _lib.load()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
     folds = _folds_of(objective, fold_start, n, dev)
     fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
     z = alloc_matrix(n, max(ck.dz, 1), dev)
     A = alloc_matrix(n + 1, n + 1, dev)
+    if objective == "ahead":   # the factor and its augmented row are all the entry reads: no X, no scratch matrix
+        vec = torch.empty(objective_vec_doubles(lib, objective, n, 0, folds), dtype=torch.float64, device=dev)
+        out = torch.empty(2, dtype=torch.float64, device=dev)
+        moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(
+            lib.gpar_ahead_dense(
+                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+                None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
+                out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), *fold_args, info.data_ptr(), _potrf_flags(lookahead, fused),
+                stream_ptr(dev),
+            ),
+            "gpar_ahead_dense",
+        )
+        return out, moments[0], moments[1], info
     X = alloc_matrix(n, n, dev)
     T = alloc_matrix(n, n, dev)
     vec = torch.empty(objective_vec_doubles(lib, objective, n, 0, folds), dtype=torch.float64, device=dev)
@@ -244,6 +267,37 @@ def upload_folds(fold_start, n, device):
     if sizes.size == 0 or int(sizes.max()) > _lib.CV_MAX_FOLD:
         raise ValueError(f"the fused cross-validation takes 1 to {_lib.CV_MAX_FOLD} rows per fold")
     return torch.tensor(starts, dtype=torch.int32, device=device), int(sizes.size), int(sizes.max())
+
+
+def origin_array(origin, n):
+    """The n origins of a rolling-origin evaluation as a checked host array (int64): -1 (not scored) or 0 ... r for row r.  The one check
+    of origins: `gp.Obs.ahead` and `upload_origin` both go through it."""
+    o = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin)
+    if o.ndim != 1 or o.size != n or (o.size and not np.issubdtype(o.dtype, np.integer)):
+        raise ValueError("origin must hold one integer per row")
+    o = o.astype(np.int64)
+    if np.any(o < -1) or np.any(o > np.arange(n)):
+        raise ValueError("origin[r] must be -1 (not scored) or lie in 0 ... r")
+    return o
+
+
+def upload_origin(origin, n, device):
+    """Device int32 array of the n origins the fused rolling-origin entries take, checked by `origin_array`."""
+    return torch.tensor(origin_array(origin, n), dtype=torch.int32, device=device)
+
+
+def ahead_dense(ck, x, y, noise_diag, jitter, origin, lookahead=True, fused=True):
+    """Rolling-origin forecast value, means and variances of one dense layer in one library call (gpar_ahead_dense): row r predicted from
+    rows 0 ... origin[r] - 1, origin[r] = -1 not scored (NaN in its mean and variance).  `origin`: a host sequence of n ints or the device
+    tensor `upload_origin` returns.  Returns (out, mean, var, info): out = [value, logdet] (device), means and variances (device), info."""
+    return _dense_value("ahead", ck, x, y, noise_diag, jitter, origin, lookahead, fused)
+
+
+def ahead_dense_grad(ck, x, y, noise_diag, jitter, periodic, origin, lookahead=True, fused=True):
+    """One dense layer's rolling-origin forecast value AND its gradient ingredients in one library call (gpar_ahead_dense_grad).  `origin`
+    as for `ahead_dense`.  Returns (out, half_diag, mean, var, info, A, W), laid out as `loo_dense_grad` returns them."""
+    out, vectors, info, A, W = _dense_grad("ahead", ck, x, y, noise_diag, jitter, periodic, origin, lookahead, fused)
+    return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 
 def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=True):

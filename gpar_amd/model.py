@@ -11,6 +11,8 @@ Tensors are torch float64 on the engine's device; numpy inputs are accepted and 
 """
 import threading
 
+import collections
+
 import numpy as np
 import torch
 
@@ -211,6 +213,19 @@ def host_index(sel):
     if host is None:
         host = sel._host_index = sel.cpu().numpy()
     return host
+
+
+_Ahead = collections.namedtuple("_Ahead", "horizon start rows")
+
+
+def rolling_origins(observed, horizon, start=0):
+    """Origins of a layer's rows for `horizon`-step-ahead forecasts: `observed` holds the (ascending) indices, in the data as given, of
+    the rows the layer observes; the row with index r is predicted from the layer's rows with index <= r - horizon - origin = their
+    number - and is not scored (-1) where r < start."""
+    observed = np.asarray(observed, dtype=np.int64)
+    origin = np.searchsorted(observed, observed - int(horizon), side="right").astype(np.int64)
+    origin[observed < int(start)] = -1
+    return origin
 
 
 def contiguous_folds(labels):
@@ -653,14 +668,34 @@ class GPAR:
             raise ValueError("folds must hold one integer label per row of x")
         return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs), self.layers, (x, y, w))
 
+    # ---- rolling-origin forecast scoring --------------------------------------------------------------
+    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None):
+        """Layer-wise rolling-origin forecast scoring, the rows in the order given (the time order): layer i's inputs [x, y_<i] are built
+        as `logpdf` builds them, and its observed entry of output i at row r is predicted from the layer's observed rows with index
+        <= r - horizon - the horizon counts rows as given, so missing values make the bands ragged.  Rows with index < start are not
+        scored.  Returns (total, pieces): the sum over the visited layers of sum_r log N(y_ri; mean_r, var_r), which for a full set of
+        layers is the exact GPAR log score of the `horizon`-step-ahead forecasts (the chain rule over the outputs; it carries a gradient
+        with respect to kernel parameters and noise where they require one), and per visited layer (rows, mean, var): the rows observed
+        at output i with the predictive mean and variance of each (NaN where the row is not scored).  One factorisation per layer, the
+        one `logpdf` computes.  `outputs` as for `loo`; `rows`: the indices, in the data as given, of the rows of the x handed in
+        where earlier layers have dropped some (None: x holds every row).  Inducing points: ValueError."""
+        if self.sparse:
+            raise ValueError("rolling-origin forecast scoring needs dense observations (no inducing points)")
+        rows = None if rows is None else np.asarray(rows, dtype=np.int64)
+        return _retry_unfused(lambda: self._held_out(x, y, w, _Ahead(int(horizon), int(start), rows), outputs), self.layers, (x, y, w))
+
     def _held_out(self, x, y, w, labels, outputs):
-        """The layer loop of `loo` (`labels` None: pieces carry the per-row log-density, and nothing is kept on the host) and `cv`."""
+        """The layer loop of `loo` (`labels` None: pieces carry the per-row log-density, and nothing is kept on the host), `cv` and
+        `ahead` (`labels` an `_Ahead`: the origins of a layer are counted on the host from the rows observed there)."""
         x, y, w = self._prep(x, y, w)
         items = list(per_output(y, w, keep=self.impute))
         eng = get_engine()
-        blocked = labels is not None
+        rolling = isinstance(labels, _Ahead)
+        blocked = labels is not None and not rolling
         rows = torch.arange(int(x.shape[0]), device=x.device)
-        rows_host = np.arange(int(x.shape[0])) if blocked else None   # (the same rows on the host: the labels live there)
+        rows_host = np.arange(int(x.shape[0])) if labels is not None else None   # (the same rows on the host: the labels live there)
+        if rolling and labels.rows is not None:
+            rows_host = labels.rows
         total, pieces = torch.zeros((), dtype=torch.float64), []
         with eng.defer_checks():
             for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
@@ -677,12 +712,17 @@ class GPAR:
                     sel = ~torch.isnan(yi[:, 0])
                     seen = rows[sel]
                 perm = None
-                if blocked:
+                if labels is not None:
                     rows_host = rows_host[host_index(mask)]
-                    perm, starts = contiguous_folds(labels[rows_host if sel is None else rows_host[host_index(sel)]])
+                    observed = rows_host if sel is None else rows_host[host_index(sel)]
+                    if blocked:
+                        perm, starts = contiguous_folds(labels[observed])
                 if perm is None:
                     obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
-                    value, mean, var = obs.cv(starts) if blocked else obs.loo()
+                    if rolling:
+                        value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start))
+                    else:
+                        value, mean, var = obs.cv(starts) if blocked else obs.loo()
                 else:
                     # the evaluation's own observations, rows sorted by fold; `obs` keeps the order the next layer reads
                     at = torch.as_tensor(perm, dtype=torch.long, device=obs.y.device)
@@ -693,7 +733,7 @@ class GPAR:
                     sorted_obs.transient = True
                     value, mean, var = sorted_obs.cv(starts)
                     mean, var = torch.empty_like(mean).index_copy_(0, at, mean), torch.empty_like(var).index_copy_(0, at, var)
-                if blocked:
+                if labels is not None:
                     pieces.append((seen, mean, var))
                 else:
                     resid = obs.y.reshape(-1) - mean

@@ -215,10 +215,24 @@ def _run_on_streams(eng, streams, shares, fn, on_exit=None):
         raise errors[0]
 
 
-def _check_objective(objective, sparse, fix, folds=None):
-    """The training objectives `fit` knows, and what the cross-validation ones need."""
-    if objective not in ("mll", "loo", "cv"):
-        raise ValueError('objective must be "mll", "loo" or "cv"')
+def _check_horizon(horizon, start, n):
+    """`horizon` (an int >= 1) and `start` (an int in 0 ... n - 1) of `ahead` / `fit(objective="ahead")`."""
+    for name, v in (("horizon", horizon), ("start", start)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"{name} must be an integer")
+    if horizon < 1:
+        raise ValueError(f"horizon={horizon}: forecasts look at least one row ahead")
+    if not 0 <= start <= max(n - 1, 0):
+        raise ValueError(f"start={start}: the first scored row must lie in 0 ... {max(n - 1, 0)}")
+    return int(horizon), int(start)
+
+
+def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None):
+    """The training objectives `fit` knows, and what the held-out ones need."""
+    if objective not in ("mll", "loo", "cv", "ahead"):
+        raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
+    if objective != "ahead" and (horizon is not None or start is not None):
+        raise ValueError('horizon and start belong to objective="ahead"')
     if objective == "cv" and folds is None:
         raise ValueError('objective="cv" needs folds: a number of contiguous blocks or one integer label per row')
     if objective != "cv" and folds is not None:
@@ -339,7 +353,8 @@ class GPARRegressor:
             self.y = torch.from_numpy((y_np - means) / stds)
         self.is_conditioned = True
 
-    def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, **kw_args):
+    def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, horizon=None, start=None,
+            **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
 
@@ -347,12 +362,14 @@ class GPARRegressor:
         (`loo`; Rasmussen & Williams 5.4.2) - more robust where the kernel family is misspecified.  "loo" needs dense layers with
         fixed inputs: ValueError with inducing points, NotImplementedError with `fix=False`.  "cv" is the blocked form for ordered data
         (`cv`): whole folds are held out and scored by their joint predictive density; it needs `folds` (as `cv` takes them), which
-        no other objective accepts, and has the restrictions of "loo".
+        no other objective accepts, and has the restrictions of "loo".  "ahead" is the rolling-origin forecast score (`ahead`): every
+        row predicted from the rows at least `horizon` (default 1) rows before it, rows before `start` (default 0) not scored - for
+        models whose purpose is the forecast at that horizon; `horizon` / `start` belong to it alone; the restrictions of "loo".
 
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
-        _check_objective(objective, self.sparse, fix, folds)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -360,14 +377,16 @@ class GPARRegressor:
             raise NotImplementedError("Greedy search is not implemented yet.")
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
-        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, **kw_args)
+        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, **kw_args)
 
-    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, **kw_args):
+    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, horizon=None, start=None, **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
-        _check_objective(objective, self.sparse, fix, folds)
-        loo, cv = objective == "loo", objective == "cv"
+        _check_objective(objective, self.sparse, fix, folds, horizon, start)
+        loo, cv, ahead = objective == "loo", objective == "cv", objective == "ahead"
         labels = _fold_labels(folds, self.n) if cv else None
+        if ahead:
+            horizon, start = _check_horizon(1 if horizon is None else horizon, 0 if start is None else start, self.n)
         self._x_ind_trainable = bool(optimise_x_ind) or getattr(self, "_x_ind_trainable", False)
         layers = list(layers)
         finals = {}
@@ -390,6 +409,8 @@ class GPARRegressor:
                 )
             # (the fold labels of the rows that reach this layer: earlier layers' masks have dropped the others from fixed_x)
             layer_labels = labels[_surviving_rows(y_cached[bool(self.impute)], pi, self.n)] if cv else None
+            # (rolling origins count rows of the data as given: the indices there of the rows that reach this layer)
+            layer_rows = _surviving_rows(y_cached[bool(self.impute)], pi, self.n) if ahead else None
 
             def neg_value(vs):
                 gpar = _construct_gpar(self, vs, self.m, pi + 1)
@@ -401,6 +422,8 @@ class GPARRegressor:
                         return -gpar.loo(fixed_x, y_cached, None, outputs=[pi])[0]
                     if cv:
                         return -gpar.cv(fixed_x, y_cached, None, layer_labels, outputs=[pi])[0]
+                    if ahead:
+                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows)[0]
                     return -gpar.logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi], x_ind=x_ind_pi)
                 return -gpar.logpdf(x_dev, y_cached, None, only_last_layer=False)
 
@@ -422,7 +445,8 @@ class GPARRegressor:
                     return general[0](x)
 
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
-                                     group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv else {}))
+                                     group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv else {}),
+                                     **({"ahead": (horizon, start, layer_rows)} if ahead else {}))
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
             if fast is not None:
@@ -454,7 +478,7 @@ class GPARRegressor:
             lanes = min(len(streams), len(layers))
             shares = [layers[k::lanes] for k in range(lanes)]
             group = None
-            if prepared and not loo and not cv and lanes > 1 and all(isinstance(item[2], slice) for item in y_cached[bool(self.impute)]):
+            if prepared and not loo and not cv and not ahead and lanes > 1 and all(isinstance(item[2], slice) for item in y_cached[bool(self.impute)]):
                 # every layer goes through the prepared objective on the same number of rows: from ~1000 rows on their
                 # factorisations are taken in lock-step, one gpar_potrf_batch per round of evaluations (fastfit.LockstepFactor)
                 from . import fastfit
@@ -487,7 +511,7 @@ class GPARRegressor:
         Returns (order, values): `order[i]` is the column of y placed at position i, `values[i]` the log marginal likelihood of
         that layer after training (of the normalised outputs, as `fit` sees them).  With `objective="loo"` among the keyword arguments
         the candidates are trained on, and ranked by, the layer's leave-one-out value instead (`fit`); with `objective="cv", folds=...` by its
-        blocked cross-validation value.  The trained hyper-parameters of the chosen
+        blocked cross-validation value; with `objective="ahead", horizon=...` by its rolling-origin forecast score.  The trained hyper-parameters of the chosen
         chain are kept in `self.greedy_vs_` (layer i there belongs to output `order[i]`): `reg.vs = reg.greedy_vs_.copy();
         reg.fit(x, y[:, order], ...)` continues from them.  `self` is conditioned on (x, y, w) in the GIVEN order, as after
         `condition`."""
@@ -681,6 +705,34 @@ class GPARRegressor:
         mean = np.full((int(x.shape[0]), p), np.nan)
         var = np.full((int(x.shape[0]), p), np.nan)
         for i, (rows, mean_i, var_i, _) in enumerate(pieces):
+            rows = rows.cpu().numpy()
+            mean[rows, i], var[rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
+        value = value.detach() if any_torch else value.detach().cpu().numpy()
+        return value, mean, var
+
+    def ahead(self, x, y, w=None, horizon=1, start=0):
+        """Rolling-origin forecast scoring under the prior model (`GPAR.ahead`): `(value, mean, var)` with the conventions of `loo`.
+        The rows are taken in the order given (the time order); every observed y_rj with r >= `start` is predicted from the rows of
+        output j observed at index <= r - `horizon` (and the layer's inputs [x, y_<j] as `logpdf` builds them) - the `horizon`-step-ahead
+        forecast at every origin, from ONE factorisation per output instead of one conditioning per origin.  `value` is the sum of
+        log N(y_rj; mean_rj, var_rj) over the scored entries, which by the chain rule over the outputs is the exact GPAR log score;
+        `mean` and `var` are n x p numpy arrays of the predictive means and variances (of the noisy observation), NaN where y is missing
+        or the row is not scored.  `horizon`: an int >= 1, counting rows as given (missing values make the bands ragged); a horizon >= n
+        predicts every row from the prior.  `start`: an int in 0 ... n - 1.  Dense layers only: ValueError with inducing points."""
+        if self.sparse:
+            raise ValueError("rolling-origin forecast scoring needs dense layers: not available with inducing points (x_ind)")
+        any_torch = isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor)
+        x = _uprank(_to_engine(x))
+        y = self._unnormalise_y(self._transform_y(_uprank(_to_engine(y))))  # (as logpdf)
+        w = _init_weights(w, y)
+        m, p = x.shape[1], y.shape[1]
+        horizon, start = _check_horizon(horizon, start, int(x.shape[0]))
+        self._prepare_kernels(m, p, int(x.shape[0]))
+        with torch.no_grad():
+            value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start)
+        mean = np.full((int(x.shape[0]), p), np.nan)
+        var = np.full((int(x.shape[0]), p), np.nan)
+        for i, (rows, mean_i, var_i) in enumerate(pieces):
             rows = rows.cpu().numpy()
             mean[rows, i], var[rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
         value = value.detach() if any_torch else value.detach().cpu().numpy()

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 11
+#define GPAR_ABI_VERSION 12
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -304,6 +304,41 @@ int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* 
                   double* vec, double* out, double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info,
                   int potrf_flags, void* stream);
 
+/* Rolling-origin forecast scoring of one dense layer (ABI v12): every scored row predicted from the rows BEFORE its origin, the rows in the
+ * order handed in (the time order).  origin: a DEVICE array of n ints; origin[r] = -1: row r is not scored; otherwise 0 <= origin[r] <= r
+ * and row r is predicted from rows 0 ... origin[r] - 1 (origin[r] = 0: from the prior).  With S = k(x, x) + diag(noise_diag) + jitter I
+ * = L L^T and a = L^-1 y the factor of a leading block of S is the leading block of L, so
+ *   e_r = y_r - ahead_mean[r] = sum_{c = origin[r] .. r} L_rc a_c,   ahead_var[r] = v_r = sum_{c = origin[r] .. r} L_rc^2
+ *   out[0] = sum_scored -1/2 [log 2 pi + log v_r + e_r^2 / v_r]   (the predictive of the noisy observation, as gpar_loo_dense reports it);
+ * unscored rows carry NaN in ahead_mean and ahead_var.  origin[r] = r for every row gives the log marginal likelihood.
+ * gpar_ahead_dense_grad mirrors gpar_loo_dense_grad argument for argument (origin before info): out[1] = log det S, out[2 .. 2 +
+ * GPAR_GRAD_NACC) and half_diag as there, for the weights
+ *   W = X (P + P^T) X^T,  X = L^-T,  P = Phi(L^T B - abar a^T),  B_rc = -q_r a_c - 2 s_r L_rc (origin[r] <= c <= r),
+ *   abar_c = -sum_{r >= c, origin[r] <= c} q_r L_rc,  q_r = e_r / v_r,  s_r = 1/2 (1 / v_r - q_r^2)
+ * (Phi: the lower triangle with its diagonal halved - the reverse mode of the Cholesky factorisation).  Its launches behind the factor: X
+ * (the first half of gpar_chol_inverse), the origins' check, the row kernel, abar, the banded product P + P^T as a full matrix into W, two
+ * gpar_gemm products (X (.) into vec, then W on its lower triangle), the weighted-sum pass, the epilogue.  The banded product costs
+ * sum_j sum_{i >= j} #{r >= i: origin[r] <= j} multiply-adds on the vector units: O(n^2 H) for a horizon H, n^3 / 6 when every row is
+ * predicted from the prior.  alpha is not written.  vec: gpar_workspace_doubles(GPAR_WS_AHEAD, n, 1, 0) doubles (it holds the n x n first
+ * product: hand it over 16-byte aligned for the vectorised products).  gpar_ahead_dense_grad_finish is the second half for a factor that
+ * already exists (same bits); info and info_out are both required.  gpar_ahead_dense: value, log det, means and variances from the factor
+ * and its augmented row alone - no X, no S^-1; vec: gpar_workspace_doubles(GPAR_WS_AHEAD, n, 0, 0).
+ * info, besides the factorisation's own codes: n + 1 + r for the first row r whose origin lies outside -1 ... r; the 1-based row of a
+ * non-positive v_r.  Whenever the info word is set - by the factorisation too - out[0], out[2 ...], half_diag, ahead_mean and ahead_var
+ * keep what they held (out[1] is the factorisation's).  No atomics in any sum: a call gives the same bits every time.
+ * [no reference counterpart] */
+int gpar_ahead_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                          const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                          double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                          double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream);
+int gpar_ahead_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                 double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                                 double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                 double* ahead_mean, double* ahead_var, const int* origin, int* info_out, void* stream);
+int gpar_ahead_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                     const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                     double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream);
+
 /* The same moment sums of  sum W dK/dtheta  for the other weight shapes the inducing-point (VFE) bound needs
  * [gradient of the PseudoObs elbo, gpar/model.py:226,286-287 under varz's optimiser]:
  *   GPAR_GRAD_SYM   z2 == z1: W symmetric n1 x n1, lower triangle read, sum over all pairs (what gpar_gram_grad does);
@@ -506,6 +541,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_CHOL_INVERSE (n, ldx, -)      the X matrix of gpar_chol_inverse
  *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_CV           (n, grad, max_fold)  the `vec` of gpar_cv_dense (grad = 0) / gpar_cv_dense_grad[_finish] (grad = 1)
+ *   GPAR_WS_AHEAD        (n, grad, -)     the `vec` of gpar_ahead_dense (grad = 0) / gpar_ahead_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol
  *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading */
 #define GPAR_WS_GEMM_SPLITK 1
@@ -517,6 +553,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_CV 7
 #define GPAR_WS_PIVOTED_CHOL 8
 #define GPAR_WS_CHOL_UPDATE 9
+#define GPAR_WS_AHEAD 10
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
