@@ -3,8 +3,9 @@
 // 0 ... o_r - 1 (o_r = origin[r]; -1: the row is not scored) has
 //     e_r = y_r - mean_r = sum_{c = o_r .. r} L_rc a_c,      v_r = var_r = sum_{c = o_r .. r} L_rc^2
 // - the factor of a leading block is the leading block of the factor -, and
-//     value = sum_scored -1/2 [log 2 pi + log v_r + e_r^2 / v_r],      dvalue/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta,
-//     q_r = e_r / v_r,  s_r = 1/2 (1 / v_r - q_r^2)   (zero on unscored rows),
+//     value = sum_scored term(e_r, v_r),      dvalue/dtheta = 1/2 sum_ab W_ab dK_ab/dtheta,
+//     q_r = -dterm/de_r,  s_r = -dterm/dv_r   (zero on unscored rows; the scoring rule decides all three: score.h - for the log score
+//     term = -1/2 [log 2 pi + log v_r + e_r^2 / v_r],  q_r = e_r / v_r,  s_r = 1/2 (1 / v_r - q_r^2)),
 //     B_rc = -q_r a_c - 2 s_r L_rc  (o_r <= c <= r),      abar_c = -sum_{r >= c, o_r <= c} q_r L_rc,
 //     P = Phi(L^T B - abar a^T),      W = X (P + P^T) X^T.
 // Four launches: ahead_check_kernel (the origins' range, the smallest origin of every 32 rows), ahead_rows_kernel (e, v, q, s, the value
@@ -59,12 +60,12 @@ __global__ __launch_bounds__(256) void ahead_check_kernel(const int* __restrict_
     }
 }
 
-// One wave per row: lanes stride the row of L from o_r to r, two wave sums.  q, s null: the value-only form.  A non-positive v_r: the
-// 1-based row into info, nothing written for it.
+// One wave per row: lanes stride the row of L from o_r to r, two wave sums; the scoring rule `rule` turns (e_r, v_r) into the value term,
+// q_r and s_r (score_row).  q, s null: the value-only form.  A non-positive v_r: the 1-based row into info, nothing written for it.
 __global__ __launch_bounds__(256) void ahead_rows_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ a,
                                                          const double* __restrict__ y, long incy, const int* __restrict__ origin,
                                                          double* __restrict__ mean, double* __restrict__ var, double* __restrict__ q,
-                                                         double* __restrict__ s, double* __restrict__ term, int* __restrict__ info) {
+                                                         double* __restrict__ s, double* __restrict__ term, int rule, int* __restrict__ info) {
     if (info[0] != 0) return;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -93,13 +94,14 @@ __global__ __launch_bounds__(256) void ahead_rows_kernel(const double* __restric
         atomicCAS(info, 0, row + 1);
         return;
     }
-    const double qr = e / v;
+    double tr, qr, sr;
+    score_row(rule, e, v, tr, qr, sr);
     mean[row] = y[(size_t)row * incy] - e;
     var[row] = v;
-    term[row] = -0.5 * (1.8378770664093453 + log(v) + e * qr);
+    term[row] = tr;
     if (q) {
         q[row] = qr;
-        s[row] = 0.5 * (1.0 / v - qr * qr);
+        s[row] = sr;
     }
 }
 
@@ -213,21 +215,21 @@ __global__ __launch_bounds__(256) void ahead_grad_epilogue_kernel(const double* 
 
 // check + rows: everything of the value-only form behind the factor, the head of the weight stage.  q, s, cmin null: value only.
 static void ahead_rows_run(const double* A, int lda, int n, const double* y, long incy, const int* origin, double* mean, double* var, double* q,
-                           double* s, double* term, int* cmin, int* info, hipStream_t st) {
+                           double* s, double* term, int* cmin, int rule, int* info, hipStream_t st) {
     hipLaunchKernelGGL(ahead_check_kernel, dim3(1), dim3(256), 0, st, origin, n, cmin, info);
     hipLaunchKernelGGL(ahead_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, A, lda, n, A + (size_t)n * lda, y, incy, origin, mean, var,
-                       q, s, term, info);
+                       q, s, term, rule, info);
 }
 
 // The weight stage of the gradient forms: W <- X (P + P^T) X^T on its lower triangle (X = L^-T in its upper triangle, whatever lies below
 // its diagonal blocks unread: both products start their K range at the tile's first row).
 static int ahead_weights_run(const double* A, int lda, int n, const double* y, long incy, const int* origin, double* mean, double* var, double* vec,
-                             const double* X, int ldx, double* W, int ldw, int* info, hipStream_t st) {
+                             const double* X, int ldx, double* W, int ldw, int rule, int* info, hipStream_t st) {
     double *q = vec, *s = vec + n, *term = vec + 2 * (size_t)n, *abar = vec + 3 * (size_t)n, *T = vec + ah_off_t(n);
     int* cmin = reinterpret_cast<int*>(vec + 4 * (size_t)n);
     const int ldt = ah_ldt(n), nt = gpar_ceil_div(n, AH_T);
     const double* a = A + (size_t)n * lda;
-    ahead_rows_run(A, lda, n, y, incy, origin, mean, var, q, s, term, cmin, info, st);
+    ahead_rows_run(A, lda, n, y, incy, origin, mean, var, q, s, term, cmin, rule, info, st);
     hipLaunchKernelGGL(ahead_abar_kernel, dim3((unsigned)nt), dim3(256), 0, st, A, lda, n, (const double*)q, origin, abar, (const int*)info);
     hipLaunchKernelGGL(ahead_band_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(256), 0, st, A, lda, n, a, (const double*)q, (const double*)s,
                        (const double*)abar, origin, (const int*)cmin, W, ldw, (const int*)info);

@@ -13,6 +13,7 @@
 #include "blas1.h"
 #include "pivchol.h"
 #include "chol_update.h"
+#include "score.h"   // the scoring rules of the held-out objectives
 
 namespace gpar {
 
@@ -878,34 +879,47 @@ __global__ __launch_bounds__(256) void dense_grad_epilogue_kernel(const double* 
 // - the shape of weights the weighted-sum pass of the marginal likelihood consumes.  Behind the inverse an evaluation adds three
 // launches to that one's chain (rows, {u, S}, the rank-2 term; the product S S^T takes the place of the rank-1 update).
 // `vec`: the four n-vectors b, sqrt c, value terms, u (gpar_workspace_doubles(GPAR_WS_LOO, n, 1, 0)).
-__device__ __forceinline__ void loo_row_write(int i, double a, double d, double yi, double* __restrict__ mean, double* __restrict__ var,
+// Under another scoring rule (ABI v13; score.h) the chain is the same with, for e_i = alpha_i / d_i, v_i = 1 / d_i and the rule's q, s:
+//     b_i = q_i v_i,   c_i = q_i e_i v_i + s_i v_i^2      (the log score: b = e, c = 1/2 (v + e^2), written as above - the same bits)
+// - c > 0 for the CRPS (sd^3 times a bracket that is 0.117 at z = 0 and grows with |z|), c = 2 e^2 v >= 0 for the squared error - and the
+// value is the sum of the rule's terms (the log score keeps its -n/2 log 2 pi in the epilogue: `loo_half_n_log_2pi`).
+__device__ __forceinline__ void loo_row_write(int i, double a, double d, double yi, int rule, double* __restrict__ mean, double* __restrict__ var,
                                               double* __restrict__ bvec, double* __restrict__ sc, double* __restrict__ term) {
-    const double v = 1.0 / d, b = a / d;
+    const double v = 1.0 / d, b = a / d;   // (b = e, the held-out error, under every rule)
     mean[i] = yi - b;
     var[i] = v;
-    term[i] = 0.5 * log(d) - 0.5 * (a * b);
-    if (bvec) bvec[i] = b;
-    if (sc) sc[i] = sqrt(0.5 * (v + b * b));
+    if (rule == GPAR_SCORE_LOG) {
+        term[i] = 0.5 * log(d) - 0.5 * (a * b);
+        if (bvec) bvec[i] = b;
+        if (sc) sc[i] = sqrt(0.5 * (v + b * b));
+        return;
+    }
+    double tr, q, s;
+    score_row(rule, b, v, tr, q, s);
+    term[i] = tr;
+    if (bvec) bvec[i] = q * v;
+    if (sc) sc[i] = sqrt(q * b * v + s * (v * v));
 }
+static double loo_half_n_log_2pi(int rule, int n) { return rule == GPAR_SCORE_LOG ? 0.5 * (double)n * 1.8378770664093453 : 0.0; }
 
 // one wave per row: alpha_i as trmv_upper_kernel forms it (same bits), then the row's leave-one-out quantities from Kinv_ii
 __global__ __launch_bounds__(256) void loo_rows_kernel(const double* __restrict__ X, int n, int ldx, const double* __restrict__ zrow,
                                                        const double* __restrict__ Kinv, int ldk, const double* __restrict__ y, long incy,
                                                        double* __restrict__ alpha, double* __restrict__ mean, double* __restrict__ var,
-                                                       double* __restrict__ vec) {
+                                                       double* __restrict__ vec, int rule) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
     const double a = trmv_upper_row(X, n, ldx, zrow, 1, row, lane);
     if (lane != 0) return;
     alpha[row] = a;
-    loo_row_write(row, a, Kinv[(size_t)row * ldk + row], y[(size_t)row * incy], mean, var, vec, vec + n, vec + 2 * (size_t)n);
+    loo_row_write(row, a, Kinv[(size_t)row * ldk + row], y[(size_t)row * incy], rule, mean, var, vec, vec + n, vec + 2 * (size_t)n);
 }
 
 // the value-only form: alpha_i = sum_j X_ij z_j and d_i = sum_j X_ij^2 over the upper-triangular row i of X = L^-T in one pass
 __global__ __launch_bounds__(256) void loo_rows_from_x_kernel(const double* __restrict__ X, int n, int ldx, const double* __restrict__ zrow,
                                                               const double* __restrict__ y, long incy, double* __restrict__ mean,
-                                                              double* __restrict__ var, double* __restrict__ term) {
+                                                              double* __restrict__ var, double* __restrict__ term, int rule) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
@@ -919,7 +933,7 @@ __global__ __launch_bounds__(256) void loo_rows_from_x_kernel(const double* __re
     }
     if (j < n) { const double x0 = Xr[j]; a0 = fma(x0, zrow[j], a0); d0 = fma(x0, x0, d0); }
     const double a = wave_sum(a0 + a1), d = wave_sum(d0 + d1);
-    if (lane == 0) loo_row_write(row, a, d, y[(size_t)row * incy], mean, var, nullptr, nullptr, term);
+    if (lane == 0) loo_row_write(row, a, d, y[(size_t)row * incy], rule, mean, var, nullptr, nullptr, term);
 }
 
 // u = P b for a symmetric P stored in its lower triangle: one wave per row (its row up to the diagonal, its column below it), a fixed
@@ -1211,6 +1225,7 @@ struct DenseObjective {
     double *vec, *mean, *var;   // OBJ_LOO, OBJ_CV: the vector workspace, held-out means and variances
     CvFolds folds;              // OBJ_CV
     const int* origin;          // OBJ_AHEAD: n origins (device)
+    int score;                  // OBJ_LOO, OBJ_AHEAD: the scoring rule (GPAR_SCORE_LOG = 0: what an entry without one scores by)
 };
 
 // What gpar_logpdf_dense does up to the factor: features (+ their frequency derivatives when zd is given; the value-only forms pass null)
@@ -1254,7 +1269,7 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
         case OBJ_LOO: {   // `vec`: b, sqrt c, value terms, u
             term = ob.vec + 2 * (size_t)n, u = ob.vec + 3 * (size_t)n;
             hipLaunchKernelGGL(loo_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw, zrow, (const double*)W, ldw,
-                               ob.y, ob.incy, alpha, ob.mean, ob.var, ob.vec);
+                               ob.y, ob.incy, alpha, ob.mean, ob.var, ob.vec, ob.score);
             const int nt = gpar_ceil_div(n, LOO_T);
             hipLaunchKernelGGL(loo_weights_kernel, dim3((unsigned)(nt * nt + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n,
                                (const double*)bvec, (const double*)(ob.vec + n), u, X, ldxw);
@@ -1273,7 +1288,7 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
         }
         case OBJ_AHEAD:   // `vec`: q, s, value terms, abar, chunk origins, the first product;  W = X (P + P^T) X^T whole (no rank-2 tail)
             term = ob.vec + 2 * (size_t)n;
-            rc = ahead_weights_run(A, lda, n, ob.y, ob.incy, ob.origin, ob.mean, ob.var, ob.vec, X, ldxw, W, ldw, info, st);
+            rc = ahead_weights_run(A, lda, n, ob.y, ob.incy, ob.origin, ob.mean, ob.var, ob.vec, X, ldxw, W, ldw, ob.score, info, st);
             break;
     }
     if (ob.kind == OBJ_LOO || ob.kind == OBJ_CV) {   // u and S (in X: alpha exists, L^-T is no longer needed) are formed: W <- -2 S S^T + alpha u^T + u alpha^T
@@ -1293,7 +1308,7 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
                            half_diag, (const double*)term, (const int*)info);
     else
         hipLaunchKernelGGL(loo_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
-                           half_diag, (const double*)term, 0.5 * n_log_2pi);
+                           half_diag, (const double*)term, ob.kind == OBJ_LOO ? loo_half_n_log_2pi(ob.score, n) : 0.5 * n_log_2pi);
     GPAR_LAUNCH_CHECK();
     return 0;
 }
@@ -1334,15 +1349,18 @@ int gpar_logpdf_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks
                                  nblocks, out, half_diag, stream, true);
 }
 
-int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                        const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
-                        double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
-                        double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+// (ABI v13: the entries that take a scoring rule do the work; the entries without one forward with GPAR_SCORE_LOG.  An unknown rule is an
+// argument error before anything is launched.)
+int gpar_loo_dense_grad_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                              const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                              double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                              double* loo_mean, double* loo_var, int score, int* info, int potrf_flags, void* stream) {
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var || !info ||
         n <= 0 || nblocks <= 0)
         return GPAR_ARG_ERROR(1);
-    const DenseObjective ob{OBJ_LOO, y, incy, vec, loo_mean, loo_var};
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
+    const DenseObjective ob{OBJ_LOO, y, incy, vec, loo_mean, loo_var, {}, nullptr, score};
     const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
                                     (hipStream_t)stream);
     if (rc) return rc;
@@ -1350,36 +1368,61 @@ int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const do
                                  stream, false);
 }
 
-int gpar_loo_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                               double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
-                               double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
-                               double* loo_mean, double* loo_var, int* info_out, void* stream) {
+int gpar_loo_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                        const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                        double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                        double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+    return gpar_loo_dense_grad_score(fs, ks, x, n, ldx, y, incy, noise_diag, jitter, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace, nblocks,
+                                     out, half_diag, loo_mean, loo_var, GPAR_SCORE_LOG, info, potrf_flags, stream);
+}
+
+int gpar_loo_dense_grad_finish_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                     double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X,
+                                     int ldxw, double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out,
+                                     double* half_diag, double* loo_mean, double* loo_var, int score, int* info_out, void* stream) {
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !logdet || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !loo_mean || !loo_var ||
         n <= 0 || nblocks <= 0)
         return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
     const int rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
     if (rc) return rc;
-    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_LOO, y, incy, vec, loo_mean, loo_var}, z, zd, ldz, A, lda, logdet, info_out, X,
-                                 ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream, true);
+    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_LOO, y, incy, vec, loo_mean, loo_var, {}, nullptr, score}, z, zd, ldz, A, lda,
+                                 logdet, info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream, true);
+}
+
+int gpar_loo_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                               double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                               double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                               double* loo_mean, double* loo_var, int* info_out, void* stream) {
+    return gpar_loo_dense_grad_finish_score(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, logdet, info, X, ldxw, W, ldw, alpha, vec, workspace,
+                                            nblocks, out, half_diag, loo_mean, loo_var, GPAR_SCORE_LOG, info_out, stream);
 }
 
 // Value, means and variances alone: no K^-1 is formed - alpha = X (L^-1 y) and d = the squared row norms of X = L^-T come out of one pass
 // over X (n^3 / 3 flops for X instead of the inverse's 2 n^3 / 3)
-int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
-                   double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+int gpar_loo_dense_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                         const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                         double* vec, double* out, double* loo_mean, double* loo_var, int score, int* info, int potrf_flags, void* stream) {
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !loo_mean || !loo_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
     hipStream_t st = (hipStream_t)stream;
     int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
     if (!rc) rc = trinv_upper_run(A, n, lda, X, ldxw, T, ldt, st);
     if (rc) return rc;
     hipLaunchKernelGGL(loo_rows_from_x_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)X, n, ldxw,
-                       (const double*)(A + (size_t)n * lda), y, incy, loo_mean, loo_var, vec);
-    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
+                       (const double*)(A + (size_t)n * lda), y, incy, loo_mean, loo_var, vec, score);
+    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, loo_half_n_log_2pi(score, n), out);
     GPAR_LAUNCH_CHECK();
     return 0;
+}
+
+int gpar_loo_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                   double* vec, double* out, double* loo_mean, double* loo_var, int* info, int potrf_flags, void* stream) {
+    return gpar_loo_dense_score(fs, ks, x, n, ldx, y, incy, noise_diag, jitter, z, ldz, A, lda, X, ldxw, T, ldt, vec, out, loo_mean, loo_var,
+                                GPAR_SCORE_LOG, info, potrf_flags, stream);
 }
 
 int gpar_cv_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
@@ -1436,15 +1479,16 @@ int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* 
 }
 
 // ---- rolling-origin forecast scoring (ABI v12; ahead.h) ----------------------------------------------------------------------------------
-int gpar_ahead_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                          const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
-                          double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
-                          double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream) {
+int gpar_ahead_dense_grad_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                                double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                double* ahead_mean, double* ahead_var, const int* origin, int score, int* info, int potrf_flags, void* stream) {
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !ahead_mean || !ahead_var ||
         !origin || !info || n <= 0 || nblocks <= 0)
         return GPAR_ARG_ERROR(1);
-    const DenseObjective ob{OBJ_AHEAD, y, incy, vec, ahead_mean, ahead_var, {}, origin};
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
+    const DenseObjective ob{OBJ_AHEAD, y, incy, vec, ahead_mean, ahead_var, {}, origin, score};
     const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
                                     (hipStream_t)stream);
     if (rc) return rc;
@@ -1452,34 +1496,60 @@ int gpar_ahead_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const 
                                  stream, false);
 }
 
+int gpar_ahead_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                          const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                          double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                          double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream) {
+    return gpar_ahead_dense_grad_score(fs, ks, x, n, ldx, y, incy, noise_diag, jitter, z, zd, ldz, A, lda, X, ldxw, W, ldw, alpha, vec, workspace,
+                                       nblocks, out, half_diag, ahead_mean, ahead_var, origin, GPAR_SCORE_LOG, info, potrf_flags, stream);
+}
+
 // (both info words are required, as for the blocked form: the kernels of the weight stage read and report into info_out)
-int gpar_ahead_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                                 double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
-                                 double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
-                                 double* ahead_mean, double* ahead_var, const int* origin, int* info_out, void* stream) {
+int gpar_ahead_dense_grad_finish_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                       double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X,
+                                       int ldxw, double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out,
+                                       double* half_diag, double* ahead_mean, double* ahead_var, const int* origin, int score, int* info_out,
+                                       void* stream) {
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !logdet || !info || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !ahead_mean ||
         !ahead_var || !origin || !info_out || n <= 0 || nblocks <= 0)
         return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
     const int rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
     if (rc) return rc;
-    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_AHEAD, y, incy, vec, ahead_mean, ahead_var, {}, origin}, z, zd, ldz, A, lda, logdet,
-                                 info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream, true);
+    return dense_grad_finish_run(fs, ks, x, n, ldx, DenseObjective{OBJ_AHEAD, y, incy, vec, ahead_mean, ahead_var, {}, origin, score}, z, zd, ldz, A, lda,
+                                 logdet, info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag, stream, true);
+}
+
+int gpar_ahead_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                 double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                                 double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                 double* ahead_mean, double* ahead_var, const int* origin, int* info_out, void* stream) {
+    return gpar_ahead_dense_grad_finish_score(fs, ks, x, n, ldx, y, incy, z, zd, ldz, A, lda, logdet, info, X, ldxw, W, ldw, alpha, vec, workspace,
+                                              nblocks, out, half_diag, ahead_mean, ahead_var, origin, GPAR_SCORE_LOG, info_out, stream);
 }
 
 // Value, means and variances alone: the factor and its augmented row are all it reads - no X, no K^-1
-int gpar_ahead_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
-                     const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
-                     double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream) {
+int gpar_ahead_dense_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                           double* ahead_mean, double* ahead_var, const int* origin, int score, int* info, int potrf_flags, void* stream) {
     GPAR_API_GUARD;
     if (!fs || !ks || !x || !y || !z || !A || !vec || !out || !ahead_mean || !ahead_var || !origin || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
     hipStream_t st = (hipStream_t)stream;
     const int rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
     if (rc) return rc;
-    ahead_rows_run(A, lda, n, y, incy, origin, ahead_mean, ahead_var, nullptr, nullptr, vec, nullptr, info, st);
+    ahead_rows_run(A, lda, n, y, incy, origin, ahead_mean, ahead_var, nullptr, nullptr, vec, nullptr, score, info, st);
     hipLaunchKernelGGL(ahead_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, out, (const int*)info);
     GPAR_LAUNCH_CHECK();
     return 0;
+}
+
+int gpar_ahead_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                     const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                     double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream) {
+    return gpar_ahead_dense_score(fs, ks, x, n, ldx, y, incy, noise_diag, jitter, z, ldz, A, lda, vec, out, ahead_mean, ahead_var, origin,
+                                  GPAR_SCORE_LOG, info, potrf_flags, stream);
 }
 
 int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int ldz1, const double* z2, int n2, int ldz2, int dz,

@@ -262,17 +262,17 @@ class HipEngine:
         out, half_diag, info, A = hip.logpdf_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2])
 
-    def loo_dense(self, ck, x, y, noise_diag, jitter):
+    def loo_dense(self, ck, x, y, noise_diag, jitter, score="log"):
         """One dense layer's leave-one-out value, predictive means and variances in one library call: (value as a 0-d device
-        tensor, info word, means, variances)."""
-        out, mean, var, info = hip.loo_dense(ck, self._mat(x), y, noise_diag, jitter, **self._factor_flags())
+        tensor, info word, means, variances).  `score`: the scoring rule ("log", "crps", "se")."""
+        out, mean, var, info = hip.loo_dense(ck, self._mat(x), y, noise_diag, jitter, score=score, **self._factor_flags())
         return out[0], info, mean, var
 
-    def loo_dense_grad(self, ck, x, y, noise_diag, jitter):
+    def loo_dense_grad(self, ck, x, y, noise_diag, jitter, score="log"):
         """The leave-one-out counterpart of `logpdf_dense_grad`, same conventions: (value, info word, a function returning (1/2 diag(W)
         on the device, kernel-parameter gradients), (factor buffer, log-determinant word)), then the predictive means and variances."""
         out, half_diag, mean, var, info, A, _ = hip.loo_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
-                                                                   **self._factor_flags())
+                                                                   score=score, **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
     def cv_dense(self, ck, x, y, noise_diag, jitter, fold_start):
@@ -288,16 +288,16 @@ class HipEngine:
                                                                   **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
-    def ahead_dense(self, ck, x, y, noise_diag, jitter, origin):
+    def ahead_dense(self, ck, x, y, noise_diag, jitter, origin, score="log"):
         """One dense layer's rolling-origin forecast value, predictive means and variances in one library call, row r predicted from rows
         0 ... origin[r] - 1 (-1: not scored, NaN in its mean and variance): (value as a 0-d device tensor, info word, means, variances)."""
-        out, mean, var, info = hip.ahead_dense(ck, self._mat(x), y, noise_diag, jitter, origin, **self._factor_flags())
+        out, mean, var, info = hip.ahead_dense(ck, self._mat(x), y, noise_diag, jitter, origin, score=score, **self._factor_flags())
         return out[0], info, mean, var
 
-    def ahead_dense_grad(self, ck, x, y, noise_diag, jitter, origin):
+    def ahead_dense_grad(self, ck, x, y, noise_diag, jitter, origin, score="log"):
         """The rolling-origin counterpart of `loo_dense_grad`, same conventions and return values."""
         out, half_diag, mean, var, info, A, _ = hip.ahead_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), origin,
-                                                                     **self._factor_flags())
+                                                                     score=score, **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
     def logpdf_lockstep(self, layers, x, y, w, jitter):

@@ -265,14 +265,18 @@ class DenseLayerObjective:
     """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or, with `objective="loo"`, minus the leave-one-out predictive
     log-density under the same covariance (gpar_loo_dense_grad), or, with `objective="cv"`, minus the blocked cross-validation value
     over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad), or, with `objective="ahead"`, minus the
-    rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad) - and its gradient with respect to
+    rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad); `score` ("log", "crps", "se") is the rule "loo"
+    and "ahead" score their held-out entries by (the *_score forms of their library calls) - and its gradient with respect to
     the latent (unconstrained) variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are
     device tensors that do not change during the optimisation."""
 
     def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
-                 fold_start=None, origin=None):
+                 fold_start=None, origin=None, score="log"):
         if objective not in ("mll", "loo", "cv", "ahead"):
             raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
+        self.score = hip.score_code(score)
+        if score != "log" and objective not in ("loo", "ahead"):
+            raise ValueError('score belongs to objective="loo" and "ahead"')
         if (objective == "cv") != (fold_start is not None):
             raise ValueError('fold_start belongs to objective="cv"')
         if (objective == "ahead") != (origin is not None):
@@ -371,9 +375,11 @@ class DenseLayerObjective:
                 p["W"], p["ldw"], p["alpha"])
         tail = (p["info"], self.flags, stream.cuda_stream)
         if self.objective != "mll":
-            name = {"loo": "gpar_loo_dense_grad", "cv": "gpar_cv_dense_grad", "ahead": "gpar_ahead_dense_grad"}[self.objective]
+            name = {"loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad", "ahead": "gpar_ahead_dense_grad_score"}[self.objective]
             fold_args = (self.folds[0].data_ptr(), *self.folds[1:]) if self.folds else ()
-            rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *tail)
+            rule = () if self.objective == "cv" else (self.score,)   # (the blocked form scores a fold's joint density: no rule to take)
+            rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *rule,
+                                         *tail)
             _lib.check(rc, name)
         elif self.group is None:
             rc = self.lib.gpar_logpdf_dense_grad(*head, p["work"], self.nblocks, p["out"], p["half"], *tail)
@@ -490,14 +496,15 @@ class DenseLayerObjective:
         return val
 
 
-def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None, ahead=None):
+def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None, ahead=None,
+          score="log"):
     """The fast objective of layer `pi` of regressor `reg` with fixed design matrix `fixed_x`, or None when this route does not
     apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised;
     `objective`: "mll" (log marginal likelihood), "loo" (leave-one-out predictive log-density) or "cv" (blocked cross-validation over
     `folds`, one integer label per row of `fixed_x`: the layer's rows are sorted by label here, once; None when its largest fold
     exceeds what the library call takes - the general route trains it) or "ahead" (rolling-origin forecast score; `ahead` = (horizon,
     start, the indices in the data as given of the rows of `fixed_x`): the layer's origins are counted here, once, from the rows that
-    survive)."""
+    survive); `score`: the scoring rule of "loo" and "ahead"."""
     from .gp import one_call_grad_rows
     from .model import contiguous_folds, host_index, rolling_origins
     from .regression import _model_generator
@@ -556,4 +563,4 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
         group = None
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
                lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}),
-               **({} if origin is None else {"origin": origin}))
+               **({} if origin is None else {"origin": origin}), **({} if score == "log" else {"score": score}))

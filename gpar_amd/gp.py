@@ -294,16 +294,16 @@ class _HeldOutValue(torch.autograd.Function):
     """A cross-validation value of dense observations of a prior process as a differentiable function of the kernel parameters and the
     noise vector: with `starts` None the leave-one-out predictive log-density sum_i log N(y_i; mean_-i, var_-i) (Rasmussen & Williams
     5.4.2), otherwise the blocked value sum_F log N(y_F; mean_-F, cov_-F) over the contiguous folds F with those row offsets.  Forward:
-    `Obs._held_out_eval`.  Backward: the same weighted-sum pass as `_LogMarginal`, on other weights - d/dtheta = 1/2 sum_ab W_ab
+    `Obs._held_out_eval`; `score` is the rule the held-out entries are scored by (`_score_rows`).  Backward: the same weighted-sum pass as `_LogMarginal`, on other weights - d/dtheta = 1/2 sum_ab W_ab
     dK_ab/dtheta with W = alpha u^T + u alpha^T - 2 K^-1 C K^-1, C diagonal or block-diagonal (`Obs._held_out_gradients`).  The inputs are
     not differentiated."""
 
     @staticmethod
-    def forward(ctx, obs, starts, noise, *tensors):
+    def forward(ctx, obs, starts, score, noise, *tensors):
         ctx.obs = obs
         ctx.noise_shape = None if noise is None else tuple(noise.shape)
         ctx.shapes = [tuple(t.shape) for t in tensors]
-        return obs._held_out_eval(starts, want_grad=True)
+        return obs._held_out_eval(starts, want_grad=True, score=score)
 
     @staticmethod
     def backward(ctx, g):
@@ -313,7 +313,34 @@ class _HeldOutValue(torch.autograd.Function):
         out_noise = None
         if ctx.noise_shape is not None:
             out_noise = _shaped_noise_grad(noise_grad * gval, ctx.noise_shape, obs._noise_device)
-        return (None, None, out_noise, *_param_grads(obs._params, ctx.shapes, grads, gval))
+        return (None, None, None, out_noise, *_param_grads(obs._params, ctx.shapes, grads, gval))
+
+
+SCORES = ("log", "crps", "se")
+
+
+def check_score(score):
+    """The scoring rules of `loo` and `ahead`: "log" (the Gaussian log density), "crps" (minus the continuous ranked probability score)
+    and "se" (minus the squared error); every value is one to maximise."""
+    if score not in SCORES:
+        raise ValueError('score must be "log", "crps" or "se"')
+    return score
+
+
+def _score_rows(score, e, v):
+    """(term, q, s) of held-out entries with errors e = y - mean and variances v under a scoring rule: what an entry adds to the value,
+    q = -dterm/de and s = -dterm/dv, the two sensitivities the gradient chains of `loo` and `ahead` run on (csrc/score.h has the
+    table).  With z = e / sqrt v: the CRPS of a Gaussian is sqrt v [z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt pi] (Gneiting & Raftery 2007)."""
+    if score == "crps":
+        sd = torch.sqrt(v)
+        z = e / sd
+        two_pdf = math.sqrt(2.0 / math.pi) * torch.exp(-0.5 * (z * z))
+        q = torch.erf(z * math.sqrt(0.5))
+        return -sd * (z * q + (two_pdf - 1.0 / math.sqrt(math.pi))), q, (two_pdf - 1.0 / math.sqrt(math.pi)) / (2.0 * sd)
+    if score == "se":
+        return -(e * e), 2.0 * e, torch.zeros_like(e)
+    q = e / v
+    return -0.5 * (_LOG_2PI + torch.log(v) + e * q), q, 0.5 * (1.0 / v - q * q)
 
 
 def _fold_groups(starts, device):
@@ -323,17 +350,28 @@ def _fold_groups(starts, device):
             for m in np.unique(sizes)]
 
 
-# The block algebra of the two cross-validation values from K^-1 and alpha, where no library call takes the evaluation: (value without
-# its -n/2 log 2 pi, b, variances, a function filling S with K^-1 R for the gradient's product S S^T = K^-1 C K^-1, C = R R^T).
-def _loo_algebra(Kinv, alpha):
-    """Leave-one-out: the diagonal, in closed form.  b = alpha / d, C = diag(1/2 (1 / d + b^2))."""
+# The block algebra of the two cross-validation values from K^-1 and alpha, where no library call takes the evaluation: (value - under
+# the log score without its -n/2 log 2 pi -, the errors y - mean, b, variances, a function filling S with K^-1 R for the gradient's
+# product S S^T = K^-1 C K^-1, C = R R^T).
+def _loo_algebra(Kinv, alpha, score="log"):
+    """Leave-one-out: the diagonal, in closed form.  With e = alpha / d, v = 1 / d and the rule's (q, s): b = q v, C = diag(q e v + s v^2);
+    under the log score b = e, C = diag(1/2 (v + e^2))."""
     d = torch.diagonal(Kinv)
-    b = alpha / d
+    e = alpha / d
+    if score == "log":
+        b = e
+
+        def fill(S):
+            S.copy_(Kinv * torch.sqrt(0.5 * (1.0 / d + b * b))[None, :])
+
+        return torch.sum(0.5 * torch.log(d) - 0.5 * alpha * b), e, b, 1.0 / d, fill
+    v = 1.0 / d
+    term, q, s = _score_rows(score, e, v)
 
     def fill(S):
-        S.copy_(Kinv * torch.sqrt(0.5 * (1.0 / d + b * b))[None, :])
+        S.copy_(Kinv * torch.sqrt(q * e * v + s * (v * v))[None, :])
 
-    return torch.sum(0.5 * torch.log(d) - 0.5 * alpha * b), b, 1.0 / d, fill
+    return torch.sum(term), e, q * v, v, fill
 
 
 def _cv_algebra(eng, Kinv, alpha, starts):
@@ -359,7 +397,7 @@ def _cv_algebra(eng, Kinv, alpha, starts):
             cols = torch.matmul(Kinv[:, idx].permute(1, 0, 2), R)   # k x n x m
             S[:, idx.reshape(-1)] = cols.permute(1, 0, 2).reshape(n, -1)
 
-    return value, b, var, fill
+    return value, b, b, var, fill
 
 
 class _Origins:
@@ -370,10 +408,11 @@ class _Origins:
         self.device = None     # the uploaded copy, made at the first fused call
 
 
-def _ahead_algebra(eng, L, a, origin):
+def _ahead_algebra(eng, L, a, origin, score="log"):
     """Rolling-origin forecasts from the factor L and a = L^-1 y, where no library call takes the evaluation: (value, e = y - mean, v with
     NaN on unscored rows, a function returning the weights W on their lower triangle from K^-1).  Row r is predicted from rows
-    0 ... origin[r] - 1: e_r = sum_{c = origin[r] .. r} L_rc a_c, v_r = sum L_rc^2.  The weights follow the reverse mode of the Cholesky
+    0 ... origin[r] - 1: e_r = sum_{c = origin[r] .. r} L_rc a_c, v_r = sum L_rc^2; `score` turns (e_r, v_r) into the value term and
+    the sensitivities q_r, s_r (`_score_rows`).  The weights follow the reverse mode of the Cholesky
     factorisation: W = L^-T (P + P^T) L^-1 = K^-1 [L (P + P^T) L^T] K^-1, P = Phi(L^T B - abar a^T), in products both engines have."""
     n, dev = a.numel(), a.device
     o = torch.as_tensor(origin, device=dev)
@@ -383,12 +422,12 @@ def _ahead_algebra(eng, L, a, origin):
     Lb = torch.where(band, torch.tril(L), torch.zeros((), dtype=torch.float64, device=dev))
     e = torch.sum(Lb * a[None, :], dim=1)
     v = torch.where(scored, torch.sum(Lb * Lb, dim=1), torch.ones((), dtype=torch.float64, device=dev))
-    q = e / v
-    value = torch.sum(torch.where(scored, -0.5 * (_LOG_2PI + torch.log(v) + e * q), torch.zeros((), dtype=torch.float64, device=dev)))
+    term, q, s_rows = _score_rows(score, e, v)
+    value = torch.sum(torch.where(scored, term, torch.zeros((), dtype=torch.float64, device=dev)))
     nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
 
     def weights(Kinv):
-        s = torch.where(scored, 0.5 * (1.0 / v - q * q), torch.zeros((), dtype=torch.float64, device=dev))
+        s = torch.where(scored, s_rows, torch.zeros((), dtype=torch.float64, device=dev))
         B = eng.new_matrix(n, n)
         B.copy_(torch.where(band, -q[:, None] * a[None, :] - 2.0 * s[:, None] * Lb, torch.zeros((), dtype=torch.float64, device=dev)))
         abar = -torch.sum(Lb * q[:, None], dim=0)
@@ -779,12 +818,14 @@ class Obs:
         return 0.5 * torch.diagonal(W).clone(), grads
 
     # ---- leave-one-out and blocked cross-validation ----------------------------------------------------------
-    def loo(self):
+    def loo(self, score="log"):
         """(value, mean, var): the leave-one-out predictive means and variances of the observations - of y_i given all the others,
         mean_-i = y_i - alpha_i / d_i and var_-i = 1 / d_i with alpha = S^-1 (y - m), d = diag S^-1, S = cov(f(X)) + D + eps I - and
         value = sum_i log N(y_i; mean_-i, var_-i), a 0-d tensor that carries a gradient with respect to the kernel parameters and the
-        noise where they require one (observations of a prior process; Rasmussen & Williams 5.4.2)."""
-        return self._held_out(None, "leave-one-out")
+        noise where they require one (observations of a prior process; Rasmussen & Williams 5.4.2).  `score`: the rule each held-out
+        entry is scored by - "log" as above, "crps": value = -sum_i CRPS(N(mean_-i, var_-i), y_i), "se": value = -sum_i (y_i - mean_-i)^2
+        (minus PRESS); mean and var are the same under every rule, and the value is always one to maximise."""
+        return self._held_out(None, "leave-one-out", check_score(score))
 
     def cv(self, fold_start):
         """(value, mean, var) of blocked (leave-fold-out) cross-validation over contiguous folds of the observations, given by their
@@ -795,22 +836,24 @@ class Obs:
         one fold of every row gives `logpdf`."""
         return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
 
-    def ahead(self, origin):
+    def ahead(self, origin, score="log"):
         """(value, mean, var) of rolling-origin forecasts, the observations in the order given (the time order): row r is predicted from
         rows 0 ... origin[r] - 1 (origin[r] in 0 ... r; 0: from the prior), origin[r] = -1 leaves it unscored (NaN in mean and var).  mean
         and var are the predictive moments of the noisy observation and value = sum_scored log N(y_r; mean_r, var_r) - a 0-d tensor that
         carries a gradient with respect to the kernel parameters and the noise where they require one (observations of a prior process).
-        All of it comes from the ONE factorisation `logpdf` computes; origin[r] = r for every row gives `logpdf`."""
+        All of it comes from the ONE factorisation `logpdf` computes; origin[r] = r for every row gives `logpdf`.  `score` as for `loo`:
+        "crps" and "se" sum minus the CRPS / minus the squared error of the scored rows instead."""
+        check_score(score)
         if self.base.is_posterior:
             raise NotImplementedError("rolling-origin forecasts are those of a prior process")
-        return self._held_out(_Origins(origin_array(origin, self.fdd.n)), "rolling-origin forecast")
+        return self._held_out(_Origins(origin_array(origin, self.fdd.n)), "rolling-origin forecast", score)
 
     def ahead_gradients(self):
         """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the rolling-origin value, with W = L^-T (P + P^T) L^-1,
         P = Phi(L^T B - abar a^T) (`_ahead_algebra`)."""
         return self._held_out_gradients()
 
-    def _held_out(self, starts, what):
+    def _held_out(self, starts, what, score="log"):
         """`loo` (`starts` None) and `cv`: through `_HeldOutValue` where a kernel parameter or the noise needs a gradient.  The two share
         one set of pending-gradient state on the observations (`_fused_held_out_gradients`, `_held_out_parts`): a second `loo()` or `cv()`
         with gradients on the same `Obs` replaces what the first left, so run each value's backward pass before evaluating the next."""
@@ -822,15 +865,16 @@ class Obs:
                     raise NotImplementedError(f"the {what} gradient covers kernel parameters and noise of a prior process")
                 self._params = params
                 self._noise_device = None if noise is None else noise.device
-                value = _HeldOutValue.apply(self, starts, noise, *[p[3] for p in params])
+                value = _HeldOutValue.apply(self, starts, score, noise, *[p[3] for p in params])
                 return value, self._held_out_mean, self._held_out_var
-        value = self._held_out_eval(starts)
+        value = self._held_out_eval(starts, score=score)
         return value, self._held_out_mean, self._held_out_var
 
-    def _held_out_eval(self, starts, want_grad=False):
+    def _held_out_eval(self, starts, want_grad=False, score="log"):
         """The value (detached; the means and variances are left in `_held_out_mean` / `_held_out_var`).  One library call where the
         engine has one, `_value_only` / `_fusable_grad` would let `logpdf` take it and no fold exceeds the call's limit; otherwise composed
-        of engine primitives (the factor, K^-1) and the objective's block algebra (`_loo_algebra`, `_cv_algebra`: folds of any size)."""
+        of engine primitives (the factor, K^-1) and the objective's block algebra (`_loo_algebra`, `_cv_algebra`: folds of any size).
+        `score`: the scoring rule of `loo` and `ahead` (blocked cross-validation scores a fold's joint density: "log" alone)."""
         eng, n = self.eng, self.fdd.n
         dev = self.y.device
         if n == 0:
@@ -840,6 +884,7 @@ class Obs:
         ahead = isinstance(starts, _Origins)
         call = "ahead_dense" if ahead else "loo_dense" if starts is None else "cv_dense"
         folds = () if starts is None else (starts,)
+        rule = {} if score == "log" else {"score": score}   # (an engine's one-call forms take the rule by keyword)
         fits = starts is None or ahead or int(np.diff(starts).max()) <= CV_MAX_FOLD
         if ahead and fits and hasattr(eng, call) and (self._fusable_grad() if want_grad else self._value_only()):
             if starts.device is None:
@@ -848,18 +893,18 @@ class Obs:
         if want_grad and fits and hasattr(eng, call + "_grad") and self._fusable_grad():
             ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
             value, info, self._fused_held_out_gradients, (A, logdet), self._held_out_mean, self._held_out_var = getattr(eng, call + "_grad")(
-                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, *folds)
+                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, *folds, **rule)
             eng.check_info(info)
             self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
             return value.detach()
         if not want_grad and fits and hasattr(eng, call) and self._value_only():
             ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._held_out_mean, self._held_out_var = getattr(eng, call)(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, *folds)
+            value, info, self._held_out_mean, self._held_out_var = getattr(eng, call)(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, *folds, **rule)
             eng.check_info(info)
             return value.detach()
         if ahead:
             fac = self.factor()
-            value, e, var, scored, weights = _ahead_algebra(eng, fac.L.detach(), fac.zrow.reshape(-1).detach(), starts.origin)
+            value, e, var, scored, weights = _ahead_algebra(eng, fac.L.detach(), fac.zrow.reshape(-1).detach(), starts.origin, score)
             self._held_out_mean = torch.where(scored, self.y.reshape(-1).detach() - e, var)
             self._held_out_var = var
             self._held_out_parts = (fac, weights) if want_grad else None
@@ -868,11 +913,12 @@ class Obs:
         low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
         Kinv = low + torch.tril(low, -1).T
         alpha = fac.alpha().reshape(-1).detach()
-        value, b, var, fill = _loo_algebra(Kinv, alpha) if starts is None else _cv_algebra(eng, Kinv, alpha, starts)
+        value, e, b, var, fill = _loo_algebra(Kinv, alpha, score) if starts is None else _cv_algebra(eng, Kinv, alpha, starts)
         y = self.y.reshape(-1).detach()
-        self._held_out_mean, self._held_out_var = y - b, var
+        self._held_out_mean, self._held_out_var = y - e, var
         self._held_out_parts = (Kinv, alpha, b, fill) if want_grad else None
-        value = value - 0.5 * n * _LOG_2PI
+        if score == "log":
+            value = value - 0.5 * n * _LOG_2PI
         return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
 
     def _held_out_gradients(self):

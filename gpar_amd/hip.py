@@ -144,11 +144,20 @@ def objective_vec_doubles(lib, objective, n, grad, folds):
     return int(lib.gpar_workspace_doubles(_lib.WS_CV, n, grad, folds[2]) if objective == "cv" else lib.gpar_workspace_doubles(_lib.WS_LOO, n, grad, 0))
 
 
-def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused):
+def score_code(score):
+    """GPAR_SCORE_* of a scoring rule's name ("log", "crps", "se"); anything else is a ValueError."""
+    if score not in _lib.SCORES:
+        raise ValueError('score must be "log", "crps" or "se"')
+    return _lib.SCORES[score]
+
+
+def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused, score="log"):
     """One dense layer's objective ("mll", "loo", "cv" or "ahead") AND its gradient ingredients in one library call (gpar_logpdf_dense_grad,
-    gpar_loo_dense_grad, gpar_cv_dense_grad, gpar_ahead_dense_grad): allocation and marshalling for the four.  Returns (out, vectors, info, A, W): out = [value,
+    gpar_loo_dense_grad_score, gpar_cv_dense_grad, gpar_ahead_dense_grad_score): allocation and marshalling for the four.  `score`: the scoring
+    rule of "loo" and "ahead".  Returns (out, vectors, info, A, W): out = [value,
     logdet, GRAD_NACC moment sums], vectors = 1/2 diag(W) and - but for "mll" - the held-out means and variances in its rows."""
     lib = _lib.load()
+    rule = (score_code(score),) if objective in ("loo", "ahead") else ()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
     folds = _folds_of(objective, fold_start, n, dev)
     fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
@@ -174,19 +183,20 @@ def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, l
     if objective == "mll":
         rc = lib.gpar_logpdf_dense_grad(*head, work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), *tail)
     else:
-        entry = {"loo": lib.gpar_loo_dense_grad, "cv": lib.gpar_cv_dense_grad, "ahead": lib.gpar_ahead_dense_grad}[objective]
+        entry = {"loo": lib.gpar_loo_dense_grad_score, "cv": lib.gpar_cv_dense_grad, "ahead": lib.gpar_ahead_dense_grad_score}[objective]
         rc = entry(*head, work[nblocks * nacc + nalpha:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(),
-                   vectors[1].data_ptr(), vectors[2].data_ptr(), *fold_args, *tail)
-    _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad", "cv": "gpar_cv_dense_grad",
-                    "ahead": "gpar_ahead_dense_grad"}[objective])
+                   vectors[1].data_ptr(), vectors[2].data_ptr(), *fold_args, *rule, *tail)
+    _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad",
+                    "ahead": "gpar_ahead_dense_grad_score"}[objective])
     return out, vectors, info, A, W
 
 
-def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead, fused):
-    """Value, held-out means and variances of one dense layer for "loo", "cv" or "ahead" in one library call (gpar_loo_dense, gpar_cv_dense,
-    gpar_ahead_dense).  Returns (out, mean, var, info): out = [value, logdet] (device), the n predictive means and variances (device), info
-    word."""
+def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead, fused, score="log"):
+    """Value, held-out means and variances of one dense layer for "loo", "cv" or "ahead" in one library call (gpar_loo_dense_score,
+    gpar_cv_dense, gpar_ahead_dense_score; `score`: the scoring rule of "loo" and "ahead").  Returns (out, mean, var, info): out = [value,
+    logdet] (device), the n predictive means and variances (device), info word."""
     lib = _lib.load()
+    rule = (score_code(score),) if objective in ("loo", "ahead") else ()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
     folds = _folds_of(objective, fold_start, n, dev)
     fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
@@ -198,13 +208,13 @@ def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead,
         moments = torch.empty(2, n, dtype=torch.float64, device=dev)
         info = torch.empty(1, dtype=torch.int32, device=dev)
         _lib.check(
-            lib.gpar_ahead_dense(
+            lib.gpar_ahead_dense_score(
                 ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
                 None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
-                out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), *fold_args, info.data_ptr(), _potrf_flags(lookahead, fused),
+                out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), *fold_args, *rule, info.data_ptr(), _potrf_flags(lookahead, fused),
                 stream_ptr(dev),
             ),
-            "gpar_ahead_dense",
+            "gpar_ahead_dense_score",
         )
         return out, moments[0], moments[1], info
     X = alloc_matrix(n, n, dev)
@@ -213,15 +223,15 @@ def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead,
     out = torch.empty(2, dtype=torch.float64, device=dev)
     moments = torch.empty(2, n, dtype=torch.float64, device=dev)
     info = torch.empty(1, dtype=torch.int32, device=dev)
-    entry = lib.gpar_cv_dense if objective == "cv" else lib.gpar_loo_dense
+    entry = lib.gpar_cv_dense if objective == "cv" else lib.gpar_loo_dense_score
     _lib.check(
         entry(
             ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
             None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
             T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(),
-            *fold_args, info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
+            *fold_args, *rule, info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
         ),
-        "gpar_cv_dense" if objective == "cv" else "gpar_loo_dense",
+        "gpar_cv_dense" if objective == "cv" else "gpar_loo_dense_score",
     )
     return out, moments[0], moments[1], info
 
@@ -234,17 +244,18 @@ def logpdf_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fu
     return out, vectors[0], info, A
 
 
-def loo_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
-    """Leave-one-out value, means and variances of one dense layer in one library call (gpar_loo_dense; no inverse is formed).
+def loo_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True, score="log"):
+    """Leave-one-out value, means and variances of one dense layer in one library call (gpar_loo_dense_score; no inverse is formed).
+    `score`: "log", "crps" or "se" - the rule every held-out entry is scored by; the value is one to maximise under each.
     Returns (out, loo_mean, loo_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
-    return _dense_value("loo", ck, x, y, noise_diag, jitter, None, lookahead, fused)
+    return _dense_value("loo", ck, x, y, noise_diag, jitter, None, lookahead, fused, score)
 
 
-def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
-    """One dense layer's leave-one-out value AND its gradient ingredients in one library call (gpar_loo_dense_grad).  Returns
+def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True, score="log"):
+    """One dense layer's leave-one-out value AND its gradient ingredients in one library call (gpar_loo_dense_grad_score).  Returns
     (out, half_diag, loo_mean, loo_var, info, A, W): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W),
     the n predictive means and variances, info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
-    out, vectors, info, A, W = _dense_grad("loo", ck, x, y, noise_diag, jitter, periodic, None, lookahead, fused)
+    out, vectors, info, A, W = _dense_grad("loo", ck, x, y, noise_diag, jitter, periodic, None, lookahead, fused, score)
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 
@@ -286,17 +297,17 @@ def upload_origin(origin, n, device):
     return torch.tensor(origin_array(origin, n), dtype=torch.int32, device=device)
 
 
-def ahead_dense(ck, x, y, noise_diag, jitter, origin, lookahead=True, fused=True):
-    """Rolling-origin forecast value, means and variances of one dense layer in one library call (gpar_ahead_dense): row r predicted from
+def ahead_dense(ck, x, y, noise_diag, jitter, origin, lookahead=True, fused=True, score="log"):
+    """Rolling-origin forecast value, means and variances of one dense layer in one library call (gpar_ahead_dense_score): row r predicted from
     rows 0 ... origin[r] - 1, origin[r] = -1 not scored (NaN in its mean and variance).  `origin`: a host sequence of n ints or the device
     tensor `upload_origin` returns.  Returns (out, mean, var, info): out = [value, logdet] (device), means and variances (device), info."""
-    return _dense_value("ahead", ck, x, y, noise_diag, jitter, origin, lookahead, fused)
+    return _dense_value("ahead", ck, x, y, noise_diag, jitter, origin, lookahead, fused, score)
 
 
-def ahead_dense_grad(ck, x, y, noise_diag, jitter, periodic, origin, lookahead=True, fused=True):
-    """One dense layer's rolling-origin forecast value AND its gradient ingredients in one library call (gpar_ahead_dense_grad).  `origin`
-    as for `ahead_dense`.  Returns (out, half_diag, mean, var, info, A, W), laid out as `loo_dense_grad` returns them."""
-    out, vectors, info, A, W = _dense_grad("ahead", ck, x, y, noise_diag, jitter, periodic, origin, lookahead, fused)
+def ahead_dense_grad(ck, x, y, noise_diag, jitter, periodic, origin, lookahead=True, fused=True, score="log"):
+    """One dense layer's rolling-origin forecast value AND its gradient ingredients in one library call (gpar_ahead_dense_grad_score).  `origin`
+    and `score` as for `ahead_dense`.  Returns (out, half_diag, mean, var, info, A, W), laid out as `loo_dense_grad` returns them."""
+    out, vectors, info, A, W = _dense_grad("ahead", ck, x, y, noise_diag, jitter, periodic, origin, lookahead, fused, score)
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 

@@ -18,7 +18,7 @@ import torch
 
 from .engine import get_engine
 from .engine import joining as _joining
-from .gp import Obs, PseudoObs, PseudoObsDTC, PseudoObsFITC, Stacked
+from .gp import Obs, PseudoObs, PseudoObsDTC, PseudoObsFITC, Stacked, _score_rows, check_score
 
 __all__ = ["GPAR", "merge", "construct_model", "last", "per_output"]
 
@@ -639,17 +639,20 @@ class GPAR:
         return total.cpu() if total.is_cuda and not total.requires_grad else total
 
     # ---- leave-one-out cross-validation -------------------------------------------------------------
-    def loo(self, x, y, w, outputs=None):
+    def loo(self, x, y, w, outputs=None, score="log"):
         """Layer-wise leave-one-out cross-validation: layer i's inputs [x, y_<i] are built and fixed exactly as `logpdf` builds them
         (observed, imputed or replaced), and its observed entries of output i are left out one at a time, under the noise diagonal
         noise_i / w_i.  Returns (total, pieces): the sum over the visited layers of sum_j log N(y_ij; mean_-j, var_-j) - it carries a
         gradient with respect to kernel parameters and noise where they require one - and per visited layer (rows, mean, var, logpdf):
         the rows of the x handed in that are observed at output i, and the leave-one-out predictive mean, variance and log-density
         of each.  `outputs` restricts the layers visited, as for `logpdf` (x is then the design matrix reached before the first of
-        them).  Inducing points have no dense K^-1 to leave a point out of: ValueError."""
+        them).  `score`: the rule every held-out entry is scored by - "log" as above, "crps" (minus the continuous ranked probability
+        score) or "se" (minus the squared error); the total and the last element of every piece then hold that rule's terms, always
+        to be maximised.  Inducing points have no dense K^-1 to leave a point out of: ValueError."""
+        check_score(score)
         if self.sparse:
             raise ValueError("leave-one-out cross-validation needs dense observations (no inducing points)")
-        return _retry_unfused(lambda: self._held_out(x, y, w, None, outputs), self.layers, (x, y, w))
+        return _retry_unfused(lambda: self._held_out(x, y, w, None, outputs, score), self.layers, (x, y, w))
 
     # ---- blocked cross-validation ---------------------------------------------------------------------
     def cv(self, x, y, w, folds, outputs=None):
@@ -669,7 +672,7 @@ class GPAR:
         return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs), self.layers, (x, y, w))
 
     # ---- rolling-origin forecast scoring --------------------------------------------------------------
-    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None):
+    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None, score="log"):
         """Layer-wise rolling-origin forecast scoring, the rows in the order given (the time order): layer i's inputs [x, y_<i] are built
         as `logpdf` builds them, and its observed entry of output i at row r is predicted from the layer's observed rows with index
         <= r - horizon - the horizon counts rows as given, so missing values make the bands ragged.  Rows with index < start are not
@@ -678,13 +681,15 @@ class GPAR:
         with respect to kernel parameters and noise where they require one), and per visited layer (rows, mean, var): the rows observed
         at output i with the predictive mean and variance of each (NaN where the row is not scored).  One factorisation per layer, the
         one `logpdf` computes.  `outputs` as for `loo`; `rows`: the indices, in the data as given, of the rows of the x handed in
-        where earlier layers have dropped some (None: x holds every row).  Inducing points: ValueError."""
+        where earlier layers have dropped some (None: x holds every row).  `score` as for `loo`: under "crps" / "se" the total is minus
+        the summed CRPS / squared error of the scored forecasts.  Inducing points: ValueError."""
+        check_score(score)
         if self.sparse:
             raise ValueError("rolling-origin forecast scoring needs dense observations (no inducing points)")
         rows = None if rows is None else np.asarray(rows, dtype=np.int64)
-        return _retry_unfused(lambda: self._held_out(x, y, w, _Ahead(int(horizon), int(start), rows), outputs), self.layers, (x, y, w))
+        return _retry_unfused(lambda: self._held_out(x, y, w, _Ahead(int(horizon), int(start), rows), outputs, score), self.layers, (x, y, w))
 
-    def _held_out(self, x, y, w, labels, outputs):
+    def _held_out(self, x, y, w, labels, outputs, score="log"):
         """The layer loop of `loo` (`labels` None: pieces carry the per-row log-density, and nothing is kept on the host), `cv` and
         `ahead` (`labels` an `_Ahead`: the origins of a layer are counted on the host from the rows observed there)."""
         x, y, w = self._prep(x, y, w)
@@ -720,9 +725,9 @@ class GPAR:
                 if perm is None:
                     obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
                     if rolling:
-                        value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start))
+                        value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start), score)
                     else:
-                        value, mean, var = obs.cv(starts) if blocked else obs.loo()
+                        value, mean, var = obs.cv(starts) if blocked else obs.loo(score)
                 else:
                     # the evaluation's own observations, rows sorted by fold; `obs` keeps the order the next layer reads
                     at = torch.as_tensor(perm, dtype=torch.long, device=obs.y.device)
@@ -737,7 +742,10 @@ class GPAR:
                     pieces.append((seen, mean, var))
                 else:
                     resid = obs.y.reshape(-1) - mean
-                    pieces.append((seen, mean, var, -0.5 * (torch.log(2.0 * np.pi * var) + resid * resid / var)))
+                    if score == "log":
+                        pieces.append((seen, mean, var, -0.5 * (torch.log(2.0 * np.pi * var) + resid * resid / var)))
+                    else:
+                        pieces.append((seen, mean, var, _score_rows(score, resid.detach(), var)[0]))
                 total = value if len(pieces) == 1 else total + value   # (0-d tensors: a host and a device scalar add)
                 if not is_last:
                     x, _ = self._next_inputs(ALL_LAYERS, i, x, None, yi, f, obs, complete)

@@ -15,7 +15,7 @@ import torch
 
 from ._lib import CHOL_UPDATE_MAX_RANK
 from .engine import get_engine
-from .gp import GP, Measure, greedy_inducing
+from .gp import GP, Measure, check_score, greedy_inducing
 from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
 from .model import GPAR, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
@@ -227,10 +227,15 @@ def _check_horizon(horizon, start, n):
     return int(horizon), int(start)
 
 
-def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None):
+def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log"):
     """The training objectives `fit` knows, and what the held-out ones need."""
     if objective not in ("mll", "loo", "cv", "ahead"):
         raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
+    check_score(score)
+    if score != "log" and objective in ("mll", "cv"):
+        raise ValueError(f'score="{score}" belongs to objective="loo" or "ahead": '
+                         + ("the marginal likelihood is a joint density of all rows" if objective == "mll" else "a fold is scored by its joint density")
+                         + ", which has no per-row scoring rule")
     if objective != "ahead" and (horizon is not None or start is not None):
         raise ValueError('horizon and start belong to objective="ahead"')
     if objective == "cv" and folds is None:
@@ -354,7 +359,7 @@ class GPARRegressor:
         self.is_conditioned = True
 
     def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, horizon=None, start=None,
-            **kw_args):
+            score="log", **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
 
@@ -366,10 +371,15 @@ class GPARRegressor:
         row predicted from the rows at least `horizon` (default 1) rows before it, rows before `start` (default 0) not scored - for
         models whose purpose is the forecast at that horizon; `horizon` / `start` belong to it alone; the restrictions of "loo".
 
+        `score` (with "loo" and "ahead" alone: ValueError otherwise): the rule each held-out entry is scored by.  "log", the Gaussian
+        log density; "crps", minus the continuous ranked probability score - linear in the error where the log score is quadratic over
+        the variance, so a few outliers do not buy themselves out through the noise, and still strictly proper; "se", minus the
+        squared error (PRESS / the rolling-origin MSE), which ignores the predictive variances altogether.
+
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -377,12 +387,13 @@ class GPARRegressor:
             raise NotImplementedError("Greedy search is not implemented yet.")
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
-        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, **kw_args)
+        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, score=score, **kw_args)
 
-    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, horizon=None, start=None, **kw_args):
+    def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, horizon=None, start=None, score="log",
+               **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score)
         loo, cv, ahead = objective == "loo", objective == "cv", objective == "ahead"
         labels = _fold_labels(folds, self.n) if cv else None
         if ahead:
@@ -419,11 +430,11 @@ class GPARRegressor:
                     if optimise_x_ind:  # the m base columns are the variable; the columns appended by earlier layers stay fixed
                         x_ind_pi = torch.cat([eng.tensor(vs["x_ind"]), fixed_x_ind[:, self.m :]], dim=1)
                     if loo:
-                        return -gpar.loo(fixed_x, y_cached, None, outputs=[pi])[0]
+                        return -gpar.loo(fixed_x, y_cached, None, outputs=[pi], score=score)[0]
                     if cv:
                         return -gpar.cv(fixed_x, y_cached, None, layer_labels, outputs=[pi])[0]
                     if ahead:
-                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows)[0]
+                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows, score=score)[0]
                     return -gpar.logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi], x_ind=x_ind_pi)
                 return -gpar.logpdf(x_dev, y_cached, None, only_last_layer=False)
 
@@ -446,7 +457,7 @@ class GPARRegressor:
 
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
                                      group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv else {}),
-                                     **({"ahead": (horizon, start, layer_rows)} if ahead else {}))
+                                     **({"ahead": (horizon, start, layer_rows)} if ahead else {}), **({} if score == "log" else {"score": score}))
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
             if fast is not None:
@@ -511,7 +522,8 @@ class GPARRegressor:
         Returns (order, values): `order[i]` is the column of y placed at position i, `values[i]` the log marginal likelihood of
         that layer after training (of the normalised outputs, as `fit` sees them).  With `objective="loo"` among the keyword arguments
         the candidates are trained on, and ranked by, the layer's leave-one-out value instead (`fit`); with `objective="cv", folds=...` by its
-        blocked cross-validation value; with `objective="ahead", horizon=...` by its rolling-origin forecast score.  The trained hyper-parameters of the chosen
+        blocked cross-validation value; with `objective="ahead", horizon=...` by its rolling-origin forecast score; `score="crps"` / `"se"`
+        beside "loo" or "ahead" trains on and ranks by that rule's value (`fit`; `values` are to be maximised under every rule).  The trained hyper-parameters of the chosen
         chain are kept in `self.greedy_vs_` (layer i there belongs to output `order[i]`): `reg.vs = reg.greedy_vs_.copy();
         reg.fit(x, y[:, order], ...)` continues from them.  `self` is conditioned on (x, y, w) in the GIVEN order, as after
         `condition`."""
@@ -685,13 +697,17 @@ class GPARRegressor:
         self.last_update_incremental_ = bool(incremental)
         return self
 
-    def loo(self, x, y, w=None):
+    def loo(self, x, y, w=None, score="log"):
         """Layer-wise leave-one-out cross-validation under the prior model (`GPAR.loo`): `(value, mean, var)`.  `value` is the sum
         over outputs and observed entries of log N(y_ij; mean_ij, var_ij), with the data handling of `logpdf(x, y, w)` (same
         transform and normalisation calls; a numpy scalar unless x or y was a torch tensor); `mean` and `var` are n x p numpy arrays
         of the predictive mean and variance of every observed y_ij given all other observations of output j (and the layer's inputs
-        [x, y_<j] as `logpdf` builds them), in the space the model sees the outputs in, NaN where y is missing.  With inducing points
-        there is no dense K^-1 to leave a point out of: ValueError."""
+        [x, y_<j] as `logpdf` builds them), in the space the model sees the outputs in, NaN where y is missing.  `score`: "log" as
+        above; "crps": `value` is minus the summed continuous ranked probability score of those Gaussian predictives; "se": minus the
+        summed squared error, -nansum((y - mean)^2) in the space the model sees the outputs in.  `value` is to be maximised under every
+        rule and is in units of the normalised outputs, summed over the outputs; `mean` and `var` do not depend on the rule.  With
+        inducing points there is no dense K^-1 to leave a point out of: ValueError."""
+        check_score(score)
         if self.sparse:
             raise ValueError("leave-one-out cross-validation needs dense layers: not available with inducing points (x_ind)")
         any_torch = isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor)
@@ -701,7 +717,7 @@ class GPARRegressor:
         m, p = x.shape[1], y.shape[1]
         self._prepare_kernels(m, p, int(x.shape[0]))
         with torch.no_grad():
-            value, pieces = _construct_gpar(self, self.vs, m, p).loo(x, y, w)
+            value, pieces = _construct_gpar(self, self.vs, m, p).loo(x, y, w, score=score)
         mean = np.full((int(x.shape[0]), p), np.nan)
         var = np.full((int(x.shape[0]), p), np.nan)
         for i, (rows, mean_i, var_i, _) in enumerate(pieces):
@@ -710,7 +726,7 @@ class GPARRegressor:
         value = value.detach() if any_torch else value.detach().cpu().numpy()
         return value, mean, var
 
-    def ahead(self, x, y, w=None, horizon=1, start=0):
+    def ahead(self, x, y, w=None, horizon=1, start=0, score="log"):
         """Rolling-origin forecast scoring under the prior model (`GPAR.ahead`): `(value, mean, var)` with the conventions of `loo`.
         The rows are taken in the order given (the time order); every observed y_rj with r >= `start` is predicted from the rows of
         output j observed at index <= r - `horizon` (and the layer's inputs [x, y_<j] as `logpdf` builds them) - the `horizon`-step-ahead
@@ -718,7 +734,9 @@ class GPARRegressor:
         log N(y_rj; mean_rj, var_rj) over the scored entries, which by the chain rule over the outputs is the exact GPAR log score;
         `mean` and `var` are n x p numpy arrays of the predictive means and variances (of the noisy observation), NaN where y is missing
         or the row is not scored.  `horizon`: an int >= 1, counting rows as given (missing values make the bands ragged); a horizon >= n
-        predicts every row from the prior.  `start`: an int in 0 ... n - 1.  Dense layers only: ValueError with inducing points."""
+        predicts every row from the prior.  `start`: an int in 0 ... n - 1.  `score` as for `loo`: "crps" / "se" sum minus the CRPS /
+        minus the squared error of the scored forecasts.  Dense layers only: ValueError with inducing points."""
+        check_score(score)
         if self.sparse:
             raise ValueError("rolling-origin forecast scoring needs dense layers: not available with inducing points (x_ind)")
         any_torch = isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor)
@@ -729,7 +747,7 @@ class GPARRegressor:
         horizon, start = _check_horizon(horizon, start, int(x.shape[0]))
         self._prepare_kernels(m, p, int(x.shape[0]))
         with torch.no_grad():
-            value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start)
+            value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start, score=score)
         mean = np.full((int(x.shape[0]), p), np.nan)
         var = np.full((int(x.shape[0]), p), np.nan)
         for i, (rows, mean_i, var_i) in enumerate(pieces):
@@ -738,7 +756,7 @@ class GPARRegressor:
         value = value.detach() if any_torch else value.detach().cpu().numpy()
         return value, mean, var
 
-    def cv(self, x, y, w=None, folds=None):
+    def cv(self, x, y, w=None, folds=None, score="log"):
         """Layer-wise blocked (leave-fold-out) cross-validation under the prior model (`GPAR.cv`): `(value, mean, var)` with the
         conventions of `loo`.  `folds`: an int k - k contiguous blocks of the rows as given, split as `np.array_split` splits them, the
         estimator for time series and other ordered data, where a single left-out point is predicted almost for free from its
@@ -746,7 +764,10 @@ class GPARRegressor:
         fold left empty vanishes).  `value` is the sum over outputs and folds of the JOINT log-density of the fold's observed entries
         given every other fold's; `mean` and `var` are n x p numpy arrays of the predictive means and marginal variances (the diagonals
         of the folds' predictive covariances), NaN where y is missing.  Folds of one row give `loo`; one fold gives `logpdf` for one
-        output.  Dense layers only: ValueError with inducing points."""
+        output.  `score`: "log" alone - a fold is scored by its JOINT density, which has no per-row scoring rule ("crps" and "se"
+        belong to `loo` and `ahead`: ValueError).  Dense layers only: ValueError with inducing points."""
+        if check_score(score) != "log":
+            raise ValueError(f'score="{score}" belongs to loo and ahead: a fold is scored by its joint density, which has no per-row scoring rule')
         if self.sparse:
             raise ValueError("cross-validation needs dense layers: not available with inducing points (x_ind)")
         if folds is None:

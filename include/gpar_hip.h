@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 12
+#define GPAR_ABI_VERSION 13
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -338,6 +338,48 @@ int gpar_ahead_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
 int gpar_ahead_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
                      const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
                      double* ahead_mean, double* ahead_var, const int* origin, int* info, int potrf_flags, void* stream);
+
+/* Scoring rules for the leave-one-out and rolling-origin entries (ABI v13).  The entries above score every held-out entry by its Gaussian
+ * log density; the *_score entries take the rule as `score`, placed before the info word, and are otherwise their namesakes argument for
+ * argument - same workspaces, same launches, same info codes, and with GPAR_SCORE_LOG the same bits (the entries above forward to them).
+ * out[0] is always a value to MAXIMISE, the sum over the scored entries of, with e = y - mean, v = var, sd = sqrt v, z = e / sd and
+ * Phi / phi the standard normal cdf / pdf:
+ *   GPAR_SCORE_LOG    -1/2 [log 2 pi + log v + e^2 / v]                  q = e / v             s = 1/2 (1 / v - q^2)
+ *   GPAR_SCORE_CRPS   -sd [z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt pi]    q = 2 Phi(z) - 1      s = (2 phi(z) - 1 / sqrt pi) / (2 sd)
+ *   GPAR_SCORE_SE     -e^2                                               q = 2 e               s = 0
+ * (minus the continuous ranked probability score of the Gaussian predictive, Gneiting & Raftery 2007; minus the squared error: PRESS for
+ * leave-one-out, the rolling-origin MSE times the number of scored rows for the forecasts).  q = -dterm/de and s = -dterm/dv are what the
+ * gradient chains run on: the rolling-origin weights as documented above with these q_r, s_r; the leave-one-out weights
+ *   W = alpha u^T + u alpha^T - 2 S^-1 C S^-1,   u = S^-1 b,   b_i = q_i v_i,   C = diag(q_i e_i v_i + s_i v_i^2)
+ * (the log score: b = e, c = 1/2 (v + e^2)).  The means and variances do not depend on the rule.  A rule other than the three is an
+ * argument error (-1014) before anything is launched: every buffer keeps what it held.
+ * [no reference counterpart] */
+#define GPAR_SCORE_LOG 0
+#define GPAR_SCORE_CRPS 1
+#define GPAR_SCORE_SE 2
+int gpar_loo_dense_grad_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                              const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                              double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                              double* loo_mean, double* loo_var, int score, int* info, int potrf_flags, void* stream);
+int gpar_loo_dense_grad_finish_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                     double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X,
+                                     int ldxw, double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out,
+                                     double* half_diag, double* loo_mean, double* loo_var, int score, int* info_out, void* stream);
+int gpar_loo_dense_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                         const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                         double* vec, double* out, double* loo_mean, double* loo_var, int score, int* info, int potrf_flags, void* stream);
+int gpar_ahead_dense_grad_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                                double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                double* ahead_mean, double* ahead_var, const int* origin, int score, int* info, int potrf_flags, void* stream);
+int gpar_ahead_dense_grad_finish_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                       double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X,
+                                       int ldxw, double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out,
+                                       double* half_diag, double* ahead_mean, double* ahead_var, const int* origin, int score, int* info_out,
+                                       void* stream);
+int gpar_ahead_dense_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                           double* ahead_mean, double* ahead_var, const int* origin, int score, int* info, int potrf_flags, void* stream);
 
 /* The same moment sums of  sum W dK/dtheta  for the other weight shapes the inducing-point (VFE) bound needs
  * [gradient of the PseudoObs elbo, gpar/model.py:226,286-287 under varz's optimiser]:
