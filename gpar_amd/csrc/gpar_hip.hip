@@ -1213,11 +1213,12 @@ static int cv_folds_launch(const double* P, int ldp, int n, const double* X, int
 }
 
 #include "ahead.h"   // rolling-origin forecast scoring: its kernels and weight stage (after loo_sum_terms and grad_epilogue_sums, which it uses)
+#include "cv_gap.h"  // purged blocked cross-validation: its kernels and weight stage (after cv_chol_lower and sym_lower_matvec_rows, which it uses)
 
 // ---- one chain for the dense objectives: marginal likelihood, leave-one-out, blocked cross-validation, rolling-origin forecasts --------
 // Every one-call entry is  prologue (features, Gram, factor) -> inverse -> the objective's weights W -> weighted-sum pass -> epilogue;
 // the objectives differ in the weight stage and in the last block of the epilogue alone (OBJ_AHEAD also stops the inverse at X = L^-T).
-enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV, OBJ_AHEAD };
+enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV, OBJ_AHEAD, OBJ_CV_GAP };
 struct DenseObjective {
     DenseObjectiveKind kind;
     const double* y;            // the observations (the finish form of OBJ_MLL has none: row n of the factor holds all it needs)
@@ -1226,6 +1227,7 @@ struct DenseObjective {
     CvFolds folds;              // OBJ_CV
     const int* origin;          // OBJ_AHEAD: n origins (device)
     int score;                  // OBJ_LOO, OBJ_AHEAD: the scoring rule (GPAR_SCORE_LOG = 0: what an entry without one scores by)
+    CvHold hold;                // OBJ_CV_GAP: the extents of the blocks left out of the conditioning set (`folds`: the scored rows)
 };
 
 // What gpar_logpdf_dense does up to the factor: features (+ their frequency derivatives when zd is given; the value-only forms pass null)
@@ -1284,6 +1286,17 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
             const int nrb = gpar_ceil_div(n, CV_T);
             hipLaunchKernelGGL(cv_weights_kernel, dim3((unsigned)(nrb * ob.folds.nfolds + (n + 3) / 4)), dim3(256), 0, st, (const double*)W, ldw, n,
                                ob.folds.start, ob.folds.nfolds, ob.folds.max_fold, (const double*)Rm, (const double*)bvec, u, X, ldxw);
+            break;
+        }
+        case OBJ_CV_GAP: {   // `vec`: b, value terms, u, the factors of C, its band image, P as a full matrix (cv_gap.h)
+            term = ob.vec + n, u = ob.vec + 2 * (size_t)n;
+            rc = cvg_weights_run(W, ldw, n, X, ldxw, zrow, ob.y, ob.incy, ob.folds.start, ob.folds.nfolds, ob.hold, alpha, ob.mean, ob.var, ob.vec, info,
+                                 st);
+            // T = C P (in X) and P whole are formed; C is indefinite, so no S S^T:  W <- -2 P T + alpha u^T + u alpha^T
+            if (!rc)
+                rc = gemm_launch(0, 0, n, n, n, -2.0, ob.vec + cvg_off_p(n, ob.hold.max_hold), cvg_ldp(n), X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
+            if (rc) return rc;
+            hipLaunchKernelGGL(loo_rank2_kernel, dim3(gpar_ceil_div(n, 256), n), dim3(256), 0, st, W, ldw, n, (const double*)alpha, (const double*)u);
             break;
         }
         case OBJ_AHEAD:   // `vec`: q, s, value terms, abar, chunk origins, the first product;  W = X (P + P^T) X^T whole (no rank-2 tail)
@@ -1472,6 +1485,70 @@ int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* 
     if (!rc) rc = chol_inverse_run(A, n, lda, X, ldxw, T, ldt, st);
     if (!rc) rc = cv_folds_launch(T, ldt, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, max_fold, nullptr, cv_mean, cv_var, nullptr,
                                   vec, nullptr, info, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- purged blocked cross-validation (ABI v14; cv_gap.h) ----------------------------------------------------------------------------------
+static int cvg_check(const int* fold_start, const int* hold_lo, const int* hold_hi, int nfolds, int max_hold, int n) {
+    if (!hold_lo || !hold_hi) return GPAR_ARG_ERROR(1);
+    return cv_check_folds(CvFolds{fold_start, nfolds, max_hold}, n);
+}
+
+int gpar_cv_gap_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                           double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                           double* cv_mean, double* cv_var, const int* fold_start, const int* hold_lo, const int* hold_hi, int nfolds,
+                           int max_hold, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !cv_mean || !cv_var || !info ||
+        n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    int rc = cvg_check(fold_start, hold_lo, hold_hi, nfolds, max_hold, n);
+    if (rc) return rc;
+    const DenseObjective ob{OBJ_CV_GAP, y, incy, vec, cv_mean, cv_var, {fold_start, nfolds, max_hold}, nullptr, GPAR_SCORE_LOG,
+                            {hold_lo, hold_hi, max_hold}};
+    rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags, (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, out + 1, info, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag,
+                                 stream, false);
+}
+
+int gpar_cv_gap_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                  double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                                  double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                  double* cv_mean, double* cv_var, const int* fold_start, const int* hold_lo, const int* hold_hi, int nfolds,
+                                  int max_hold, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !logdet || !info || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !cv_mean ||
+        !cv_var || !info_out || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    const DenseObjective ob{OBJ_CV_GAP, y, incy, vec, cv_mean, cv_var, {fold_start, nfolds, max_hold}, nullptr, GPAR_SCORE_LOG,
+                            {hold_lo, hold_hi, max_hold}};
+    int rc = cvg_check(fold_start, hold_lo, hold_hi, nfolds, max_hold, n);
+    if (!rc) rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, logdet, info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out,
+                                 half_diag, stream, true);
+}
+
+// Value, means and variances alone: K^-1 whole (as gpar_cv_dense forms it), then the purged fold kernel without its gradient outputs.
+int gpar_cv_gap_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                      const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                      double* vec, double* out, double* cv_mean, double* cv_var, const int* fold_start, const int* hold_lo, const int* hold_hi,
+                      int nfolds, int max_hold, int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !T || !vec || !out || !cv_mean || !cv_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = cvg_check(fold_start, hold_lo, hold_hi, nfolds, max_hold, n);
+    if (!rc) rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
+    if (!rc) rc = chol_inverse_run(A, n, lda, X, ldxw, T, ldt, st);
+    if (!rc) rc = cvg_folds_launch(T, ldt, n, X, ldxw, A + (size_t)n * lda, y, incy, fold_start, nfolds, CvHold{hold_lo, hold_hi, max_hold}, nullptr,
+                                   cv_mean, cv_var, vec, nullptr, nullptr, nullptr, nullptr, info, st);
     if (rc) return rc;
     hipLaunchKernelGGL(loo_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, 0.5 * (double)n * 1.8378770664093453, out);
     GPAR_LAUNCH_CHECK();
@@ -1745,6 +1822,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
             if (c < 1 || c > GPAR_CV_MAX_FOLD) return -1;
             return (long long)(a > 0 ? a : 0) * (b ? 3 + c : 1);
         case GPAR_WS_AHEAD: return ah_workspace_doubles(a, b);                          /* n, with gradient */
+        case GPAR_WS_CV_GAP: return cvg_workspace_doubles(a, b, c);                     /* n, with gradient, max_hold */
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         default: return -1;

@@ -288,6 +288,18 @@ class HipEngine:
                                                                   **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
+    def cv_gap_dense(self, ck, x, y, noise_diag, jitter, fold_start, hold):
+        """`cv_dense` with purged rows: `hold` = (hold_lo, hold_hi), per fold the block of at most `_lib.CV_MAX_FOLD` rows - the fold and
+        the purged rows on either side of it - that it is not predicted from (checked on the host: `hip.hold_extents`)."""
+        out, mean, var, info = hip.cv_gap_dense(ck, self._mat(x), y, noise_diag, jitter, fold_start, hold, **self._factor_flags())
+        return out[0], info, mean, var
+
+    def cv_gap_dense_grad(self, ck, x, y, noise_diag, jitter, fold_start, hold):
+        """The purged counterpart of `cv_dense_grad`, same conventions and return values."""
+        out, half_diag, mean, var, info, A, _ = hip.cv_gap_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), fold_start, hold,
+                                                                      **self._factor_flags())
+        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
+
     def ahead_dense(self, ck, x, y, noise_diag, jitter, origin, score="log"):
         """One dense layer's rolling-origin forecast value, predictive means and variances in one library call, row r predicted from rows
         0 ... origin[r] - 1 (-1: not scored, NaN in its mean and variance): (value as a 0-d device tensor, info word, means, variances)."""

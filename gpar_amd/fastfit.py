@@ -264,14 +264,15 @@ class LockstepFactor:
 class DenseLayerObjective:
     """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or, with `objective="loo"`, minus the leave-one-out predictive
     log-density under the same covariance (gpar_loo_dense_grad), or, with `objective="cv"`, minus the blocked cross-validation value
-    over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad), or, with `objective="ahead"`, minus the
+    over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad; with `hold` = (hold_lo, hold_hi), the
+    blocks the folds are not predicted from, its purged form: gpar_cv_gap_dense_grad), or, with `objective="ahead"`, minus the
     rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad); `score` ("log", "crps", "se") is the rule "loo"
     and "ahead" score their held-out entries by (the *_score forms of their library calls) - and its gradient with respect to
     the latent (unconstrained) variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are
     device tensors that do not change during the optimisation."""
 
     def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
-                 fold_start=None, origin=None, score="log"):
+                 fold_start=None, origin=None, score="log", hold=None):
         if objective not in ("mll", "loo", "cv", "ahead"):
             raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
         self.score = hip.score_code(score)
@@ -281,12 +282,16 @@ class DenseLayerObjective:
             raise ValueError('fold_start belongs to objective="cv"')
         if (objective == "ahead") != (origin is not None):
             raise ValueError('origin belongs to objective="ahead"')
+        if hold is not None and objective != "cv":
+            raise ValueError('hold belongs to objective="cv"')
         # (host origins of the rows; their device copy is made once, with the other buffers)
         self.origin = None if origin is None else np.asarray(origin, dtype=np.int64).reshape(-1)
         self.eng, self.vs, self.names = eng, vs, list(names)
         self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
         # (host offsets of the folds; their device copy is made once, with the other buffers)
         self.fold_start = None if fold_start is None else np.asarray(fold_start, dtype=np.int64).reshape(-1)
+        self.hold = None if hold is None else tuple(np.asarray(h, dtype=np.int64).reshape(-1) for h in hold)   # (purged folds: block extents)
+        self.call = "cv_gap" if self.hold is not None else objective   # (the library call's family: `hip.objective_vec_doubles`)
         if objective != "mll":
             group = lane = None      # (cross-validation lanes take no part in the lock-step rendezvous)
         self.group, self.lane = group, lane   # a LockstepFactor and this objective's slot in it, or None
@@ -332,9 +337,11 @@ class DenseLayerObjective:
         nacc = _lib.GRAD_NACC
         # gradient partials, alpha; for the cross-validation objectives their vectors, the predictive means and variances behind them
         self.folds = hip.upload_folds(self.fold_start, n, dev) if self.objective == "cv" else ()   # (device offsets, number of folds, largest fold)
+        if self.hold is not None:
+            self.folds = hip.upload_hold(self.fold_start, self.hold, n, dev)   # (device offsets and block extents, number of folds, largest block)
         if self.objective == "ahead":
             self.folds = (hip.upload_origin(self.origin, n, dev),)   # (the one argument the entry takes in the folds' place)
-        nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.objective, n, 1, self.folds) + 2 * n
+        nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.call, n, 1, self.folds) + 2 * n
         nalpha = n + (n & 1)   # (the vectors start at an even offset: "ahead" keeps a matrix among them)
         self.work = torch.empty(self.nblocks * nacc + nalpha + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
@@ -375,8 +382,9 @@ class DenseLayerObjective:
                 p["W"], p["ldw"], p["alpha"])
         tail = (p["info"], self.flags, stream.cuda_stream)
         if self.objective != "mll":
-            name = {"loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad", "ahead": "gpar_ahead_dense_grad_score"}[self.objective]
-            fold_args = (self.folds[0].data_ptr(), *self.folds[1:]) if self.folds else ()
+            name = {"loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad", "cv_gap": "gpar_cv_gap_dense_grad",
+                    "ahead": "gpar_ahead_dense_grad_score"}[self.call]
+            fold_args = hip._fold_args(self.folds)
             rule = () if self.objective == "cv" else (self.score,)   # (the blocked form scores a fold's joint density: no rule to take)
             rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *rule,
                                          *tail)
@@ -497,16 +505,18 @@ class DenseLayerObjective:
 
 
 def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None, ahead=None,
-          score="log"):
+          score="log", purge=None):
     """The fast objective of layer `pi` of regressor `reg` with fixed design matrix `fixed_x`, or None when this route does not
     apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised;
     `objective`: "mll" (log marginal likelihood), "loo" (leave-one-out predictive log-density) or "cv" (blocked cross-validation over
     `folds`, one integer label per row of `fixed_x`: the layer's rows are sorted by label here, once; None when its largest fold
     exceeds what the library call takes - the general route trains it) or "ahead" (rolling-origin forecast score; `ahead` = (horizon,
     start, the indices in the data as given of the rows of `fixed_x`): the layer's origins are counted here, once, from the rows that
-    survive); `score`: the scoring rule of "loo" and "ahead"."""
+    survive); `score`: the scoring rule of "loo" and "ahead".  `purge` = (gap, the indices in the data as given of the rows of
+    `fixed_x`): purged cross-validation - `folds` then holds one non-decreasing label per row of the data AS GIVEN, and the layer's
+    fold offsets and block extents are counted here, once (`model.purged_folds`); None when its largest block exceeds the call's limit."""
     from .gp import one_call_grad_rows
-    from .model import contiguous_folds, host_index, rolling_origins
+    from .model import contiguous_folds, host_index, purged_folds, rolling_origins
     from .regression import _model_generator
 
     on_device = cls is None   # (the CPU tests of the host logic hand in a class with its own device side)
@@ -531,8 +541,16 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     n = int(X.shape[0])
     if not 0 < n <= one_call_grad_rows():
         return None
-    fold_start = None
-    if objective == "cv":
+    fold_start = hold = None
+    if objective == "cv" and purge is not None:
+        gap, rows = purge
+        observed = np.asarray(rows, dtype=np.int64).reshape(-1)[host_index(mask)]
+        if not isinstance(mask, slice) and n_missing:
+            observed = observed[host_index(keep)]
+        fold_start, hold = purged_folds(folds, observed, gap)
+        if int((hold[1] - hold[0]).max()) > _lib.CV_MAX_FOLD:
+            return None
+    elif objective == "cv":
         labels = np.asarray(folds).reshape(-1)[host_index(mask)]
         if not isinstance(mask, slice) and n_missing:
             labels = labels[host_index(keep)]
@@ -563,4 +581,5 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
         group = None
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
                lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}),
-               **({} if origin is None else {"origin": origin}), **({} if score == "log" else {"score": score}))
+               **({} if origin is None else {"origin": origin}), **({} if score == "log" else {"score": score}),
+               **({} if hold is None else {"hold": hold}))

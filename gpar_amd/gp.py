@@ -39,7 +39,7 @@ import torch
 
 from ._lib import CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
 from .engine import get_engine, joining
-from .hip import fold_offsets, origin_array, upload_origin
+from .hip import fold_offsets, hold_extents, origin_array, upload_hold, upload_origin
 from .kernels import Kernel
 
 __all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs", "greedy_inducing"]
@@ -398,6 +398,62 @@ def _cv_algebra(eng, Kinv, alpha, starts):
             S[:, idx.reshape(-1)] = cols.permute(1, 0, 2).reshape(n, -1)
 
     return value, b, b, var, fill
+
+
+class _Purged:
+    """The fourth held-out scheme: contiguous folds, each predicted from the rows outside a block that contains it (`Obs.cv(..., hold)`)."""
+
+    def __init__(self, starts, lo, hi):
+        self.starts, self.lo, self.hi = starts, lo, hi   # checked host arrays (int64): nfolds + 1 offsets, nfolds block extents
+        self.device = None                               # the uploaded copy, made at the first fused call
+
+
+class _DenseC:
+    """What `_cv_gap_algebra` hands the gradient in the place of a function filling S: C itself, which is indefinite - no S S^T."""
+
+    def __init__(self, C):
+        self.C = C
+
+
+def _cv_gap_algebra(eng, Kinv, alpha, purged):
+    """Purged folds with blocks of any size: batched algebra over the folds of equal (|F|, |G left|, |G right|).  Per fold, with the block
+    P_HH ordered (G, F) and factored, P_HH = L L^T, N = L^-1, w = N alpha_H: the leading pivots factor P_GG and the trailing ones the
+    Schur complement Dt, so value term = sum_F log L_ii - 1/2 |w_F|^2; e = N^T w = P_HH^-1 alpha_H holds y_F - mean on F; the predictive
+    covariance is N_FF^T N_FF; b_H = N_F^T w_F, g = e - b_H = N_G^T w_G and C_H = 1/2 (N_F^T N_F + e e^T - g g^T).  The
+    blocks of neighbouring folds overlap: b and C are summed group by group, the folds of a group chosen with disjoint blocks, so that
+    every sum has a fixed order."""
+    n, dev = alpha.numel(), alpha.device
+    starts, lo, hi = purged.starts, purged.lo, purged.hi
+    first, end = starts[:-1], starts[1:]
+    err, var, b = torch.empty_like(alpha), torch.empty_like(alpha), torch.zeros_like(alpha)
+    C = torch.zeros(n, n, dtype=torch.float64, device=dev)
+    value = torch.zeros((), dtype=torch.float64, device=dev)
+    colour, reach = np.zeros(first.size, dtype=np.int64), []   # (greedy: the first colour whose last block ends before this one begins)
+    for f in range(first.size):
+        c = next((c for c, h in enumerate(reach) if h <= lo[f]), len(reach))
+        reach[c:c + 1] = [hi[f]]
+        colour[f] = c
+    shape = np.stack([end - first, first - lo, hi - end, colour], axis=1)
+    for m, gl, gr, c in np.unique(shape, axis=0):
+        fs = np.nonzero(np.all(shape == [m, gl, gr, c], axis=1))[0]
+        g = int(gl + gr)
+        rows = np.concatenate([lo[fs, None] + np.arange(gl), end[fs, None] + np.arange(gr), first[fs, None] + np.arange(m)], axis=1)
+        idx = torch.as_tensor(rows, dtype=torch.long, device=dev)   # k x |H|, in the block's order
+        L, info = torch.linalg.cholesky_ex(Kinv[idx[:, :, None], idx[:, None, :]])
+        eng.check_info(info.max().reshape(1).to(torch.int32))
+        N = torch.linalg.solve_triangular(L, torch.eye(g + int(m), dtype=torch.float64, device=dev).expand_as(L), upper=False)
+        w = torch.matmul(N, alpha[idx][:, :, None])
+        NF = N[:, g:, :]
+        b_h = torch.matmul(NF.transpose(1, 2), w[:, g:])[:, :, 0]
+        g_h = torch.matmul(N[:, :g, :].transpose(1, 2), w[:, :g])[:, :, 0]
+        e_h = b_h + g_h
+        F = idx[:, g:]
+        err[F], var[F] = e_h[:, g:], torch.sum(NF[:, :, g:] ** 2, dim=1)
+        value = value + torch.sum(torch.log(torch.diagonal(L, dim1=1, dim2=2)[:, g:])) - 0.5 * torch.sum(w[:, g:] ** 2)
+        b[idx] = b[idx] + b_h
+        at = (idx[:, :, None], idx[:, None, :])
+        C[at] = C[at] + 0.5 * (torch.matmul(NF.transpose(1, 2), NF) + e_h[:, :, None] * e_h[:, None, :] - g_h[:, :, None] * g_h[:, None, :])
+    return value, err, b, var, _DenseC(C)
 
 
 class _Origins:
@@ -827,14 +883,20 @@ class Obs:
         (minus PRESS); mean and var are the same under every rule, and the value is always one to maximise."""
         return self._held_out(None, "leave-one-out", check_score(score))
 
-    def cv(self, fold_start):
+    def cv(self, fold_start, hold=None):
         """(value, mean, var) of blocked (leave-fold-out) cross-validation over contiguous folds of the observations, given by their
         nfolds + 1 ascending row offsets (0 ... n).  With P = S^-1, alpha = P (y - m) and per fold D_F = P[F, F], b_F = D_F^-1 alpha_F:
         y_F given all other observations ~ N(y_F - b_F, D_F^-1); mean and var hold y_F - b_F and the marginal variances diag D_F^-1, and
         value = sum_F log N(y_F; y_F - b_F, D_F^-1), the JOINT fold densities - a 0-d tensor that carries a gradient with respect to
         the kernel parameters and the noise where they require one (observations of a prior process).  Folds of one row give `loo`;
-        one fold of every row gives `logpdf`."""
-        return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
+        one fold of every row gives `logpdf`.  `hold`: purged (hv-block) cross-validation, the observations in the order given (the time
+        order) - the pair (hold_lo, hold_hi), one int per fold: fold f is predicted from the rows OUTSIDE hold_lo[f] ... hold_hi[f] - 1, a
+        block that contains the fold (`hip.hold_extents`); its other rows are neither scored nor conditioned on.  With G = H without F the
+        formulas above hold for Dt = P_FF - P_FG P_GG^-1 P_GF and at = alpha_F - P_FG P_GG^-1 alpha_G in the place of D_F and alpha_F.
+        None: the blocks are the folds themselves, today's route."""
+        if hold is None:
+            return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
+        return self._held_out(_Purged(*hold_extents(fold_start, hold, self.fdd.n)), "cross-validation")
 
     def ahead(self, origin, score="log"):
         """(value, mean, var) of rolling-origin forecasts, the observations in the order given (the time order): row r is predicted from
@@ -881,11 +943,18 @@ class Obs:
             self._held_out_mean = self._held_out_var = torch.zeros(0, dtype=torch.float64, device=dev)
             self._held_out_parts = None
             return torch.zeros((), dtype=torch.float64, device=dev)
-        ahead = isinstance(starts, _Origins)
-        call = "ahead_dense" if ahead else "loo_dense" if starts is None else "cv_dense"
+        ahead, purged = isinstance(starts, _Origins), isinstance(starts, _Purged)
+        call = "ahead_dense" if ahead else "cv_gap_dense" if purged else "loo_dense" if starts is None else "cv_dense"
         folds = () if starts is None else (starts,)
         rule = {} if score == "log" else {"score": score}   # (an engine's one-call forms take the rule by keyword)
-        fits = starts is None or ahead or int(np.diff(starts).max()) <= CV_MAX_FOLD
+        if purged:   # (the fused calls hold a fold AND its purged rows in one tile)
+            fits = int((starts.hi - starts.lo).max()) <= CV_MAX_FOLD
+            if fits and hasattr(eng, call) and (self._fusable_grad() if want_grad else self._value_only()):
+                if starts.device is None:
+                    starts.device = upload_hold(starts.starts, (starts.lo, starts.hi), n, dev)
+                folds = (starts.device, None)
+        else:
+            fits = starts is None or ahead or int(np.diff(starts).max()) <= CV_MAX_FOLD
         if ahead and fits and hasattr(eng, call) and (self._fusable_grad() if want_grad else self._value_only()):
             if starts.device is None:
                 starts.device = upload_origin(starts.origin, n, dev)
@@ -913,7 +982,10 @@ class Obs:
         low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
         Kinv = low + torch.tril(low, -1).T
         alpha = fac.alpha().reshape(-1).detach()
-        value, e, b, var, fill = _loo_algebra(Kinv, alpha, score) if starts is None else _cv_algebra(eng, Kinv, alpha, starts)
+        if purged:
+            value, e, b, var, fill = _cv_gap_algebra(eng, Kinv, alpha, starts)
+        else:
+            value, e, b, var, fill = _loo_algebra(Kinv, alpha, score) if starts is None else _cv_algebra(eng, Kinv, alpha, starts)
         y = self.y.reshape(-1).detach()
         self._held_out_mean, self._held_out_var = y - e, var
         self._held_out_parts = (Kinv, alpha, b, fill) if want_grad else None
@@ -943,9 +1015,17 @@ class Obs:
         self._held_out_parts = None
         u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
         S = eng.new_matrix(n, n)
-        fill(S)
         W = eng.new_matrix(n, n)
-        eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
+        if isinstance(fill, _DenseC):   # purged folds: C is indefinite and banded, not block-diagonal R R^T:  K^-1 C K^-1 as K^-1 (C K^-1)
+            P, Cm = eng.new_matrix(n, n), eng.new_matrix(n, n)
+            P.copy_(Kinv)
+            Cm.copy_(fill.C)
+            eng.gemm(Cm, P, out=S)
+            eng.gemm(P, S, alpha=-2.0, out=W, c_lower=True)
+            del P, Cm
+        else:
+            fill(S)
+            eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
         left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
         left.copy_(torch.stack([alpha, u]))
         right.copy_(torch.stack([u, alpha]))

@@ -130,9 +130,16 @@ def _folds_of(objective, fold_start, n, dev):
     the one-element tuple of the device origins (`fold_start` holds them), uploaded unless they are a device tensor already."""
     if objective == "ahead":
         return (fold_start if isinstance(fold_start, torch.Tensor) and fold_start.is_cuda else upload_origin(fold_start, n, dev),)
+    if objective == "cv_gap":   # (`fold_start`: the pair (offsets, (hold_lo, hold_hi)), or the five-tuple `upload_hold` returns)
+        return fold_start if len(fold_start) == 5 else upload_hold(fold_start[0], fold_start[1], n, dev)
     if objective != "cv":
         return ()
     return fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
+
+
+def _fold_args(folds):
+    """The folds of `_folds_of` as the arguments an entry takes: device arrays by their pointers, counts as they are."""
+    return tuple(f.data_ptr() if isinstance(f, torch.Tensor) else f for f in folds)
 
 
 def objective_vec_doubles(lib, objective, n, grad, folds):
@@ -141,6 +148,8 @@ def objective_vec_doubles(lib, objective, n, grad, folds):
         return 0
     if objective == "ahead":
         return int(lib.gpar_workspace_doubles(_lib.WS_AHEAD, n, grad, 0))
+    if objective == "cv_gap":
+        return int(lib.gpar_workspace_doubles(_lib.WS_CV_GAP, n, grad, folds[4]))
     return int(lib.gpar_workspace_doubles(_lib.WS_CV, n, grad, folds[2]) if objective == "cv" else lib.gpar_workspace_doubles(_lib.WS_LOO, n, grad, 0))
 
 
@@ -160,7 +169,7 @@ def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, l
     rule = (score_code(score),) if objective in ("loo", "ahead") else ()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
     folds = _folds_of(objective, fold_start, n, dev)
-    fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
+    fold_args = _fold_args(folds)
     dz = max(ck.dz, 1)
     z = alloc_matrix(n, dz, dev)
     zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
@@ -183,11 +192,12 @@ def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, l
     if objective == "mll":
         rc = lib.gpar_logpdf_dense_grad(*head, work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), *tail)
     else:
-        entry = {"loo": lib.gpar_loo_dense_grad_score, "cv": lib.gpar_cv_dense_grad, "ahead": lib.gpar_ahead_dense_grad_score}[objective]
+        entry = {"loo": lib.gpar_loo_dense_grad_score, "cv": lib.gpar_cv_dense_grad, "cv_gap": lib.gpar_cv_gap_dense_grad,
+                 "ahead": lib.gpar_ahead_dense_grad_score}[objective]
         rc = entry(*head, work[nblocks * nacc + nalpha:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(),
                    vectors[1].data_ptr(), vectors[2].data_ptr(), *fold_args, *rule, *tail)
     _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad",
-                    "ahead": "gpar_ahead_dense_grad_score"}[objective])
+                    "cv_gap": "gpar_cv_gap_dense_grad", "ahead": "gpar_ahead_dense_grad_score"}[objective])
     return out, vectors, info, A, W
 
 
@@ -199,7 +209,7 @@ def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead,
     rule = (score_code(score),) if objective in ("loo", "ahead") else ()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
     folds = _folds_of(objective, fold_start, n, dev)
-    fold_args = (folds[0].data_ptr(), *folds[1:]) if folds else ()
+    fold_args = _fold_args(folds)
     z = alloc_matrix(n, max(ck.dz, 1), dev)
     A = alloc_matrix(n + 1, n + 1, dev)
     if objective == "ahead":   # the factor and its augmented row are all the entry reads: no X, no scratch matrix
@@ -223,7 +233,8 @@ def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead,
     out = torch.empty(2, dtype=torch.float64, device=dev)
     moments = torch.empty(2, n, dtype=torch.float64, device=dev)
     info = torch.empty(1, dtype=torch.int32, device=dev)
-    entry = lib.gpar_cv_dense if objective == "cv" else lib.gpar_loo_dense_score
+    name = {"cv": "gpar_cv_dense", "cv_gap": "gpar_cv_gap_dense"}.get(objective, "gpar_loo_dense_score")
+    entry = getattr(lib, name)
     _lib.check(
         entry(
             ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
@@ -231,7 +242,7 @@ def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead,
             T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(),
             *fold_args, *rule, info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
         ),
-        "gpar_cv_dense" if objective == "cv" else "gpar_loo_dense_score",
+        name,
     )
     return out, moments[0], moments[1], info
 
@@ -280,6 +291,35 @@ def upload_folds(fold_start, n, device):
     return torch.tensor(starts, dtype=torch.int32, device=device), int(sizes.size), int(sizes.max())
 
 
+def hold_extents(fold_start, hold, n):
+    """(offsets, hold_lo, hold_hi) of purged cross-validation as checked host arrays (int64): the offsets as `fold_offsets` checks them, and
+    per fold the block [hold_lo[f], hold_hi[f]) it is not predicted from - inside 0 ... n, containing the fold, neither end decreasing from
+    one fold to the next.  The one check of these extents: `gp.Obs.cv` and `upload_hold` both go through it."""
+    starts = fold_offsets(fold_start, n)
+    if not isinstance(hold, (tuple, list)) or len(hold) != 2:
+        raise ValueError("hold must be the pair (hold_lo, hold_hi)")
+    lo, hi = (np.asarray(h.cpu() if isinstance(h, torch.Tensor) else h) for h in hold)
+    nfolds = starts.size - 1
+    for h in (lo, hi):
+        if h.ndim != 1 or h.size != nfolds or (h.size and not np.issubdtype(h.dtype, np.integer)):
+            raise ValueError("hold_lo and hold_hi must hold one integer per fold")
+    lo, hi = lo.astype(np.int64), hi.astype(np.int64)
+    if nfolds and (np.any(lo < 0) or np.any(hi > n) or np.any(lo > starts[:-1]) or np.any(hi < starts[1:]) or np.any(np.diff(lo) < 0)
+                   or np.any(np.diff(hi) < 0)):
+        raise ValueError("every block hold_lo[f] ... hold_hi[f] must lie in 0 ... n and contain its fold, neither end decreasing along the folds")
+    return starts, lo, hi
+
+
+def upload_hold(fold_start, hold, n, device):
+    """(device int32 offsets, hold_lo, hold_hi, nfolds, largest block): what the fused purged cross-validation entries take, from extents
+    checked by `hold_extents`; a block of more than GPAR_CV_MAX_FOLD rows is a ValueError."""
+    starts, lo, hi = hold_extents(fold_start, hold, n)
+    if lo.size == 0 or int((hi - lo).max()) > _lib.CV_MAX_FOLD:
+        raise ValueError(f"the fused purged cross-validation takes 1 to {_lib.CV_MAX_FOLD} rows per fold, its purged rows included")
+    up = lambda a: torch.tensor(a, dtype=torch.int32, device=device)   # noqa: E731
+    return up(starts), up(lo), up(hi), int(lo.size), int((hi - lo).max())
+
+
 def origin_array(origin, n):
     """The n origins of a rolling-origin evaluation as a checked host array (int64): -1 (not scored) or 0 ... r for row r.  The one check
     of origins: `gp.Obs.ahead` and `upload_origin` both go through it."""
@@ -322,6 +362,21 @@ def cv_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead=
     """One dense layer's blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_dense_grad).
     `fold_start` as for `cv_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
     out, vectors, info, A, W = _dense_grad("cv", ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused)
+    return out, vectors[0], vectors[1], vectors[2], info, A, W
+
+
+def cv_gap_dense(ck, x, y, noise_diag, jitter, fold_start, hold, lookahead=True, fused=True):
+    """Purged blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_gap_dense).
+    `fold_start`: the offsets of the scored folds; `hold`: the pair (hold_lo, hold_hi) of the blocks the folds are not predicted from
+    (`hold_extents`); or `fold_start` the five-tuple `upload_hold` returns and `hold` None.  Returns what `cv_dense` returns."""
+    return _dense_value("cv_gap", ck, x, y, noise_diag, jitter, fold_start if hold is None else (fold_start, hold), lookahead, fused)
+
+
+def cv_gap_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, hold, lookahead=True, fused=True):
+    """One dense layer's purged blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_gap_dense_grad).
+    `fold_start`, `hold` as for `cv_gap_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
+    out, vectors, info, A, W = _dense_grad("cv_gap", ck, x, y, noise_diag, jitter, periodic, fold_start if hold is None else (fold_start, hold),
+                                           lookahead, fused)
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 

@@ -242,6 +242,31 @@ def contiguous_folds(labels):
     return perm, starts
 
 
+def check_gap(gap):
+    """`gap` of purged cross-validation: an int >= 0 (no bool, no float)."""
+    if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)) or gap < 0:
+        raise ValueError(f"gap={gap!r}: the number of purged rows on either side of a fold must be an int >= 0")
+    return int(gap)
+
+
+def purged_folds(labels, observed, gap):
+    """(starts, (hold_lo, hold_hi)) of a layer for purged cross-validation.  `labels`: one fold label per row of the data as given,
+    non-decreasing - fold F is the run of rows span_lo ... span_hi with its label, missing values or not; `observed`: the (ascending)
+    indices, in the data as given, of the rows the layer observes.  Among the layer's rows, fold F scores those with index in
+    span_lo ... span_hi and is predicted from those outside span_lo - gap ... span_hi + gap: the gap counts rows as given, so missing
+    values make the purge ragged (as `rolling_origins` counts a horizon).  Folds that score no row of the layer vanish.  `starts`: the
+    offsets of the scored runs among the layer's rows; hold_lo / hold_hi: per fold the first row of its block and one past the last."""
+    labels, observed = np.asarray(labels).reshape(-1), np.asarray(observed, dtype=np.int64)
+    change = np.nonzero(np.diff(labels))[0] + 1
+    span_lo, span_end = np.concatenate([[0], change]), np.concatenate([change, [labels.size]])   # (one past the last row of the span)
+    first, end = np.searchsorted(observed, span_lo), np.searchsorted(observed, span_end)
+    keep = end > first
+    starts = np.concatenate([first[keep], [observed.size]]).astype(np.int64)
+    hold_lo = np.searchsorted(observed, span_lo[keep] - int(gap)).astype(np.int64)
+    hold_hi = np.searchsorted(observed, span_end[keep] + int(gap)).astype(np.int64)
+    return starts, (hold_lo, hold_hi)
+
+
 def per_output(y, w=None, keep=False):
     """Per layer: `(y_i (n_i x 1), w_i (n_i,), mask_i)` where `mask_i` selects, among the rows that survived
     layer i-1, those observed at output i (or, with `keep`, at any later output: rows needed to keep the data
@@ -655,7 +680,7 @@ class GPAR:
         return _retry_unfused(lambda: self._held_out(x, y, w, None, outputs, score), self.layers, (x, y, w))
 
     # ---- blocked cross-validation ---------------------------------------------------------------------
-    def cv(self, x, y, w, folds, outputs=None):
+    def cv(self, x, y, w, folds, outputs=None, gap=0, rows=None):
         """Layer-wise blocked (leave-fold-out) cross-validation: `loo` with whole folds held out and scored by their joint predictive
         density.  `folds`: one integer label per row of the x handed in; per layer the labels are restricted to the rows observed at
         that output (folds left empty vanish) and each fold's observed entries are left out together.  Returns (total, pieces): the
@@ -663,13 +688,27 @@ class GPAR:
         and noise where they require one - and per visited layer (rows, mean, var): the rows of the x handed in that are observed at
         output i, in their order there, with the predictive mean and marginal variance of each given every fold but its own.  Rows
         are sorted by label (stably; not at all where the labels already ascend) for the evaluation alone: the inputs forwarded to the
-        next layer keep their order.  `outputs` as for `loo`.  Inducing points: ValueError."""
+        next layer keep their order.  `outputs` as for `loo`.  Inducing points: ValueError.  `gap` > 0: purged (hv-block)
+        cross-validation, the rows in the order given (the time order) - when a fold is held out, the layer's observed rows within `gap`
+        rows, counted in the data as given, before its first and after its last row are taken out of the conditioning set too, without
+        being scored (`purged_folds`).  The labels must then be non-decreasing - every fold one run of consecutive rows: ValueError
+        otherwise.  gap = 0 is the evaluation above, bit for bit.  `rows` (with a gap alone): the indices, in the data as given, of the
+        rows of the x handed in where earlier layers have dropped some, as for `ahead` - `folds` then labels the rows of the data as
+        given."""
         if self.sparse:
             raise ValueError("cross-validation needs dense observations (no inducing points)")
+        gap = check_gap(gap)
         labels = np.asarray(folds.cpu() if _is_torch(folds) else folds).reshape(-1)
-        if labels.size != int(x.shape[0]) or not np.issubdtype(labels.dtype, np.integer):
+        rows = None if rows is None or not gap else np.asarray(rows, dtype=np.int64)
+        if rows is None:
+            sized = labels.size == int(x.shape[0])
+        else:
+            sized = rows.size == int(x.shape[0]) and (rows.size == 0 or labels.size > int(rows.max()))
+        if not sized or not np.issubdtype(labels.dtype, np.integer):
             raise ValueError("folds must hold one integer label per row of x")
-        return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs), self.layers, (x, y, w))
+        if gap and np.any(np.diff(labels) < 0):
+            raise ValueError("gap > 0 needs fold labels that do not decrease along the rows: a gap in time has no meaning for scattered folds")
+        return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs, gap=gap, rows=rows), self.layers, (x, y, w))
 
     # ---- rolling-origin forecast scoring --------------------------------------------------------------
     def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None, score="log"):
@@ -689,7 +728,7 @@ class GPAR:
         rows = None if rows is None else np.asarray(rows, dtype=np.int64)
         return _retry_unfused(lambda: self._held_out(x, y, w, _Ahead(int(horizon), int(start), rows), outputs, score), self.layers, (x, y, w))
 
-    def _held_out(self, x, y, w, labels, outputs, score="log"):
+    def _held_out(self, x, y, w, labels, outputs, score="log", gap=0, rows=None):
         """The layer loop of `loo` (`labels` None: pieces carry the per-row log-density, and nothing is kept on the host), `cv` and
         `ahead` (`labels` an `_Ahead`: the origins of a layer are counted on the host from the rows observed there)."""
         x, y, w = self._prep(x, y, w)
@@ -697,10 +736,13 @@ class GPAR:
         eng = get_engine()
         rolling = isinstance(labels, _Ahead)
         blocked = labels is not None and not rolling
+        given = rows   # (purged folds: where in the data as given the rows of x lie, None: x holds every row)
         rows = torch.arange(int(x.shape[0]), device=x.device)
         rows_host = np.arange(int(x.shape[0])) if labels is not None else None   # (the same rows on the host: the labels live there)
         if rolling and labels.rows is not None:
             rows_host = labels.rows
+        if blocked and given is not None:
+            rows_host = given
         total, pieces = torch.zeros((), dtype=torch.float64), []
         with eng.defer_checks():
             for is_last, (i, ((yi, wi, mask), model)) in last(enumerate(zip(items, self.layers)), select=outputs):
@@ -716,18 +758,20 @@ class GPAR:
                 else:
                     sel = ~torch.isnan(yi[:, 0])
                     seen = rows[sel]
-                perm = None
+                perm = hold = None
                 if labels is not None:
                     rows_host = rows_host[host_index(mask)]
                     observed = rows_host if sel is None else rows_host[host_index(sel)]
-                    if blocked:
+                    if blocked and gap:   # (the labels ascend: nothing to sort)
+                        starts, hold = purged_folds(labels, observed, gap)
+                    elif blocked:
                         perm, starts = contiguous_folds(labels[observed])
                 if perm is None:
                     obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
                     if rolling:
                         value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start), score)
                     else:
-                        value, mean, var = obs.cv(starts) if blocked else obs.loo(score)
+                        value, mean, var = obs.cv(starts, hold) if blocked else obs.loo(score)
                 else:
                     # the evaluation's own observations, rows sorted by fold; `obs` keeps the order the next layer reads
                     at = torch.as_tensor(perm, dtype=torch.long, device=obs.y.device)

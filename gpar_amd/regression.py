@@ -17,7 +17,7 @@ from ._lib import CHOL_UPDATE_MAX_RANK
 from .engine import get_engine
 from .gp import GP, Measure, check_score, greedy_inducing
 from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
-from .model import GPAR, host_index, host_masks, per_output
+from .model import GPAR, check_gap, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
 from .vars import Vars
 
@@ -227,7 +227,7 @@ def _check_horizon(horizon, start, n):
     return int(horizon), int(start)
 
 
-def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log"):
+def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log", gap=None):
     """The training objectives `fit` knows, and what the held-out ones need."""
     if objective not in ("mll", "loo", "cv", "ahead"):
         raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
@@ -242,10 +242,22 @@ def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=Non
         raise ValueError('objective="cv" needs folds: a number of contiguous blocks or one integer label per row')
     if objective != "cv" and folds is not None:
         raise ValueError('folds belong to objective="cv"')
+    if gap is not None:
+        check_gap(gap)
+        if objective != "cv":
+            raise ValueError('gap belongs to objective="cv"')
     if objective != "mll" and sparse:
         raise ValueError(f'objective="{objective}" needs dense layers: not available with inducing points (x_ind)')
     if objective != "mll" and not fix:
         raise NotImplementedError(f'objective="{objective}" trains layers with fixed inputs (fix=True) only')
+
+
+def _check_purge(gap, labels):
+    """`gap` of `cv` / `fit(objective="cv")` (None: 0) against the fold labels: purged rows need every fold to be one run of rows."""
+    gap = 0 if gap is None else check_gap(gap)
+    if gap and np.any(np.diff(labels) < 0):
+        raise ValueError("gap > 0 needs fold labels that do not decrease along the rows: a gap in time has no meaning for scattered folds")
+    return gap
 
 
 def _fold_labels(folds, n):
@@ -359,7 +371,7 @@ class GPARRegressor:
         self.is_conditioned = True
 
     def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, horizon=None, start=None,
-            score="log", **kw_args):
+            score="log", gap=None, **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
 
@@ -367,7 +379,8 @@ class GPARRegressor:
         (`loo`; Rasmussen & Williams 5.4.2) - more robust where the kernel family is misspecified.  "loo" needs dense layers with
         fixed inputs: ValueError with inducing points, NotImplementedError with `fix=False`.  "cv" is the blocked form for ordered data
         (`cv`): whole folds are held out and scored by their joint predictive density; it needs `folds` (as `cv` takes them), which
-        no other objective accepts, and has the restrictions of "loo".  "ahead" is the rolling-origin forecast score (`ahead`): every
+        no other objective accepts, and has the restrictions of "loo"; `gap` (an int >= 0, default 0, "cv" alone) purges that many rows
+        on either side of a held-out fold from the rows it is predicted from (`cv`), for which the labels must not decrease.  "ahead" is the rolling-origin forecast score (`ahead`): every
         row predicted from the rows at least `horizon` (default 1) rows before it, rows before `start` (default 0) not scored - for
         models whose purpose is the forecast at that horizon; `horizon` / `start` belong to it alone; the restrictions of "loo".
 
@@ -379,7 +392,7 @@ class GPARRegressor:
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start, score)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -387,15 +400,17 @@ class GPARRegressor:
             raise NotImplementedError("Greedy search is not implemented yet.")
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
-        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, score=score, **kw_args)
+        self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, score=score,
+                    **({} if gap is None else {"gap": gap}), **kw_args)
 
     def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, horizon=None, start=None, score="log",
-               **kw_args):
+               gap=None, **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start, score)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap)
         loo, cv, ahead = objective == "loo", objective == "cv", objective == "ahead"
         labels = _fold_labels(folds, self.n) if cv else None
+        gap = _check_purge(gap, labels) if cv else 0   # (0: blocked cross-validation as it was - the calls below are then today's)
         if ahead:
             horizon, start = _check_horizon(1 if horizon is None else horizon, 0 if start is None else start, self.n)
         self._x_ind_trainable = bool(optimise_x_ind) or getattr(self, "_x_ind_trainable", False)
@@ -421,7 +436,7 @@ class GPARRegressor:
             # (the fold labels of the rows that reach this layer: earlier layers' masks have dropped the others from fixed_x)
             layer_labels = labels[_surviving_rows(y_cached[bool(self.impute)], pi, self.n)] if cv else None
             # (rolling origins count rows of the data as given: the indices there of the rows that reach this layer)
-            layer_rows = _surviving_rows(y_cached[bool(self.impute)], pi, self.n) if ahead else None
+            layer_rows = _surviving_rows(y_cached[bool(self.impute)], pi, self.n) if ahead or gap else None
 
             def neg_value(vs):
                 gpar = _construct_gpar(self, vs, self.m, pi + 1)
@@ -431,6 +446,8 @@ class GPARRegressor:
                         x_ind_pi = torch.cat([eng.tensor(vs["x_ind"]), fixed_x_ind[:, self.m :]], dim=1)
                     if loo:
                         return -gpar.loo(fixed_x, y_cached, None, outputs=[pi], score=score)[0]
+                    if cv and gap:   # (a gap counts rows of the data as given, as a horizon does: the labels of all rows, and which reach this layer)
+                        return -gpar.cv(fixed_x, y_cached, None, labels, outputs=[pi], gap=gap, rows=layer_rows)[0]
                     if cv:
                         return -gpar.cv(fixed_x, y_cached, None, layer_labels, outputs=[pi])[0]
                     if ahead:
@@ -456,7 +473,8 @@ class GPARRegressor:
                     return general[0](x)
 
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
-                                     group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv else {}),
+                                     group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv and not gap else {}),
+                                     **({"folds": labels, "purge": (gap, layer_rows)} if gap else {}),
                                      **({"ahead": (horizon, start, layer_rows)} if ahead else {}), **({} if score == "log" else {"score": score}))
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
@@ -756,7 +774,7 @@ class GPARRegressor:
         value = value.detach() if any_torch else value.detach().cpu().numpy()
         return value, mean, var
 
-    def cv(self, x, y, w=None, folds=None, score="log"):
+    def cv(self, x, y, w=None, folds=None, score="log", gap=0):
         """Layer-wise blocked (leave-fold-out) cross-validation under the prior model (`GPAR.cv`): `(value, mean, var)` with the
         conventions of `loo`.  `folds`: an int k - k contiguous blocks of the rows as given, split as `np.array_split` splits them, the
         estimator for time series and other ordered data, where a single left-out point is predicted almost for free from its
@@ -765,7 +783,15 @@ class GPARRegressor:
         given every other fold's; `mean` and `var` are n x p numpy arrays of the predictive means and marginal variances (the diagonals
         of the folds' predictive covariances), NaN where y is missing.  Folds of one row give `loo`; one fold gives `logpdf` for one
         output.  `score`: "log" alone - a fold is scored by its JOINT density, which has no per-row scoring rule ("crps" and "se"
-        belong to `loo` and `ahead`: ValueError).  Dense layers only: ValueError with inducing points."""
+        belong to `loo` and `ahead`: ValueError).  Dense layers only: ValueError with inducing points.
+
+        `gap` (an int >= 0): purged, or hv-block, cross-validation (Burman, Chow & Nolan 1994; Racine 2000), the rows in the order given
+        (the time order).  When a fold is held out, the `gap` rows before its first and after its last row are removed from the
+        conditioning set as well, without being scored - the first and last rows of a held-out block otherwise keep a training row
+        one step away.  The fold's span comes from the labels (missing values or not) and the gap counts rows as given, so per output
+        missing values make the purge ragged; the first and last fold are purged on one side.  The labels must then not decrease
+        along the rows (an int k never does): ValueError otherwise.  Every observed row is still scored exactly once; one fold gives
+        `logpdf` whatever the gap, a gap >= n predicts every fold from the prior, and gap = 0 is the evaluation above, bit for bit."""
         if check_score(score) != "log":
             raise ValueError(f'score="{score}" belongs to loo and ahead: a fold is scored by its joint density, which has no per-row scoring rule')
         if self.sparse:
@@ -778,9 +804,10 @@ class GPARRegressor:
         w = _init_weights(w, y)
         m, p = x.shape[1], y.shape[1]
         labels = _fold_labels(folds, int(x.shape[0]))
+        gap = _check_purge(check_gap(gap), labels)
         self._prepare_kernels(m, p, int(x.shape[0]))
         with torch.no_grad():
-            value, pieces = _construct_gpar(self, self.vs, m, p).cv(x, y, w, labels)
+            value, pieces = _construct_gpar(self, self.vs, m, p).cv(x, y, w, labels, **({"gap": gap} if gap else {}))
         mean = np.full((int(x.shape[0]), p), np.nan)
         var = np.full((int(x.shape[0]), p), np.nan)
         for i, (rows, mean_i, var_i) in enumerate(pieces):

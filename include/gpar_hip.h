@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 13
+#define GPAR_ABI_VERSION 14
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -303,6 +303,49 @@ int gpar_cv_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* 
                   const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
                   double* vec, double* out, double* cv_mean, double* cv_var, const int* fold_start, int nfolds, int max_fold, int* info,
                   int potrf_flags, void* stream);
+
+/* Purged (hv-block) blocked cross-validation of one dense layer (ABI v14; Burman, Chow & Nolan 1994, Racine 2000): gpar_cv_dense* with,
+ * per fold, further rows on either side of it taken out of the conditioning set without being scored - on ordered data the first and last
+ * rows of a held-out block otherwise keep a training row one step away.  The entries mirror gpar_cv_dense* argument for argument, with
+ * (fold_start, hold_lo, hold_hi, nfolds, max_hold) in the place of (fold_start, nfolds, max_fold).  fold_start: as there - the SCORED rows
+ * F_f = [fold_start[f], fold_start[f + 1]).  hold_lo, hold_hi: DEVICE arrays of nfolds ints, the block H_f = [hold_lo[f], hold_hi[f])
+ * that fold f is NOT predicted from: 0 <= hold_lo[f] <= fold_start[f], fold_start[f + 1] <= hold_hi[f] <= n, neither decreasing in f.
+ * max_hold: the host's bound on the largest block, 1 <= max_hold <= GPAR_CV_MAX_FOLD (otherwise an argument error: nothing is launched).
+ * With P = S^-1, alpha = P y, G = H \ F and the block P_HH:
+ *   Dt = P_FF - P_FG P_GG^-1 P_GF,  at = alpha_F - P_FG P_GG^-1 alpha_G,  bt = Dt^-1 at:   y_F given the rows outside H ~ N(y_F - bt, Dt^-1),
+ *   cv_mean[F] = y_F - bt,  cv_var[F] = diag(Dt^-1),  out[0] = sum_F [1/2 log|Dt| - 1/2 at^T bt] - n/2 log 2 pi.
+ * hold = the folds' own extents gives gpar_cv_dense* (other bits: another chain); one fold gives the log marginal likelihood; blocks that
+ * reach both ends predict every fold from the prior.  The gradient forms return out[1], out[2 ...] and half_diag as gpar_cv_dense_grad for
+ *   W = alpha u^T + u alpha^T - 2 P C P,  u = P b,  b = sum_f E_H b_H,  C = sum_f E_H C_H E_H^T,
+ *   Sigma = P_HH^-1,  e = Sigma alpha_H,  b_H = Sigma[:, F] at,  C_H = Sigma Sm Sigma + 1/2 (e b_H^T + b_H e^T),  Sm = 1/2 (Dt - at at^T) on F.
+ * The blocks of neighbouring folds overlap and C_H is indefinite, so C is a symmetric band matrix of half-bandwidth < max_hold and no
+ * R R^T.  Launches behind K^-1: the purged fold kernel (one workgroup per fold, in LDS: alpha_H, one factorisation of P_HH ordered
+ * (G, F) - P_GG's pivots, then Dt's -, its inverse, the moments, the value term, the factors of C_H); the assembly of b and of the band
+ * image of C (one thread per entry, folds in ascending order, no atomics: a call gives the same bits every time); {u, P as a full
+ * matrix}; T = C P into X (band times dense: 2 max_hold n^2 multiply-adds on the vector ALU); W <- -2 P T by gpar_gemm
+ * (GPAR_GEMM_C_LOWER: a full product where gpar_cv_dense_grad has a SYRK); then the rank-2 term, the weighted-sum pass and the epilogue
+ * of gpar_cv_dense_grad.  vec: gpar_workspace_doubles(GPAR_WS_CV_GAP, n, 1, max_hold) doubles (it holds P as an n x n matrix: hand it
+ * over 16-byte aligned); the value-only form: gpar_workspace_doubles(GPAR_WS_CV_GAP, n, 0, max_hold).  gpar_cv_gap_dense_grad_finish is
+ * the second half for a factor that already exists (same bits); info and info_out are both required.
+ * info, besides the factorisation's own codes: the 1-based row of a non-positive pivot in a fold's P_GG or Dt; n + 1 + f for a fold f
+ * whose extents are malformed - fold_start as gpar_cv_dense judges it, a block that does not contain its fold, leaves [0, n), exceeds
+ * max_hold, or whose hold_lo / hold_hi decrease from fold f - 1 (that fold is skipped, and every kernel of the weight stage behind the
+ * fold kernel returns at once).  Results are garbage then.  Limits: dense layers; blocks of at most GPAR_CV_MAX_FOLD rows.
+ * [no reference counterpart] */
+int gpar_cv_gap_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                           double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                           double* cv_mean, double* cv_var, const int* fold_start, const int* hold_lo, const int* hold_hi, int nfolds,
+                           int max_hold, int* info, int potrf_flags, void* stream);
+int gpar_cv_gap_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                  double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X, int ldxw,
+                                  double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                  double* cv_mean, double* cv_var, const int* fold_start, const int* hold_lo, const int* hold_hi, int nfolds,
+                                  int max_hold, int* info_out, void* stream);
+int gpar_cv_gap_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                      const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* X, int ldxw, double* T, int ldt,
+                      double* vec, double* out, double* cv_mean, double* cv_var, const int* fold_start, const int* hold_lo, const int* hold_hi,
+                      int nfolds, int max_hold, int* info, int potrf_flags, void* stream);
 
 /* Rolling-origin forecast scoring of one dense layer (ABI v12): every scored row predicted from the rows BEFORE its origin, the rows in the
  * order handed in (the time order).  origin: a DEVICE array of n ints; origin[r] = -1: row r is not scored; otherwise 0 <= origin[r] <= r
@@ -584,6 +627,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_LOO          (n, grad, -)     the `vec` of gpar_loo_dense (grad = 0) / gpar_loo_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_CV           (n, grad, max_fold)  the `vec` of gpar_cv_dense (grad = 0) / gpar_cv_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_AHEAD        (n, grad, -)     the `vec` of gpar_ahead_dense (grad = 0) / gpar_ahead_dense_grad[_finish] (grad = 1)
+ *   GPAR_WS_CV_GAP       (n, grad, max_hold)  the `vec` of gpar_cv_gap_dense (grad = 0) / gpar_cv_gap_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol
  *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading */
 #define GPAR_WS_GEMM_SPLITK 1
@@ -596,6 +640,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_PIVOTED_CHOL 8
 #define GPAR_WS_CHOL_UPDATE 9
 #define GPAR_WS_AHEAD 10
+#define GPAR_WS_CV_GAP 11
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
