@@ -24,13 +24,15 @@ POTRF_NO_LOOKAHEAD = 1
 POTRF_UNFUSED = 2
 WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO, WS_CV, WS_PIVOTED_CHOL, WS_CHOL_UPDATE, WS_AHEAD = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 WS_CV_GAP = 11
+WS_AHEAD_MULTI = 12
+AHEAD_MAX_HORIZONS = 8   # GPAR_AHEAD_MAX_HORIZONS: the most horizons the fused multi-horizon rolling-origin entries take
 PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
 CHOL_UPDATE_MAX_RANK = 1024   # GPAR_CHOL_UPDATE_MAX_RANK: the most leading rows gpar_chol_drop_leading forgets in one call
 SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the scoring rules of the leave-one-out and rolling-origin entries
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -228,6 +230,22 @@ SIGNATURES = {
         _c_int,
         [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _c_int, _ptr, _c_int,
          _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr],
+    ),
+    # (the multi-horizon forms: `origins, nh, weights, values` where the *_score forms take `origin`)
+    "gpar_ahead_multi_dense_grad": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _ptr, _c_int, _ptr, _c_int,
+         _ptr, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr],
+    ),
+    "gpar_ahead_multi_dense_grad_finish": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr,
+         _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _ptr],
+    ),
+    "gpar_ahead_multi_dense": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _c_int, _ptr, _c_int,
+         _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr],
     ),
     "gpar_logpdf_dense_build": (
         _c_int,

@@ -238,4 +238,303 @@ static int ahead_weights_run(const double* A, int lda, int n, const double* y, l
     return rc;
 }
 
+// ---- several horizons in one pass (ABI v15) -------------------------------------------------------------------------------------------
+// K = nh origin arrays (origins[k n + r] = o_k[r]) and weights w_k > 0 over ONE factor:
+//     e_kr = sum_{c = o_k[r] .. r} L_rc a_c,   v_kr = sum_{c = o_k[r] .. r} L_rc^2,   value_k = sum_r term(e_kr, v_kr),   value = sum_k w_k value_k,
+//     Q_r(c) = sum_k w_k q_kr [o_k[r] <= c],   S_r(c) = sum_k w_k s_kr [o_k[r] <= c]      (step functions of c, one step per horizon),
+//     B_rc = -Q_r(c) a_c - 2 S_r(c) L_rc,   abar_c = -sum_{r >= c} Q_r(c) L_rc,   P, W as above.
+// The row kernel stores w_k q_kr and w_k s_kr, so the kernels behind it take no weights.  A row's K sums come from ONE walk along its row
+// of L, from its smallest scored origin.  The band kernel folds the steps into the column slab of a chunk once - Lc[rr][tx] becomes
+// Q_r(c) a_c + 2 S_r(c) L_rc, K compares per (r, c) - and its inner loop over the 32 rows j of the tile is the single-horizon one without
+// the compare.  LDS: the two 32 x 33 tiles (16896 bytes) + K x 32 x (8 + 8 + 4) bytes of steps: 17536 bytes at K = 1 (the single-horizon
+// kernel's), 18816 at K = 3, 22016 at K = 8.  With one horizon and weight 1 every kernel here forms the single-horizon kernels' bits.
+struct AheadWeights { double w[GPAR_AHEAD_MAX_HORIZONS]; };
+
+// `vec` of the gradient forms: w q, w s, value terms (K x n each), abar (n), cmin (ceil(n / AH_T) ints in n doubles), then the n x ah_ldt(n)
+// matrix of the first product at an even offset; of the value-only form: the K x n value terms.
+inline long long ahm_off_t(int n, int nh) {
+    const long long o = 3LL * nh * n + 2LL * n;
+    return o + (o & 1);
+}
+inline long long ahm_workspace_doubles(int n, int grad, int nh) {
+    if (n <= 0 || nh <= 0) return 0;
+    return grad ? ahm_off_t(n, nh) + (long long)n * ah_ldt(n) : (long long)nh * n;
+}
+inline size_t ahm_band_lds_bytes(int nh) { return (size_t)nh * AH_T * (2 * sizeof(double) + sizeof(int)); }
+
+// ahead_check_kernel over the K arrays: n + 1 + r of the smallest r with an origin outside -1 ... r in any of them; cmin[chunk] = the smallest
+// scored origin of the chunk's rows over all horizons.
+__global__ __launch_bounds__(256) void ahead_multi_check_kernel(const int* __restrict__ origins, int n, int nh, int* __restrict__ cmin,
+                                                                int* __restrict__ info) {
+    __shared__ int sm[256];
+    const int t = threadIdx.x;
+    int bad = AH_NONE;
+    for (int r = t; r < n && bad == AH_NONE; r += 256)
+        for (int k = 0; k < nh; ++k) {
+            const int o = origins[(size_t)k * n + r];
+            if (o < -1 || o > r) bad = r;
+        }
+    sm[t] = bad;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) sm[t] = min(sm[t], sm[t + off]);
+        __syncthreads();
+    }
+    if (sm[0] != AH_NONE) {
+        if (t == 0) atomicCAS(info, 0, n + 1 + sm[0]);
+        return;
+    }
+    if (!cmin) return;
+    const int nchunks = (n + AH_T - 1) / AH_T;
+    for (int c = t; c < nchunks; c += 256) {
+        int m = AH_NONE;
+        for (int k = 0; k < nh; ++k)
+            for (int r = c * AH_T; r < min(n, (c + 1) * AH_T); ++r) {
+                const int o = origins[(size_t)k * n + r];
+                if (o >= 0) m = min(m, o);
+            }
+        cmin[c] = m;
+    }
+}
+
+// One wave per row, one walk: lanes stride the row of L from the row's smallest scored origin to r, and an element at column j enters the
+// sums of every horizon with o_k[r] <= j.  q, s null: the value-only form.  A non-positive v_kr: the 1-based row into info, nothing written
+// for the row.  NH: the number of horizons (the sums live in registers; C++ linkage: this header is included among the C entries).
+extern "C++" {
+template <int NH>
+__global__ __launch_bounds__(256) void ahead_multi_rows_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ a,
+                                                               const double* __restrict__ y, long incy, const int* __restrict__ origins,
+                                                               AheadWeights wt, double* __restrict__ mean, double* __restrict__ var,
+                                                               double* __restrict__ q, double* __restrict__ s, double* __restrict__ term, int rule,
+                                                               int* __restrict__ info) {
+    if (info[0] != 0) return;
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    int o[NH], omin = AH_NONE;
+    double e[NH], v[NH];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) {
+        const int ok = origins[(size_t)k * n + row];
+        o[k] = ok >= 0 ? ok : AH_NONE;
+        omin = min(omin, o[k]);
+        e[k] = v[k] = 0.0;
+    }
+    if (omin != AH_NONE) {
+        const double* Lr = L + (size_t)row * ldl;
+#pragma unroll 2
+        for (int j = omin + lane; j <= row; j += 64) {
+            const double l = Lr[j], aj = a[j];
+#pragma unroll
+            for (int k = 0; k < NH; ++k)
+                if (j >= o[k]) {
+                    e[k] = fma(l, aj, e[k]);
+                    v[k] = fma(l, l, v[k]);
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < NH; ++k) {
+            e[k] = wave_sum(e[k]);
+            v[k] = wave_sum(v[k]);
+        }
+    }
+    if (lane != 0) return;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < NH; ++k) ok = ok && (o[k] == AH_NONE || v[k] > 0.0);
+    if (!ok) {
+        atomicCAS(info, 0, row + 1);
+        return;
+    }
+    const double yr = y[(size_t)row * incy];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) {
+        const size_t at = (size_t)k * n + row;
+        double tr = 0.0, qr = 0.0, sr = 0.0;
+        if (o[k] == AH_NONE) {
+            mean[at] = var[at] = __builtin_nan("");
+        } else {
+            score_row(rule, e[k], v[k], tr, qr, sr);
+            mean[at] = yr - e[k];
+            var[at] = v[k];
+        }
+        term[at] = tr;
+        if (q) {
+            q[at] = wt.w[k] * qr;
+            s[at] = wt.w[k] * sr;
+        }
+    }
+}
+}  // extern "C++"
+
+// ahead_abar_kernel with the step weight Q_r(c) in the place of q_r [o_r <= c] (`q` holds w_k q_kr)
+__global__ __launch_bounds__(256) void ahead_multi_abar_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ q,
+                                                               const int* __restrict__ origins, int nh, double* __restrict__ abar,
+                                                               const int* __restrict__ info) {
+    __shared__ double part[8][AH_T + 1];
+    if (info[0] != 0) return;
+    const int tx = threadIdx.x & (AH_T - 1), ty = threadIdx.x / AH_T;
+    const int c0 = blockIdx.x * AH_T, c = c0 + tx;
+    double acc = 0.0;
+    if (c < n) {
+        for (int r = c0 + ty; r < n; r += 8) {
+            if (r < c) continue;
+            double Q = 0.0;
+            for (int k = 0; k < nh; ++k) {
+                const int o = origins[(size_t)k * n + r];
+                if (o >= 0 && o <= c) Q += q[(size_t)k * n + r];
+            }
+            acc = fma(Q, L[(size_t)r * ldl + c], acc);
+        }
+    }
+    part[ty][tx] = acc;
+    __syncthreads();
+    if (ty == 0 && c < n) {
+        double sum = 0.0;
+        for (int k = 0; k < 8; ++k) sum += part[k][tx];
+        abar[c] = -sum;
+    }
+}
+
+// ahead_band_kernel for K horizons: per chunk the steps (w q, 2 w s, origins; AH_NONE on unscored (k, r)) go to LDS, every thread folds
+// them into its four entries of the column slab - Lc[rr][tx] = Q_r(c) a_c + 2 S_r(c) L_rc -, and the inner loop multiplies the two tiles.
+// Dynamic LDS: ahm_band_lds_bytes(nh) behind the two static tiles.
+__global__ __launch_bounds__(256) void ahead_multi_band_kernel(const double* __restrict__ L, int ldl, int n, const double* __restrict__ a,
+                                                               const double* __restrict__ q, const double* __restrict__ s,
+                                                               const double* __restrict__ abar, const int* __restrict__ origins, int nh,
+                                                               const int* __restrict__ cmin, double* __restrict__ S, int lds,
+                                                               const int* __restrict__ info) {
+    __shared__ double Lj[AH_T][AH_T + 1];
+    __shared__ double Lc[AH_T][AH_T + 1];
+    extern __shared__ double ahm_steps[];
+    double *qs = ahm_steps, *ss = ahm_steps + nh * AH_T;
+    int* os = reinterpret_cast<int*>(ahm_steps + 2 * nh * AH_T);
+    const int bc = blockIdx.x, bj = blockIdx.y;
+    if (bc > bj || info[0] != 0) return;
+    const int t = threadIdx.x, tx = t & (AH_T - 1), ty = t / AH_T;
+    const int j0 = bj * AH_T, c0 = bc * AH_T, gc = c0 + tx;
+    const int nchunks = (n + AH_T - 1) / AH_T;
+    const double ac = gc < n ? a[gc] : 0.0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = bj; k < nchunks; ++k) {
+        if (cmin[k] > c0 + AH_T - 1) continue;   // (the same verdict in every thread)
+        const int r0 = k * AH_T;
+        __syncthreads();
+        for (int idx = t; idx < nh * AH_T; idx += 256) {
+            const int h = idx / AH_T, gr = r0 + (idx & (AH_T - 1));
+            const int o = gr < n ? origins[(size_t)h * n + gr] : -1;
+            qs[idx] = o >= 0 ? q[(size_t)h * n + gr] : 0.0;
+            ss[idx] = o >= 0 ? 2.0 * s[(size_t)h * n + gr] : 0.0;
+            os[idx] = o >= 0 ? o : AH_NONE;
+        }
+        double lc[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rr = ty + 8 * i, gr = r0 + rr;
+            Lj[rr][tx] = (gr < n && j0 + tx <= gr) ? L[(size_t)gr * ldl + j0 + tx] : 0.0;
+            lc[i] = (gr < n && gc <= gr) ? L[(size_t)gr * ldl + gc] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rr = ty + 8 * i;
+            double Q = 0.0, S2 = 0.0;
+            for (int h = 0; h < nh; ++h)
+                if (os[h * AH_T + rr] <= gc) {
+                    Q += qs[h * AH_T + rr];
+                    S2 += ss[h * AH_T + rr];
+                }
+            Lc[rr][tx] = fma(S2, lc[i], Q * ac);
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int rr = 0; rr < AH_T; ++rr) {
+            const double wv = Lc[rr][tx];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = fma(Lj[rr][ty + 8 * i], wv, acc[i]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int gj = j0 + ty + 8 * i;
+        Lj[ty + 8 * i][tx] = gj < n ? -acc[i] - abar[gj] * ac : 0.0;
+    }
+    __syncthreads();
+    const bool diag = bj == bc;
+    for (int r = ty; r < AH_T; r += 8) {
+        const int gr = j0 + r;
+        if (gr < n && gc < n) S[(size_t)gr * lds + gc] = (diag && tx > r) ? Lj[tx][r] : Lj[r][tx];
+        const int mr = c0 + r, mc = j0 + tx;
+        if (!diag && mr < n && mc < n) S[(size_t)mr * lds + mc] = Lj[tx][r];
+    }
+}
+
+// values[k] = the sum of horizon k's terms in loo_sum_terms' order; out[0] = sum_k w_k values[k], added in the order of k (one workgroup)
+__device__ __forceinline__ void ahead_multi_sum_values(const double* __restrict__ term, int n, int nh, const AheadWeights& wt,
+                                                       double* __restrict__ values, double* __restrict__ out, double* sm) {
+    double total = 0.0;
+    for (int k = 0; k < nh; ++k) {
+        const double v = loo_sum_terms(term + (size_t)k * n, n, sm);
+        __syncthreads();   // (every thread has read sm[0] before the next sum writes it)
+        if (threadIdx.x == 0) values[k] = v;
+        total += wt.w[k] * v;
+    }
+    if (threadIdx.x == 0) out[0] = total;
+}
+
+__global__ __launch_bounds__(256) void ahead_multi_value_kernel(const double* __restrict__ term, int n, int nh, AheadWeights wt,
+                                                                double* __restrict__ values, double* __restrict__ out,
+                                                                const int* __restrict__ info) {
+    __shared__ double sm[256];
+    if (info[0] != 0) return;
+    ahead_multi_sum_values(term, n, nh, wt, values, out, sm);
+}
+
+__global__ __launch_bounds__(256) void ahead_multi_grad_epilogue_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ out,
+                                                                        const double* __restrict__ W, int ldw, int n, double* __restrict__ half_diag,
+                                                                        const double* __restrict__ term, int nh, AheadWeights wt,
+                                                                        double* __restrict__ values, const int* __restrict__ info) {
+    __shared__ double sm[256];
+    if (info[0] != 0) return;
+    if (grad_epilogue_sums(partial, nblocks, out, W, ldw, n, half_diag)) return;
+    ahead_multi_sum_values(term, n, nh, wt, values, out, sm);
+}
+
+// check + rows for K horizons.  q, s, cmin null: value only.
+static void ahead_multi_rows_run(const double* A, int lda, int n, const double* y, long incy, const int* origins, int nh, const AheadWeights& wt,
+                                 double* mean, double* var, double* q, double* s, double* term, int* cmin, int rule, int* info, hipStream_t st) {
+    hipLaunchKernelGGL(ahead_multi_check_kernel, dim3(1), dim3(256), 0, st, origins, n, nh, cmin, info);
+    const dim3 grid((unsigned)((n + 3) / 4));
+    const double* a = A + (size_t)n * lda;
+#define GPAR_AHM_ROWS(NH)                                                                                                                    \
+    case NH:                                                                                                                                 \
+        hipLaunchKernelGGL(ahead_multi_rows_kernel<NH>, grid, dim3(256), 0, st, A, lda, n, a, y, incy, origins, wt, mean, var, q, s, term, rule, \
+                           info);                                                                                                            \
+        break;
+    switch (nh) {
+        GPAR_AHM_ROWS(1) GPAR_AHM_ROWS(2) GPAR_AHM_ROWS(3) GPAR_AHM_ROWS(4) GPAR_AHM_ROWS(5) GPAR_AHM_ROWS(6) GPAR_AHM_ROWS(7) GPAR_AHM_ROWS(8)
+    }
+#undef GPAR_AHM_ROWS
+}
+
+// ahead_weights_run for K horizons: the same launches with the multi-horizon kernels, the two products unchanged
+static int ahead_multi_weights_run(const double* A, int lda, int n, const double* y, long incy, const int* origins, int nh, const AheadWeights& wt,
+                                   double* mean, double* var, double* vec, const double* X, int ldx, double* W, int ldw, int rule, int* info,
+                                   hipStream_t st) {
+    const size_t kn = (size_t)nh * n;
+    double *q = vec, *s = vec + kn, *term = vec + 2 * kn, *abar = vec + 3 * kn, *T = vec + ahm_off_t(n, nh);
+    int* cmin = reinterpret_cast<int*>(vec + 3 * kn + n);
+    const int ldt = ah_ldt(n), nt = gpar_ceil_div(n, AH_T);
+    const double* a = A + (size_t)n * lda;
+    ahead_multi_rows_run(A, lda, n, y, incy, origins, nh, wt, mean, var, q, s, term, cmin, rule, info, st);
+    hipLaunchKernelGGL(ahead_multi_abar_kernel, dim3((unsigned)nt), dim3(256), 0, st, A, lda, n, (const double*)q, origins, nh, abar,
+                       (const int*)info);
+    hipLaunchKernelGGL(ahead_multi_band_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(256), ahm_band_lds_bytes(nh), st, A, lda, n, a,
+                       (const double*)q, (const double*)s, (const double*)abar, origins, nh, (const int*)cmin, W, ldw, (const int*)info);
+    int rc = gemm_launch(0, 1, n, n, n, 1.0, X, ldx, W, ldw, 0.0, T, ldt, GPAR_GEMM_K_FROM_ROW, st);
+    if (!rc) rc = gemm_launch(0, 1, n, n, n, 1.0, X, ldx, T, ldt, 0.0, W, ldw, GPAR_GEMM_C_LOWER | GPAR_GEMM_K_FROM_ROW, st);
+    return rc;
+}
+
 }  // namespace gpar

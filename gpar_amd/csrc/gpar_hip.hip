@@ -1218,7 +1218,7 @@ static int cv_folds_launch(const double* P, int ldp, int n, const double* X, int
 // ---- one chain for the dense objectives: marginal likelihood, leave-one-out, blocked cross-validation, rolling-origin forecasts --------
 // Every one-call entry is  prologue (features, Gram, factor) -> inverse -> the objective's weights W -> weighted-sum pass -> epilogue;
 // the objectives differ in the weight stage and in the last block of the epilogue alone (OBJ_AHEAD also stops the inverse at X = L^-T).
-enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV, OBJ_AHEAD, OBJ_CV_GAP };
+enum DenseObjectiveKind { OBJ_MLL, OBJ_LOO, OBJ_CV, OBJ_AHEAD, OBJ_CV_GAP, OBJ_AHEAD_MULTI };
 struct DenseObjective {
     DenseObjectiveKind kind;
     const double* y;            // the observations (the finish form of OBJ_MLL has none: row n of the factor holds all it needs)
@@ -1228,6 +1228,9 @@ struct DenseObjective {
     const int* origin;          // OBJ_AHEAD: n origins (device)
     int score;                  // OBJ_LOO, OBJ_AHEAD: the scoring rule (GPAR_SCORE_LOG = 0: what an entry without one scores by)
     CvHold hold;                // OBJ_CV_GAP: the extents of the blocks left out of the conditioning set (`folds`: the scored rows)
+    int nh;                     // OBJ_AHEAD_MULTI: the number of horizons (`origin`: nh x n origins; `mean`, `var`: nh x n)
+    AheadWeights wt;            // OBJ_AHEAD_MULTI: the horizons' weights
+    double* values;             // OBJ_AHEAD_MULTI: the nh unweighted values
 };
 
 // What gpar_logpdf_dense does up to the factor: features (+ their frequency derivatives when zd is given; the value-only forms pass null)
@@ -1259,7 +1262,8 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
         const long total = (long)n * fs->dz;
         hipLaunchKernelGGL(featurize_dfreq_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, zd, ldz);
     }
-    int rc = ob.kind == OBJ_AHEAD ? trinv_upper_run(A, n, lda, X, ldxw, W, ldw, st) : chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
+    const bool ahead = ob.kind == OBJ_AHEAD || ob.kind == OBJ_AHEAD_MULTI;
+    int rc = ahead ? trinv_upper_run(A, n, lda, X, ldxw, W, ldw, st) : chol_inverse_run(A, n, lda, X, ldxw, W, ldw, st);
     if (rc) return rc;
     const double* zrow = A + (size_t)n * lda;   // L^-1 y
     double *bvec = ob.vec, *term = nullptr, *u = nullptr;
@@ -1303,6 +1307,10 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
             term = ob.vec + 2 * (size_t)n;
             rc = ahead_weights_run(A, lda, n, ob.y, ob.incy, ob.origin, ob.mean, ob.var, ob.vec, X, ldxw, W, ldw, ob.score, info, st);
             break;
+        case OBJ_AHEAD_MULTI:   // `vec`: w q, w s, value terms (nh x n each), abar, chunk origins, the first product
+            term = ob.vec + 2 * (size_t)ob.nh * n;
+            rc = ahead_multi_weights_run(A, lda, n, ob.y, ob.incy, ob.origin, ob.nh, ob.wt, ob.mean, ob.var, ob.vec, X, ldxw, W, ldw, ob.score, info, st);
+            break;
     }
     if (ob.kind == OBJ_LOO || ob.kind == OBJ_CV) {   // u and S (in X: alpha exists, L^-T is no longer needed) are formed: W <- -2 S S^T + alpha u^T + u alpha^T
         rc = gemm_launch(0, 1, n, n, n, -2.0, X, ldxw, X, ldxw, 0.0, W, ldw, GPAR_GEMM_C_LOWER, st);
@@ -1319,6 +1327,9 @@ static int dense_grad_finish_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
     else if (ob.kind == OBJ_AHEAD)
         hipLaunchKernelGGL(ahead_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
                            half_diag, (const double*)term, (const int*)info);
+    else if (ob.kind == OBJ_AHEAD_MULTI)
+        hipLaunchKernelGGL(ahead_multi_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
+                           half_diag, (const double*)term, ob.nh, ob.wt, ob.values, (const int*)info);
     else
         hipLaunchKernelGGL(loo_grad_epilogue_kernel, grid, dim3(256), 0, st, (const double*)workspace, nblocks, out, (const double*)W, ldw, n,
                            half_diag, (const double*)term, ob.kind == OBJ_LOO ? loo_half_n_log_2pi(ob.score, n) : 0.5 * n_log_2pi);
@@ -1629,6 +1640,75 @@ int gpar_ahead_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const doubl
                                   GPAR_SCORE_LOG, info, potrf_flags, stream);
 }
 
+// ---- several horizons in one pass (ABI v15; ahead.h) ---------------------------------------------------------------------------------------
+// nh outside 1 ... GPAR_AHEAD_MAX_HORIZONS, a weight that is not positive and finite: argument errors before anything is launched
+static int ahead_multi_check_args(int nh, const double* weights, AheadWeights& wt) {
+    if (nh < 1 || nh > GPAR_AHEAD_MAX_HORIZONS) return GPAR_ARG_ERROR(15);
+    for (int k = 0; k < GPAR_AHEAD_MAX_HORIZONS; ++k) {
+        if (k < nh && (!(weights[k] > 0.0) || !__builtin_isfinite(weights[k]))) return GPAR_ARG_ERROR(16);
+        wt.w[k] = k < nh ? weights[k] : 0.0;
+    }
+    return 0;
+}
+
+int gpar_ahead_multi_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                                double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights, double* values, int score,
+                                int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !ahead_mean || !ahead_var ||
+        !origins || !weights || !values || !info || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
+    DenseObjective ob{OBJ_AHEAD_MULTI, y, incy, vec, ahead_mean, ahead_var, {}, origins, score, {}, nh, {}, values};
+    int rc = ahead_multi_check_args(nh, weights, ob.wt);
+    if (!rc) rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, info, potrf_flags,
+                                   (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, out + 1, info, X, ldxw, W, ldw, alpha, workspace, nblocks, out, half_diag,
+                                 stream, false);
+}
+
+// (both info words are required, as for gpar_ahead_dense_grad_finish)
+int gpar_ahead_multi_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                       double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X,
+                                       int ldxw, double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out,
+                                       double* half_diag, double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights,
+                                       double* values, int score, int* info_out, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !logdet || !info || !X || !W || !alpha || !vec || !workspace || !out || !half_diag || !ahead_mean ||
+        !ahead_var || !origins || !weights || !values || !info_out || n <= 0 || nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
+    DenseObjective ob{OBJ_AHEAD_MULTI, y, incy, vec, ahead_mean, ahead_var, {}, origins, score, {}, nh, {}, values};
+    int rc = ahead_multi_check_args(nh, weights, ob.wt);
+    if (!rc) rc = finish_carry_words(logdet, info, out, info_out, (hipStream_t)stream);
+    if (rc) return rc;
+    return dense_grad_finish_run(fs, ks, x, n, ldx, ob, z, zd, ldz, A, lda, logdet, info_out, X, ldxw, W, ldw, alpha, workspace, nblocks, out,
+                                 half_diag, stream, true);
+}
+
+// Values, means and variances alone: the factor and its augmented row are all it reads
+int gpar_ahead_multi_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                           double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights, double* values, int score,
+                           int* info, int potrf_flags, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !vec || !out || !ahead_mean || !ahead_var || !origins || !weights || !values || !info || n <= 0)
+        return GPAR_ARG_ERROR(1);
+    if (!score_known(score)) return GPAR_ARG_ERROR(14);
+    AheadWeights wt;
+    int rc = ahead_multi_check_args(nh, weights, wt);
+    hipStream_t st = (hipStream_t)stream;
+    if (!rc) rc = dense_factor_run(fs, ks, x, n, ldx, y, incy, nullptr, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, info, potrf_flags, st);
+    if (rc) return rc;
+    ahead_multi_rows_run(A, lda, n, y, incy, origins, nh, wt, ahead_mean, ahead_var, nullptr, nullptr, vec, nullptr, score, info, st);
+    hipLaunchKernelGGL(ahead_multi_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, nh, wt, values, out, (const int*)info);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
 int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int ldz1, const double* z2, int n2, int ldz2, int dz,
                          const double* W, int ldw, int mode, int nsplit, double* workspace, double* out, int ldo, void* stream) {
     GPAR_API_GUARD;
@@ -1823,6 +1903,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
             return (long long)(a > 0 ? a : 0) * (b ? 3 + c : 1);
         case GPAR_WS_AHEAD: return ah_workspace_doubles(a, b);                          /* n, with gradient */
         case GPAR_WS_CV_GAP: return cvg_workspace_doubles(a, b, c);                     /* n, with gradient, max_hold */
+        case GPAR_WS_AHEAD_MULTI: return ahm_workspace_doubles(a, b, c);                /* n, with gradient, horizons */
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         default: return -1;

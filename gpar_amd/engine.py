@@ -312,6 +312,19 @@ class HipEngine:
                                                                      score=score, **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
 
+    def ahead_multi_dense(self, ck, x, y, noise_diag, jitter, origins, weights=None, score="log"):
+        """`ahead_dense` at K horizons in one library call (`origins`: K x n, `weights`: K positive numbers): (weighted value as a 0-d
+        device tensor, info word, K x n means, K x n variances, the K unweighted values)."""
+        out, values, mean, var, info = hip.ahead_multi_dense(ck, self._mat(x), y, noise_diag, jitter, origins, weights, score=score,
+                                                             **self._factor_flags())
+        return out[0], info, mean, var, values
+
+    def ahead_multi_dense_grad(self, ck, x, y, noise_diag, jitter, origins, weights=None, score="log"):
+        """The multi-horizon counterpart of `ahead_dense_grad`: its return values, then the K unweighted values."""
+        out, values, half_diag, mean, var, info, A, _ = hip.ahead_multi_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
+                                                                                  origins, weights, score=score, **self._factor_flags())
+        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var, values
+
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""
         safe = getattr(self._tls, "safe", False)

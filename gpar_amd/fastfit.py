@@ -266,13 +266,14 @@ class DenseLayerObjective:
     log-density under the same covariance (gpar_loo_dense_grad), or, with `objective="cv"`, minus the blocked cross-validation value
     over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad; with `hold` = (hold_lo, hold_hi), the
     blocks the folds are not predicted from, its purged form: gpar_cv_gap_dense_grad), or, with `objective="ahead"`, minus the
-    rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad); `score` ("log", "crps", "se") is the rule "loo"
+    rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad; a K x n `origin` with `weights`: the weighted
+    sum over K horizons in one pass, gpar_ahead_multi_dense_grad); `score` ("log", "crps", "se") is the rule "loo"
     and "ahead" score their held-out entries by (the *_score forms of their library calls) - and its gradient with respect to
     the latent (unconstrained) variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are
     device tensors that do not change during the optimisation."""
 
     def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
-                 fold_start=None, origin=None, score="log", hold=None):
+                 fold_start=None, origin=None, score="log", hold=None, weights=None):
         if objective not in ("mll", "loo", "cv", "ahead"):
             raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
         self.score = hip.score_code(score)
@@ -285,7 +286,14 @@ class DenseLayerObjective:
         if hold is not None and objective != "cv":
             raise ValueError('hold belongs to objective="cv"')
         # (host origins of the rows; their device copy is made once, with the other buffers)
-        self.origin = None if origin is None else np.asarray(origin, dtype=np.int64).reshape(-1)
+        # (a K x n origin array: K horizons in one pass, the multi-horizon call with `weights`, K positive numbers, default all 1)
+        self.origin = None if origin is None else np.asarray(origin, dtype=np.int64)
+        self.multi = self.origin is not None and self.origin.ndim == 2
+        if self.origin is not None and not self.multi:
+            self.origin = self.origin.reshape(-1)
+        if weights is not None and not self.multi:
+            raise ValueError("weights belong to a K x n origin array")
+        self.weights = hip.horizon_weight_array(weights, self.origin.shape[0]) if self.multi else None
         self.eng, self.vs, self.names = eng, vs, list(names)
         self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
         # (host offsets of the folds; their device copy is made once, with the other buffers)
@@ -339,9 +347,17 @@ class DenseLayerObjective:
         self.folds = hip.upload_folds(self.fold_start, n, dev) if self.objective == "cv" else ()   # (device offsets, number of folds, largest fold)
         if self.hold is not None:
             self.folds = hip.upload_hold(self.fold_start, self.hold, n, dev)   # (device offsets and block extents, number of folds, largest block)
-        if self.objective == "ahead":
+        if self.objective == "ahead" and not self.multi:
             self.folds = (hip.upload_origin(self.origin, n, dev),)   # (the one argument the entry takes in the folds' place)
-        nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.call, n, 1, self.folds) + 2 * n
+        nmom = n   # (doubles of the held-out means, and of the variances)
+        if self.multi:   # origins (K x n, uploaded once), K, the weights (host), the K values (device): what the multi call takes in the origin's place
+            k = int(self.origin.shape[0])
+            self.values = torch.zeros(k, dtype=torch.float64, device=dev)
+            self.folds = (hip.upload_origins(self.origin, n, dev), k, (ctypes.c_double * k)(*self.weights), self.values)
+            nmom = k * n
+            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 1, k)) + 2 * nmom
+        else:
+            nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.call, n, 1, self.folds) + 2 * n
         nalpha = n + (n & 1)   # (the vectors start at an even offset: "ahead" keeps a matrix among them)
         self.work = torch.empty(self.nblocks * nacc + nalpha + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
@@ -362,8 +378,8 @@ class DenseLayerObjective:
         )
         if self.objective != "mll":
             at = self.nblocks * nacc + nalpha
-            self._ptrs.update(vec=self.work[at:].data_ptr(), loo_mean=self.work[at + nloo - 2 * n:].data_ptr(),
-                              loo_var=self.work[at + nloo - n:].data_ptr())
+            self._ptrs.update(vec=self.work[at:].data_ptr(), loo_mean=self.work[at + nloo - 2 * nmom:].data_ptr(),
+                              loo_var=self.work[at + nloo - nmom:].data_ptr())
 
     def _device_eval(self, ck, noise):
         """One library call + one device-to-host copy: (the objective - log marginal likelihood, leave-one-out or blocked cross-
@@ -383,7 +399,7 @@ class DenseLayerObjective:
         tail = (p["info"], self.flags, stream.cuda_stream)
         if self.objective != "mll":
             name = {"loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad", "cv_gap": "gpar_cv_gap_dense_grad",
-                    "ahead": "gpar_ahead_dense_grad_score"}[self.call]
+                    "ahead": "gpar_ahead_multi_dense_grad" if self.multi else "gpar_ahead_dense_grad_score"}[self.call]
             fold_args = hip._fold_args(self.folds)
             rule = () if self.objective == "cv" else (self.score,)   # (the blocked form scores a fold's joint density: no rule to take)
             rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *rule,
@@ -512,7 +528,8 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     `folds`, one integer label per row of `fixed_x`: the layer's rows are sorted by label here, once; None when its largest fold
     exceeds what the library call takes - the general route trains it) or "ahead" (rolling-origin forecast score; `ahead` = (horizon,
     start, the indices in the data as given of the rows of `fixed_x`): the layer's origins are counted here, once, from the rows that
-    survive); `score`: the scoring rule of "loo" and "ahead".  `purge` = (gap, the indices in the data as given of the rows of
+    survive; `horizon` a tuple of K ints, then with the horizons' weights as a fourth element: K origin arrays and the multi-horizon call,
+    None above `_lib.AHEAD_MAX_HORIZONS`); `score`: the scoring rule of "loo" and "ahead".  `purge` = (gap, the indices in the data as given of the rows of
     `fixed_x`): purged cross-validation - `folds` then holds one non-decreasing label per row of the data AS GIVEN, and the layer's
     fold offsets and block extents are counted here, once (`model.purged_folds`); None when its largest block exceeds the call's limit."""
     from .gp import one_call_grad_rows
@@ -562,11 +579,16 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
             X, yi, wi = X.index_select(0, at), yi.index_select(0, at), wi.index_select(0, at)
     origin = None
     if objective == "ahead":
-        horizon, start, rows = ahead
+        horizon, start, rows, *weights = ahead   # (`horizon` a tuple: K origin arrays, with the horizons' weights behind `rows`)
         observed = np.asarray(rows, dtype=np.int64).reshape(-1)[host_index(mask)]
         if not isinstance(mask, slice) and n_missing:
             observed = observed[host_index(keep)]
-        origin = rolling_origins(observed, horizon, start)
+        if isinstance(horizon, tuple):
+            if len(horizon) > _lib.AHEAD_MAX_HORIZONS:
+                return None   # (more horizons than the library call takes: the general route trains it)
+            origin = np.stack([rolling_origins(observed, h, start) for h in horizon])
+        else:
+            origin = rolling_origins(observed, horizon, start)
     tracer = _TracingVars(vs)
     f, noise = _model_generator(tracer, reg.m, pi, **reg.model_config)()
     kernel = f.kernel
@@ -582,4 +604,5 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
                lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}),
                **({} if origin is None else {"origin": origin}), **({} if score == "log" else {"score": score}),
+               **({"weights": weights[0]} if origin is not None and origin.ndim == 2 and weights else {}),
                **({} if hold is None else {"hold": hold}))

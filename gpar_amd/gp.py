@@ -37,9 +37,9 @@ import math
 import numpy as np
 import torch
 
-from ._lib import CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
+from ._lib import AHEAD_MAX_HORIZONS, CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
 from .engine import get_engine, joining
-from .hip import fold_offsets, hold_extents, origin_array, upload_hold, upload_origin
+from .hip import fold_offsets, hold_extents, horizon_weight_array, origin_array, origins_array, upload_hold, upload_origin, upload_origins
 from .kernels import Kernel
 
 __all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs", "greedy_inducing"]
@@ -459,9 +459,14 @@ def _cv_gap_algebra(eng, Kinv, alpha, purged):
 class _Origins:
     """The third held-out scheme beside `None` (leave-one-out) and fold offsets: rolling origins, one per row (`Obs.ahead`)."""
 
-    def __init__(self, origin):
-        self.origin = origin   # checked host array (int64), -1: not scored
+    def __init__(self, origin, weights=None):
+        self.origin = origin   # checked host array (int64), -1: not scored; K x n for K horizons scored in one pass
+        self.weights = weights   # K horizons: their K positive weights (host array)
         self.device = None     # the uploaded copy, made at the first fused call
+
+    @property
+    def multi(self):
+        return self.origin.ndim == 2
 
 
 def _ahead_algebra(eng, L, a, origin, score="log"):
@@ -898,16 +903,27 @@ class Obs:
             return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
         return self._held_out(_Purged(*hold_extents(fold_start, hold, self.fdd.n)), "cross-validation")
 
-    def ahead(self, origin, score="log"):
+    def ahead(self, origin, score="log", weights=None):
         """(value, mean, var) of rolling-origin forecasts, the observations in the order given (the time order): row r is predicted from
         rows 0 ... origin[r] - 1 (origin[r] in 0 ... r; 0: from the prior), origin[r] = -1 leaves it unscored (NaN in mean and var).  mean
         and var are the predictive moments of the noisy observation and value = sum_scored log N(y_r; mean_r, var_r) - a 0-d tensor that
         carries a gradient with respect to the kernel parameters and the noise where they require one (observations of a prior process).
         All of it comes from the ONE factorisation `logpdf` computes; origin[r] = r for every row gives `logpdf`.  `score` as for `loo`:
-        "crps" and "se" sum minus the CRPS / minus the squared error of the scored rows instead."""
+        "crps" and "se" sum minus the CRPS / minus the squared error of the scored rows instead.
+
+        A K x n `origin` scores K horizons from the one factorisation: mean and var are K x n, value = sum_k weights[k] value_k (`weights`:
+        K positive finite numbers, default all 1; with a 1-D origin: ValueError) and the K unweighted value_k are left, detached, in
+        `self._held_out_values`.  One library call where `logpdf` would take one and K <= `_lib.AHEAD_MAX_HORIZONS`; otherwise composed of
+        `_ahead_algebra`'s terms and weights W, summed over the horizons - any K."""
         check_score(score)
         if self.base.is_posterior:
             raise NotImplementedError("rolling-origin forecasts are those of a prior process")
+        shaped = origin.cpu() if isinstance(origin, torch.Tensor) else origin
+        if np.ndim(shaped) == 2:
+            origins = origins_array(shaped, self.fdd.n)
+            return self._held_out(_Origins(origins, horizon_weight_array(weights, origins.shape[0])), "rolling-origin forecast", score)
+        if weights is not None:
+            raise ValueError("weights belong to a K x n origin array: one horizon has nothing to weigh against")
         return self._held_out(_Origins(origin_array(origin, self.fdd.n)), "rolling-origin forecast", score)
 
     def ahead_gradients(self):
@@ -939,11 +955,15 @@ class Obs:
         `score`: the scoring rule of `loo` and `ahead` (blocked cross-validation scores a fold's joint density: "log" alone)."""
         eng, n = self.eng, self.fdd.n
         dev = self.y.device
+        ahead, purged = isinstance(starts, _Origins), isinstance(starts, _Purged)
         if n == 0:
-            self._held_out_mean = self._held_out_var = torch.zeros(0, dtype=torch.float64, device=dev)
+            shape = (starts.origin.shape[0], 0) if ahead and starts.multi else (0,)
+            self._held_out_mean = self._held_out_var = torch.zeros(shape, dtype=torch.float64, device=dev)
+            self._held_out_values = torch.zeros(shape[0], dtype=torch.float64, device=dev) if len(shape) == 2 else None
             self._held_out_parts = None
             return torch.zeros((), dtype=torch.float64, device=dev)
-        ahead, purged = isinstance(starts, _Origins), isinstance(starts, _Purged)
+        if ahead and starts.multi:
+            return self._ahead_multi_eval(starts, want_grad, score)
         call = "ahead_dense" if ahead else "cv_gap_dense" if purged else "loo_dense" if starts is None else "cv_dense"
         folds = () if starts is None else (starts,)
         rule = {} if score == "log" else {"score": score}   # (an engine's one-call forms take the rule by keyword)
@@ -992,6 +1012,49 @@ class Obs:
         if score == "log":
             value = value - 0.5 * n * _LOG_2PI
         return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+
+    def _ahead_multi_eval(self, starts, want_grad, score):
+        """`_held_out_eval` for K horizons (`starts.origin` K x n): the weighted value; K x n means and variances and the K unweighted
+        values are left in `_held_out_mean` / `_held_out_var` / `_held_out_values`."""
+        eng, n = self.eng, self.fdd.n
+        dev = self.y.device
+        K, w = starts.origin.shape[0], starts.weights
+        rule = {} if score == "log" else {"score": score}
+        if K <= AHEAD_MAX_HORIZONS and hasattr(eng, "ahead_multi_dense") and (self._fusable_grad() if want_grad else self._value_only()):
+            if starts.device is None:
+                starts.device = upload_origins(starts.origin, n, dev)
+            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
+            if want_grad:
+                value, info, self._fused_held_out_gradients, (A, logdet), mean, var, values = eng.ahead_multi_dense_grad(
+                    ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, starts.device, w, **rule)
+                eng.check_info(info)
+                self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
+            else:
+                value, info, mean, var, values = eng.ahead_multi_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, starts.device, w, **rule)
+                eng.check_info(info)
+            self._held_out_mean, self._held_out_var, self._held_out_values = mean, var, values
+            return value.detach()
+        fac = self.factor()
+        L, a, y = fac.L.detach(), fac.zrow.reshape(-1).detach(), self.y.reshape(-1).detach()
+        total, means, variances, values, parts = None, [], [], [], []
+        for k in range(K):
+            value, e, var, scored, weights = _ahead_algebra(eng, L, a, starts.origin[k], score)
+            means.append(torch.where(scored, y - e, var))
+            variances.append(var)
+            values.append(value.detach())
+            parts.append(weights)
+            total = float(w[k]) * value if total is None else total + float(w[k]) * value
+        self._held_out_mean, self._held_out_var, self._held_out_values = torch.stack(means), torch.stack(variances), torch.stack(values)
+
+        def summed(Kinv):   # W is linear in the horizons' (q, s): the weighted sum of their W
+            W = parts[0](Kinv)
+            W.mul_(float(w[0]))
+            for k in range(1, K):
+                W.add_(parts[k](Kinv), alpha=float(w[k]))
+            return W
+
+        self._held_out_parts = (fac, summed) if want_grad else None
+        return total.detach() if getattr(eng, "_deferred", None) is not None else total.detach().cpu()
 
     def _held_out_gradients(self):
         """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the value `_held_out_eval(want_grad=True)` has just formed, with

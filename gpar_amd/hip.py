@@ -351,6 +351,113 @@ def ahead_dense_grad(ck, x, y, noise_diag, jitter, periodic, origin, lookahead=T
     return out, vectors[0], vectors[1], vectors[2], info, A, W
 
 
+def origins_array(origins, n):
+    """The K x n origins of a multi-horizon rolling-origin evaluation as a checked host array (int64), every row as `origin_array` checks
+    it.  The one check of such origins: `gp.Obs.ahead` and `upload_origins` both go through it."""
+    o = np.asarray(origins.cpu() if isinstance(origins, torch.Tensor) else origins)
+    if o.ndim != 2 or o.shape[0] < 1:
+        raise ValueError("origins must hold one row of n integers per horizon")
+    return np.stack([origin_array(row, n) for row in o])
+
+
+def upload_origins(origins, n, device):
+    """Device int32 array of the K x n origins the fused multi-horizon entries take, checked by `origins_array`; more than
+    GPAR_AHEAD_MAX_HORIZONS rows are a ValueError."""
+    o = origins_array(origins, n)
+    if o.shape[0] > _lib.AHEAD_MAX_HORIZONS:
+        raise ValueError(f"the fused multi-horizon entries take 1 to {_lib.AHEAD_MAX_HORIZONS} horizons")
+    return torch.tensor(o, dtype=torch.int32, device=device)
+
+
+def horizon_weight_array(weights, k):
+    """The k weights of a multi-horizon evaluation as a checked host array (float64): positive and finite; None: all 1."""
+    if weights is None:
+        return np.ones(k)
+    if isinstance(weights, (str, bytes)) or np.ndim(weights) != 1:
+        raise ValueError(f"the horizons' weights must be {k} positive finite numbers")
+    try:
+        w = np.array([float(v) for v in weights], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"the horizons' weights must be {k} positive finite numbers") from None
+    if w.size != k or not np.all(np.isfinite(w)) or np.any(w <= 0.0):
+        raise ValueError(f"the horizons' weights must be {k} positive finite numbers")
+    return w
+
+
+def _multi_args(origins, weights, n, dev):
+    """(device origins, K, the weights as the host array of doubles the entries take)"""
+    dev_origins = origins if isinstance(origins, torch.Tensor) and origins.is_cuda else upload_origins(origins, n, dev)
+    if dev_origins.dim() != 2 or dev_origins.shape[1] != n or dev_origins.dtype != torch.int32 or not dev_origins.is_contiguous():
+        raise ValueError("device origins must be a contiguous K x n int32 tensor (upload_origins)")
+    k = int(dev_origins.shape[0])
+    w = horizon_weight_array(weights, k)
+    return dev_origins, k, (ctypes.c_double * k)(*w)
+
+
+def ahead_multi_dense(ck, x, y, noise_diag, jitter, origins, weights=None, lookahead=True, fused=True, score="log"):
+    """Rolling-origin forecast values, means and variances of one dense layer at K horizons in one library call (gpar_ahead_multi_dense):
+    `origins` a K x n host array or the device tensor `upload_origins` returns, `weights` K positive numbers (None: all 1).  Returns
+    (out, values, mean, var, info): out = [weighted value, logdet] (device), the K unweighted values (device), K x n means and variances."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    og, k, w = _multi_args(origins, weights, n, dev)
+    z = alloc_matrix(n, max(ck.dz, 1), dev)
+    A = alloc_matrix(n + 1, n + 1, dev)
+    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 0, k)), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    values = torch.empty(k, dtype=torch.float64, device=dev)
+    moments = torch.empty(2, k, n, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(
+        lib.gpar_ahead_multi_dense(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
+            out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), og.data_ptr(), k, w, values.data_ptr(), score_code(score),
+            info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
+        ),
+        "gpar_ahead_multi_dense",
+    )
+    return out, values, moments[0], moments[1], info
+
+
+def ahead_multi_dense_grad(ck, x, y, noise_diag, jitter, periodic, origins, weights=None, lookahead=True, fused=True, score="log"):
+    """One dense layer's weighted multi-horizon rolling-origin value AND its gradient ingredients in one library call
+    (gpar_ahead_multi_dense_grad); `origins`, `weights` and `score` as for `ahead_multi_dense`.  Returns (out, values, half_diag, mean, var,
+    info, A, W): out = [weighted value, logdet, GRAD_NACC moment sums], the K unweighted values, 1/2 diag(W), K x n means and variances,
+    info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    og, k, w = _multi_args(origins, weights, n, dev)
+    dz = max(ck.dz, 1)
+    z = alloc_matrix(n, dz, dev)
+    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
+    A = alloc_matrix(n + 1, n + 1, dev)
+    X = alloc_matrix(n, n, dev)
+    W = alloc_matrix(n, n, dev)
+    nt = (n + 63) // 64
+    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
+    nacc = _lib.GRAD_NACC
+    nalpha = n + (n & 1)   # (the vector workspace starts at an even offset: it keeps a matrix)
+    work = torch.empty(nblocks * nacc + nalpha + int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 1, k)), dtype=torch.float64, device=dev)
+    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
+    values = torch.empty(k, dtype=torch.float64, device=dev)
+    half_diag = torch.empty(n, dtype=torch.float64, device=dev)
+    moments = torch.empty(2, k, n, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(
+        lib.gpar_ahead_multi_dense_grad(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
+            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(),
+            work[nblocks * nacc + nalpha:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), half_diag.data_ptr(), moments[0].data_ptr(),
+            moments[1].data_ptr(), og.data_ptr(), k, w, values.data_ptr(), score_code(score), info.data_ptr(), _potrf_flags(lookahead, fused),
+            stream_ptr(dev),
+        ),
+        "gpar_ahead_multi_dense_grad",
+    )
+    return out, values, half_diag, moments[0], moments[1], info, A, W
+
+
 def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=True):
     """Blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_dense).
     `fold_start`: the nfolds + 1 row offsets of the contiguous folds (host sequence, or the triple `upload_folds` returns).

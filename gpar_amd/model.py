@@ -215,7 +215,7 @@ def host_index(sel):
     return host
 
 
-_Ahead = collections.namedtuple("_Ahead", "horizon start rows")
+_Ahead = collections.namedtuple("_Ahead", "horizon start rows weights", defaults=(None,))   # (`horizon` a tuple: several in one pass, with `weights`)
 
 
 def rolling_origins(observed, horizon, start=0):
@@ -711,7 +711,7 @@ class GPAR:
         return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs, gap=gap, rows=rows), self.layers, (x, y, w))
 
     # ---- rolling-origin forecast scoring --------------------------------------------------------------
-    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None, score="log"):
+    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None, score="log", weights=None):
         """Layer-wise rolling-origin forecast scoring, the rows in the order given (the time order): layer i's inputs [x, y_<i] are built
         as `logpdf` builds them, and its observed entry of output i at row r is predicted from the layer's observed rows with index
         <= r - horizon - the horizon counts rows as given, so missing values make the bands ragged.  Rows with index < start are not
@@ -721,12 +721,22 @@ class GPAR:
         at output i with the predictive mean and variance of each (NaN where the row is not scored).  One factorisation per layer, the
         one `logpdf` computes.  `outputs` as for `loo`; `rows`: the indices, in the data as given, of the rows of the x handed in
         where earlier layers have dropped some (None: x holds every row).  `score` as for `loo`: under "crps" / "se" the total is minus
-        the summed CRPS / squared error of the scored forecasts.  Inducing points: ValueError."""
+        the summed CRPS / squared error of the scored forecasts.  Inducing points: ValueError.
+
+        `horizon` a list or tuple of K ints: the K horizons are scored from each layer's one factorisation (`Obs.ahead` with K origin arrays).
+        The total is sum_k weights[k] (the total of horizon k) - `weights`: K positive numbers, default all 1 - and the pieces are (rows,
+        mean, var, values) with K x rows means and variances and the K unweighted values of the layer (detached)."""
         check_score(score)
         if self.sparse:
             raise ValueError("rolling-origin forecast scoring needs dense observations (no inducing points)")
         rows = None if rows is None else np.asarray(rows, dtype=np.int64)
-        return _retry_unfused(lambda: self._held_out(x, y, w, _Ahead(int(horizon), int(start), rows), outputs, score), self.layers, (x, y, w))
+        if isinstance(horizon, (list, tuple, np.ndarray)):
+            labels = _Ahead(tuple(int(h) for h in horizon), int(start), rows, weights)
+        else:
+            if weights is not None:
+                raise ValueError("weights belong to several horizons")
+            labels = _Ahead(int(horizon), int(start), rows)
+        return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs, score), self.layers, (x, y, w))
 
     def _held_out(self, x, y, w, labels, outputs, score="log", gap=0, rows=None):
         """The layer loop of `loo` (`labels` None: pieces carry the per-row log-density, and nothing is kept on the host), `cv` and
@@ -768,7 +778,10 @@ class GPAR:
                         perm, starts = contiguous_folds(labels[observed])
                 if perm is None:
                     obs.transient = is_last or not self._feeds_estimate(yi, complete)   # nobody conditions on it: the value-only call serves
-                    if rolling:
+                    if rolling and isinstance(labels.horizon, tuple):
+                        origins = np.stack([rolling_origins(observed, h, labels.start) for h in labels.horizon])
+                        value, mean, var = obs.ahead(origins, score, weights=labels.weights)
+                    elif rolling:
                         value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start), score)
                     else:
                         value, mean, var = obs.cv(starts, hold) if blocked else obs.loo(score)
@@ -782,7 +795,9 @@ class GPAR:
                     sorted_obs.transient = True
                     value, mean, var = sorted_obs.cv(starts)
                     mean, var = torch.empty_like(mean).index_copy_(0, at, mean), torch.empty_like(var).index_copy_(0, at, var)
-                if labels is not None:
+                if rolling and isinstance(labels.horizon, tuple):
+                    pieces.append((seen, mean, var, obs._held_out_values))
+                elif labels is not None:
                     pieces.append((seen, mean, var))
                 else:
                     resid = obs.y.reshape(-1) - mean

@@ -216,18 +216,38 @@ def _run_on_streams(eng, streams, shares, fn, on_exit=None):
 
 
 def _check_horizon(horizon, start, n):
-    """`horizon` (an int >= 1) and `start` (an int in 0 ... n - 1) of `ahead` / `fit(objective="ahead")`."""
-    for name, v in (("horizon", horizon), ("start", start)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+    """`horizon` (an int >= 1, or a non-empty list, tuple or 1-D integer array of distinct ints >= 1: several horizons scored in one pass,
+    returned as a tuple) and `start` (an int in 0 ... n - 1) of `ahead` / `fit(objective="ahead")`."""
+    several = isinstance(horizon, (list, tuple, np.ndarray))
+    if several:
+        if np.ndim(horizon) != 1 or len(horizon) == 0:
+            raise ValueError("horizon must be an integer or a non-empty sequence of integers")
+        if len(set(horizon)) != len(horizon):
+            raise ValueError(f"horizon={tuple(horizon)}: the horizons must be distinct")
+    for name, v in [("horizon", h) for h in (horizon if several else (horizon,))] + [("start", start)]:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)):
             raise ValueError(f"{name} must be an integer")
-    if horizon < 1:
-        raise ValueError(f"horizon={horizon}: forecasts look at least one row ahead")
+    for h in horizon if several else (horizon,):
+        if h < 1:
+            raise ValueError(f"horizon={h}: forecasts look at least one row ahead")
     if not 0 <= start <= max(n - 1, 0):
         raise ValueError(f"start={start}: the first scored row must lie in 0 ... {max(n - 1, 0)}")
-    return int(horizon), int(start)
+    return (tuple(int(h) for h in horizon) if several else int(horizon)), int(start)
 
 
-def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log", gap=None):
+def _check_horizon_weights(horizon_weights, horizon):
+    """`horizon_weights` of `ahead` / `fit(objective="ahead")` for the checked `horizon`: None, or one positive finite number per horizon of
+    a sequence (returned as a float64 array)."""
+    if horizon_weights is None:
+        return None
+    if not isinstance(horizon, tuple):
+        raise ValueError("horizon_weights belong to a sequence of horizons: one horizon has nothing to weigh against")
+    from .hip import horizon_weight_array
+
+    return horizon_weight_array(horizon_weights, len(horizon))
+
+
+def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log", gap=None, horizon_weights=None):
     """The training objectives `fit` knows, and what the held-out ones need."""
     if objective not in ("mll", "loo", "cv", "ahead"):
         raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
@@ -238,6 +258,8 @@ def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=Non
                          + ", which has no per-row scoring rule")
     if objective != "ahead" and (horizon is not None or start is not None):
         raise ValueError('horizon and start belong to objective="ahead"')
+    if objective != "ahead" and horizon_weights is not None:
+        raise ValueError('horizon_weights belong to objective="ahead"')
     if objective == "cv" and folds is None:
         raise ValueError('objective="cv" needs folds: a number of contiguous blocks or one integer label per row')
     if objective != "cv" and folds is not None:
@@ -371,7 +393,7 @@ class GPARRegressor:
         self.is_conditioned = True
 
     def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, horizon=None, start=None,
-            score="log", gap=None, **kw_args):
+            score="log", gap=None, horizon_weights=None, **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
 
@@ -383,6 +405,9 @@ class GPARRegressor:
         on either side of a held-out fold from the rows it is predicted from (`cv`), for which the labels must not decrease.  "ahead" is the rolling-origin forecast score (`ahead`): every
         row predicted from the rows at least `horizon` (default 1) rows before it, rows before `start` (default 0) not scored - for
         models whose purpose is the forecast at that horizon; `horizon` / `start` belong to it alone; the restrictions of "loo".
+        `horizon` may be a sequence of distinct ints >= 1: the layers are trained on sum_k horizon_weights[k] (the score at horizon k), every
+        evaluation scoring all of them from one factorisation (`ahead`); `horizon_weights`: one positive finite number per horizon of
+        such a sequence (default all 1) - ValueError with a single horizon or another objective.
 
         `score` (with "loo" and "ahead" alone: ValueError otherwise): the rule each held-out entry is scored by.  "log", the Gaussian
         log density; "crps", minus the continuous ranked probability score - linear in the error where the log score is quadratic over
@@ -392,7 +417,7 @@ class GPARRegressor:
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap, horizon_weights)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -401,18 +426,20 @@ class GPARRegressor:
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
         self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, score=score,
-                    **({} if gap is None else {"gap": gap}), **kw_args)
+                    **({} if gap is None else {"gap": gap}), **({} if horizon_weights is None else {"horizon_weights": horizon_weights}), **kw_args)
 
     def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, horizon=None, start=None, score="log",
-               gap=None, **kw_args):
+               gap=None, horizon_weights=None, **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap, horizon_weights)
         loo, cv, ahead = objective == "loo", objective == "cv", objective == "ahead"
         labels = _fold_labels(folds, self.n) if cv else None
         gap = _check_purge(gap, labels) if cv else 0   # (0: blocked cross-validation as it was - the calls below are then today's)
         if ahead:
             horizon, start = _check_horizon(1 if horizon is None else horizon, 0 if start is None else start, self.n)
+            horizon_weights = _check_horizon_weights(horizon_weights, horizon)
+        several = {"weights": horizon_weights} if ahead and isinstance(horizon, tuple) else {}   # (a single horizon: the calls below are today's)
         self._x_ind_trainable = bool(optimise_x_ind) or getattr(self, "_x_ind_trainable", False)
         layers = list(layers)
         finals = {}
@@ -451,7 +478,7 @@ class GPARRegressor:
                     if cv:
                         return -gpar.cv(fixed_x, y_cached, None, layer_labels, outputs=[pi])[0]
                     if ahead:
-                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows, score=score)[0]
+                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows, score=score, **several)[0]
                     return -gpar.logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi], x_ind=x_ind_pi)
                 return -gpar.logpdf(x_dev, y_cached, None, only_last_layer=False)
 
@@ -475,7 +502,7 @@ class GPARRegressor:
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
                                      group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv and not gap else {}),
                                      **({"folds": labels, "purge": (gap, layer_rows)} if gap else {}),
-                                     **({"ahead": (horizon, start, layer_rows)} if ahead else {}), **({} if score == "log" else {"score": score}))
+                                     **({"ahead": (horizon, start, layer_rows, *several.values())} if ahead else {}), **({} if score == "log" else {"score": score}))
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
             if fast is not None:
@@ -744,7 +771,7 @@ class GPARRegressor:
         value = value.detach() if any_torch else value.detach().cpu().numpy()
         return value, mean, var
 
-    def ahead(self, x, y, w=None, horizon=1, start=0, score="log"):
+    def ahead(self, x, y, w=None, horizon=1, start=0, score="log", horizon_weights=None):
         """Rolling-origin forecast scoring under the prior model (`GPAR.ahead`): `(value, mean, var)` with the conventions of `loo`.
         The rows are taken in the order given (the time order); every observed y_rj with r >= `start` is predicted from the rows of
         output j observed at index <= r - `horizon` (and the layer's inputs [x, y_<j] as `logpdf` builds them) - the `horizon`-step-ahead
@@ -753,7 +780,12 @@ class GPARRegressor:
         `mean` and `var` are n x p numpy arrays of the predictive means and variances (of the noisy observation), NaN where y is missing
         or the row is not scored.  `horizon`: an int >= 1, counting rows as given (missing values make the bands ragged); a horizon >= n
         predicts every row from the prior.  `start`: an int in 0 ... n - 1.  `score` as for `loo`: "crps" / "se" sum minus the CRPS /
-        minus the squared error of the scored forecasts.  Dense layers only: ValueError with inducing points."""
+        minus the squared error of the scored forecasts.  Dense layers only: ValueError with inducing points.
+
+        `horizon` a non-empty list, tuple or 1-D integer array of K distinct ints >= 1 (any order): all K horizons are scored from the one
+        factorisation per output.  `mean` and `var` are then K x n x p (also for K = 1), `value` is sum_k horizon_weights[k] value_k with
+        `horizon_weights` K positive finite numbers (default all 1; ValueError with an int `horizon`), and the K unweighted value_k,
+        summed over the outputs, are left in `self.ahead_values_` (with an int `horizon`: the one value)."""
         check_score(score)
         if self.sparse:
             raise ValueError("rolling-origin forecast scoring needs dense layers: not available with inducing points (x_ind)")
@@ -763,7 +795,21 @@ class GPARRegressor:
         w = _init_weights(w, y)
         m, p = x.shape[1], y.shape[1]
         horizon, start = _check_horizon(horizon, start, int(x.shape[0]))
+        horizon_weights = _check_horizon_weights(horizon_weights, horizon)
         self._prepare_kernels(m, p, int(x.shape[0]))
+        if isinstance(horizon, tuple):
+            with torch.no_grad():
+                value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start, score=score, weights=horizon_weights)
+            mean = np.full((len(horizon), int(x.shape[0]), p), np.nan)
+            var = np.full((len(horizon), int(x.shape[0]), p), np.nan)
+            values = np.zeros(len(horizon))
+            for i, (rows, mean_i, var_i, values_i) in enumerate(pieces):
+                rows = rows.cpu().numpy()
+                mean[:, rows, i], var[:, rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
+                values += values_i.cpu().numpy()
+            self.ahead_values_ = values
+            value = value.detach() if any_torch else value.detach().cpu().numpy()
+            return value, mean, var
         with torch.no_grad():
             value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start, score=score)
         mean = np.full((int(x.shape[0]), p), np.nan)
@@ -771,6 +817,7 @@ class GPARRegressor:
         for i, (rows, mean_i, var_i) in enumerate(pieces):
             rows = rows.cpu().numpy()
             mean[rows, i], var[rows, i] = mean_i.cpu().numpy(), var_i.cpu().numpy()
+        self.ahead_values_ = np.array([float(value.detach())])
         value = value.detach() if any_torch else value.detach().cpu().numpy()
         return value, mean, var
 

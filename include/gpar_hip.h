@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 14
+#define GPAR_ABI_VERSION 15
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -424,6 +424,41 @@ int gpar_ahead_dense_score(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const
                            const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
                            double* ahead_mean, double* ahead_var, const int* origin, int score, int* info, int potrf_flags, void* stream);
 
+/* Rolling-origin forecast scoring at several horizons in one pass (ABI v15).  K = nh origin arrays over ONE factor: origins is a DEVICE
+ * array of nh x n ints, row k holding horizon k's origins as gpar_ahead_dense takes them (origins[k n + r] = -1: (k, r) is not scored,
+ * otherwise 0 ... r); weights is a HOST array of nh doubles, all positive and finite, handed to the kernels by value.  With e_kr, v_kr the
+ * sums of gpar_ahead_dense from origins[k n + r], term / q / s the scoring rule's (above):
+ *   values[k] = sum_r term(e_kr, v_kr)  (unweighted, DEVICE array of nh doubles),   out[0] = sum_k weights[k] values[k],
+ *   ahead_mean[k n + r] = y_r - e_kr,  ahead_var[k n + r] = v_kr  (nh x n each; NaN on unscored (k, r)),
+ *   Q_r(c) = sum_k weights[k] q_kr [origins[k n + r] <= c],   S_r(c) = sum_k weights[k] s_kr [origins[k n + r] <= c],
+ *   B_rc = -Q_r(c) a_c - 2 S_r(c) L_rc  (c <= r),   abar_c = -sum_{r >= c} Q_r(c) L_rc,   P and W as for gpar_ahead_dense_grad.
+ * The three entries are gpar_ahead_dense_grad_score, gpar_ahead_dense_grad_finish_score and gpar_ahead_dense_score argument for argument
+ * with `origins, nh, weights, values` in the place of `origin`: out[1], out[2 ...] and half_diag as there, the same launches (the check,
+ * row, abar and band kernels in their multi-horizon forms; the factor, X, the two products and the weighted-sum pass are shared by the
+ * horizons).  A row's nh sums come from one walk along its row of L; the band kernel skips chunks by the smallest origin over all
+ * horizons, so its cost follows the longest horizon.  vec: gpar_workspace_doubles(GPAR_WS_AHEAD_MULTI, n, 1, nh) doubles (16-byte
+ * aligned); the value-only form: gpar_workspace_doubles(GPAR_WS_AHEAD_MULTI, n, 0, nh).
+ * nh outside 1 ... GPAR_AHEAD_MAX_HORIZONS (-1015) and a weight that is not positive and finite (-1016) are argument errors before anything
+ * is launched: every buffer keeps what it held.  info: n + 1 + r for the smallest row r with an origin outside -1 ... r in any horizon;
+ * the 1-based row of a non-positive v_kr.  Whenever the info word is set, out[0], out[2 ...], values, half_diag, ahead_mean and ahead_var
+ * keep what they held.  One horizon with weight 1 gives the bits of gpar_ahead_dense_grad_score.  No atomics in any sum.
+ * [no reference counterpart] */
+#define GPAR_AHEAD_MAX_HORIZONS 8
+int gpar_ahead_multi_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* X, int ldxw,
+                                double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out, double* half_diag,
+                                double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights, double* values, int score,
+                                int* info, int potrf_flags, void* stream);
+int gpar_ahead_multi_dense_grad_finish(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                       double* z, double* zd, int ldz, double* A, int lda, const double* logdet, const int* info, double* X,
+                                       int ldxw, double* W, int ldw, double* alpha, double* vec, double* workspace, int nblocks, double* out,
+                                       double* half_diag, double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights,
+                                       double* values, int score, int* info_out, void* stream);
+int gpar_ahead_multi_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                           const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                           double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights, double* values, int score,
+                           int* info, int potrf_flags, void* stream);
+
 /* The same moment sums of  sum W dK/dtheta  for the other weight shapes the inducing-point (VFE) bound needs
  * [gradient of the PseudoObs elbo, gpar/model.py:226,286-287 under varz's optimiser]:
  *   GPAR_GRAD_SYM   z2 == z1: W symmetric n1 x n1, lower triangle read, sum over all pairs (what gpar_gram_grad does);
@@ -629,7 +664,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_AHEAD        (n, grad, -)     the `vec` of gpar_ahead_dense (grad = 0) / gpar_ahead_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_CV_GAP       (n, grad, max_hold)  the `vec` of gpar_cv_gap_dense (grad = 0) / gpar_cv_gap_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol
- *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading */
+ *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading
+ *   GPAR_WS_AHEAD_MULTI  (n, grad, nh)    the `vec` of gpar_ahead_multi_dense (grad = 0) / gpar_ahead_multi_dense_grad[_finish] (grad = 1) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -641,6 +677,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_CHOL_UPDATE 9
 #define GPAR_WS_AHEAD 10
 #define GPAR_WS_CV_GAP 11
+#define GPAR_WS_AHEAD_MULTI 12
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
