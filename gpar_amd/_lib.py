@@ -25,6 +25,8 @@ POTRF_UNFUSED = 2
 WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO, WS_CV, WS_PIVOTED_CHOL, WS_CHOL_UPDATE, WS_AHEAD = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 WS_CV_GAP = 11
 WS_AHEAD_MULTI = 12
+WS_AHEAD_WINDOW = 13
+AHEAD_WINDOW_MAX = 64   # GPAR_AHEAD_WINDOW_MAX: the longest window (rows) the fused sliding-window forecast entries take
 AHEAD_MAX_HORIZONS = 8   # GPAR_AHEAD_MAX_HORIZONS: the most horizons the fused multi-horizon rolling-origin entries take
 PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
 CHOL_UPDATE_MAX_RANK = 1024   # GPAR_CHOL_UPDATE_MAX_RANK: the most leading rows gpar_chol_drop_leading forgets in one call
@@ -32,7 +34,7 @@ SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the sc
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -246,6 +248,17 @@ SIGNATURES = {
         _c_int,
         [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _c_int, _ptr, _c_int,
          _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr],
+    ),
+    # (the sliding-window forms: no X, no alpha, no potrf flags; `lo, origin, score` before the info word)
+    "gpar_ahead_window_dense_grad": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _ptr, _c_int, _ptr, _c_int,
+         _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr],
+    ),
+    "gpar_ahead_window_dense": (
+        _c_int,
+        [ctypes.POINTER(FSpec), ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, ctypes.c_long, _ptr, _c_dbl, _ptr, _c_int, _ptr, _c_int,
+         _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr],
     ),
     "gpar_logpdf_dense_build": (
         _c_int,

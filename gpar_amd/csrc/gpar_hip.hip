@@ -413,6 +413,18 @@ __global__ void cv_folds_kernel(const double* __restrict__ P, int ldp, int n, co
                                 double* __restrict__ alpha, double* __restrict__ mean, double* __restrict__ var, double* __restrict__ bvec,
                                 double* __restrict__ term, double* __restrict__ Rm, int* __restrict__ info);
 
+// The rows kernel of the sliding-window forecast scoring (ahead_window.h, with its entry points below) and its dynamic LDS: the tile of
+// the largest block - GPAR_AHEAD_WINDOW_MAX rows and the scored one - and three vectors.
+namespace gpar {
+constexpr int AW_LD = GPAR_AHEAD_WINDOW_MAX + 1;   // rows of the largest block, and the (odd) leading dimension of its tile
+constexpr int AW_VEC = AW_LD + 1;                  // doubles between the vectors behind the tile
+constexpr int AW_LDS_BYTES = (AW_LD * AW_LD + 3 * AW_VEC) * (int)sizeof(double);   // 35,384 B: four workgroups share a compute unit's 160 KiB
+__global__ void ahead_window_rows_kernel(const double* __restrict__ K, int ldk, int n, const double* __restrict__ y, long incy,
+                                         const int* __restrict__ lo, const int* __restrict__ origin, double* __restrict__ mean,
+                                         double* __restrict__ var, double* __restrict__ q, double* __restrict__ s, double* __restrict__ term,
+                                         double* __restrict__ cp, int rule, int* __restrict__ info);
+}  // namespace gpar
+
 // Everything the library creates lazily, created now: the look-ahead side stream paired with `stream`, the event ring and
 // every kernel's dynamic-LDS attribute on the device that owns `stream`.  After it, entry points called
 // on `stream` make no HIP object-creation call - the precondition of capturing them into a hipGraph (the run-time compiled
@@ -432,6 +444,7 @@ int gpar_init(void* stream) {
                         reinterpret_cast<const void*>(&trsm_block2_back_kernel), reinterpret_cast<const void*>(&trinv_blocks2_kernel)};
     for (const void* fn : p2) GPAR_HIP_TRY(gpar_set_max_lds(fn, P2_LDS_BYTES));
     GPAR_HIP_TRY(gpar_set_max_lds(reinterpret_cast<const void*>(&cv_folds_kernel), CV_LDS_BYTES));
+    GPAR_HIP_TRY(gpar_set_max_lds(reinterpret_cast<const void*>(&ahead_window_rows_kernel), AW_LDS_BYTES));
     return 0;
 }
 
@@ -1214,6 +1227,7 @@ static int cv_folds_launch(const double* P, int ldp, int n, const double* X, int
 
 #include "ahead.h"   // rolling-origin forecast scoring: its kernels and weight stage (after loo_sum_terms and grad_epilogue_sums, which it uses)
 #include "cv_gap.h"  // purged blocked cross-validation: its kernels and weight stage (after cv_chol_lower and sym_lower_matvec_rows, which it uses)
+#include "ahead_window.h"   // sliding-window forecast scoring: its kernels and the head of its chain (after cv_chol_lower, ahead.h and the prep kernel)
 
 // ---- one chain for the dense objectives: marginal likelihood, leave-one-out, blocked cross-validation, rolling-origin forecasts --------
 // Every one-call entry is  prologue (features, Gram, factor) -> inverse -> the objective's weights W -> weighted-sum pass -> epilogue;
@@ -1709,6 +1723,51 @@ int gpar_ahead_multi_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const
     return 0;
 }
 
+// ---- sliding-window forecast scoring (ABI v16; ahead_window.h) ------------------------------------------------------------------------------
+// No factor of K is formed: out[1], the log-determinant word of the other entries, is 0, and there is no finish form.
+int gpar_ahead_window_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                 const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* W, int ldw,
+                                 double* vec, double* workspace, int nblocks, double* out, double* half_diag, double* ahead_mean, double* ahead_var,
+                                 const int* lo, const int* origin, int score, int* info, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !W || !vec || !workspace || !out || !half_diag || !ahead_mean || !ahead_var || !info || n <= 0 ||
+        nblocks <= 0)
+        return GPAR_ARG_ERROR(1);
+    int rc = aw_check_args(lo, origin, score);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *term = vec, *q = vec + n, *s = vec + 2 * (size_t)n, *cp = vec + 3 * (size_t)n;
+    rc = ahead_window_rows_run(fs, ks, x, n, ldx, y, incy, noise_diag, jitter, z, zd, ldz, A, lda, out + 1, lo, origin, ahead_mean, ahead_var, q, s,
+                               term, cp, score, info, st);
+    if (rc) return rc;
+    const int nt = gpar_ceil_div(n, AW_T);
+    hipLaunchKernelGGL(ahead_window_gather_kernel, dim3((unsigned)nt, (unsigned)nt), dim3(256), 0, st, (const double*)cp, (const double*)q,
+                       (const double*)s, lo, origin, n, W, ldw, (const int*)info);
+    rc = gram_grad_launch(ks, z, zd, n, ldz, z, zd, n, ldz, fs->dz, W, ldw, GPAR_GRAD_SYM, workspace, nblocks, out + 2, stream, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ahead_grad_epilogue_kernel, dim3((unsigned)(GRAD_NACC + (n + 255) / 256 + 1)), dim3(256), 0, st, (const double*)workspace,
+                       nblocks, out, (const double*)W, ldw, n, half_diag, (const double*)term, (const int*)info);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
+// Value, means and variances alone: the Gram matrix, the check, the rows, the sum of their terms
+int gpar_ahead_window_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                            const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                            double* ahead_mean, double* ahead_var, const int* lo, const int* origin, int score, int* info, void* stream) {
+    GPAR_API_GUARD;
+    if (!fs || !ks || !x || !y || !z || !A || !vec || !out || !ahead_mean || !ahead_var || !info || n <= 0) return GPAR_ARG_ERROR(1);
+    int rc = aw_check_args(lo, origin, score);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = ahead_window_rows_run(fs, ks, x, n, ldx, y, incy, noise_diag, jitter, z, nullptr, ldz, A, lda, out + 1, lo, origin, ahead_mean, ahead_var,
+                               nullptr, nullptr, vec, nullptr, score, info, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ahead_value_kernel, dim3(1), dim3(256), 0, st, (const double*)vec, n, out, (const int*)info);
+    GPAR_LAUNCH_CHECK();
+    return 0;
+}
+
 int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int ldz1, const double* z2, int n2, int ldz2, int dz,
                          const double* W, int ldw, int mode, int nsplit, double* workspace, double* out, int ldo, void* stream) {
     GPAR_API_GUARD;
@@ -1904,6 +1963,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_AHEAD: return ah_workspace_doubles(a, b);                          /* n, with gradient */
         case GPAR_WS_CV_GAP: return cvg_workspace_doubles(a, b, c);                     /* n, with gradient, max_hold */
         case GPAR_WS_AHEAD_MULTI: return ahm_workspace_doubles(a, b, c);                /* n, with gradient, horizons */
+        case GPAR_WS_AHEAD_WINDOW: return aw_workspace_doubles(a, b);                   /* n, with gradient */
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         default: return -1;

@@ -325,6 +325,19 @@ class HipEngine:
                                                                                   origins, weights, score=score, **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var, values
 
+    def ahead_window_dense(self, ck, x, y, noise_diag, jitter, lo, origin, score="log"):
+        """`ahead_dense` from a window: row r predicted from rows lo[r] ... origin[r] - 1 alone (at most `_lib.AHEAD_WINDOW_MAX` of them),
+        in one library call that factors no n x n matrix: (value as a 0-d device tensor, info word, means, variances)."""
+        out, mean, var, info = hip.ahead_window_dense(ck, self._mat(x), y, noise_diag, jitter, lo, origin, score=score)
+        return out[0], info, mean, var
+
+    def ahead_window_dense_grad(self, ck, x, y, noise_diag, jitter, lo, origin, score="log"):
+        """The sliding-window counterpart of `ahead_dense_grad`: (value, info word, a function returning (1/2 diag(W) on the device,
+        kernel-parameter gradients), means, variances) - no factor: the call forms none."""
+        out, half_diag, mean, var, info, _ = hip.ahead_window_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), lo, origin,
+                                                                         score=score)
+        return out[0], info, self._gradients_of(ck, out, half_diag), mean, var
+
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""
         safe = getattr(self._tls, "safe", False)

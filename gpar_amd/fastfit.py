@@ -273,7 +273,7 @@ class DenseLayerObjective:
     device tensors that do not change during the optimisation."""
 
     def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
-                 fold_start=None, origin=None, score="log", hold=None, weights=None):
+                 fold_start=None, origin=None, score="log", hold=None, weights=None, lo=None):
         if objective not in ("mll", "loo", "cv", "ahead"):
             raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
         self.score = hip.score_code(score)
@@ -293,6 +293,10 @@ class DenseLayerObjective:
             self.origin = self.origin.reshape(-1)
         if weights is not None and not self.multi:
             raise ValueError("weights belong to a K x n origin array")
+        # (a sliding window: the first row of every scored row's window beside its origin - gpar_ahead_window_dense_grad in the call's place)
+        if lo is not None and (self.origin is None or self.multi):
+            raise ValueError("lo belongs to one array of origins")
+        self.lo = None if lo is None else np.asarray(lo, dtype=np.int64).reshape(-1)
         self.weights = hip.horizon_weight_array(weights, self.origin.shape[0]) if self.multi else None
         self.eng, self.vs, self.names = eng, vs, list(names)
         self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
@@ -300,6 +304,8 @@ class DenseLayerObjective:
         self.fold_start = None if fold_start is None else np.asarray(fold_start, dtype=np.int64).reshape(-1)
         self.hold = None if hold is None else tuple(np.asarray(h, dtype=np.int64).reshape(-1) for h in hold)   # (purged folds: block extents)
         self.call = "cv_gap" if self.hold is not None else objective   # (the library call's family: `hip.objective_vec_doubles`)
+        if self.lo is not None:
+            self.call = "ahead_window"
         if objective != "mll":
             group = lane = None      # (cross-validation lanes take no part in the lock-step rendezvous)
         self.group, self.lane = group, lane   # a LockstepFactor and this objective's slot in it, or None
@@ -349,6 +355,8 @@ class DenseLayerObjective:
             self.folds = hip.upload_hold(self.fold_start, self.hold, n, dev)   # (device offsets and block extents, number of folds, largest block)
         if self.objective == "ahead" and not self.multi:
             self.folds = (hip.upload_origin(self.origin, n, dev),)   # (the one argument the entry takes in the folds' place)
+        if self.lo is not None:
+            self.folds = hip.upload_window(self.lo, self.origin, n, dev)   # (lo and origin on the device)
         nmom = n   # (doubles of the held-out means, and of the variances)
         if self.multi:   # origins (K x n, uploaded once), K, the weights (host), the K values (device): what the multi call takes in the origin's place
             k = int(self.origin.shape[0])
@@ -356,6 +364,8 @@ class DenseLayerObjective:
             self.folds = (hip.upload_origins(self.origin, n, dev), k, (ctypes.c_double * k)(*self.weights), self.values)
             nmom = k * n
             nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 1, k)) + 2 * nmom
+        elif self.lo is not None:
+            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_AHEAD_WINDOW, n, 1, 0)) + 2 * n
         else:
             nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.call, n, 1, self.folds) + 2 * n
         nalpha = n + (n & 1)   # (the vectors start at an even offset: "ahead" keeps a matrix among them)
@@ -397,7 +407,13 @@ class DenseLayerObjective:
         head = (fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"],
                 p["W"], p["ldw"], p["alpha"])
         tail = (p["info"], self.flags, stream.cuda_stream)
-        if self.objective != "mll":
+        if self.call == "ahead_window":   # (nothing is factored whole: no X, no alpha, no factorisation flags)
+            rc = self.lib.gpar_ahead_window_dense_grad(fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["zd"], p["ldz"],
+                                                       p["A"], p["lda"], p["W"], p["ldw"], p["vec"], p["work"], self.nblocks, p["out"], p["half"],
+                                                       p["loo_mean"], p["loo_var"], *hip._fold_args(self.folds), self.score, p["info"],
+                                                       stream.cuda_stream)
+            _lib.check(rc, "gpar_ahead_window_dense_grad")
+        elif self.objective != "mll":
             name = {"loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad", "cv_gap": "gpar_cv_gap_dense_grad",
                     "ahead": "gpar_ahead_multi_dense_grad" if self.multi else "gpar_ahead_dense_grad_score"}[self.call]
             fold_args = hip._fold_args(self.folds)
@@ -521,7 +537,7 @@ class DenseLayerObjective:
 
 
 def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None, ahead=None,
-          score="log", purge=None):
+          score="log", purge=None, window=None):
     """The fast objective of layer `pi` of regressor `reg` with fixed design matrix `fixed_x`, or None when this route does not
     apply.  `item` = (y_i, w_i, mask) as `model.per_output` yields it for output pi; `names` the variable names being optimised;
     `objective`: "mll" (log marginal likelihood), "loo" (leave-one-out predictive log-density) or "cv" (blocked cross-validation over
@@ -531,9 +547,11 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     survive; `horizon` a tuple of K ints, then with the horizons' weights as a fourth element: K origin arrays and the multi-horizon call,
     None above `_lib.AHEAD_MAX_HORIZONS`); `score`: the scoring rule of "loo" and "ahead".  `purge` = (gap, the indices in the data as given of the rows of
     `fixed_x`): purged cross-validation - `folds` then holds one non-decreasing label per row of the data AS GIVEN, and the layer's
-    fold offsets and block extents are counted here, once (`model.purged_folds`); None when its largest block exceeds the call's limit."""
+    fold offsets and block extents are counted here, once (`model.purged_folds`); None when its largest block exceeds the call's limit.
+    `window` (with "ahead" and one horizon): the sliding-window score - the first rows of the layer's windows are counted here, once, beside
+    its origins (`model.rolling_window_starts`) and uploaded with them; None where a window holds more than `_lib.AHEAD_WINDOW_MAX` rows."""
     from .gp import one_call_grad_rows
-    from .model import contiguous_folds, host_index, purged_folds, rolling_origins
+    from .model import contiguous_folds, host_index, purged_folds, rolling_origins, rolling_window_starts
     from .regression import _model_generator
 
     on_device = cls is None   # (the CPU tests of the host logic hand in a class with its own device side)
@@ -589,6 +607,13 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
             origin = np.stack([rolling_origins(observed, h, start) for h in horizon])
         else:
             origin = rolling_origins(observed, horizon, start)
+    lo = None
+    if window is not None:
+        if origin is None or origin.ndim != 1:
+            raise ValueError('window belongs to objective="ahead" with one horizon')
+        lo = rolling_window_starts(observed, horizon, window)
+        if int((origin - lo)[origin >= 0].max(initial=0)) > _lib.AHEAD_WINDOW_MAX:
+            return None   # (a window longer than the library call takes: the general route trains the layer)
     tracer = _TracingVars(vs)
     f, noise = _model_generator(tracer, reg.m, pi, **reg.model_config)()
     kernel = f.kernel
@@ -605,4 +630,4 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
                lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}),
                **({} if origin is None else {"origin": origin}), **({} if score == "log" else {"score": score}),
                **({"weights": weights[0]} if origin is not None and origin.ndim == 2 and weights else {}),
-               **({} if hold is None else {"hold": hold}))
+               **({} if hold is None else {"hold": hold}), **({} if lo is None else {"lo": lo}))

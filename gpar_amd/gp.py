@@ -37,9 +37,10 @@ import math
 import numpy as np
 import torch
 
-from ._lib import AHEAD_MAX_HORIZONS, CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
+from ._lib import AHEAD_MAX_HORIZONS, AHEAD_WINDOW_MAX, CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
 from .engine import get_engine, joining
-from .hip import fold_offsets, hold_extents, horizon_weight_array, origin_array, origins_array, upload_hold, upload_origin, upload_origins
+from .hip import (fold_offsets, hold_extents, horizon_weight_array, origin_array, origins_array, upload_hold, upload_origin, upload_origins,
+                  upload_window, window_arrays)
 from .kernels import Kernel
 
 __all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs", "greedy_inducing"]
@@ -505,6 +506,74 @@ def _ahead_algebra(eng, L, a, origin, score="log"):
     return value, e, torch.where(scored, v, nan), scored, weights
 
 
+class _Window:
+    """The fifth held-out scheme: rolling origins with a window - row r predicted from rows lo[r] ... origin[r] - 1 alone (`Obs.ahead(origin,
+    lo=...)`)."""
+
+    def __init__(self, lo, origin):
+        self.lo, self.origin = lo, origin   # checked host arrays (int64); origin -1: not scored
+        scored = origin >= 0
+        self.longest = int((origin - lo)[scored].max()) if scored.any() else 0
+        self.device = None                  # the uploaded pair, made at the first fused call
+
+
+def _ahead_window_algebra(eng, K, y, lo, origin, score="log"):
+    """Sliding-window forecasts from the covariance K = k + D + eps I itself (symmetric, whole), where no library call takes the evaluation:
+    (value, e = y - mean, v with NaN on unscored rows, scored, a function returning the weights W).  Per scored row r the block J = (lo[r]
+    ... origin[r] - 1, r) is gathered and factored, K_JJ = G G^T with r last: z = G^-1 y_J, e_r = G_rr z_r, v_r = G_rr^2; `score` turns them
+    into the value term and the sensitivities q_r, s_r (`_score_rows`); c = G_rr G^-T e_r = [-K_SS^-1 k_Sr; 1], p = [K_SS^-1 y_S; 0] and
+    the row adds W^r = -2 s_r c c^T + q_r (p c^T + c p^T) on J.  Rows with windows of equal length share batched Cholesky algebra, as
+    `_fold_groups` groups folds; the blocks of neighbouring rows overlap, so W is summed group by group, the rows of a group chosen
+    with disjoint blocks - every sum has a fixed order (as `_cv_gap_algebra` sums C).  Windows of any length."""
+    n, dev = y.numel(), y.device
+    lo, origin = np.asarray(lo, dtype=np.int64), np.asarray(origin, dtype=np.int64)
+    rows = np.nonzero(origin >= 0)[0]
+    scored = torch.as_tensor(origin >= 0, device=dev)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    e, v = torch.zeros(n, dtype=torch.float64, device=dev), torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    value = torch.zeros((), dtype=torch.float64, device=dev)
+    colour, reach = np.zeros(rows.size, dtype=np.int64), []   # (greedy: the first colour whose last block ends before this one begins)
+    for k, r in enumerate(rows):
+        c = next((c for c, h in enumerate(reach) if h < lo[r]), len(reach))
+        reach[c:c + 1] = [r]
+        colour[k] = c
+    shape = np.stack([origin[rows] - lo[rows], colour], axis=1) if rows.size else np.zeros((0, 2), dtype=np.int64)
+    parts = []
+    for m, c in np.unique(shape, axis=0):
+        rs = rows[np.all(shape == [m, c], axis=1)]
+        m = int(m)
+        idx = torch.as_tensor(np.concatenate([lo[rs, None] + np.arange(m), rs[:, None]], axis=1), dtype=torch.long, device=dev)   # k x (m + 1)
+        G, info = torch.linalg.cholesky_ex(K[idx[:, :, None], idx[:, None, :]])
+        eng.check_info(info.max().reshape(1).to(torch.int32))   # (one word: the largest failing pivot of the group, 0 if none)
+        z = torch.linalg.solve_triangular(G, y[idx][:, :, None], upper=False)[:, :, 0]
+        g = G[:, m, m]
+        at = torch.as_tensor(rs, dtype=torch.long, device=dev)
+        e_g, v_g = g * z[:, m], g * g
+        term, q, s = _score_rows(score, e_g, v_g)
+        e[at], v[at] = e_g, v_g
+        value = value + torch.sum(term)
+        parts.append((idx, G, z, g, q, s, m))
+
+    def weights():
+        W = torch.zeros(n, n, dtype=torch.float64, device=dev)
+        for idx, G, z, g, q, s, m in parts:
+            unit = torch.zeros(idx.shape[0], m + 1, 1, dtype=torch.float64, device=dev)
+            unit[:, m, 0] = g
+            c = torch.linalg.solve_triangular(G.transpose(1, 2), unit, upper=True)[:, :, 0]
+            p = torch.zeros_like(c)
+            if m:
+                p[:, :m] = torch.linalg.solve_triangular(G[:, :m, :m].transpose(1, 2), z[:, :m, None], upper=True)[:, :, 0]
+            pc = p[:, :, None] * c[:, None, :]
+            block = -2.0 * s[:, None, None] * (c[:, :, None] * c[:, None, :]) + q[:, None, None] * (pc + pc.transpose(1, 2))
+            at = (idx[:, :, None], idx[:, None, :])
+            W[at] = W[at] + block
+        out = eng.new_matrix(n, n)
+        out.copy_(W)
+        return out
+
+    return value, e, torch.where(scored, v, nan), scored, weights
+
+
 class _PosteriorMean(torch.autograd.Function):
     """Posterior mean of `f | obs` at x* as a differentiable function of the kernel parameters, the noise, the training
     inputs X, the inducing inputs Z and x* itself: the column `_update_inputs` feeds to the next layer
@@ -903,7 +972,7 @@ class Obs:
             return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
         return self._held_out(_Purged(*hold_extents(fold_start, hold, self.fdd.n)), "cross-validation")
 
-    def ahead(self, origin, score="log", weights=None):
+    def ahead(self, origin, score="log", weights=None, lo=None):
         """(value, mean, var) of rolling-origin forecasts, the observations in the order given (the time order): row r is predicted from
         rows 0 ... origin[r] - 1 (origin[r] in 0 ... r; 0: from the prior), origin[r] = -1 leaves it unscored (NaN in mean and var).  mean
         and var are the predictive moments of the noisy observation and value = sum_scored log N(y_r; mean_r, var_r) - a 0-d tensor that
@@ -914,10 +983,20 @@ class Obs:
         A K x n `origin` scores K horizons from the one factorisation: mean and var are K x n, value = sum_k weights[k] value_k (`weights`:
         K positive finite numbers, default all 1; with a 1-D origin: ValueError) and the K unweighted value_k are left, detached, in
         `self._held_out_values`.  One library call where `logpdf` would take one and K <= `_lib.AHEAD_MAX_HORIZONS`; otherwise composed of
-        `_ahead_algebra`'s terms and weights W, summed over the horizons - any K."""
+        `_ahead_algebra`'s terms and weights W, summed over the horizons - any K.
+
+        `lo` (n ints, with a 1-D origin): a sliding window - row r is predicted from rows lo[r] ... origin[r] - 1 ALONE (0 <= lo[r] <=
+        origin[r]; lo[r] = origin[r]: from the prior; neither array may decrease over the scored rows).  Nothing n x n is factored: every
+        scored row conditions on its own block of the covariance.  One library call where `logpdf` would take one and no window exceeds
+        `_lib.AHEAD_WINDOW_MAX` rows; otherwise composed of the Gram matrix and batched block algebra (`_ahead_window_algebra`) - any
+        length.  lo = 0 everywhere gives the values above (by other arithmetic).  None: today's evaluation, untouched."""
         check_score(score)
         if self.base.is_posterior:
             raise NotImplementedError("rolling-origin forecasts are those of a prior process")
+        if lo is not None:
+            if np.ndim(origin.cpu() if isinstance(origin, torch.Tensor) else origin) != 1 or weights is not None:
+                raise ValueError("a window belongs to one horizon: lo and origin hold one integer per row each, without weights")
+            return self._held_out(_Window(*window_arrays(lo, origin, self.fdd.n)), "sliding-window forecast", score)
         shaped = origin.cpu() if isinstance(origin, torch.Tensor) else origin
         if np.ndim(shaped) == 2:
             origins = origins_array(shaped, self.fdd.n)
@@ -964,6 +1043,8 @@ class Obs:
             return torch.zeros((), dtype=torch.float64, device=dev)
         if ahead and starts.multi:
             return self._ahead_multi_eval(starts, want_grad, score)
+        if isinstance(starts, _Window):
+            return self._ahead_window_eval(starts, want_grad, score)
         call = "ahead_dense" if ahead else "cv_gap_dense" if purged else "loo_dense" if starts is None else "cv_dense"
         folds = () if starts is None else (starts,)
         rule = {} if score == "log" else {"score": score}   # (an engine's one-call forms take the rule by keyword)
@@ -1056,6 +1137,34 @@ class Obs:
         self._held_out_parts = (fac, summed) if want_grad else None
         return total.detach() if getattr(eng, "_deferred", None) is not None else total.detach().cpu()
 
+    def _ahead_window_eval(self, starts, want_grad, score):
+        """`_held_out_eval` for a sliding window (`starts` a `_Window`): the fused calls where `_value_only` / `_fusable_grad` allow and every
+        window holds at most `AHEAD_WINDOW_MAX` rows, `_ahead_window_algebra` on the covariance otherwise.  No factor is formed or kept."""
+        eng, n = self.eng, self.fdd.n
+        rule = {} if score == "log" else {"score": score}
+        if starts.longest <= AHEAD_WINDOW_MAX and hasattr(eng, "ahead_window_dense") and (self._fusable_grad() if want_grad else self._value_only()):
+            if starts.device is None:
+                starts.device = upload_window(starts.lo, starts.origin, n, self.y.device)
+            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
+            if want_grad:
+                value, info, self._fused_held_out_gradients, self._held_out_mean, self._held_out_var = eng.ahead_window_dense_grad(
+                    ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, *starts.device, **rule)
+            else:
+                value, info, self._held_out_mean, self._held_out_var = eng.ahead_window_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon,
+                                                                                              *starts.device, **rule)
+            eng.check_info(info)
+            return value.detach()
+        block = eng.new_matrix(n, n)
+        with torch.no_grad():
+            self.fdd._fill_cov(block, eng.epsilon)   # (a prior process: the mean is zero)
+            low = torch.tril(block)
+            y = self.y.reshape(-1).detach()
+            value, e, var, scored, weights = _ahead_window_algebra(eng, low + torch.tril(low, -1).T, y, starts.lo, starts.origin, score)
+        self._held_out_mean = torch.where(scored, y - e, var)
+        self._held_out_var = var
+        self._held_out_parts = (weights,) if want_grad else None
+        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+
     def _held_out_gradients(self):
         """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the value `_held_out_eval(want_grad=True)` has just formed, with
         W = alpha u^T + u alpha^T - 2 S S^T,  u = K^-1 b,  S from the objective's block algebra."""
@@ -1064,6 +1173,12 @@ class Obs:
             self._fused_held_out_gradients = None
             return fused()
         eng, n = self.eng, self.fdd.n
+        if len(self._held_out_parts) == 1:   # a sliding window: W from the rows' blocks, no K^-1 anywhere
+            W = self._held_out_parts[0]()
+            self._held_out_parts = None
+            ck, _ = self.fdd.features()
+            grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
+            return 0.5 * torch.diagonal(W).clone(), grads
         if len(self._held_out_parts) == 2:   # rolling origins: W is not of the form below; its algebra returns it whole
             fac, weights = self._held_out_parts
             self._held_out_parts = None

@@ -458,6 +458,99 @@ def ahead_multi_dense_grad(ck, x, y, noise_diag, jitter, periodic, origins, weig
     return out, values, half_diag, moments[0], moments[1], info, A, W
 
 
+def window_arrays(lo, origin, n):
+    """(lo, origin) of a sliding-window forecast evaluation as checked host arrays (int64): origin as `origin_array` checks it, and on every
+    scored row 0 <= lo[r] <= origin[r] - row r is predicted from rows lo[r] ... origin[r] - 1 -, neither array decreasing over the scored
+    rows.  The one check of these arrays: `gp.Obs.ahead` and `upload_window` both go through it."""
+    o = origin_array(origin, n)
+    l = np.asarray(lo.cpu() if isinstance(lo, torch.Tensor) else lo)
+    if l.ndim != 1 or l.size != n or (l.size and not np.issubdtype(l.dtype, np.integer)):
+        raise ValueError("lo must hold one integer per row")
+    l = l.astype(np.int64)
+    scored = o >= 0
+    if np.any(l[scored] < 0) or np.any(l[scored] > o[scored]):
+        raise ValueError("lo[r] must lie in 0 ... origin[r] on every scored row")
+    if np.any(np.diff(l[scored]) < 0) or np.any(np.diff(o[scored]) < 0):
+        raise ValueError("lo and origin must not decrease over the scored rows: a window slides forward")
+    return l, o
+
+
+def upload_window(lo, origin, n, device):
+    """(device int32 lo, device int32 origin): what the fused sliding-window entries take, from arrays checked by `window_arrays`; a window
+    of more than GPAR_AHEAD_WINDOW_MAX rows is a ValueError."""
+    l, o = window_arrays(lo, origin, n)
+    if l.size and int((o - l)[o >= 0].max(initial=0)) > _lib.AHEAD_WINDOW_MAX:
+        raise ValueError(f"the fused sliding-window entries take windows of at most {_lib.AHEAD_WINDOW_MAX} rows")
+    return torch.tensor(l, dtype=torch.int32, device=device), torch.tensor(o, dtype=torch.int32, device=device)
+
+
+def _window_args(lo, origin, n, dev):
+    if isinstance(lo, torch.Tensor) and lo.is_cuda and isinstance(origin, torch.Tensor) and origin.is_cuda:
+        for a in (lo, origin):
+            if a.dim() != 1 or a.numel() != n or a.dtype != torch.int32 or not a.is_contiguous():
+                raise ValueError("device lo and origin must be contiguous int32 tensors of n entries (upload_window)")
+        return lo, origin
+    return upload_window(lo, origin, n, dev)
+
+
+def ahead_window_dense(ck, x, y, noise_diag, jitter, lo, origin, score="log"):
+    """Sliding-window forecast value, means and variances of one dense layer in one library call (gpar_ahead_window_dense): row r predicted
+    from rows lo[r] ... origin[r] - 1 alone, origin[r] = -1 not scored (NaN in its mean and variance).  `lo`, `origin`: host sequences of n
+    ints or the device tensors `upload_window` returns.  Returns (out, mean, var, info): out = [value, 0] (device; nothing is factored
+    whole, so there is no log-determinant), means and variances (device), info word."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    lo_dev, og = _window_args(lo, origin, n, dev)
+    z = alloc_matrix(n, max(ck.dz, 1), dev)
+    A = alloc_matrix(n + 1, n + 1, dev)
+    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_WINDOW, n, 0, 0)), dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(
+        lib.gpar_ahead_window_dense(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
+            out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), lo_dev.data_ptr(), og.data_ptr(), score_code(score), info.data_ptr(),
+            stream_ptr(dev),
+        ),
+        "gpar_ahead_window_dense",
+    )
+    return out, moments[0], moments[1], info
+
+
+def ahead_window_dense_grad(ck, x, y, noise_diag, jitter, periodic, lo, origin, score="log"):
+    """One dense layer's sliding-window forecast value AND its gradient ingredients in one library call (gpar_ahead_window_dense_grad); `lo`,
+    `origin` and `score` as for `ahead_window_dense`.  Returns (out, half_diag, mean, var, info, W): out = [value, 0, GRAD_NACC moment sums],
+    1/2 diag(W), means and variances, info word, the weights W (lower triangle).  No factor of the whole matrix is formed or returned."""
+    lib = _lib.load()
+    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
+    lo_dev, og = _window_args(lo, origin, n, dev)
+    dz = max(ck.dz, 1)
+    z = alloc_matrix(n, dz, dev)
+    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
+    A = alloc_matrix(n + 1, n + 1, dev)
+    W = alloc_matrix(n, n, dev)
+    nt = (n + 63) // 64
+    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
+    nacc = _lib.GRAD_NACC
+    work = torch.empty(nblocks * nacc + int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_WINDOW, n, 1, 0)), dtype=torch.float64, device=dev)
+    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
+    vectors = torch.empty(3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(
+        lib.gpar_ahead_window_dense_grad(
+            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
+            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
+            A.data_ptr(), _ld(A), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(),
+            vectors[0].data_ptr(), vectors[1].data_ptr(), vectors[2].data_ptr(), lo_dev.data_ptr(), og.data_ptr(), score_code(score),
+            info.data_ptr(), stream_ptr(dev),
+        ),
+        "gpar_ahead_window_dense_grad",
+    )
+    return out, vectors[0], vectors[1], vectors[2], info, W
+
+
 def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=True):
     """Blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_dense).
     `fold_start`: the nfolds + 1 row offsets of the contiguous folds (host sequence, or the triple `upload_folds` returns).

@@ -215,7 +215,7 @@ def host_index(sel):
     return host
 
 
-_Ahead = collections.namedtuple("_Ahead", "horizon start rows weights", defaults=(None,))   # (`horizon` a tuple: several in one pass, with `weights`)
+_Ahead = collections.namedtuple("_Ahead", "horizon start rows weights window", defaults=(None, None))   # (`horizon` a tuple: several in one pass, with `weights`; `window`: a sliding one)
 
 
 def rolling_origins(observed, horizon, start=0):
@@ -226,6 +226,22 @@ def rolling_origins(observed, horizon, start=0):
     origin = np.searchsorted(observed, observed - int(horizon), side="right").astype(np.int64)
     origin[observed < int(start)] = -1
     return origin
+
+
+def check_window(window):
+    """`window` of sliding-window forecast scoring: an int >= 1 (no bool, no float)."""
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError(f"window={window!r}: the number of rows a forecast is made from must be an int >= 1")
+    return int(window)
+
+
+def rolling_window_starts(observed, horizon, window):
+    """First rows of a layer's sliding windows, beside `rolling_origins`: the row with index r is predicted from the layer's rows with
+    index in r - horizon - window + 1 ... r - horizon, rows lo ... origin - 1 of the layer with lo = the number of its rows with index
+    <= r - horizon - window.  `window` counts rows as given, like `horizon`: missing values make the windows ragged and shorter, never
+    longer; lo = origin is an empty window (the row is predicted from the prior)."""
+    observed = np.asarray(observed, dtype=np.int64)
+    return np.searchsorted(observed, observed - int(horizon) - int(window), side="right").astype(np.int64)
 
 
 def contiguous_folds(labels):
@@ -711,7 +727,7 @@ class GPAR:
         return _retry_unfused(lambda: self._held_out(x, y, w, labels, outputs, gap=gap, rows=rows), self.layers, (x, y, w))
 
     # ---- rolling-origin forecast scoring --------------------------------------------------------------
-    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None, score="log", weights=None):
+    def ahead(self, x, y, w, horizon, start=0, outputs=None, rows=None, score="log", weights=None, window=None):
         """Layer-wise rolling-origin forecast scoring, the rows in the order given (the time order): layer i's inputs [x, y_<i] are built
         as `logpdf` builds them, and its observed entry of output i at row r is predicted from the layer's observed rows with index
         <= r - horizon - the horizon counts rows as given, so missing values make the bands ragged.  Rows with index < start are not
@@ -725,12 +741,21 @@ class GPAR:
 
         `horizon` a list or tuple of K ints: the K horizons are scored from each layer's one factorisation (`Obs.ahead` with K origin arrays).
         The total is sum_k weights[k] (the total of horizon k) - `weights`: K positive numbers, default all 1 - and the pieces are (rows,
-        mean, var, values) with K x rows means and variances and the K unweighted values of the layer (detached)."""
+        mean, var, values) with K x rows means and variances and the K unweighted values of the layer (detached).
+
+        `window` (an int >= 1, with one horizon): a sliding window instead of the expanding origin - the entry at row r is predicted from
+        the layer's observed rows with index in r - horizon - window + 1 ... r - horizon alone (`rolling_window_starts`; the window counts
+        rows as given), from the prior where none is observed there.  No layer factors its whole covariance.  A window >= the number of
+        rows gives the expanding score; None is that evaluation itself, untouched."""
         check_score(score)
         if self.sparse:
             raise ValueError("rolling-origin forecast scoring needs dense observations (no inducing points)")
         rows = None if rows is None else np.asarray(rows, dtype=np.int64)
-        if isinstance(horizon, (list, tuple, np.ndarray)):
+        if window is not None:
+            if isinstance(horizon, (list, tuple, np.ndarray)) or weights is not None:
+                raise ValueError("window takes one horizon: several horizons in one pass share a factor the windowed score does not have")
+            labels = _Ahead(int(horizon), int(start), rows, None, check_window(window))
+        elif isinstance(horizon, (list, tuple, np.ndarray)):
             labels = _Ahead(tuple(int(h) for h in horizon), int(start), rows, weights)
         else:
             if weights is not None:
@@ -781,6 +806,9 @@ class GPAR:
                     if rolling and isinstance(labels.horizon, tuple):
                         origins = np.stack([rolling_origins(observed, h, labels.start) for h in labels.horizon])
                         value, mean, var = obs.ahead(origins, score, weights=labels.weights)
+                    elif rolling and labels.window is not None:
+                        value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start), score,
+                                                     lo=rolling_window_starts(observed, labels.horizon, labels.window))
                     elif rolling:
                         value, mean, var = obs.ahead(rolling_origins(observed, labels.horizon, labels.start), score)
                     else:

@@ -17,7 +17,7 @@ from ._lib import CHOL_UPDATE_MAX_RANK
 from .engine import get_engine
 from .gp import GP, Measure, check_score, greedy_inducing
 from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
-from .model import GPAR, check_gap, host_index, host_masks, per_output
+from .model import GPAR, check_gap, check_window, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
 from .vars import Vars
 
@@ -247,7 +247,18 @@ def _check_horizon_weights(horizon_weights, horizon):
     return horizon_weight_array(horizon_weights, len(horizon))
 
 
-def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log", gap=None, horizon_weights=None):
+def _check_window(window, horizon, horizon_weights=None):
+    """`window` of `ahead` / `fit(objective="ahead")` (None: the expanding origin): an int >= 1, beside ONE horizon."""
+    if window is None:
+        return None
+    window = check_window(window)
+    if isinstance(horizon, (list, tuple, np.ndarray)) or horizon_weights is not None:
+        raise ValueError("window takes one horizon, not a sequence of horizons: the multi-horizon pass shares one factorisation of all rows, "
+                         "which the windowed score never forms")
+    return window
+
+
+def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=None, score="log", gap=None, horizon_weights=None, window=None):
     """The training objectives `fit` knows, and what the held-out ones need."""
     if objective not in ("mll", "loo", "cv", "ahead"):
         raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
@@ -260,6 +271,10 @@ def _check_objective(objective, sparse, fix, folds=None, horizon=None, start=Non
         raise ValueError('horizon and start belong to objective="ahead"')
     if objective != "ahead" and horizon_weights is not None:
         raise ValueError('horizon_weights belong to objective="ahead"')
+    if window is not None:
+        if objective != "ahead":
+            raise ValueError('window belongs to objective="ahead"')
+        _check_window(window, horizon, horizon_weights)
     if objective == "cv" and folds is None:
         raise ValueError('objective="cv" needs folds: a number of contiguous blocks or one integer label per row')
     if objective != "cv" and folds is not None:
@@ -393,7 +408,7 @@ class GPARRegressor:
         self.is_conditioned = True
 
     def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, horizon=None, start=None,
-            score="log", gap=None, horizon_weights=None, **kw_args):
+            score="log", gap=None, horizon_weights=None, window=None, **kw_args):
         """Train layer by layer with L-BFGS-B on the negative log marginal likelihood; keyword arguments go to
         `minimise_l_bfgs_b` (`iters`, `f_calls`, `trace`).  (reference regression.py:391-459)
 
@@ -408,6 +423,9 @@ class GPARRegressor:
         `horizon` may be a sequence of distinct ints >= 1: the layers are trained on sum_k horizon_weights[k] (the score at horizon k), every
         evaluation scoring all of them from one factorisation (`ahead`); `horizon_weights`: one positive finite number per horizon of
         such a sequence (default all 1) - ValueError with a single horizon or another objective.
+        `window` (an int >= 1, "ahead" with ONE horizon alone: ValueError otherwise): the layers are trained on the sliding-window score
+        (`ahead(window=)`), every row predicted from the `window` rows before its origin alone - the objective of a model that `update(...,
+        drop=k)` keeps on a window of recent rows; no evaluation factors a layer's whole covariance.  None: the expanding origin, untouched.
 
         `score` (with "loo" and "ahead" alone: ValueError otherwise): the rule each held-out entry is scored by.  "log", the Gaussian
         log density; "crps", minus the continuous ranked probability score - linear in the error where the log score is quadratic over
@@ -417,7 +435,7 @@ class GPARRegressor:
         `optimise_x_ind` (an addition, off by default; the reference's todo.tasks:5): the inducing inputs `x_ind` become the
         variable "x_ind" of `self.vs` and are trained along with every layer's hyper-parameters (the gradient with respect to
         inducing locations comes from the same device passes as the joint gradient of `fix=False`)."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap, horizon_weights)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap, horizon_weights, window)
         self.condition(x, y, w)
         if greedy:
             # (as the reference, regression.py:409-410 and its test tests/test_regression.py:241-243; the search itself is
@@ -426,13 +444,14 @@ class GPARRegressor:
         if optimise_x_ind and not self.sparse:
             raise ValueError("optimise_x_ind needs inducing points (x_ind)")
         self._train(range(self.p), fix, optimise_x_ind, objective=objective, folds=folds, horizon=horizon, start=start, score=score,
-                    **({} if gap is None else {"gap": gap}), **({} if horizon_weights is None else {"horizon_weights": horizon_weights}), **kw_args)
+                    **({} if gap is None else {"gap": gap}), **({} if horizon_weights is None else {"horizon_weights": horizon_weights}),
+                    **({} if window is None else {"window": window}), **kw_args)
 
     def _train(self, layers, fix=True, optimise_x_ind=False, concurrent=True, objective="mll", folds=None, horizon=None, start=None, score="log",
-               gap=None, horizon_weights=None, **kw_args):
+               gap=None, horizon_weights=None, window=None, **kw_args):
         """Train the given layers of the conditioned model, one after the other (or, where they do not feed one another, on the
         engine's worker streams); returns {layer: final value of its objective}."""
-        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap, horizon_weights)
+        _check_objective(objective, self.sparse, fix, folds, horizon, start, score, gap, horizon_weights, window)
         loo, cv, ahead = objective == "loo", objective == "cv", objective == "ahead"
         labels = _fold_labels(folds, self.n) if cv else None
         gap = _check_purge(gap, labels) if cv else 0   # (0: blocked cross-validation as it was - the calls below are then today's)
@@ -440,6 +459,7 @@ class GPARRegressor:
             horizon, start = _check_horizon(1 if horizon is None else horizon, 0 if start is None else start, self.n)
             horizon_weights = _check_horizon_weights(horizon_weights, horizon)
         several = {"weights": horizon_weights} if ahead and isinstance(horizon, tuple) else {}   # (a single horizon: the calls below are today's)
+        windowed = {} if window is None else {"window": int(window)}   # (no window: no new argument reaches any call below)
         self._x_ind_trainable = bool(optimise_x_ind) or getattr(self, "_x_ind_trainable", False)
         layers = list(layers)
         finals = {}
@@ -478,7 +498,7 @@ class GPARRegressor:
                     if cv:
                         return -gpar.cv(fixed_x, y_cached, None, layer_labels, outputs=[pi])[0]
                     if ahead:
-                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows, score=score, **several)[0]
+                        return -gpar.ahead(fixed_x, y_cached, None, horizon, start, outputs=[pi], rows=layer_rows, score=score, **several, **windowed)[0]
                     return -gpar.logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi], x_ind=x_ind_pi)
                 return -gpar.logpdf(x_dev, y_cached, None, only_last_layer=False)
 
@@ -502,7 +522,8 @@ class GPARRegressor:
                 fast = fastfit.build(self, eng, self.vs, pi, names, fixed_x, y_cached[bool(self.impute)][pi], general_fg=general_fg,
                                      group=group, lane=lane, objective=objective, **({"folds": layer_labels} if cv and not gap else {}),
                                      **({"folds": labels, "purge": (gap, layer_rows)} if gap else {}),
-                                     **({"ahead": (horizon, start, layer_rows, *several.values())} if ahead else {}), **({} if score == "log" else {"score": score}))
+                                     **({"ahead": (horizon, start, layer_rows, *several.values())} if ahead else {}), **({} if score == "log" else {"score": score}),
+                                     **windowed)
             if group is not None and (fast is None or fast.group is None):
                 group.leave(lane)   # (this lane trains through the general route from here on: the others must not wait for it)
             if fast is not None:
@@ -771,7 +792,7 @@ class GPARRegressor:
         value = value.detach() if any_torch else value.detach().cpu().numpy()
         return value, mean, var
 
-    def ahead(self, x, y, w=None, horizon=1, start=0, score="log", horizon_weights=None):
+    def ahead(self, x, y, w=None, horizon=1, start=0, score="log", horizon_weights=None, window=None):
         """Rolling-origin forecast scoring under the prior model (`GPAR.ahead`): `(value, mean, var)` with the conventions of `loo`.
         The rows are taken in the order given (the time order); every observed y_rj with r >= `start` is predicted from the rows of
         output j observed at index <= r - `horizon` (and the layer's inputs [x, y_<j] as `logpdf` builds them) - the `horizon`-step-ahead
@@ -785,10 +806,17 @@ class GPARRegressor:
         `horizon` a non-empty list, tuple or 1-D integer array of K distinct ints >= 1 (any order): all K horizons are scored from the one
         factorisation per output.  `mean` and `var` are then K x n x p (also for K = 1), `value` is sum_k horizon_weights[k] value_k with
         `horizon_weights` K positive finite numbers (default all 1; ValueError with an int `horizon`), and the K unweighted value_k,
-        summed over the outputs, are left in `self.ahead_values_` (with an int `horizon`: the one value)."""
+        summed over the outputs, are left in `self.ahead_values_` (with an int `horizon`: the one value).
+
+        `window` (an int >= 1, with an int `horizon`: ValueError beside a sequence): the sliding-window form of the evaluation - y_rj is
+        predicted from the rows of output j observed at index r - horizon - window + 1 ... r - horizon ALONE, the forecast of a model kept
+        on a window of recent rows (`update(..., drop=k)`); with no row observed there, from the prior.  `window` counts rows as given:
+        missing values make the windows shorter, never longer.  window >= n gives the expanding score above; None is that evaluation
+        itself."""
         check_score(score)
         if self.sparse:
             raise ValueError("rolling-origin forecast scoring needs dense layers: not available with inducing points (x_ind)")
+        window = _check_window(window, horizon, horizon_weights)
         any_torch = isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor)
         x = _uprank(_to_engine(x))
         y = self._unnormalise_y(self._transform_y(_uprank(_to_engine(y))))  # (as logpdf)
@@ -811,7 +839,8 @@ class GPARRegressor:
             value = value.detach() if any_torch else value.detach().cpu().numpy()
             return value, mean, var
         with torch.no_grad():
-            value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start, score=score)
+            value, pieces = _construct_gpar(self, self.vs, m, p).ahead(x, y, w, horizon, start, score=score,
+                                                                       **({} if window is None else {"window": window}))
         mean = np.full((int(x.shape[0]), p), np.nan)
         var = np.full((int(x.shape[0]), p), np.nan)
         for i, (rows, mean_i, var_i) in enumerate(pieces):

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 15
+#define GPAR_ABI_VERSION 16
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -459,6 +459,36 @@ int gpar_ahead_multi_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const
                            double* ahead_mean, double* ahead_var, const int* origins, int nh, const double* weights, double* values, int score,
                            int* info, int potrf_flags, void* stream);
 
+/* Sliding-window forecast scoring of one dense layer (ABI v16): gpar_ahead_dense with every scored row predicted from a WINDOW of the
+ * rows before its origin instead of all of them - the score of the model gpar_chol_drop_leading / gpar_chol_append keep alive.  lo and
+ * origin are DEVICE arrays of n ints: origin[r] = -1 leaves row r unscored (NaN in ahead_mean and ahead_var); otherwise row r is predicted
+ * from rows lo[r] ... origin[r] - 1 (lo[r] = origin[r]: from the prior), with 0 <= lo[r] <= origin[r] <= r, origin[r] - lo[r] <=
+ * GPAR_AHEAD_WINDOW_MAX, and neither array decreasing over the scored rows.  With S = k(x, x) + diag(noise_diag) + jitter I, J the run
+ * followed by r itself and S_JJ = G G^T (r last):
+ *   z = G^-1 y_J,   e_r = y_r - ahead_mean[r] = G_rr z_r,   ahead_var[r] = v_r = G_rr^2,   out[0] = sum_scored term(e_r, v_r),
+ *   c = G_rr G^-T e_r = [-S_SS^-1 s_Sr; 1],   p = [S_SS^-1 y_S; 0],   W = sum_r scatter_J(-2 s_r c c^T + q_r (p c^T + c p^T)),
+ * term / q / s the scoring rule's (above), d out[0] / d theta = 1/2 sum_ab W_ab dS_ab/dtheta and half_diag = 1/2 diag W the noise gradient.
+ * S is built as for gpar_logpdf_dense_grad (z, zd, A: the workspaces there; A holds S on its lower triangle afterwards and y in row n)
+ * and is NOT factored: out[1] = 0, there is no X, no alpha and no finish form.  Launches: features + observations, Gram, a check of lo and
+ * origin, one workgroup per row (the block S_JJ factored in LDS; c and p of the row stored compactly), for the gradient a gather of W on
+ * its lower triangle (every entry the sum over the rows whose blocks hold it, in increasing r), the weighted-sum pass of
+ * gpar_logpdf_dense_grad and its epilogue (out[2 .. 2 + gpar_grad_nacc()), half_diag, the sum of the terms in a fixed order).  No atomics
+ * in any sum: a call returns the same bits every time.  vec: gpar_workspace_doubles(GPAR_WS_AHEAD_WINDOW, n, 1, 0) doubles;
+ * gpar_ahead_window_dense (value, means and variances alone): gpar_workspace_doubles(GPAR_WS_AHEAD_WINDOW, n, 0, 0).
+ * info: n + 1 + r for the first row r whose lo / origin break the rules above; the 1-based row of S at which a block's factorisation met a
+ * non-positive pivot.  Whenever the info word is set, out[0], out[2 ...] and half_diag keep what they held; so do ahead_mean and ahead_var
+ * when the check has set it (after a non-positive pivot the rows whose own blocks were sound have written theirs).  An unknown score
+ * (-1014) is an argument error before anything is launched.  Limits: dense layers; windows of at most
+ * GPAR_AHEAD_WINDOW_MAX rows (longer windows: compose gpar_gram with host-side block algebra).  [no reference counterpart] */
+#define GPAR_AHEAD_WINDOW_MAX 64
+int gpar_ahead_window_dense_grad(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                                 const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda, double* W, int ldw,
+                                 double* vec, double* workspace, int nblocks, double* out, double* half_diag, double* ahead_mean, double* ahead_var,
+                                 const int* lo, const int* origin, int score, int* info, void* stream);
+int gpar_ahead_window_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const double* x, int n, int ldx, const double* y, long incy,
+                            const double* noise_diag, double jitter, double* z, int ldz, double* A, int lda, double* vec, double* out,
+                            double* ahead_mean, double* ahead_var, const int* lo, const int* origin, int score, int* info, void* stream);
+
 /* The same moment sums of  sum W dK/dtheta  for the other weight shapes the inducing-point (VFE) bound needs
  * [gradient of the PseudoObs elbo, gpar/model.py:226,286-287 under varz's optimiser]:
  *   GPAR_GRAD_SYM   z2 == z1: W symmetric n1 x n1, lower triangle read, sum over all pairs (what gpar_gram_grad does);
@@ -665,7 +695,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_CV_GAP       (n, grad, max_hold)  the `vec` of gpar_cv_gap_dense (grad = 0) / gpar_cv_gap_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol
  *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading
- *   GPAR_WS_AHEAD_MULTI  (n, grad, nh)    the `vec` of gpar_ahead_multi_dense (grad = 0) / gpar_ahead_multi_dense_grad[_finish] (grad = 1) */
+ *   GPAR_WS_AHEAD_MULTI  (n, grad, nh)    the `vec` of gpar_ahead_multi_dense (grad = 0) / gpar_ahead_multi_dense_grad[_finish] (grad = 1)
+ *   GPAR_WS_AHEAD_WINDOW (n, grad, -)     the `vec` of gpar_ahead_window_dense (grad = 0) / gpar_ahead_window_dense_grad (grad = 1) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -678,6 +709,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_AHEAD 10
 #define GPAR_WS_CV_GAP 11
 #define GPAR_WS_AHEAD_MULTI 12
+#define GPAR_WS_AHEAD_WINDOW 13
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
