@@ -13,7 +13,7 @@ __version__ = "0.2.0"
 
 from .regression import GPARRegressor, log_transform, squishing_transform  # noqa: F401
 from .model import GPAR  # noqa: F401
-from .kernels import Matern12, Matern32, Matern52  # noqa: F401
+from .kernels import Cosine, Matern12, Matern32, Matern52  # noqa: F401
 from .gp import greedy_inducing  # noqa: F401
 
-__all__ = ["GPARRegressor", "GPAR", "log_transform", "squishing_transform", "Matern12", "Matern32", "Matern52", "greedy_inducing"]
+__all__ = ["GPARRegressor", "GPAR", "log_transform", "squishing_transform", "Matern12", "Matern32", "Matern52", "Cosine", "greedy_inducing"]

@@ -14,6 +14,7 @@ GPAR_MAX_TERMS = 8
 EMBED_ID, EMBED_SIN, EMBED_COS = 0, 1, 2
 K_EQ, K_RQ, K_LINEAR = 0, 1, 2
 K_MATERN12, K_MATERN32, K_MATERN52 = 3, 4, 5
+K_COS = 6
 
 GRAM_LOWER = 1
 GEMM_C_LOWER = 1
@@ -34,7 +35,7 @@ SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the sc
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)

@@ -32,6 +32,9 @@ FAMILIES = {
     "matern52": dict(linear=True, nonlinear=True, matern=2.5),
 }
 
+# GPARRegressor(spectral=Q) at m = 1: with the default linear output term and without it (Gram and parameter-gradient kinds)
+SPECTRAL = [dict(spectral=q, linear=linear) for q in (1, 2, 4) for linear in (True, False)]
+
 
 def structures():
     """{structure: (compiled kernel, periodic?, sparse kinds wanted?)} over the families, m = 1 .. 4 and the first eight layers (with
@@ -49,6 +52,8 @@ def structures():
     cases.append((FAMILIES["nonlinear"], 2, 4, 8, False))     # C3
     cases.append((FAMILIES["nonlinear"], None, 8, 4, True))   # C4 (inducing points: rectangular weights, input gradients)
     cases.append((FAMILIES["per_rq"], None, 3, 16, False))    # C5
+    for kw in SPECTRAL:
+        cases.append((kw, None, 1, 8 if kw["linear"] else 1, False))
     out = {}
     with torch.no_grad():
         for kw, markov, m, p, sparse in cases:

@@ -236,6 +236,7 @@ static int ahead_window_rows_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks,
                                  const int* lo, const int* origin, double* mean, double* var, double* q, double* s, double* term, double* cp,
                                  int rule, int* info, hipStream_t st) {
     if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    if (ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || !kspec_cos_embed_ok(fs, ks)) return GPAR_ARG_ERROR(3);
     const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
     hipLaunchKernelGGL(dense_grad_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *fs, x, n, ldx, z, zd, ldz, y, incy, A, lda,
                        logdet, info);

@@ -245,6 +245,7 @@ static int gram_launch(const gpar_kspec_t* ks, const double* z1, int n1, int ldz
                        int batch = 1, long long batch_z = 0, long long batch_k = 0) {
     if (!ks || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS)
         return GPAR_ARG_ERROR(3);
+    if (!kspec_cos_ok(ks)) return GPAR_ARG_ERROR(3);
     if (dz < 0 || dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(4);
     if (n1 <= 0 || n2 <= 0) return 0;
     const int sym = (z1 == z2 && n1 == n2) ? 1 : 0;
@@ -454,7 +455,7 @@ static bool jit_request(int kind, const gpar_kspec_t& ks, int dz, int& jkind, in
 int gpar_jit_compile_check(int kind, const gpar_kspec_t* ks, int dz, const char* arch, char* log, int log_len) {
     // (no library lock: nothing shared is touched - source generation and hiprtc only -, and several threads may check at once)
     if (!ks || !arch || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || dz < 0 ||
-        dz > GPAR_MAX_DIMS)
+        dz > GPAR_MAX_DIMS || !kspec_cos_ok(ks))
         return GPAR_ARG_ERROR(1);
     std::string source, entry;
     int jkind = 0, extra = 0;
@@ -474,7 +475,7 @@ int gpar_jit_compile_check(int kind, const gpar_kspec_t* ks, int dz, const char*
 long long gpar_jit_compile(int kind, const gpar_kspec_t* ks, int dz, const char* arch, void* code_out, long long capacity, char* key_out,
                            int key_len, char* log, int log_len) {
     if (!ks || !arch || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || dz < 0 ||
-        dz > GPAR_MAX_DIMS)
+        dz > GPAR_MAX_DIMS || !kspec_cos_ok(ks))
         return GPAR_ARG_ERROR(1);
     std::string source, entry;
     int jkind = 0, extra = 0;
@@ -498,21 +499,25 @@ long long gpar_jit_compile(int kind, const gpar_kspec_t* ks, int dz, const char*
 }
 
 // Fingerprint of the kernel generators: FNV-1a over the sources of every kernel kind for one probe structure that uses every factor
-// type (EQ x RQ product, a linear term, a constant term, a product of the three Matern factors; nine feature dims), + the ABI version.  Pure host code, needs no GPU.
+// type (EQ x RQ product, a linear term, a constant term, a product of the three Matern factors, an EQ x cosine product, a cosine
+// term without an exponential; thirteen feature dims), + the ABI version.  Pure host code, needs no GPU.
 unsigned long long gpar::aot_fingerprint() {
     static unsigned long long cached = 0ull;
     if (cached) return cached;
     gpar_kspec_t ks;
     memset(&ks, 0, sizeof ks);
-    ks.nterms = 4;
-    ks.nfactors = 6;
-    ks.coef[0] = 1.0; ks.coef[1] = 1.0; ks.coef[2] = 1.0; ks.coef[3] = 1.0;
+    ks.nterms = 6;
+    ks.nfactors = 9;
+    ks.coef[0] = 1.0; ks.coef[1] = 1.0; ks.coef[2] = 1.0; ks.coef[3] = 1.0; ks.coef[4] = 1.0; ks.coef[5] = 1.0;
     ks.factor[0] = gpar_factor_t{GPAR_K_EQ, 0, 0, 2, 0.0};
     ks.factor[1] = gpar_factor_t{GPAR_K_RQ, 0, 2, 2, 0.5};
     ks.factor[2] = gpar_factor_t{GPAR_K_LINEAR, 1, 4, 2, 0.0};
     ks.factor[3] = gpar_factor_t{GPAR_K_MATERN12, 3, 6, 1, 0.0};
     ks.factor[4] = gpar_factor_t{GPAR_K_MATERN32, 3, 7, 1, 0.0};
     ks.factor[5] = gpar_factor_t{GPAR_K_MATERN52, 3, 8, 1, 0.0};
+    ks.factor[6] = gpar_factor_t{GPAR_K_EQ, 4, 9, 1, 0.0};
+    ks.factor[7] = gpar_factor_t{GPAR_K_COS, 4, 10, 2, 0.0};
+    ks.factor[8] = gpar_factor_t{GPAR_K_COS, 5, 12, 1, 0.0};
     unsigned long long h = 1469598103934665603ull;
     auto mix = [&](const std::string& text) {
         for (unsigned char ch : text) h = (h ^ ch) * 1099511628211ull;
@@ -522,11 +527,13 @@ unsigned long long gpar::aot_fingerprint() {
     for (int kind : kinds) {
         std::string source, entry;
         int jkind = 0, extra = 0;
-        if (jit_request(kind, ks, 9, jkind, extra, entry, source, true)) mix(entry + "\n" + source);
+        if (jit_request(kind, ks, 13, jkind, extra, entry, source, true)) mix(entry + "\n" + source);
         else mix("-");
     }
     {   // ... and the wide form of the Gram generator (more than GRAM_JIT_MAX_DZ feature dims): the same factor types over 23 dims
+        // (without the cosine term: a wide structure that holds one has no generated Gram kernel)
         gpar_kspec_t wide = ks;
+        wide.nterms = 4; wide.nfactors = 6;
         wide.factor[0].nd = 8; wide.factor[1].off = 8; wide.factor[1].nd = 7; wide.factor[2].off = 15; wide.factor[2].nd = 5;
         wide.factor[3].off = 20; wide.factor[4].off = 21; wide.factor[5].off = 22;
         std::string source, entry;
@@ -553,6 +560,7 @@ static bool jit_request(int kind, const gpar_kspec_t& ks, int dz, int& jkind, in
     if (kind == JIT_GRAM) {
         const int strip = gram_jit_strip(1 << 20, dz);
         if (strip <= 0) return false;   // wide structure: there is no generated Gram kernel (gram_jit.h)
+        if (!gram_jit_serves(ks, dz)) return false;   // ... nor for a cosine factor beside more than GRAM_JIT_MAX_DZ dims
         jkind = JIT_GRAM; extra = 1; entry = "gram_jit";
         if (want_source) source = gram_jit_source(ks, dz, strip);
     } else if (kind == JIT_GRAD || kind == JIT_GRAD + 10 || kind == JIT_GRAD + 20 || kind == JIT_GRAD + 30) {
@@ -574,7 +582,8 @@ static bool jit_request(int kind, const gpar_kspec_t& ks, int dz, int& jkind, in
 // evaluation (where it would also hold the mutex every other thread's launches need).  Returns 0 (ready), 1 (compilation failed:
 // the interpreter will be used) or an argument error.
 int gpar_jit_prepare(int kind, const gpar_kspec_t* ks, int dz, void* stream) {
-    if (!ks || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || dz < 0 || dz > GPAR_MAX_DIMS)
+    if (!ks || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || dz < 0 || dz > GPAR_MAX_DIMS ||
+        !kspec_cos_ok(ks))
         return GPAR_ARG_ERROR(1);
     int jkind = 0, extra = 0;
     std::string entry, source, key, arch;
@@ -629,6 +638,7 @@ int gpar_logpdf_dense(const gpar_fspec_t* fs, const gpar_kspec_t* ks, const doub
     GPAR_API_GUARD;
     if (!fs || !ks || !A || !logdet || !info || !value || (n > 0 && (!x || !y))) return GPAR_ARG_ERROR(1);
     hipStream_t st = (hipStream_t)stream;
+    if (ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || !kspec_cos_embed_ok(fs, ks)) return GPAR_ARG_ERROR(3);
     int rc = featurize_launch(fs, x, n, ldx, z, ldz, st);
     if (!rc && n > 0) rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
     if (rc) return rc;
@@ -655,6 +665,7 @@ int gpar_logpdf_dense_build(const gpar_fspec_t* fs, const gpar_kspec_t* ks, cons
     GPAR_API_GUARD;
     if (!fs || !ks || !A || !logdet || !info || (n > 0 && (!x || !y))) return GPAR_ARG_ERROR(1);
     hipStream_t st = (hipStream_t)stream;
+    if (ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || !kspec_cos_embed_ok(fs, ks)) return GPAR_ARG_ERROR(3);
     int rc = featurize_launch(fs, x, n, ldx, z, ldz, st);
     if (!rc && n > 0) rc = gram_launch(ks, z, n, ldz, z, n, ldz, fs->dz, A, lda, GPAR_GRAM_LOWER, noise_diag, jitter, nullptr, st);
     if (rc) return rc;
@@ -690,6 +701,10 @@ int gpar_logpdf_lockstep(const gpar_layer_t* layers, int batch, const double* x,
     hipStream_t st = (hipStream_t)stream;
     for (int b = 0; b < batch; ++b)
         if (!layers[b].fs || !layers[b].ks || layers[b].y_col < 0) return GPAR_ARG_ERROR(2);
+    for (int b = 0; b < batch; ++b) {   // (the fused build below does not pass through gram_launch)
+        const gpar_kspec_t* ks = layers[b].ks;
+        if (ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || !kspec_cos_ok(ks) || !kspec_cos_embed_ok(layers[b].fs, ks)) return GPAR_ARG_ERROR(3);
+    }
     // Small evaluations: ONE launch per LS_CHUNK layers builds everything (gram.h: lockstep_build_kernel; same bits as the launches
     // below) - when every feature map fits its compact form and the build is short enough for launch latency to matter.
     bool fused_build = n > 0 && n <= env_int("GPAR_LOCKSTEP_FUSED_BUILD_ROWS", 4096) && w != nullptr;
@@ -759,6 +774,7 @@ int gpar_gram_diag(const gpar_kspec_t* ks, const double* z, int n, int ldz, int 
     GPAR_API_GUARD;
     (void)dz;
     if (!ks) return GPAR_ARG_ERROR(3);
+    if (ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || !kspec_cos_ok(ks)) return GPAR_ARG_ERROR(3);
     if (n <= 0) return 0;
     hipLaunchKernelGGL(gram_diag_kernel, dim3(gpar_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, *ks, z, n, ldz, out);
     GPAR_LAUNCH_CHECK();
@@ -789,6 +805,7 @@ static int gram_grad_launch(const gpar_kspec_t* ks, const double* z1, const doub
                             int nblocks, double* out, void* stream, bool reduce = true) {
     if (!ks || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS)
         return GPAR_ARG_ERROR(3);
+    if (!kspec_cos_ok(ks)) return GPAR_ARG_ERROR(3);
     if (dz < 0 || dz > GPAR_MAX_DIMS || nblocks <= 0) return GPAR_ARG_ERROR(4);
     if (mode != GPAR_GRAD_SYM && mode != GPAR_GRAD_RECT && mode != GPAR_GRAD_DIAG) return GPAR_ARG_ERROR(13);
     if (mode != GPAR_GRAD_RECT && (n2 != n1 || z2 != z1)) return GPAR_ARG_ERROR(9);
@@ -1254,6 +1271,7 @@ static int dense_factor_run(const gpar_fspec_t* fs, const gpar_kspec_t* ks, cons
                             const CvFolds* folds, const double* noise_diag, double jitter, double* z, double* zd, int ldz, double* A, int lda,
                             double* logdet, int* info, int potrf_flags, hipStream_t st) {
     if (fs->dz < 0 || fs->dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(2);
+    if (ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS || !kspec_cos_embed_ok(fs, ks)) return GPAR_ARG_ERROR(3);
     int rc = folds ? cv_check_folds(*folds, n) : 0;
     if (rc) return rc;
     const long total = (long)n * fs->dz > (long)n + 1 ? (long)n * fs->dz : (long)n + 1;
@@ -1773,6 +1791,7 @@ int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int l
     GPAR_API_GUARD;
     if (!ks || ks->nterms < 0 || ks->nterms > GPAR_MAX_TERMS || ks->nfactors < 0 || ks->nfactors > GPAR_MAX_FACTORS)
         return GPAR_ARG_ERROR(3);
+    if (!kspec_cos_ok(ks)) return GPAR_ARG_ERROR(3);
     if (dz < 0 || dz > GPAR_MAX_DIMS || nsplit <= 0) return GPAR_ARG_ERROR(4);
     if (mode != GPAR_GRAD_SYM && mode != GPAR_GRAD_RECT) return GPAR_ARG_ERROR(13);
     if (mode == GPAR_GRAD_SYM && (n2 != n1 || z2 != z1)) return GPAR_ARG_ERROR(9);

@@ -18,7 +18,8 @@
 namespace gpar {
 
 // Code that evaluates term `t` on the micro-tile: for each of its factors f the squared distances / inner products s<f>[8] and
-// the factor values phi<f>[8]; for RQ factors also tq<f>[8] = s / 2 alpha and lg<f>[8] = log1p(tq), for Matern factors dk<f>[8] = d phi / d s.
+// the factor values phi<f>[8]; for RQ factors also tq<f>[8] = s / 2 alpha and lg<f>[8] = log1p(tq), for Matern factors dk<f>[8] = d phi / d s;
+// for a cosine factor s<f>[8] is the SUM of the differences sigma and dk<f>[8] = d phi / d sigma.
 static std::string grad_jit_term_values(const gpar_kspec_t& ks, int t, int f0, int nf) {
     std::string o;
     for (int k = 0; k < nf; ++k) {
@@ -26,6 +27,12 @@ static std::string grad_jit_term_values(const gpar_kspec_t& ks, int t, int f0, i
         const std::string F = std::to_string(f0 + k), off = std::to_string(fa.off), nd = std::to_string(fa.nd);
         o += "            double s" + F + "[8], phi" + F + "[8];\n";
         o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) s" + F + "[e] = 0.0;\n";
+        if (fa.type == GPAR_K_COS) {
+            o += "            gram_accum_diff_static<" + off + ", " + nd + ">(Za, Zb, ty, cb, s" + F + ");\n";
+            o += "            double dk" + F + "[8];\n";
+            o += "            gram_cos_grad8(s" + F + ", phi" + F + ", dk" + F + ");\n";
+            continue;
+        }
         o += "            gram_accum_static<" + off + ", " + nd + ", " + (fa.type == GPAR_K_LINEAR ? "true" : "false") + ">(Za, Zb, ty, cb, s" + F + ");\n";
         if (fa.type == GPAR_K_LINEAR) {
             o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) phi" + F + "[e] = s" + F + "[e];\n";
@@ -175,13 +182,16 @@ extern "C" __global__ __launch_bounds__(256, 2) void gram_grad_jit(gj_kspec ks, 
                 o += "                        g[e] = wr * (-0.5 * ib);\n";
                 o += "                        al = fma(wr, tq" + F + "[e] * ib - lg" + F + "[e], al);\n";
                 o += "                    }\n                    accAl[" + F + "] = al;\n                }\n";
-            } else if (gram_jit_is_matern(fa.type)) {
+            } else if (gram_jit_is_matern(fa.type) || fa.type == GPAR_K_COS) {
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e] * dk" + F + "[e];\n";
             } else {
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e];\n";
             }
-            o += "                grad_dims_static<" + off + ", " + nd + ", " + (fa.type == GPAR_K_LINEAR ? "true" : "false") +
-                 ", HAS_ZD, DZ>(Za, Zb, Zda, Zdb, ty, cb, g, accA, accP);\n";
+            if (fa.type == GPAR_K_COS)   // g (za - zb) / 2 per dim; no period sums (a cosine factor's dims are never embedded)
+                o += "                grad_dims_cos_static<" + off + ", " + nd + ", DZ>(Za, Zb, ty, cb, g, accA);\n";
+            else
+                o += "                grad_dims_static<" + off + ", " + nd + ", " + (fa.type == GPAR_K_LINEAR ? "true" : "false") +
+                     ", HAS_ZD, DZ>(Za, Zb, Zda, Zdb, ty, cb, g, accA, accP);\n";
             o += "            }\n";
         }
         o += "            }\n";
@@ -201,7 +211,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void gram_grad_jit(gj_kspec ks, 
         for (int d = fa.off; d < fa.off + fa.nd; ++d) {
             const std::string D = std::to_string(d);
             o += "    { const double v = gj_wave_sum(accA[" + D + "]); if (lane == 0) red[wv][OFF_A + " + D + "] = v; }\n";
-            if (has_zd && fa.type != GPAR_K_LINEAR)
+            if (has_zd && fa.type != GPAR_K_LINEAR && fa.type != GPAR_K_COS)
                 o += "    { const double v = gj_wave_sum(accP[" + D + "]); if (lane == 0) red[wv][OFF_P + " + D + "] = v; }\n";
         }
     }
@@ -329,9 +339,14 @@ extern "C" __global__ __launch_bounds__(256, 2) void gram_input_grad_jit(gj_kspe
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = -w[e] * rest[e] * phi" + F + "[e] / (1.0 + tq" + F + "[e]);\n";
             else if (gram_jit_is_matern(fa.type))
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = 2.0 * w[e] * rest[e] * dk" + F + "[e];\n";
+            else if (fa.type == GPAR_K_COS)   // d phi / d za_q = d phi / d sigma for each of the factor's dims
+                o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e] * dk" + F + "[e];\n";
             else
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) g[e] = w[e] * rest[e];\n";
-            o += "                grad_rows_static<" + off + ", " + nd + ", " + (fa.type == GPAR_K_LINEAR ? "true" : "false") + ", DZ>(Za, Zb, ty, cb, g, accX);\n";
+            if (fa.type == GPAR_K_COS)
+                o += "                grad_rows_cos_static<" + off + ", " + nd + ", DZ>(g, accX);\n";
+            else
+                o += "                grad_rows_static<" + off + ", " + nd + ", " + (fa.type == GPAR_K_LINEAR ? "true" : "false") + ", DZ>(Za, Zb, ty, cb, g, accX);\n";
             o += "            }\n";
         }
         o += "            }\n";

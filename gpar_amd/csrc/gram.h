@@ -13,7 +13,7 @@
 
 namespace gpar {
 
-// shared with the generated kernels (gram_jit.h), one text for both: typedefs, GRAM_T / GRAM_LD, gram_accum*, gram_exph8, gram_rqh8, gram_maternh8
+// shared with the generated kernels (gram_jit.h), one text for both: typedefs, GRAM_T / GRAM_LD, gram_accum*, gram_exph8, gram_rqh8, gram_maternh8, gram_cosh8
 #define GPAR_DEVICE_CODE(...) __VA_ARGS__
 #include "gram_math.inc"
 #undef GPAR_DEVICE_CODE
@@ -42,6 +42,27 @@ __device__ __forceinline__ double gram_nonlin(int type, double s, double alpha) 
 }
 
 __device__ __forceinline__ bool gram_is_matern(int type) { return type >= GPAR_K_MATERN12 && type <= GPAR_K_MATERN52; }
+
+// Host-side checks of cosine factors, made by every entry that takes a kernel specification: a cosine over NO dims is refused (an
+// argument error rather than the constant 1: a spectral component without a period is a mistake of the caller's, and the empty
+// EQ factor's 1 is kept only for the reference's sake) ...
+static inline bool kspec_cos_ok(const gpar_kspec_t* ks) {
+    for (int f = 0; f < ks->nfactors; ++f)
+        if (ks->factor[f].type == GPAR_K_COS && ks->factor[f].nd < 1) return false;
+    return true;
+}
+// ... and so is one over an embedded (periodic) feature dim, where the feature map is at hand: sigma is a sum of differences of the
+// inputs themselves.
+static inline bool kspec_cos_embed_ok(const gpar_fspec_t* fs, const gpar_kspec_t* ks) {
+    for (int f = 0; f < ks->nfactors; ++f) {
+        const gpar_factor_t& fa = ks->factor[f];
+        if (fa.type != GPAR_K_COS) continue;
+        if (fa.off < 0 || fa.off + fa.nd > fs->dz || fa.off + fa.nd > GPAR_MAX_DIMS) return false;
+        for (int q = fa.off; q < fa.off + fa.nd; ++q)
+            if (fs->embed[q] != GPAR_EMBED_ID) return false;
+    }
+    return true;
+}
 
 // d k / d s of a Matern factor (s the squared scaled distance, r = sqrt(s)).  nu = 1/2 is singular at r = 0, where it only ever
 // multiplies (z_a - z_b)^2 or (z_a - z_b) = 0: it is taken as 0 there, by selecting the divisor - no 0 / 0, no infinity is formed.
@@ -111,6 +132,9 @@ __global__ __launch_bounds__(256) void gram_kernel(gpar_kspec_t ks, const double
                     gram_accum_dims<true>(Za, Zb, off, nd, ty, cb, s);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) lin[e] *= s[e];
+                } else if (type == GPAR_K_COS) {   // cos(2 pi sum of differences): multiplies into lin, no exponent
+                    gram_accum_diff_dims(Za, Zb, off, nd, ty, cb, s);
+                    gram_cosh8(s, lin);
                 } else {
                     gram_accum_dims<false>(Za, Zb, off, nd, ty, cb, s);
                     any_exp = true;
@@ -252,6 +276,9 @@ __global__ __launch_bounds__(256) void lockstep_build_kernel(LockstepSpecs sp, c
                     gram_accum_dims<true>(Za, Zb, off, nd, ty, cb, s);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) lin[e] *= s[e];
+                } else if (type == GPAR_K_COS) {   // cos(2 pi sum of differences): multiplies into lin, no exponent
+                    gram_accum_diff_dims(Za, Zb, off, nd, ty, cb, s);
+                    gram_cosh8(s, lin);
                 } else {
                     gram_accum_dims<false>(Za, Zb, off, nd, ty, cb, s);
                     any_exp = true;
@@ -311,6 +338,7 @@ __device__ __forceinline__ double gram_diag_value(const gpar_kspec_t& ks, const 
         double prod = ks.coef[term];
         while (f < ks.nfactors && ks.factor[f].term == term) {
             double s = 0.0;
+            if (ks.factor[f].type == GPAR_K_COS) { ++f; continue; }   // cos(0) = 1 exactly (gram_nonlin does not know the factor: no cospi here)
             if (ks.factor[f].type == GPAR_K_LINEAR) {
                 for (int d = ks.factor[f].off; d < ks.factor[f].off + ks.factor[f].nd; ++d) {
                     const double v = zr[d];
@@ -340,7 +368,7 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(gpar_kspec_t ks, const d
 // pass accumulates a fixed vector of moment sums from which the host forms every derivative:
 //   C_t  = sum W * prod_f phi_f                               (term coefficient)
 //   Al_f = sum W * rest_f * phi_f * ((s/2a)/(1+s/2a) - log1p(s/2a))        (RQ alpha)
-//   A_q  = sum W * g_f * m_q,   m_q = (z_aq - z_bq)^2 (EQ/RQ)  or  z_aq z_bq (linear)    (length scales)
+//   A_q  = sum W * g_f * m_q,   m_q = (z_aq - z_bq)^2 (EQ/RQ/Matern),  z_aq z_bq (linear)  or  (z_aq - z_bq) / 2 (cosine: g_f = rest_f * dphi_f/dsigma)    (length scales)
 //   P_q  = sum W * g_f * (z_aq - z_bq)(z'_aq - z'_bq),  z' = dz/dfreq                      (periods)
 // with rest_f = coef * prod_{f' != f} phi_f' and g_f = rest_f * dphi_f/ds.  Algorithmic HBM traffic: the lower
 // triangle of W once (4 n^2 bytes).  Deterministic: per-wave LDS slots, per-block partials, ordered reduce.
@@ -466,13 +494,24 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(gpar_kspec_t ks, const d
 #pragma unroll
                             for (int j = 0; j < 4; ++j) {
                                 if (fa.type == GPAR_K_LINEAR) s[i][j] = fma(za[i], zb[j], s[i][j]);
+                                else if (fa.type == GPAR_K_COS) s[i][j] += za[i] - zb[j];
                                 else { const double df = za[i] - zb[j]; s[i][j] = fma(df, df, s[i][j]); }
                             }
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { sv[ff][i][j] = s[i][j]; phi[ff][i][j] = gram_nonlin(fa.type, s[i][j], fa.alpha); }
+                        for (int j = 0; j < 4; ++j) {
+                            if (fa.type == GPAR_K_COS) {   // value and d phi / d sigma = -2 pi sin(2 pi sigma) (kept where the others keep s)
+                                double sn, cs;
+                                sincospi(2.0 * s[i][j], &sn, &cs);
+                                sv[ff][i][j] = -GRAM_2PI * sn;
+                                phi[ff][i][j] = cs;
+                            } else {
+                                sv[ff][i][j] = s[i][j];
+                                phi[ff][i][j] = gram_nonlin(fa.type, s[i][j], fa.alpha);
+                            }
+                        }
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -510,6 +549,7 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(gpar_kspec_t ks, const d
                             g[i][j] = w[i][j] * rest * (-0.5 * phi[ff][i][j] / base);
                             al = fma(w[i][j] * rest * phi[ff][i][j], tq / base - log1p(tq), al);
                         } else if (gram_is_matern(fa.type)) g[i][j] = w[i][j] * rest * gram_matern_dkds(fa.type, sv[ff][i][j]);
+                        else if (fa.type == GPAR_K_COS) g[i][j] = w[i][j] * rest * sv[ff][i][j];
                         else g[i][j] = w[i][j] * rest;
                     }
                 if (fa.type == GPAR_K_RQ) {
@@ -528,6 +568,11 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(gpar_kspec_t ks, const d
                         for (int i = 0; i < 4; ++i)
 #pragma unroll
                             for (int j = 0; j < 4; ++j) a = fma(g[i][j], za[i] * zb[j], a);
+                    } else if (fa.type == GPAR_K_COS) {   // half the first difference: the host's -2 A / scale is the cosine's rule too
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) a = fma(g[i][j], 0.5 * (za[i] - zb[j]), a);
                     } else {
                         double zda[4] = {0, 0, 0, 0}, zdb[4] = {0, 0, 0, 0};
                         if (has_zd) {
@@ -547,7 +592,7 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(gpar_kspec_t ks, const d
                     }
                     a = wave_sum(a);
                     if (lane == 0) myacc[GRAD_OFF_A + d] += a;
-                    if (has_zd && fa.type != GPAR_K_LINEAR) {
+                    if (has_zd && fa.type != GPAR_K_LINEAR && fa.type != GPAR_K_COS) {
                         pp = wave_sum(pp);
                         if (lane == 0) myacc[GRAD_OFF_P + d] += pp;
                     }
@@ -566,6 +611,7 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(gpar_kspec_t ks, const d
 //     out[a][q] = sum_b W(a, b) * d k(z1_a, z2_b) / d z1_a[q]
 //               = sum_b W(a, b) * rest_f(a, b) * dphi_f/ds(a, b) * 2 (z1_a[q] - z2_b[q])     (EQ / RQ factor f holding feature q)
 //               = sum_b W(a, b) * rest_f(a, b) * z2_b[q]                                      (linear factor)
+//               = sum_b W(a, b) * rest_f(a, b) * (-2 pi sin(2 pi sigma_f(a, b)))                (cosine factor: the same for each of its dims)
 // with rest_f = coef * prod_{f' != f} phi_f'.  What torch autograd computes in the reference when a layer's inputs are
 // themselves functions of hyper-parameters - posterior means fed forward by `replace` / `impute` / inducing points under
 // `fit(fix=False)` (gpar/regression.py:447-456, gpar/model.py:291-322) - and what moving inducing points needs.
@@ -638,13 +684,24 @@ __global__ __launch_bounds__(256) void gram_input_grad_kernel(gpar_kspec_t ks, c
 #pragma unroll
                             for (int j = 0; j < 4; ++j) {
                                 if (fa.type == GPAR_K_LINEAR) s[i][j] = fma(za[i], zb[j], s[i][j]);
+                                else if (fa.type == GPAR_K_COS) s[i][j] += za[i] - zb[j];
                                 else { const double df = za[i] - zb[j]; s[i][j] = fma(df, df, s[i][j]); }
                             }
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { sv[ff][i][j] = s[i][j]; phi[ff][i][j] = gram_nonlin(fa.type, s[i][j], fa.alpha); }
+                        for (int j = 0; j < 4; ++j) {
+                            if (fa.type == GPAR_K_COS) {   // value and d phi / d sigma = -2 pi sin(2 pi sigma) (kept where the others keep s)
+                                double sn, cs;
+                                sincospi(2.0 * s[i][j], &sn, &cs);
+                                sv[ff][i][j] = -GRAM_2PI * sn;
+                                phi[ff][i][j] = cs;
+                            } else {
+                                sv[ff][i][j] = s[i][j];
+                                phi[ff][i][j] = gram_nonlin(fa.type, s[i][j], fa.alpha);
+                            }
+                        }
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
@@ -668,6 +725,7 @@ __global__ __launch_bounds__(256) void gram_input_grad_kernel(gpar_kspec_t ks, c
                         if (fa.type == GPAR_K_EQ) g[i][j] = -w[i][j] * rest * phi[ff][i][j];
                         else if (fa.type == GPAR_K_RQ) g[i][j] = -w[i][j] * rest * phi[ff][i][j] / (1.0 + sv[ff][i][j] / (2.0 * fa.alpha));
                         else if (gram_is_matern(fa.type)) g[i][j] = 2.0 * w[i][j] * rest * gram_matern_dkds(fa.type, sv[ff][i][j]);
+                        else if (fa.type == GPAR_K_COS) g[i][j] = w[i][j] * rest * sv[ff][i][j];
                         else g[i][j] = w[i][j] * rest;
                     }
                 for (int d = fa.off; d < fa.off + fa.nd; ++d) {
@@ -680,7 +738,7 @@ __global__ __launch_bounds__(256) void gram_input_grad_kernel(gpar_kspec_t ks, c
                     for (int i = 0; i < 4; ++i) {
                         double p = 0.0;
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) p = fma(g[i][j], fa.type == GPAR_K_LINEAR ? zb[j] : za[i] - zb[j], p);
+                        for (int j = 0; j < 4; ++j) p = fma(g[i][j], fa.type == GPAR_K_LINEAR ? zb[j] : (fa.type == GPAR_K_COS ? 1.0 : za[i] - zb[j]), p);
                         // the 16 lanes tx = 0 .. 15 of one ty are consecutive lanes: reduce within the 16-lane row
 #pragma unroll
                         for (int off = 8; off > 0; off >>= 1) p += __shfl_xor(p, off, 16);

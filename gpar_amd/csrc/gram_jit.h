@@ -29,9 +29,15 @@ static_assert(sizeof(gpar_factor_t) == 24 && sizeof(gpar_kspec_t) == 8 + 8 * 8 +
 static bool gram_jit_is_matern(int type) { return type >= GPAR_K_MATERN12 && type <= GPAR_K_MATERN52; }
 static const char* gram_jit_matern_nu2(int type) { return type == GPAR_K_MATERN12 ? "1" : (type == GPAR_K_MATERN32 ? "3" : "5"); }
 
+static bool gram_jit_has_cos(const gpar_kspec_t& ks) {
+    for (int f = 0; f < ks.nfactors; ++f)
+        if (ks.factor[f].type == GPAR_K_COS) return true;
+    return false;
+}
+
 // Straight-line evaluation of all terms into total[8] for the micro-tile (ty, cb).  Mirrors the interpreter's order of
 // operations exactly: per term expo = DOUBLED sum of factor exponents (EQ: expo += s - the first one a plain copy, 0 + s being s -; RQ: gram_rqh8; Matern: gram_maternh8), lin = coef * product of
-// linear factors and Matern polynomials, one gram_exph8 per term that has a nonlinear factor, total = fma(lin, expo, total) or total += lin.
+// linear factors, Matern polynomials and cosine factors (gram_cosh8), one gram_exph8 per term that has a nonlinear factor, total = fma(lin, expo, total) or total += lin.
 static std::string gram_jit_terms(const gpar_kspec_t& ks) {
     std::string o;
     int f = 0;
@@ -40,7 +46,7 @@ static std::string gram_jit_terms(const gpar_kspec_t& ks) {
         o += "        {   // term " + ts + "\n";
         o += "            double expo[8], lin[8];\n";
         o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) { expo[e] = 0.0; lin[e] = ks.coef[" + ts + "]; }\n";
-        bool any_exp = false, first_exp = true;
+        bool any_exp = false, first_exp = true, any_cos = false;
         while (f < ks.nfactors && ks.factor[f].term == t) {
             const gpar_factor_t& fa = ks.factor[f];
             const std::string off = std::to_string(fa.off), nd = std::to_string(fa.nd), fs = std::to_string(f);
@@ -48,6 +54,10 @@ static std::string gram_jit_terms(const gpar_kspec_t& ks) {
             if (fa.type == GPAR_K_LINEAR) {
                 o += "                gram_accum_static<" + off + ", " + nd + ", true>(Za, Zb, ty, cb, s);\n";
                 o += "                _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) lin[e] *= s[e];\n";
+            } else if (fa.type == GPAR_K_COS) {   // cos(2 pi sum of differences) into lin; no exponent
+                o += "                gram_accum_diff_static<" + off + ", " + nd + ">(Za, Zb, ty, cb, s);\n";
+                o += "                gram_cosh8(s, lin);\n";
+                any_cos = true;
             } else {
                 any_exp = true;
                 o += "                gram_accum_static<" + off + ", " + nd + ", false>(Za, Zb, ty, cb, s);\n";
@@ -63,6 +73,10 @@ static std::string gram_jit_terms(const gpar_kspec_t& ks) {
             o += "            gram_exph8(expo, tab);\n";
             o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) total[e] = fma(lin[e], expo[e], total[e]);\n";
         } else {
+            // (a term of a cosine factor without an exponential: in this straight-line code the last product of lin and the addition
+            // would be fused into one multiply-add, which the interpreter's factor loop never forms - the empty statement pins the
+            // product; it emits nothing.  Terms without a cosine factor keep the source they always had.)
+            if (any_cos) o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) asm volatile(\"\" : \"+v\"(lin[e]));\n";
             o += "            _Pragma(\"unroll\") for (int e = 0; e < 8; ++e) total[e] += lin[e];\n";
         }
         o += "        }\n";
@@ -77,6 +91,8 @@ static std::string gram_jit_terms(const gpar_kspec_t& ks) {
 // compute unit's LDS for exactly its 128 bytes per clock - so it takes gram_jit_wide_source (round 5): a 4 x 4 micro-tile (three
 // reads per 32 instructions), dims in ROLLED loops of four.  Same arithmetic per entry, same bits.
 constexpr int GRAM_JIT_MAX_DZ = 16;
+// (the wide form below knows no cosine factor: a structure that holds one beside more than GRAM_JIT_MAX_DZ dims stays on the interpreter)
+static bool gram_jit_serves(const gpar_kspec_t& ks, int dz) { return dz <= GRAM_JIT_MAX_DZ || !gram_jit_has_cos(ks); }
 static int gram_jit_smax(int dz) { return dz <= 9 ? 8 : 4; }   // (1 + SMAX) panels of dz x 68 doubles: <= 44 KB
 
 // Column tiles per workgroup: a workgroup walks a strip of up to `strip` consecutive 64 x 64 tiles of one tile row (a kernel
@@ -466,7 +482,7 @@ static bool gram_jit_launch(const gpar_kspec_t* ks, const double* z1, int n1, in
     const int nt1 = gpar_ceil_div(n1, GRAM_T), nt2 = gpar_ceil_div(n2, GRAM_T);
     const long long tiles = ((flags & GPAR_GRAM_LOWER) ? (long long)nt1 * (nt1 + 1) / 2 : (long long)nt1 * nt2) * grid.z;
     const int strip = gram_jit_strip(tiles, dz);
-    if (strip <= 0) return false;   // more than 48 dims: the interpreter
+    if (strip <= 0 || !gram_jit_serves(*ks, dz)) return false;   // more than 48 dims, or a cosine factor beside more than 16: the interpreter
     hipFunction_t fn = jit_get(JIT_GRAM, *ks, dz, 1, "gram_jit", [&]() { return gram_jit_source(*ks, dz, strip); });
     if (!fn) return false;
     if (flags & GPAR_GRAM_LOWER) {

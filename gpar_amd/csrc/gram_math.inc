@@ -298,6 +298,82 @@ __device__ __forceinline__ void gram_matern_grad8(const double (&s)[8], double (
     }
 }
 
+// Cosine factor: phi = cos(2 pi sigma), sigma = sum_d (za_d - zb_d) over the factor's dims - the cosine of a SUM over the dims, the
+// spectral-mixture component (a length scale of the dim is its period).  sigma is summed from the explicit differences, in dim order:
+// per-row angles A = sum_d za_d with cos A cos A' + sin A sin A' would round the phase at the size of the rows' angles (time stamps of
+// 1e5 over periods near 1: four digits left), the differences of nearby rows are exact.  sigma(b, a) = -sigma(a, b) exactly, so a
+// Gram matrix of one point set is symmetric in bits; sigma = 0 gives exactly 1.  Plain additions only: nothing a compilation could fuse.
+template <int ND>
+__device__ __forceinline__ void gram_accum_diff(const double* __restrict__ Za, const double* __restrict__ Zb, int d0, int ty, int cb,
+                                                double (&s)[8]) {
+    g_d4 za[ND];
+    g_d2 zb[ND];
+    _Pragma("unroll")
+    for (int q = 0; q < ND; ++q) {
+        za[q] = *reinterpret_cast<const g_d4*>(&Za[(d0 + q) * GRAM_LD + 4 * ty]);
+        zb[q] = *reinterpret_cast<const g_d2*>(&Zb[(d0 + q) * GRAM_LD + cb]);
+    }
+    _Pragma("unroll")
+    for (int q = 0; q < ND; ++q) {
+        _Pragma("unroll")
+        for (int i = 0; i < 4; ++i) {
+            s[2 * i] += za[q][i] - zb[q][0];
+            s[2 * i + 1] += za[q][i] - zb[q][1];
+        }
+    }
+}
+
+// ... over a run-time range of dims (the interpreter) and over a compile-time range (generated kernels): the same order, the same sums.
+__device__ __forceinline__ void gram_accum_diff_dims(const double* __restrict__ Za, const double* __restrict__ Zb, int off, int nd, int ty,
+                                                     int cb, double (&s)[8]) {
+    int d = off;
+    for (; d + 4 <= off + nd; d += 4) gram_accum_diff<4>(Za, Zb, d, ty, cb, s);
+    switch (off + nd - d) {
+        case 3: gram_accum_diff<3>(Za, Zb, d, ty, cb, s); break;
+        case 2: gram_accum_diff<2>(Za, Zb, d, ty, cb, s); break;
+        case 1: gram_accum_diff<1>(Za, Zb, d, ty, cb, s); break;
+        default: break;
+    }
+}
+
+template <int OFF, int ND>
+__device__ __forceinline__ void gram_accum_diff_static(const double* __restrict__ Za, const double* __restrict__ Zb, int ty, int cb,
+                                                       double (&s)[8]) {
+    if constexpr (ND >= 4) {
+        gram_accum_diff<4>(Za, Zb, OFF, ty, cb, s);
+        _Pragma("unroll")
+        for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(s[e]) : : "memory");   // (as in gram_accum_static)
+        gram_accum_diff_static<OFF + 4, ND - 4>(Za, Zb, ty, cb, s);
+    } else if constexpr (ND > 0) {
+        gram_accum_diff<ND>(Za, Zb, OFF, ty, cb, s);
+    }
+}
+
+// The factor's value multiplies into the product of the term's linear factors: lin *= cospi(2 sigma) - the argument is reduced in units
+// of half periods, exactly (2 sigma is exact), where cos(2 pi sigma) would first round 2 pi sigma.  fp64 cospi is a software sequence
+// (fraction, two short polynomials, a select): two chains in flight at a time, as gram_rqh8 keeps it.
+__device__ __forceinline__ void gram_cosh8(const double (&s)[8], double (&lin)[8]) {
+    _Pragma("unroll")
+    for (int i = 0; i < 8; ++i) {
+        lin[i] *= cospi(2.0 * s[i]);
+        if (i & 1) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ... and for the gradient passes: value phi = cos(2 pi sigma) and derivative dk = d phi / d sigma = -2 pi sin(2 pi sigma) of eight
+// entries from one range reduction each.  sigma = 0 (every pair of the DIAG mode) gives phi = 1 and dk = 0 exactly.
+constexpr double GRAM_2PI = 0x1.921fb54442d18p+2;
+__device__ __forceinline__ void gram_cos_grad8(const double (&s)[8], double (&phi)[8], double (&dk)[8]) {
+    _Pragma("unroll")
+    for (int i = 0; i < 8; ++i) {
+        double sn, cs;
+        sincospi(2.0 * s[i], &sn, &cs);
+        phi[i] = cs;
+        dk[i] = -GRAM_2PI * sn;
+        if (i & 1) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // ---- gradient passes (generated kernels only; grad_jit.h) ---------------------------------------------------------------------
 // Per-dim moment sums of one factor over a 4 x 2 micro-tile, dims [OFF, OFF + ND) at compile time:
 //   EQ / RQ:  accA[d] += g (za - zb)^2,   accP[d] += g (za - zb)(zda - zdb)   (HAS_ZD: frequency derivatives of periodic features)
@@ -361,6 +437,35 @@ __device__ __forceinline__ void grad_rows_static(const double* __restrict__ Za, 
             accX[i][OFF] = a;
         }
         grad_rows_static<OFF + 1, ND - 1, LINEAR, NA>(Za, Zb, ty, cb, g, accX);
+    }
+}
+
+// The two sums of a COSINE factor, g = w * rest * d phi / d sigma:   accA[d] += g (za - zb) / 2   - half the first difference, so that the
+// host's rule for the squared-distance factors, d / d scale = -2 A / scale, is the cosine's too (d sigma / d scale_d = -(za - zb) / scale_d) -
+// and   accX[i][d] += sum_j g   (d sigma / d za_d = 1 for every dim of the factor).
+template <int OFF, int ND, int NA>
+__device__ __forceinline__ void grad_dims_cos_static(const double* __restrict__ Za, const double* __restrict__ Zb, int ty, int cb,
+                                                     const double (&g)[8], double (&accA)[NA]) {
+    if constexpr (ND > 0) {
+        const g_d4 za = *reinterpret_cast<const g_d4*>(&Za[OFF * GRAM_LD + 4 * ty]);
+        const g_d2 zb = *reinterpret_cast<const g_d2*>(&Zb[OFF * GRAM_LD + cb]);
+        double a = accA[OFF];
+        _Pragma("unroll")
+        for (int i = 0; i < 4; ++i) {
+            a = fma(g[2 * i], 0.5 * (za[i] - zb[0]), a);
+            a = fma(g[2 * i + 1], 0.5 * (za[i] - zb[1]), a);
+        }
+        accA[OFF] = a;
+        grad_dims_cos_static<OFF + 1, ND - 1, NA>(Za, Zb, ty, cb, g, accA);
+    }
+}
+
+template <int OFF, int ND, int NA>
+__device__ __forceinline__ void grad_rows_cos_static(const double (&g)[8], double (&accX)[4][NA]) {
+    if constexpr (ND > 0) {
+        _Pragma("unroll")
+        for (int i = 0; i < 4; ++i) accX[i][OFF] += g[2 * i] + g[2 * i + 1];
+        grad_rows_cos_static<OFF + 1, ND - 1, NA>(g, accX);
     }
 }
 

@@ -55,6 +55,11 @@ __device__ __forceinline__ double pc_kernel_entry(const gpar_kspec_t& ks, const 
             double s = 0.0;
             if (ks.factor[f].type == GPAR_K_LINEAR) {
                 for (int d = off; d < end; ++d) s = fma(zi[d], zp[d], s);
+            } else if (ks.factor[f].type == GPAR_K_COS) {   // cos(2 pi sum of the differences, in dim order)
+                for (int d = off; d < end; ++d) s += zi[d] - zp[d];
+                prod *= cospi(2.0 * s);
+                ++f;
+                continue;
             } else {
                 for (int d = off; d < end; ++d) {
                     const double diff = zi[d] - zp[d];
@@ -222,6 +227,7 @@ static int pivoted_chol_run(const gpar_kspec_t* ks, const double* z, int n, int 
     if (dz < 0 || dz > GPAR_MAX_DIMS) return GPAR_ARG_ERROR(4);
     for (int f = 0; f < ks->nfactors; ++f)   // the kernels index the pivot's LDS copy by these
         if (ks->factor[f].off < 0 || ks->factor[f].nd < 0 || ks->factor[f].off + ks->factor[f].nd > dz) return GPAR_ARG_ERROR(3);
+    if (!kspec_cos_ok(ks)) return GPAR_ARG_ERROR(3);
     if (n < 1 || n > INT_MAX - PC_T || max_rank < 1 || max_rank > PC_MAX_RANK || ldz < dz || ldl < n) return GPAR_ARG_ERROR(1);
     if (!(floor_ >= 0.0) || !(tol_trace >= 0.0)) return GPAR_ARG_ERROR(2);   // (a picked row holds d = 0: never above a floor >= 0)
     if (!Lt || !piv || !trace || !rank || !info || !ws || (dz > 0 && !z)) return GPAR_ARG_ERROR(5);

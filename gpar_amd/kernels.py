@@ -2,7 +2,8 @@
 
 Host-side counterpart of the mlkernels subset the reference composes per layer
 (/root/reference/gpar/regression.py:92-180): `EQ`, `RQ`, `Linear`, `ZeroKernel`, `.stretch`, `.periodic`,
-`.select`, `+`, `*` and scalar offsets - plus the Matern kernels of smoothness 1/2, 3/2 and 5/2, which the reference lacks.  Instead of an expression tree evaluated term by term (one n x n
+`.select`, `+`, `*` and scalar offsets - plus the Matern kernels of smoothness 1/2, 3/2 and 5/2 and the `Cosine` kernel (the oscillating
+factor of a spectral mixture), which the reference lacks.  Instead of an expression tree evaluated term by term (one n x n
 temporary per node), a kernel here is kept in the normal form
 
     k(x, y) = sum_t coef_t * prod_{f in t} phi_f(z_f(x), z_f(y)),   z_f = stretch(periodic(select(x)))
@@ -18,7 +19,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["Kernel", "EQ", "RQ", "Matern12", "Matern32", "Matern52", "Linear", "ZeroKernel", "OneKernel", "compile_kernel", "CompiledKernel", "linear_tail"]
+__all__ = ["Kernel", "EQ", "RQ", "Matern12", "Matern32", "Matern52", "Cosine", "Linear", "ZeroKernel", "OneKernel", "compile_kernel", "CompiledKernel", "linear_tail"]
 
 
 def _value(v):
@@ -145,6 +146,9 @@ class Kernel:
         def fn(f):
             if f.periods is not None:
                 raise NotImplementedError("periodic applied twice")
+            if f.type == "cos":
+                raise NotImplementedError("periodic() does not apply to a Cosine factor: it is the cosine of a SUM of differences over its "
+                                          "columns, and the feature map embeds every column on its own - Cosine().stretch(periods) is periodic already")
             return f.copy(periods=periods)
 
         return self._map_factors(fn)
@@ -214,6 +218,12 @@ def Matern52():
     return Kernel([Term(1.0, [Factor("matern52")])])
 
 
+def Cosine():
+    """cos(2 pi sum_d (x_d - y_d)): the cosine of a SUM over the selected columns.  Under `.stretch(T)` the scale of column d is its
+    period T_d; `EQ().stretch(l) * Cosine().stretch(T)` is one component of the spectral mixture of Wilson & Adams (2013)."""
+    return Kernel([Term(1.0, [Factor("cos")])])
+
+
 def Linear():
     return Kernel([Term(1.0, [Factor("linear")])])
 
@@ -227,7 +237,7 @@ def OneKernel():
 
 
 _TYPE_CODE = {"eq": _lib.K_EQ, "rq": _lib.K_RQ, "linear": _lib.K_LINEAR, "matern12": _lib.K_MATERN12, "matern32": _lib.K_MATERN32,
-              "matern52": _lib.K_MATERN52}
+              "matern52": _lib.K_MATERN52, "cos": _lib.K_COS}
 
 
 class CompiledKernel:

@@ -13,10 +13,10 @@ import os
 import numpy as np
 import torch
 
-from ._lib import CHOL_UPDATE_MAX_RANK
+from ._lib import CHOL_UPDATE_MAX_RANK, GPAR_MAX_DIMS, GPAR_MAX_FACTORS, GPAR_MAX_TERMS
 from .engine import get_engine
 from .gp import GP, Measure, check_score, greedy_inducing
-from .kernels import EQ, RQ, Linear, Matern12, Matern32, Matern52, ZeroKernel
+from .kernels import EQ, RQ, Cosine, Linear, Matern12, Matern32, Matern52, ZeroKernel
 from .model import GPAR, check_gap, check_window, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
 from .vars import Vars
@@ -86,13 +86,51 @@ def _uprank(x):
 _MATERN = {0.5: Matern12, 1.5: Matern32, 2.5: Matern52}
 
 
+def _spectral_periods(spectral, spectral_period):
+    """Initial period of each of the `spectral` components: a scalar T gives the harmonics T / (q + 1) - distinct starting points, so that
+    the components do not stay copies of one another -, a vector of Q gives component q its entry."""
+    if np.size(spectral_period) == 1:
+        return [float(np.reshape(spectral_period, -1)[0]) / (q + 1) for q in range(spectral)]
+    periods = np.asarray(spectral_period, dtype=np.float64).reshape(-1)
+    if periods.size != spectral:
+        raise ValueError(f"spectral_period holds {periods.size} periods for spectral={spectral} components")
+    return [float(v) for v in periods]
+
+
+def _layer_kernel_size(config, m, p):
+    """(terms, factors, feature dims) of the widest layer kernel the configuration produces for m inputs and p outputs - the last layer,
+    which sees the most previous outputs."""
+    markov, q = config["markov"], config.get("spectral") or 0
+    p_num = max(p - 1, 0) if markov is None else min(max(p - 1, 0), markov)
+    per, inlin = bool(config["per"]), bool(config["input_linear"])
+    lin, nonlin = bool(config["linear"]) and p_num > 0, bool(config["nonlinear"]) and p_num > 0
+    terms = 1 + per + 2 * inlin + lin + nonlin + q
+    factors = 1 + 2 * per + inlin + lin + nonlin + 2 * q
+    dims = m + 3 * m * per + m * inlin + p_num * lin + p_num * nonlin + 2 * q * m
+    return terms, factors, dims
+
+
+def _check_layer_kernel_size(config, m, p):
+    """ValueError if the widest layer kernel does not fit the device's kernel specification (include/gpar_hip.h)."""
+    terms, factors, dims = _layer_kernel_size(config, m, p)
+    what = f"spectral={config.get('spectral')}" + (f" with {m} inputs and {p} outputs" if m is not None and p > 2 else "")
+    if terms > GPAR_MAX_TERMS:
+        raise ValueError(f"{what}: the layer kernel would have {terms} terms; the device specification holds GPAR_MAX_TERMS = {GPAR_MAX_TERMS}")
+    if factors > GPAR_MAX_FACTORS:
+        raise ValueError(f"{what}: the layer kernel would have {factors} factors; the device specification holds GPAR_MAX_FACTORS = {GPAR_MAX_FACTORS}")
+    if dims > GPAR_MAX_DIMS:
+        raise ValueError(f"{what}: the layer kernel would have {dims} feature dims; the device specification holds GPAR_MAX_DIMS = {GPAR_MAX_DIMS}")
+
+
 def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, per_decay, input_linear,
-                     input_linear_scale, linear, linear_scale, nonlinear, nonlinear_scale, rq, markov, noise, matern=None):
+                     input_linear_scale, linear, linear_scale, nonlinear, nonlinear_scale, rq, markov, noise, matern=None,
+                     spectral=None, spectral_period=1.0, spectral_scale=10.0):
     """Constructor of layer `pi`: kernel over the inputs + kernel over the selected previous outputs, and the
     observation-noise variance; hyper-parameters are created in `vs` on first use (reference regression.py:72-182)."""
 
     config = repr((m, pi, scale, scale_tie, per, per_period, per_scale, per_decay, input_linear, input_linear_scale, linear,
-                   linear_scale, nonlinear, nonlinear_scale, rq, markov, noise) + (() if matern is None else (matern,)))
+                   linear_scale, nonlinear, nonlinear_scale, rq, markov, noise) + (() if matern is None else (matern,))
+                  + (() if spectral is None else (("spectral", spectral, spectral_period, spectral_scale),)))
 
     def model():
         return vs.memo(config, build)
@@ -118,6 +156,15 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
             periods = vs.bnd(name=f"{pi}/input/per/pers", init=_vector_from_init(per_period, m))
             decays = vs.bnd(name=f"{pi}/input/per/decay", init=_vector_from_init(per_decay, m))
             k_in = k_in + var * EQ().stretch(scales).periodic(periods) * EQ().stretch(decays)
+
+        # spectral mixture over the inputs (Wilson & Adams 2013): Q Gaussian-windowed cosines of a SUM over the inputs, periods learned.
+        # The envelope stays EQ under `matern` / `rq` (as the locally periodic term's factors do); `scale_tie` does not tie these.
+        if spectral is not None:
+            for q, period in enumerate(_spectral_periods(spectral, spectral_period)):
+                var = vs.bnd(name=f"{pi}/input/sm{q}/var", init=1.0 / spectral)
+                scales = vs.bnd(name=f"{pi}/input/sm{q}/scales", init=_vector_from_init(spectral_scale, m))
+                periods = vs.bnd(name=f"{pi}/input/sm{q}/pers", init=_vector_from_init(period, m))
+                k_in = k_in + var * EQ().stretch(scales) * Cosine().stretch(periods)
 
         # linear kernel (plus constant) over the inputs
         if input_linear:
@@ -160,6 +207,8 @@ def _construct_gpar(reg, vs, m, p):
         # inducing inputs as a variable of the store (an addition: the reference keeps them fixed, todo.tasks:5)
         x_ind = vs.get(init=np.asarray(x_ind, dtype=np.float64), name="x_ind")
     gpar = GPAR(replace=reg.replace, impute=reg.impute, x_ind=x_ind, sparse_method=reg.sparse_method)
+    if reg.model_config.get("spectral") is not None:   # (the feature dims grow with m and p, which the constructor did not know)
+        _check_layer_kernel_size(reg.model_config, m, p)
     for pi in range(p):
         gpar = gpar.add_layer(_model_generator(vs, m, pi, **reg.model_config))
     return gpar
@@ -336,7 +385,8 @@ class GPARRegressor:
     def __init__(self, replace=False, impute=True, scale=1.0, scale_tie=False, per=False, per_period=1.0,
                  per_scale=1.0, per_decay=10.0, input_linear=False, input_linear_scale=100.0, linear=True,
                  linear_scale=100.0, nonlinear=False, nonlinear_scale=1.0, rq=False, markov=None, noise=0.1,
-                 x_ind=None, normalise_y=True, transform_y=(lambda x: x, lambda x: x), sparse_method="vfe", matern=None):
+                 x_ind=None, normalise_y=True, transform_y=(lambda x: x, lambda x: x), sparse_method="vfe", matern=None, spectral=None,
+                 spectral_period=1.0, spectral_scale=10.0):
         self.replace = replace
         if sparse_method not in ("vfe", "fitc", "dtc"):
             raise ValueError('sparse_method must be "vfe", "fitc" or "dtc"')
@@ -359,6 +409,20 @@ class GPARRegressor:
                 raise ValueError("matern and rq=True exclude one another")
             self.model_config["matern"] = float(matern)
         self.matern = None if matern is None else float(matern)
+        # an addition as well: `spectral` = Q >= 1 adds, to every layer's kernel over the inputs, the spectral mixture
+        # sum_q var_q EQ().stretch(l_q) * Cosine().stretch(T_q) - oscillating components whose periods are learned (`spectral_period`: a scalar
+        # T starts them at the harmonics T / (q + 1), a vector of Q gives each its own; `spectral_scale`: the envelopes' length scales)
+        if spectral is not None:
+            if isinstance(spectral, (bool, np.bool_)) or not isinstance(spectral, (int, np.integer)) or spectral < 1:
+                raise ValueError("spectral must be None or an integer >= 1 (the number of spectral-mixture components)")
+            spectral = int(spectral)
+            spectral_period = float(spectral_period) if np.ndim(spectral_period) == 0 else tuple(float(v) for v in np.reshape(spectral_period, -1))
+            spectral_scale = float(spectral_scale) if np.ndim(spectral_scale) == 0 else tuple(float(v) for v in np.reshape(spectral_scale, -1))
+            _spectral_periods(spectral, spectral_period)
+            self.model_config.update(spectral=spectral, spectral_period=spectral_period, spectral_scale=spectral_scale)
+            # terms and factors of the widest layer (one with previous outputs) are known now; its feature dims once m and p are
+            _check_layer_kernel_size(self.model_config, 1, 2)
+        self.spectral = spectral
         self.vs = Vars(dtype=torch.float64)
         self.is_conditioned = False
         self.x = self.y = self.w = None

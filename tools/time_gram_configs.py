@@ -2,10 +2,11 @@
 layer's symmetric lower-triangle build for C2 / C3 / C5 and the n x M cross-Gram of C4, alone on the GPU.
 Prints one JSON line per kernel: algorithmic bytes (8 per stored entry) / time against the 8 TB/s HBM peak.
 
-    python tools/time_gram_configs.py [--matern NU] [C2 C3 C4 C5]
+    python tools/time_gram_configs.py [--matern NU] [--spectral Q] [C2 C3 C4 C5]
 
 `--matern 0.5|1.5|2.5`: the same layer structures with the Matern kernel of that smoothness where the configuration has EQ
-(GPARRegressor(matern=...); configurations with rq=True cannot take it)."""
+(GPARRegressor(matern=...); configurations with rq=True cannot take it).
+`--spectral Q`: the same layer structures with Q spectral-mixture components over the inputs (GPARRegressor(spectral=Q))."""
 import json
 import os
 import sys
@@ -54,11 +55,21 @@ if "--matern" in argv:
     matern = float(argv[at + 1])
     del argv[at:at + 2]
 
+spectral = None
+if "--spectral" in argv:
+    at = argv.index("--spectral")
+    spectral = int(argv[at + 1])
+    del argv[at:at + 2]
+
 out = []
 for name in argv or ["C2", "C3", "C4", "C5"]:
     cfg, reg, x, y = build(name, eng)
-    if matern is not None:
-        kw = dict(cfg["kw"], normalise_y=False, matern=matern)
+    if matern is not None or spectral is not None:
+        kw = dict(cfg["kw"], normalise_y=False)
+        if matern is not None:
+            kw["matern"] = matern
+        if spectral is not None:
+            kw["spectral"] = spectral
         if reg.x_ind is not None:
             kw["x_ind"] = reg.x_ind
         reg = GPARRegressor(**kw)
@@ -82,7 +93,7 @@ for name in argv or ["C2", "C3", "C4", "C5"]:
         ms = timeit(lambda: hip.gram(ck, z, None, out=K, lower=True, diag_add=d, diag_const=1e-12))
         nbytes, kind = 8.0 * n * (n + 1) / 2, f"symmetric lower, n = {n}"
     terms = [[fa.type for fa in t.factors] for t in ck.kernel.terms]
-    rec = {"config": name, "matern": matern, "kernel": kind, "layer": p - 1, "feature_dims": int(ck.dz), "terms": terms, "ms": ms["sustained"], "ms_burst": ms["burst"],
+    rec = {"config": name, "matern": matern, "spectral": spectral, "kernel": kind, "layer": p - 1, "feature_dims": int(ck.dz), "terms": terms, "ms": ms["sustained"], "ms_burst": ms["burst"],
            "ms_best": ms["best"], "algorithmic_bytes": nbytes}
     for key in ("sustained", "burst"):
         rec["tb_per_s_" + key] = nbytes / ms[key] * 1e-9
