@@ -72,6 +72,22 @@ def layer_spec(hypers, m, pi, config):
                 ],
             }
         )
+    # `spectral` = Q (the product's addition as well): Q components var * EQ(scales) * cos(pers) over the input columns, after the
+    # locally periodic term.  The envelope stays EQ under `matern` / `rq`; `scale_tie` does not tie these.
+    spectral = config.get("spectral")
+    if spectral is not None:
+        if isinstance(spectral, bool) or not isinstance(spectral, (int, np.integer)) or spectral < 1:
+            raise ValueError("spectral must be None or an integer >= 1")
+        for q in range(int(spectral)):
+            terms.append(
+                {
+                    "coef": float(g(f"{pi}/input/sm{q}/var")),
+                    "factors": [
+                        {"type": "eq", "cols": m_inds, "scales": list(np.atleast_1d(g(f"{pi}/input/sm{q}/scales"))), "periods": None, "alpha": 0.0},
+                        {"type": "cos", "cols": m_inds, "scales": list(np.atleast_1d(g(f"{pi}/input/sm{q}/pers"))), "periods": None, "alpha": 0.0},
+                    ],
+                }
+            )
     if config.get("input_linear", False):
         terms.append({"coef": 1.0, "factors": [{"type": "linear", "cols": m_inds, "scales": list(np.atleast_1d(g(f"{pi}/input/lin/scales"))), "periods": None, "alpha": 0.0}]})
         terms.append({"coef": float(g(f"{pi}/input/lin/const")), "factors": []})

@@ -22,10 +22,20 @@ r = sqrt(|x - y|^2):
 (nu = 1/2 has a kink at r = 0: its derivative with respect to r2 is singular there, and every gradient - here as in the
 product - leaves coincident pairs out of the sums.)
 
+and the cosine factor of include/gpar_hip.h (the oscillating factor of a spectral mixture, Wilson & Adams 2013; the reference lacks
+it as well), in sigma = ((0 + (z_0 - z'_0)) + (z_1 - z'_1)) + ..., the SUM of the scaled differences in dim order:
+
+    cos           k = cos(2 pi sigma)                                dk/dsigma = -2 pi sin(2 pi sigma)
+                  d sigma / d s_q = -(z_q - z'_q) / s_q,  d sigma / d x[a, c] = 1 / s_q  (q the feature of column c);  k(x, x) = 1
+
+(2 sigma is reduced to [-1/2, 1/2] half periods exactly - fmod and the fold round nothing, tests/cosine_math_emulation.py - BEFORE
+pi enters, and the remainder is evaluated in long double where that is wider than float64.  cos(2 * pi * sigma) in float64 would
+round the phase by 2 pi |sigma| 2^-52 first.  No periods - `.stretch(T)` makes a scale the period - and at least one feature.)
+
 A kernel is handed around as a plain dict (no product classes are imported here):
 
     {"terms": [{"coef": float,
-                "factors": [{"type": "eq" | "rq" | "linear",
+                "factors": [{"type": "eq" | "rq" | "linear" | "matern12" | "matern32" | "matern52" | "cos",
                              "cols": [int, ...],        # columns of the design matrix
                              "scales": [float, ...],    # one per feature (2 * len(cols) if periodic)
                              "periods": None | [float, ...],   # one per column
@@ -69,6 +79,42 @@ def _stationary(factor, r2):
     raise ValueError(f"unknown factor type {kind!r}")
 
 
+_LD = np.longdouble
+_LD_PI = _LD("3.14159265358979323846264338327950288")
+
+
+def _cos_check(factor):
+    if factor.get("periods") is not None:
+        raise ValueError("a cosine factor takes no periods: it is the cosine of a sum of differences of the columns themselves")
+    if len(factor["cols"]) == 0 or len(factor["scales"]) == 0:
+        raise ValueError("a cosine factor needs at least one feature")
+
+
+def _cos_sigma(z1, z2):
+    """sigma[a, b] = ((0 + (z1[a, 0] - z2[b, 0])) + (z1[a, 1] - z2[b, 1])) + ... in float64, in dim order."""
+    sigma = np.zeros((z1.shape[0], z2.shape[0]))
+    for d in range(z1.shape[1]):
+        sigma = sigma + (z1[:, d][:, None] - z2[:, d][None, :])
+    return sigma
+
+
+def _cos_pair(sigma):
+    """(cos(2 pi sigma), -2 pi sin(2 pi sigma)) of float64 sigma: t = 2 sigma, t mod 2 and the fold onto [-1/2, 1/2] are exact in
+    binary floating point (done in float64: nothing to gain from more digits); pi multiplies the remainder, of size at most 1/2, in long
+    double, and the result is rounded to float64 once."""
+    t = 2.0 * np.asarray(sigma, dtype=np.float64)
+    r = np.fmod(t, 2.0)                           # (-2, 2)
+    r = np.where(r > 1.0, r - 2.0, r)
+    r = np.where(r < -1.0, r + 2.0, r)            # [-1, 1]
+    sign = np.where(np.abs(r) > 0.5, -1.0, 1.0)
+    r = np.where(r > 0.5, r - 1.0, r)
+    r = np.where(r < -0.5, r + 1.0, r)            # [-1/2, 1/2]: cos(pi (r +- 1)) = -cos(pi r), sin likewise
+    angle = _LD_PI * r.astype(_LD)
+    value = sign * np.cos(angle)
+    slope = -(2 * _LD_PI) * (sign * np.sin(angle))
+    return value.astype(np.float64), slope.astype(np.float64)
+
+
 def features(factor, x):
     """Feature rows of one factor: select -> (periodic embedding) -> stretch."""
     x = np.asarray(x, dtype=np.float64)
@@ -85,9 +131,13 @@ def features(factor, x):
 
 
 def factor_matrix(factor, x1, x2):
-    if factor["type"] != "linear" and factor["type"] not in STATIONARY:
+    if factor["type"] not in ("linear", "cos") and factor["type"] not in STATIONARY:
         raise ValueError(f"unknown factor type {factor['type']!r}")
+    if factor["type"] == "cos":
+        _cos_check(factor)
     z1, z2 = features(factor, x1), features(factor, x2)
+    if factor["type"] == "cos":
+        return _cos_pair(_cos_sigma(z1, z2))[0]
     if factor["type"] == "linear":
         out = np.zeros((z1.shape[0], z2.shape[0]))
         for d in range(z1.shape[1]):
@@ -121,7 +171,8 @@ def gram(spec, x1, x2=None, noise_diag=None, jitter=0.0):
 
 
 def gram_diag(spec, x):
-    """k(x_a, x_a): every stationary factor (EQ, RQ, the Matern kernels) is 1 on the diagonal, a linear factor |z_a|^2."""
+    """k(x_a, x_a): every stationary factor (EQ, RQ, the Matern kernels) and the cosine factor (sigma = 0 exactly) is 1 on the
+    diagonal, a linear factor |z_a|^2."""
     x = np.asarray(x, dtype=np.float64)
     out = np.zeros(x.shape[0])
     for term in spec["terms"]:
@@ -130,6 +181,8 @@ def gram_diag(spec, x):
             if factor["type"] == "linear":
                 z = features(factor, x)
                 prod = prod * np.sum(z * z, axis=1)
+            elif factor["type"] == "cos":
+                _cos_check(factor)
             elif factor["type"] not in STATIONARY:
                 raise ValueError(f"unknown factor type {factor['type']!r}")
         out += prod
@@ -162,8 +215,8 @@ def spec_to_dict(kernel):
 
 def kernel_grads(spec, x, W):
     """d/d(theta) of  1/2 sum_ab W_ab K_ab(theta)  for every parameter of the kernel `spec` (W symmetric, n x n):
-    term coefficients, per-feature length scales, per-column periods and RQ alphas (the Matern kernels have none beyond their
-    scales; nu = 1/2 contributes nothing at r = 0, see the module docstring).  Each derivative matrix
+    term coefficients, per-feature length scales, per-column periods and RQ alphas (the Matern kernels and the cosine factor have
+    none beyond their scales; nu = 1/2 contributes nothing at r = 0, see the module docstring).  Each derivative matrix
     dK/dtheta is formed explicitly (test sizes only) — deliberately a different route from the HIP kernel, which
     accumulates per-feature moment sums in one pass.  Verified against central finite differences in
     tests/test_oracle.py."""
@@ -190,6 +243,13 @@ def kernel_grads(spec, x, W):
                 for q in range(nd):
                     dF = -2.0 * (z[:, q][:, None] * z[:, q][None, :]) / scales[q]
                     g["scales"][q] = 0.5 * np.sum(W * rest * dF)
+            elif f["type"] == "cos":
+                _cos_check(f)
+                slope = _cos_pair(_cos_sigma(z, z))[1]           # d phi / d sigma
+                for q in range(nd):
+                    # d sigma / d s_q = -(z_q - z'_q) / s_q
+                    dsigma = -(z[:, q][:, None] - z[:, q][None, :]) / scales[q]
+                    g["scales"][q] = 0.5 * np.sum(W * rest * slope * dsigma)
             else:
                 r2 = np.zeros_like(full)
                 diffs = []
@@ -243,7 +303,10 @@ def kernel_input_grads(spec, x1, x2, W):
             scales = np.asarray(f["scales"], dtype=np.float64)
             periods = f.get("periods")
             ncol = len(cols)
-            if f["type"] != "linear":
+            if f["type"] == "cos":
+                _cos_check(f)
+                slope = _cos_pair(_cos_sigma(z1, z2))[1]         # d phi / d sigma; d sigma / d z1[:, q] = 1 for every feature
+            elif f["type"] != "linear":
                 r2 = np.zeros_like(rest)
                 for q in range(z1.shape[1]):
                     r2 += (z1[:, q][:, None] - z2[:, q][None, :]) ** 2
@@ -259,6 +322,8 @@ def kernel_input_grads(spec, x1, x2, W):
                     dz = (omega * np.cos(omega * x1[:, c]) if q < ncol else -omega * np.sin(omega * x1[:, c])) / scales[q]
                 if f["type"] == "linear":
                     dF = z2[:, q][None, :] * np.ones((n1, 1))            # d <z1, z2> / d z1[q]
+                elif f["type"] == "cos":
+                    dF = slope
                 else:
                     dF = dF_dr2 * 2.0 * (z1[:, q][:, None] - z2[:, q][None, :])
                 out[:, c] += np.sum(W * rest * dF, axis=1) * dz

@@ -28,6 +28,10 @@ def _features(factor, x):
 def _factor_entry(factor, za, zb):
     if factor["type"] == "linear":
         return mp.fsum(a * b for a, b in zip(za, zb))
+    if factor["type"] == "cos":   # the cosine factor of include/gpar_hip.h: the cosine of the SUM of the scaled differences
+        if factor.get("periods") is not None or len(za) == 0:
+            raise ValueError("a cosine factor takes no periods and needs at least one feature")
+        return mp.cos(2 * mp.pi * mp.fsum(a - b for a, b in zip(za, zb)))
     r2 = mp.fsum((a - b) ** 2 for a, b in zip(za, zb))
     if factor["type"] == "eq":
         return mp.exp(-r2 / 2)

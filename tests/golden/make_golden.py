@@ -35,6 +35,10 @@ def hypers_for(m, p, config, rng):
             h[f"{pi}/input/per/scales"] = rng.uniform(0.5, 2.0, 2 * m).tolist()
             h[f"{pi}/input/per/pers"] = rng.uniform(0.7, 1.5, m).tolist()
             h[f"{pi}/input/per/decay"] = rng.uniform(3.0, 10.0, m).tolist()
+        for q in range(config.get("spectral") or 0):   # (after every earlier draw of the layer's input kernel but the linear one:
+            h[f"{pi}/input/sm{q}/var"] = rng.uniform(0.3, 1.0)         # no earlier case has the key, so their streams are untouched)
+            h[f"{pi}/input/sm{q}/scales"] = rng.uniform(0.8, 3.0, m).tolist()
+            h[f"{pi}/input/sm{q}/pers"] = rng.uniform(0.4, 1.6, m).tolist()
         if config.get("input_linear"):
             h[f"{pi}/input/lin/scales"] = rng.uniform(1.0, 5.0, m).tolist()
             h[f"{pi}/input/lin/const"] = rng.uniform(0.1, 1.0)
@@ -115,6 +119,14 @@ MATERN_CASES = [
     ("matern12-missing-impute", dict(n=20, m=1, p=3, config=dict(linear=True, nonlinear=True, matern=0.5), impute=True, replace=False, missing=0.25, weights=True)),
     ("matern52-replace", dict(n=15, m=1, p=3, config=dict(linear=True, nonlinear=True, matern=2.5), impute=True, replace=True, missing=0.15, weights=False)),
     ("matern32-inducing", dict(n=24, m=1, p=3, config=dict(linear=True, nonlinear=True, matern=1.5), impute=True, replace=False, missing=0.2, weights=False, x_ind=8)),
+]
+
+
+# The spectral mixture (`spectral` = Q, the cosine factor: an addition as well, pinned by the periodic-embedding identity, finite
+# differences and 50-digit arithmetic, tests/test_oracle.py, tests/test_oracle_precision.py).  A stream of their own again, appended.
+SPECTRAL_CASES = [
+    ("spectral2-missing-weights", dict(n=20, m=2, p=3, config=dict(linear=True, nonlinear=True, spectral=2), impute=True, replace=False, missing=0.25, weights=True)),
+    ("spectral2-inducing", dict(n=24, m=1, p=3, config=dict(linear=True, nonlinear=True, spectral=2), impute=True, replace=False, missing=0.2, weights=False, x_ind=8)),
 ]
 
 
@@ -272,6 +284,9 @@ def main():
         out["gpar_logpdf"].append(micro_case(name, c, micro_rng))
     for name, c in MATERN_CASES:
         out["gpar_logpdf"].append(dense_case(name, c, matern_rng))
+    spectral_rng = np.random.default_rng(20261020)   # (a stream of its own, see SPECTRAL_CASES)
+    for name, c in SPECTRAL_CASES:
+        out["gpar_logpdf"].append(dense_case(name, c, spectral_rng))
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gpar_cases.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)

@@ -60,8 +60,9 @@ def main():
 
     with open(os.path.join(HERE, "gpar_cases.json")) as f:
         cases = json.load(f)
-    # the Matern cases (`matern` in the configuration) are an addition of the port: the reference has no such kernel and is not asked
-    cases = {key: [c for c in rows if "matern" not in c["config"]] for key, rows in cases.items()}
+    # the Matern and spectral cases (`matern` / `spectral` in the configuration) are additions of the port: the reference has no such
+    # kernels and is not asked
+    cases = {key: [c for c in rows if "matern" not in c["config"] and "spectral" not in c["config"]] for key, rows in cases.items()}
     out = {"generator": "wesselb/gpar + stheno (see header of make_reference_golden.py)", "versions": {}, "gpar_logpdf": [], "single_gp": [], "vfe": []}
     for mod in ("gpar", "stheno", "lab", "matrix", "varz", "mlkernels", "torch", "numpy"):
         try:

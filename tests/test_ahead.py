@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from gpar_amd.gp import GP, Obs
-from gpar_amd.kernels import EQ, Linear
+from gpar_amd.kernels import EQ, Cosine, Linear
 from gpar_amd.model import rolling_origins
 from gpar_amd.regression import GPARRegressor
 
@@ -79,13 +79,33 @@ def k_periodic(x, theta):
     return np.exp(-0.5 * r2) * np.exp(-0.5 * e2)
 
 
-THETA = {"eq_linear": np.array([0.5, 0.7, 0.3]), "periodic": np.array([0.6, 0.8, 1.3])}
-KFUN = {"eq_linear": k_eq_linear, "periodic": k_periodic}
+def k_eq_cos(x, theta):
+    """One component of a spectral mixture over both columns: EQ with scales s0, s1 times the cosine of the SUM of the differences over
+    the periods T0, T1 (include/gpar_hip.h: GPAR_K_COS)."""
+    s0, s1, t0, t1 = theta
+    d0, d1 = x[:, None, 0] - x[None, :, 0], x[:, None, 1] - x[None, :, 1]
+    return np.exp(-0.5 * (d0**2 / s0**2 + d1**2 / s1**2)) * np.cos(2.0 * np.pi * (d0 / t0 + d1 / t1))
+
+
+def spectral_terms(xs, periods, scale):
+    """What GPARRegressor(spectral=len(periods), spectral_period=periods, spectral_scale=scale) adds to every layer's kernel over the
+    inputs xs at its initial values: sum_q (1 / Q) EQ(scale) cos(2 pi sum_d (x_d - x'_d) / periods[q])."""
+    d = xs[:, None, :] - xs[None, :, :]
+    envelope = np.exp(-0.5 * (d**2).sum(-1) / scale**2)
+    return sum(envelope * np.cos(2.0 * np.pi * d.sum(-1) / t) for t in periods) / len(periods)
+
+
+THETA = {"eq_linear": np.array([0.5, 0.7, 0.3]), "periodic": np.array([0.6, 0.8, 1.3]), "eq_cos": np.array([0.5, 0.7, 0.45, 1.3])}
+KFUN = {"eq_linear": k_eq_linear, "periodic": k_periodic, "eq_cos": k_eq_cos}
+SPECTRAL = dict(spectral=2, spectral_period=(0.7, 0.31), spectral_scale=0.8)
 
 
 def library_kernel(name, params):
     if name == "eq_linear":
         return EQ().stretch(params[:2]).select([0, 1]) + params[2] * Linear().select([0, 1])
+    if name == "eq_cos":   # (params: floats, or tensors that carry gradients)
+        stack = torch.stack if torch.is_tensor(params[0]) else np.array
+        return EQ().stretch(stack(list(params[:2]))).select([0, 1]) * Cosine().stretch(stack(list(params[2:4]))).select([0, 1])
     return EQ().stretch(params[0]).select([0]) * EQ().stretch(params[1]).periodic(params[2]).select([1])
 
 
@@ -149,7 +169,7 @@ def test_horizon_one_from_the_first_row_is_logpdf_and_its_weights_are_those_of_t
     np.testing.assert_allclose(got[il], W[il], rtol=1e-6, atol=1e-7)
 
 
-@pytest.mark.parametrize("name", ["eq_linear", "periodic"])
+@pytest.mark.parametrize("name", ["eq_linear", "periodic", "eq_cos"])
 @pytest.mark.parametrize("which", ["h3", "ragged"])
 def test_kernel_parameter_and_noise_gradients_against_the_complex_step(engine, name, which):
     x, y, noise = layer_data(N, seed=8)
@@ -160,6 +180,8 @@ def test_kernel_parameter_and_noise_gradients_against_the_complex_step(engine, n
     params = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in theta]
     if name == "eq_linear":
         kernel = EQ().stretch(torch.stack(params[:2])).select([0, 1]) + params[2] * Linear().select([0, 1])
+    elif name == "eq_cos":
+        kernel = library_kernel(name, params)
     else:
         kernel = EQ().stretch(params[0]).select([0]) * EQ().stretch(params[1]).periodic(params[2]).select([1])
     noise_t = engine.tensor(noise).clone().requires_grad_(True)
@@ -186,11 +208,11 @@ def regressor_data(n, p, seed, missing):
     return x, y
 
 
-def regressor_brute_force(x, y, horizon, start, scale=0.5, noise=0.1):
+def regressor_brute_force(x, y, horizon, start, scale=0.5, noise=0.1, spectral=None):
     """Every layer's rows, inputs [x, y_<i], covariance and origins built here, independently of the model code: rows missing at an earlier
     output never reach a later layer (`impute=False`); the origin of the row with index r is the number of the layer's rows with index
     <= r - horizon.  The kernel is the regressor's at its initial values: EQ(scale) over x, plus, behind the first layer, a linear kernel
-    (scales 100) and a unit EQ over the previous outputs."""
+    (scales 100) and a unit EQ over the previous outputs; `spectral` = (periods, scale): and `spectral_terms` over x in every layer."""
     n, p = y.shape
     value, mean, var = 0.0, np.full((n, p), np.nan), np.full((n, p), np.nan)
     alive = np.ones(n, dtype=bool)
@@ -199,6 +221,8 @@ def regressor_brute_force(x, y, horizon, start, scale=0.5, noise=0.1):
         rows = np.flatnonzero(alive)
         xs, ys = x[rows], y[rows][:, :i]
         K = np.exp(-0.5 * ((xs[:, None, :] - xs[None, :, :]) ** 2).sum(-1) / scale**2)
+        if spectral is not None:
+            K = K + spectral_terms(xs, *spectral)
         if i:
             K = K + (ys / 100.0) @ (ys / 100.0).T + np.exp(-0.5 * ((ys[:, None, :] - ys[None, :, :]) ** 2).sum(-1))
         origin = np.array([-1 if r < start else int(np.sum(rows <= r - horizon)) for r in rows])
@@ -225,6 +249,33 @@ def test_regressor_ahead_against_a_brute_force_that_builds_every_layer_itself(en
     assert (~scored).any() and np.array_equal(np.isnan(mean), ~scored) and np.array_equal(np.isnan(var), ~scored)
     # torch inputs give a tensor value
     assert isinstance(reg.ahead(torch.tensor(x), y, horizon=horizon, start=start)[0], torch.Tensor)
+
+
+def test_spectral_regressor_ahead_against_a_brute_force_that_builds_every_layer_itself(engine):
+    """The same with spectral=2 (periods 0.7 and 0.31, envelopes of 0.8): value, means and variances of a spectral model."""
+    n, p, horizon, start = 60, 3, 3, 5
+    x, y = regressor_data(n, p, seed=11, missing=0.1)
+    reg = GPARRegressor(impute=False, **_KW, **SPECTRAL)
+    value, mean, var = reg.ahead(x, y, horizon=horizon, start=start)
+    want = regressor_brute_force(x, y, horizon, start, spectral=(SPECTRAL["spectral_period"], SPECTRAL["spectral_scale"]))
+    plain = regressor_brute_force(x, y, horizon, start)
+    assert abs(want[0] - plain[0]) > 1e-3 * abs(plain[0])   # (the spectral terms are not lost in the tolerance)
+    np.testing.assert_allclose(float(value), want[0], rtol=1e-10)
+    np.testing.assert_allclose(mean, want[1], rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(var, want[2], rtol=1e-8, atol=1e-10)
+
+
+@pytest.mark.parametrize("which", ["h3", "ragged"])
+def test_eq_x_cosine_value_means_and_variances_against_the_brute_force(engine, which):
+    x, y, noise = layer_data(N)
+    origin = ragged_origin(N) if which == "ragged" else origins_for(N, 3)
+    K = k_eq_cos(x, THETA["eq_cos"]) + np.diag(noise) + 1e-12 * np.eye(N)
+    want = brute_force(K, y, origin)
+    with torch.no_grad():
+        value, mean, var = _obs(engine, "eq_cos", THETA["eq_cos"], x, y, engine.tensor(noise)).ahead(origin)
+    np.testing.assert_allclose(float(value), want[0], rtol=1e-10)
+    np.testing.assert_allclose(to_np(mean), want[1], rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(to_np(var), want[2], rtol=1e-8, atol=1e-10)
 
 
 def test_error_surface(oracle_engine):

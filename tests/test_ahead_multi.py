@@ -17,7 +17,8 @@ from gpar_amd.kernels import EQ, Linear
 from gpar_amd.regression import GPARRegressor
 
 from .conftest import to_np
-from .test_ahead import _KW, KFUN, THETA, complex_step, layer_data, origins_for, ragged_origin, regressor_data
+from .test_ahead import (_KW, KFUN, SPECTRAL, THETA, complex_step, layer_data, library_kernel, origins_for, ragged_origin, regressor_data,
+                         spectral_terms)
 from .test_scores import brute_force
 
 N, P, START = 36, 3, 2
@@ -31,7 +32,7 @@ def multi_brute_force(K, y, origins, weights, rule="log"):
     return np.sum(np.asarray(weights) * values), values, np.stack([p[1] for p in parts]), np.stack([p[2] for p in parts])
 
 
-def regressor_multi_brute_force(x, y, horizons, start, rule="log", weights=None, scale=0.5, noise=0.1):
+def regressor_multi_brute_force(x, y, horizons, start, rule="log", weights=None, scale=0.5, noise=0.1, spectral=None):
     """`regressor_brute_force` of tests/test_ahead.py for several horizons and any rule: every layer's rows, inputs [x, y_<i], covariance
     and origins are built here (`impute=False`: rows missing at an earlier output never reach a later layer)."""
     n, p = y.shape
@@ -44,6 +45,8 @@ def regressor_multi_brute_force(x, y, horizons, start, rule="log", weights=None,
         rows = np.flatnonzero(alive)
         xs, ys = x[rows], y[rows][:, :i]
         K = np.exp(-0.5 * ((xs[:, None, :] - xs[None, :, :]) ** 2).sum(-1) / scale**2)
+        if spectral is not None:   # (periods, scale): tests/test_ahead.py's `spectral_terms` over x in every layer
+            K = K + spectral_terms(xs, *spectral)
         if i:
             K = K + (ys / 100.0) @ (ys / 100.0).T + np.exp(-0.5 * ((ys[:, None, :] - ys[None, :, :]) ** 2).sum(-1))
         origins = [np.array([-1 if r < start else int(np.sum(rows <= r - h)) for r in rows]) for h in horizons]
@@ -77,6 +80,21 @@ def test_three_horizons_against_the_brute_force(oracle_engine, data, rule):
     value_w = reg.ahead(x, y, horizon=HORIZONS, start=START, score=rule, horizon_weights=weights)[0]
     np.testing.assert_allclose(float(value_w), np.sum(np.array(weights) * want[1]), rtol=1e-10)
     np.testing.assert_allclose(reg.ahead_values_, want[1], rtol=1e-10)
+
+
+@pytest.mark.parametrize("rule", ["log", "crps"])
+def test_three_horizons_of_a_spectral_model_against_the_brute_force(oracle_engine, data, rule):
+    x, y = data
+    reg = GPARRegressor(impute=False, **_KW, **SPECTRAL)
+    value, mean, var = reg.ahead(x, y, horizon=HORIZONS, start=START, score=rule)
+    want = regressor_multi_brute_force(x, y, HORIZONS, START, rule, spectral=(SPECTRAL["spectral_period"], SPECTRAL["spectral_scale"]))
+    plain = regressor_multi_brute_force(x, y, HORIZONS, START, rule)
+    assert abs(want[0] - plain[0]) > 1e-3 * abs(plain[0])
+    np.testing.assert_allclose(float(value), want[0], rtol=1e-10)
+    np.testing.assert_allclose(reg.ahead_values_, want[1], rtol=1e-10)
+    for k in range(3):
+        np.testing.assert_allclose(mean[k], want[2][k], rtol=1e-8, atol=1e-10)
+        np.testing.assert_allclose(var[k], want[3][k], rtol=1e-8, atol=1e-10)
 
 
 def test_the_value_is_the_weighted_sum_of_the_single_horizon_calls_and_the_order_permutes_the_outputs(oracle_engine, data):
@@ -136,7 +154,7 @@ def _layer_origins(n):
 WEIGHTS = np.array([0.5, 2.0, 1.25])
 
 
-@pytest.mark.parametrize("name", ["eq_linear", "periodic"])
+@pytest.mark.parametrize("name", ["eq_linear", "periodic", "eq_cos"])
 @pytest.mark.parametrize("rule", ["log", "crps"])
 def test_kernel_parameter_and_noise_gradients_against_the_complex_step(oracle_engine, name, rule):
     engine, n = oracle_engine, 40
@@ -152,6 +170,8 @@ def test_kernel_parameter_and_noise_gradients_against_the_complex_step(oracle_en
     params = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in theta]
     if name == "eq_linear":
         kernel = EQ().stretch(torch.stack(params[:2])).select([0, 1]) + params[2] * Linear().select([0, 1])
+    elif name == "eq_cos":
+        kernel = library_kernel(name, params)
     else:
         kernel = EQ().stretch(params[0]).select([0]) * EQ().stretch(params[1]).periodic(params[2]).select([1])
     noise_t = engine.tensor(noise).clone().requires_grad_(True)

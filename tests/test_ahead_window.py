@@ -18,7 +18,8 @@ from gpar_amd.kernels import EQ, Linear
 from gpar_amd.regression import GPARRegressor
 
 from .conftest import to_np
-from .test_ahead import _KW, THETA, _obs, brute_force, complex_step, k_eq_linear, layer_data, origins_for, regressor_data
+from .test_ahead import (_KW, SPECTRAL, THETA, _obs, brute_force, complex_step, k_eq_cos, k_eq_linear, layer_data, library_kernel, origins_for,
+                         regressor_data, spectral_terms)
 
 N = 40
 
@@ -58,7 +59,7 @@ def window_starts(n, horizon, window):
     return np.clip(np.arange(n) - horizon - window + 1, 0, None)
 
 
-def regressor_window_brute_force(x, y, horizon, start, window, scale=0.5, noise=0.1):
+def regressor_window_brute_force(x, y, horizon, start, window, scale=0.5, noise=0.1, spectral=None):
     """Every layer built here, as tests/test_ahead.py's `regressor_brute_force` builds it, with the window: the row with index r is
     predicted from the layer's rows with index in r - horizon - window + 1 ... r - horizon."""
     n, p = y.shape
@@ -69,6 +70,8 @@ def regressor_window_brute_force(x, y, horizon, start, window, scale=0.5, noise=
         rows = np.flatnonzero(alive)
         xs, ys = x[rows], y[rows][:, :i]
         K = np.exp(-0.5 * ((xs[:, None, :] - xs[None, :, :]) ** 2).sum(-1) / scale**2)
+        if spectral is not None:   # (periods, scale): tests/test_ahead.py's `spectral_terms` over x in every layer
+            K = K + spectral_terms(xs, *spectral)
         if i:
             K = K + (ys / 100.0) @ (ys / 100.0).T + np.exp(-0.5 * ((ys[:, None, :] - ys[None, :, :]) ** 2).sum(-1))
         origin = np.array([-1 if r < start else int(np.sum(rows <= r - horizon)) for r in rows])
@@ -113,6 +116,45 @@ def test_composed_route_against_one_conditioning_per_row(oracle_engine, horizon,
     if horizon == N:   # every window is empty: the prior
         np.testing.assert_allclose(to_np(mean)[origin >= 0], 0.0, atol=1e-10)
         np.testing.assert_allclose(to_np(var)[origin >= 0], np.diag(K)[origin >= 0], rtol=1e-8)
+
+
+@pytest.mark.parametrize("horizon,window,score", [(1, 2, "log"), (3, 5, "log"), (3, 5, "crps"), (1, N, "se")])
+def test_composed_route_with_an_eq_x_cosine_kernel_against_one_conditioning_per_row(oracle_engine, horizon, window, score):
+    """As above with one spectral-mixture component, EQ x cosine of the sum over both columns: value, means, variances, the gradients of
+    the envelope's scales and the cosine's periods, and the noise gradient; start = 2."""
+    x, y, noise = layer_data(N, seed=6)
+    theta = THETA["eq_cos"]
+    origin, lo = origins_for(N, horizon, start=2), window_starts(N, horizon, window)
+
+    def ref(t, d):
+        return window_brute_force(k_eq_cos(x, t) + np.diag(d) + 1e-12 * np.eye(N), y, lo, origin, score)
+
+    want = ref(theta, noise)
+    want_theta = complex_step(lambda t: ref(t, noise)[0], theta)
+    want_noise = complex_step(lambda d: ref(theta.astype(complex), d)[0], noise)
+    params = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in theta]
+    noise_t = oracle_engine.tensor(noise).clone().requires_grad_(True)
+    value, mean, var = Obs(GP(library_kernel("eq_cos", params))(oracle_engine.tensor(x), noise_t), oracle_engine.tensor(y)).ahead(origin, score, lo=lo)
+    value.backward()
+    got = np.array([float(p.grad) for p in params])
+    np.testing.assert_allclose(float(value.detach()), want[0], rtol=1e-10)
+    np.testing.assert_allclose(to_np(mean), want[1], rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(to_np(var), want[2], rtol=1e-8, atol=1e-10)
+    assert np.max(np.abs(want_theta[2:])) > 1e-2   # (the periods matter)
+    np.testing.assert_allclose(got, want_theta, rtol=1e-6, atol=1e-7)
+    np.testing.assert_allclose(to_np(noise_t.grad), want_noise, rtol=1e-6, atol=1e-7)
+
+
+def test_ragged_windows_of_a_spectral_model_with_missing_values(oracle_engine):
+    """tests below: `test_ragged_windows_with_missing_values_in_two_outputs`, with spectral=2 in every layer."""
+    n, p, horizon, start, window = 60, 3, 3, 5, 5
+    x, y = regressor_data(n, p, seed=11, missing=0.1)
+    value, mean, var = GPARRegressor(impute=False, **_KW, **SPECTRAL).ahead(x, y, horizon=horizon, start=start, window=window)
+    want = regressor_window_brute_force(x, y, horizon, start, window, spectral=(SPECTRAL["spectral_period"], SPECTRAL["spectral_scale"]))
+    assert abs(want[0] - regressor_window_brute_force(x, y, horizon, start, window)[0]) > 1e-3 * abs(want[0])
+    np.testing.assert_allclose(float(value), want[0], rtol=1e-10)
+    np.testing.assert_allclose(mean, want[1], rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(var, want[2], rtol=1e-8, atol=1e-10)
 
 
 @pytest.mark.parametrize("horizon", [1, 3])

@@ -23,7 +23,7 @@ from gpar_amd.regression import GPARRegressor, _construct_gpar, _surviving_rows
 
 from .conftest import to_np
 from .test_fastfit import _layer_objectives
-from .test_loo import _KW, _data, _eq_linear, _fd, _one_layer
+from .test_loo import _KW, _SPECTRAL_KW, _data, _eq_linear, _fd, _one_layer, _spectral_first_layer
 
 _LOG_2PI = np.log(2.0 * np.pi)
 
@@ -207,14 +207,34 @@ def test_missing_entries_are_nan_and_contribute_nothing(engine, replace):
     np.testing.assert_allclose(var[seen, 0], s_ref, rtol=1e-8, atol=1e-10)
 
 
+def test_first_layer_of_a_spectral_model_equals_the_closed_form_and_the_brute_force_with_weights(engine):
+    """The VALUE of cv, its means and variances for a spectral model against the dense restatement: the closed form and one deletion
+    per fold, folds of 3 and 4 rows, weights."""
+    x, y = _data(30, 1, seed=37)
+    w = np.random.default_rng(37).uniform(0.5, 2.0, y.shape)
+    starts = _fold_starts(30, [3, 4])
+    labels = np.repeat(np.arange(len(starts) - 1), np.diff(starts))
+    value, mean, var = GPARRegressor(**_SPECTRAL_KW).cv(x, y, w, folds=labels)
+    K = _spectral_first_layer(x) + np.diag(0.05 / w[:, 0]) + engine.epsilon * np.eye(30)
+    v_ref, m_ref, s_ref = _closed_form(K, y[:, 0], starts)[:3]
+    v_brute, m_brute, s_brute = _brute_force(K, y[:, 0], starts)
+    assert abs(v_ref - v_brute) <= 1e-11 * abs(v_brute)
+    assert abs(float(value) - v_brute) <= 1e-10 * abs(v_brute)
+    np.testing.assert_allclose(mean[:, 0], m_brute, rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(var[:, 0], s_brute, rtol=1e-8, atol=1e-10)
+    plain = GPARRegressor(scale=0.5, linear=False, nonlinear=False, noise=0.05, normalise_y=False).cv(x, y, w, folds=labels)[0]
+    assert abs(float(plain) - v_brute) > 1e-3 * abs(v_brute)
+
+
 # ---- gradient ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("matern", [None, 1.5], ids=["eq", "matern32"])
-def test_autograd_gradient_of_the_cv_value_against_central_differences(engine, matern):
+@pytest.mark.parametrize("matern,spectral", [(None, None), (1.5, None), (None, 2)], ids=["eq", "matern32", "spectral2"])
+def test_autograd_gradient_of_the_cv_value_against_central_differences(engine, matern, spectral):
     x, y = _data(40, 2, seed=36)
     rng = np.random.default_rng(36)
     w = rng.uniform(0.5, 2.0, y.shape)
     labels = rng.integers(0, 6, 40)   # (unsorted: the gradient passes through the permutation)
-    reg = GPARRegressor(matern=matern, **_KW)
+    # (spectral: two components at periods 0.7 and 0.31 with short envelopes - periods, envelope scales and variances are differentiated)
+    reg = GPARRegressor(matern=matern, **_KW, **({} if spectral is None else dict(spectral=spectral, spectral_period=(0.7, 0.31), spectral_scale=0.8)))
 
     def value():
         return _construct_gpar(reg, reg.vs, 2, 2).cv(x, y, w, labels)[0]
@@ -233,9 +253,12 @@ def test_autograd_gradient_of_the_cv_value_against_central_differences(engine, m
         with torch.no_grad():
             return float(value())
 
-    want = _fd(f, x0)
+    # The stencil's step is relative to the optimiser's variable, ~ -10 for a value of 0.3 between the bounds 1e-4 and 1e4, where
+    # d log(value) / d variable ~ 1: the default 1e-3 moves a period by 1 % and the phase 2 pi |x - x'| / T ~ 20 by h k = 0.2, a truncation
+    # error (h k)^4 / 30 ~ 5e-5 of that component - above the tolerance below.  A tenth of the step: 5e-9; rounding 1e-16 |L| / h ~ 1e-11.
+    want = _fd(f, x0, rel_step=1e-3 if spectral is None else 1e-4)
     reg.vs.set_vector(x0, names)
-    print(f"matern={matern}: {got.size} variables, largest |fd| {np.max(np.abs(want)):.3e}, max error {np.max(np.abs(got - want)):.2e}")
+    print(f"matern={matern} spectral={spectral}: {got.size} variables, largest |fd| {np.max(np.abs(want)):.3e}, max error {np.max(np.abs(got - want)):.2e}")
     assert np.max(np.abs(want)) > 1e-2
     np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6 * np.max(np.abs(want)))
 

@@ -23,14 +23,18 @@ import torch
 
 from gpar_amd import fastfit
 from gpar_amd.gp import GP, Obs
-from gpar_amd.kernels import EQ, Linear
+from gpar_amd.kernels import EQ, Cosine, Linear
 from gpar_amd.model import purged_folds
 from gpar_amd.regression import GPARRegressor
 
 from .conftest import to_np
 from .test_cv import _fold_starts
 from .test_loo import _KW, _data
+from .test_ahead import SPECTRAL, k_eq_cos, spectral_terms
 from .test_loo_gpu import KERNELS
+
+# (one spectral-mixture component over the first two of the three columns beside the kernels of tests/test_loo_gpu.py)
+KERNELS = dict(KERNELS, eq_cos=(k_eq_cos, np.array([0.5, 0.7, 0.45, 1.3])))
 
 _LOG_2PI = np.log(2.0 * np.pi)
 CASES = [(7, 1, 1), (7, 3, 2), (40, 5, 3), (40, 8, 50), (65, 16, 24), (66, 17, 24), (130, 16, 24), (130, 17, 24)]
@@ -147,10 +151,14 @@ def eq_linear_kernel(theta):
     return EQ().stretch(torch.stack(list(theta[:2]))).select([0, 1]) + theta[2] * Linear().stretch(theta[3]).select([2])
 
 
+def eq_cos_kernel(theta):
+    return EQ().stretch(torch.stack(list(theta[:2]))).select([0, 1]) * Cosine().stretch(torch.stack(list(theta[2:4]))).select([0, 1])
+
+
 def _obs(engine, case, theta=None, noise=None):
-    theta = [torch.tensor(float(v), dtype=torch.float64) for v in KERNELS["eq_linear"][1]] if theta is None else theta
+    theta = [torch.tensor(float(v), dtype=torch.float64) for v in KERNELS[case["name"]][1]] if theta is None else theta
     noise = engine.tensor(case["noise"]) if noise is None else noise
-    return Obs(GP(eq_linear_kernel(theta))(engine.tensor(case["x"]), noise), engine.tensor(case["y"]))
+    return Obs(GP((eq_cos_kernel if case["name"] == "eq_cos" else eq_linear_kernel)(theta))(engine.tensor(case["x"]), noise), engine.tensor(case["y"]))
 
 
 # ---- one layer ---------------------------------------------------------------------------------------------------------------
@@ -253,6 +261,26 @@ def test_kernel_parameter_and_noise_gradients_against_the_complex_step(engine, n
     np.testing.assert_allclose(0.5 * np.diag(case["W"]), want_noise, rtol=1e-6, atol=1e-7)
 
 
+@pytest.mark.parametrize("n,fold,gap", [(40, 5, 3), (66, 17, 24)], ids=lambda v: str(v))
+def test_eq_x_cosine_value_and_gradients_against_brute_force_deletion_and_the_complex_step(engine, n, fold, gap):
+    """Value, means and variances against the brute force, and the gradients of the envelope's scales, the cosine's periods and the
+    noise against its complex step, for one spectral-mixture component."""
+    case = layer_case(n, fold, gap, True, name="eq_cos")
+    want_theta, want_noise = complex_step_grads(case)
+    params = [torch.tensor(float(v), dtype=torch.float64, requires_grad=True) for v in KERNELS["eq_cos"][1]]
+    noise_t = engine.tensor(case["noise"]).clone().requires_grad_(True)
+    with engine.defer_checks():
+        value, mean, var = _obs(engine, case, params, noise_t).cv(case["starts"], (case["lo"], case["hi"]))
+        value.backward()
+    got = np.array([float(p.grad) for p in params])
+    np.testing.assert_allclose(float(value), case["value"], rtol=1e-10)
+    np.testing.assert_allclose(to_np(mean), case["mean"], rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(to_np(var), case["var"], rtol=1e-8, atol=1e-10)
+    assert np.max(np.abs(want_theta[2:])) > 1e-2   # (the periods matter)
+    np.testing.assert_allclose(got, want_theta, rtol=1e-6, atol=1e-7)
+    np.testing.assert_allclose(to_np(noise_t.grad), want_noise, rtol=1e-6, atol=1e-7)
+
+
 # ---- the public API ----------------------------------------------------------------------------------------------------------
 def _missing_data():
     x, y = _data(30, 3, seed=45, missing=0.2)
@@ -263,10 +291,18 @@ def _missing_data():
 
 
 def test_regressor_cv_with_a_gap_counts_rows_as_given_against_per_output_brute_force(engine):
+    _regressor_cv_with_a_gap(engine, {})
+
+
+def test_spectral_regressor_cv_with_a_gap_against_per_output_brute_force(engine):
+    _regressor_cv_with_a_gap(engine, SPECTRAL)
+
+
+def _regressor_cv_with_a_gap(engine, spectral):
     x, y = _missing_data()
     n, gap = 30, 2
     assert 0.1 < np.isnan(y).mean() < 0.35
-    reg = GPARRegressor(scale=0.5, linear=False, nonlinear=False, noise=0.05, normalise_y=False, impute=True)
+    reg = GPARRegressor(scale=0.5, linear=False, nonlinear=False, noise=0.05, normalise_y=False, impute=True, **spectral)
     value, mean, var = reg.cv(x, y, folds=5, gap=gap)
     np.testing.assert_array_equal(np.isnan(mean), np.isnan(y))
     np.testing.assert_array_equal(np.isnan(var), np.isnan(y))
@@ -276,6 +312,8 @@ def test_regressor_cv_with_a_gap_counts_rows_as_given_against_per_output_brute_f
         # (no layer of this model looks at earlier outputs: output i is a GP over x on the rows observed there)
         seen = np.nonzero(~np.isnan(y[:, i]))[0]
         K = np.exp(-0.5 * ((x[seen, None, :] - x[None, seen, :]) ** 2).sum(-1) / 0.5**2) + (0.05 + engine.epsilon) * np.eye(seen.size)
+        if spectral:
+            K = K + spectral_terms(x[seen], spectral["spectral_period"], spectral["spectral_scale"])
         starts, lo, hi = [0], [], []
         for a, b in spans:
             inside = np.nonzero((seen >= a) & (seen < b))[0]

@@ -11,7 +11,13 @@ tests cover by design, this covers by accident.
 Seeds from MATERN_FIRST on are the same draws with `matern` = 0.5 / 1.5 / 2.5 set in addition (which excludes rq): the Matern
 kernels under missing data, weights, markov orders, tied scales, the three inducing-point approximations, impute / replace and
 posterior samples on the shared stream, at the tolerances of every other case.  tests/test_fuzz_cases.py (CPU) checks what the
-block contains.  The tests print their error / tolerance ratios for these seeds (pytest -s)."""
+block contains.  The tests print their error / tolerance ratios for these seeds (pytest -s).
+
+Seeds from SPECTRAL_FIRST on are, again, the same draws, with `spectral` = 1 / 2 components set in addition (periods 0.5, 1.0 or the
+pair (0.7, 0.31) against inputs in [0, 1]; every other seed a short envelope, `spectral_scale` = 0.8): the cosine factor under
+everything the Matern block lists.  Three seeds of four force the EQ model beside the spectral terms; the fourth keeps a drawn
+rq=True or else takes a Matern smoothness by seed, so that RQ and Matern factors are evaluated next to the cosine.  Q <= 2 always
+fits the device's eight terms (1 + per + 2 input_linear + linear + nonlinear + Q)."""
 import numpy as np
 import pytest
 
@@ -26,13 +32,55 @@ MATERN_GRADIENT_SEEDS = list(range(MATERN_FIRST + 100, MATERN_FIRST + 115))
 MATERN_MID_SEEDS = list(range(MATERN_FIRST, MATERN_FIRST + 6))
 
 
+SPECTRAL_FIRST = 2000                                 # first seed of the spectral block (the seeds below it keep their cases)
+SPECTRAL_SEEDS = list(range(SPECTRAL_FIRST, SPECTRAL_FIRST + 36))
+SPECTRAL_GRADIENT_SEEDS = list(range(SPECTRAL_FIRST + 100, SPECTRAL_FIRST + 112))
+# (chosen: the numpy engine forms every derivative matrix explicitly, which takes minutes for dense `replace` at n = 2475 - seed 2001 - and
+# at n = 1536 - seed 2006; these six hold both Q, inducing points with a periodic term, an RQ and a Matern factor beside the cosine)
+SPECTRAL_MID_SEEDS = [SPECTRAL_FIRST + k for k in (0, 2, 3, 4, 5, 7)]
+
+
 def _matern(seed):
-    """Smoothness of a seed of the Matern block (each value every third seed), None below the block."""
+    """Smoothness of a seed of the Matern block (each value every third seed), None below the block; in the spectral block the
+    smoothness every fourth seed takes unless it drew rq=True, None for the others."""
+    if seed >= SPECTRAL_FIRST:
+        k = seed - SPECTRAL_FIRST
+        return [0.5, 1.5, 2.5][(k // 4) % 3] if k % 4 == 3 else None
     return None if seed < MATERN_FIRST else [0.5, 1.5, 2.5][(seed - MATERN_FIRST) % 3]
 
 
-def _report(label, seed, ratios):
-    if seed >= MATERN_FIRST:
+def _spectral(seed):
+    """The spectral keywords of a seed of the spectral block, None below it."""
+    if seed < SPECTRAL_FIRST:
+        return None
+    k = seed - SPECTRAL_FIRST
+    q = [1, 2][k % 2]
+    period = [0.5, 1.0, (0.7, 0.31)][k % 3]
+    out = dict(spectral=q, spectral_period=period if q == 2 or not isinstance(period, tuple) else 0.5)
+    if (k // 2) % 2:   # every other pair of seeds (so that both Q meet it): an envelope that is not flat over [0, 1]
+        out["spectral_scale"] = 0.8
+    return out
+
+
+def _block_kernel_switches(seed, kw):
+    """`matern` / `rq` / `spectral*` of the seed's block, set into the drawn keywords (nothing is drawn for them: the stream is that
+    of every other seed)."""
+    if seed >= SPECTRAL_FIRST:
+        if (seed - SPECTRAL_FIRST) % 4 != 3:
+            kw["rq"] = False                       # the EQ model beside the spectral terms
+        elif not kw["rq"]:
+            kw["matern"] = _matern(seed)           # a drawn rq=True stays; else the Matern kernel of the seed
+        kw.update(_spectral(seed))
+    elif _matern(seed) is not None:
+        kw["matern"], kw["rq"] = _matern(seed), False
+
+
+def _report(label, seed, ratios, kw=None):
+    if seed >= SPECTRAL_FIRST:
+        sp = _spectral(seed)
+        print(f"[spectral] {label} seed={seed} Q={sp['spectral']} T={sp['spectral_period']} matern={(kw or {}).get('matern')} "
+              f"rq={(kw or {}).get('rq')}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
+    elif seed >= MATERN_FIRST:
         print(f"[matern] {label} seed={seed} nu={_matern(seed)}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
 
 
@@ -46,8 +94,7 @@ def _case(seed):
         markov=[None, None, 0, 1, 2][int(rng.integers(5))],
         impute=bool(rng.integers(2)), replace=bool(rng.integers(3) == 0),
     )
-    if _matern(seed) is not None:   # (nothing is drawn for it: the stream below is that of every other seed)
-        kw["matern"], kw["rq"] = _matern(seed), False
+    _block_kernel_switches(seed, kw)   # (nothing is drawn for them: the stream below is that of every other seed)
     if kw["per"]:
         kw["per_period"] = float(rng.uniform(0.3, 1.2))
     if rng.integers(3) == 0 and n >= 6:
@@ -96,7 +143,8 @@ def _run(kind, kw, x, y, w, xs):
         set_engine(previous)
 
 
-@pytest.mark.parametrize("seed", [-s - 1 for s in range(24)] + list(range(96)) + MATERN_SEEDS + [-s - 1 for s in MATERN_SEEDS[:12]])
+@pytest.mark.parametrize("seed", [-s - 1 for s in range(24)] + list(range(96)) + MATERN_SEEDS + [-s - 1 for s in MATERN_SEEDS[:12]]
+                         + SPECTRAL_SEEDS + [-s - 1 for s in SPECTRAL_SEEDS[:8]])
 def test_random_configuration(seed, monkeypatch):
     """(negative seeds: case -seed - 1 once more with GPAR_HOST_MASKS=0 - boolean device masks computed layer by layer, the
     path every engine but the HIP one still takes - so that both ways through the missing-data bookkeeping stay covered)"""
@@ -118,8 +166,9 @@ def test_random_configuration(seed, monkeypatch):
     if kw.get("sparse_method", "vfe") == "vfe":   # the independent restatement implements the reference's default approximation
         want = gpar_ref.gpar_logpdf(x, y, w, hypers, config, impute=kw["impute"], replace=kw["replace"], x_ind=kw.get("x_ind"))
         ratios["restatement"] = abs(prior - want) / (tol * max(abs(want), 1.0))
-    _report("fuzz", seed, ratios)
-    assert config.get("matern") == _matern(seed)
+    _report("fuzz", seed, ratios, kw)
+    assert config.get("matern") == kw.get("matern") and (seed >= SPECTRAL_FIRST or kw.get("matern") == _matern(seed))
+    assert config.get("spectral") == kw.get("spectral") == (_spectral(seed) or {}).get("spectral")
     assert abs(prior - o_prior) <= tol * scale, (kw, prior, o_prior)
     assert abs(post - o_post) <= tol * max(abs(o_post), 1.0), (kw, post, o_post)
     np.testing.assert_allclose(sample, o_sample, rtol=0, atol=(1e-4 if sparse else 1e-7) * max(1.0, np.abs(o_sample).max()))
@@ -156,7 +205,7 @@ def _gradient_ratios(sparse, value, o_value, got, ref):
             "gradient": float(np.max(np.abs(got - ref) / (atol + rtol * np.abs(ref))))}
 
 
-@pytest.mark.parametrize("seed", list(range(32)) + MATERN_GRADIENT_SEEDS)
+@pytest.mark.parametrize("seed", list(range(32)) + MATERN_GRADIENT_SEEDS + SPECTRAL_GRADIENT_SEEDS)
 def test_random_configuration_gradient(seed):
     """d logpdf / d(every hyper-parameter) - the joint objective of fit(fix=False), through imputed / replaced columns and
     extended inducing inputs where the drawn configuration has them - HIP kernels against the numpy engine."""
@@ -164,7 +213,7 @@ def test_random_configuration_gradient(seed):
     sparse = "x_ind" in kw
     value, got = _grads("hip", kw, x, y, w)
     o_value, ref = _grads("oracle", kw, x, y, w)
-    _report("fuzz gradient", seed, _gradient_ratios(sparse, value, o_value, got, ref))
+    _report("fuzz gradient", seed, _gradient_ratios(sparse, value, o_value, got, ref), kw)
     assert abs(value - o_value) <= (1e-6 if sparse else 1e-9) * max(abs(o_value), 1.0)
     big = max(np.max(np.abs(ref)), 1e-3)
     np.testing.assert_allclose(got, ref, rtol=1e-4 if sparse else 1e-6, atol=(1e-5 if sparse else 1e-7) * big, err_msg=str(kw))
@@ -179,8 +228,7 @@ def _mid_case(seed):
     kw = dict(scale=float(rng.uniform(0.3, 1.0)), noise=float(rng.uniform(0.05, 0.3)), normalise_y=False, linear=True,
               nonlinear=bool(rng.integers(2)), rq=bool(rng.integers(2)), per=bool(rng.integers(4) == 0),
               markov=[None, 1, 2][int(rng.integers(3))], impute=bool(rng.integers(2)), replace=bool(rng.integers(4) == 0))
-    if _matern(seed) is not None:
-        kw["matern"], kw["rq"] = _matern(seed), False
+    _block_kernel_switches(seed, kw)
     if rng.integers(3) == 0:
         kw["x_ind"] = rng.uniform(0, 1, (int(rng.integers(40, 321)), m))
     x = rng.uniform(0, 1, (n, m))
@@ -198,13 +246,13 @@ def _mid_case(seed):
     return kw, x, y, w
 
 
-@pytest.mark.parametrize("seed", list(range(20)) + MATERN_MID_SEEDS)
+@pytest.mark.parametrize("seed", list(range(20)) + MATERN_MID_SEEDS + SPECTRAL_MID_SEEDS)
 def test_random_configuration_at_blocked_sizes(seed):
     kw, x, y, w = _mid_case(seed)
     sparse = "x_ind" in kw
     value, got = _grads("hip", kw, x, y, w)
     o_value, ref = _grads("oracle", kw, x, y, w)
-    _report("fuzz blocked sizes", seed, _gradient_ratios(sparse, value, o_value, got, ref))
+    _report("fuzz blocked sizes", seed, _gradient_ratios(sparse, value, o_value, got, ref), kw)
     assert abs(value - o_value) <= (1e-6 if sparse else 1e-9) * max(abs(o_value), 1.0), (kw, value, o_value)
     big = max(np.max(np.abs(ref)), 1e-3)
     np.testing.assert_allclose(got, ref, rtol=1e-4 if sparse else 1e-6, atol=(1e-5 if sparse else 1e-7) * big, err_msg=str(kw))

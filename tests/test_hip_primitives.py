@@ -1447,3 +1447,157 @@ def test_build_time_archive_serves_mid_size_training_without_a_compilation(env):
     assert entries.value >= 300
     assert after[0].value == before[0].value, "hiprtc compiled a kernel the archive should hold"
     assert loaded.value > loaded0.value or after[2].value > 0   # (loaded now, or already cached by an earlier test of this process)
+
+
+# ---- the cosine factor (GPAR_K_COS) at the dispatch sites tests/test_spectral_gpu.py does not reach ---------------------------------
+# the inducing-point gradient pass in its three modes, the diagonal input gradients, gpar_gram_diag beside a Linear factor and the
+# lock-step build - against oracle/kernels.py, which knows the factor.  Sizes: one row, two rows, either side of the 32- and 64-row
+# tiles, more than one block; inducing points in odd numbers.
+_COSINE_WIDTH = 3
+
+
+def _cosine_structures():
+    """Cosine alone over two dims; 0.8 EQ x cosine + Linear; 1.1 Matern-3/2 + 0.5 RQ x cosine; the regressor's Q = 2 structure over two
+    inputs with the locally periodic term beside it (16 feature dims); and a cosine TIMES a Linear factor (the diagonal is coef |z|^2)."""
+    from gpar_amd.kernels import EQ, RQ, Cosine, Linear, Matern32
+
+    a = np.array
+    spectral = (1.0 * EQ().stretch(a([0.6, 0.9])) + 0.9 * EQ().stretch(a([0.9, 1.4, 1.1, 0.8])).periodic(a([0.8, 1.3])) * EQ().stretch(a([3.0, 4.0]))
+                + 0.5 * EQ().stretch(a([0.8, 1.2])) * Cosine().stretch(a([0.7, 1.1])) + 0.4 * EQ().stretch(a([1.5, 0.7])) * Cosine().stretch(a([0.31, 0.45])))
+    return {
+        "cos-nd2": (1.3 * Cosine().stretch(a([0.6, 1.7]))).select([0, 1]),
+        "eq-x-cos+lin": (0.8 * EQ().stretch(a([0.7, 1.1])) * Cosine().stretch(a([0.45, 1.3]))).select([0, 1]) + Linear().stretch(a([1.5])).select([2]),
+        "matern32+rq-x-cos": (1.1 * Matern32().stretch(a([0.7, 1.1]))).select([0, 1])
+                             + (0.5 * RQ(0.8).stretch(a([0.9, 1.2])) * Cosine().stretch(a([0.5, 0.9]))).select([1, 2]),
+        "spectral2+per": spectral.select([0, 1]),
+        "lin-x-cos": 0.9 * Linear().stretch(a([1.5, 2.5])).select([1, 2]) * Cosine().stretch(a([0.45])).select([0]),
+    }
+
+
+def _flat_grads(g):
+    out = [np.asarray(g["coef"], dtype=np.float64).reshape(-1)]
+    for fgrads in g["factors"]:
+        for f in fgrads:
+            out += [np.asarray(f[key], dtype=np.float64).reshape(-1) for key in ("scales", "periods", "alpha") if f[key] is not None]
+    return np.concatenate(out)
+
+
+@pytest.mark.parametrize("n,M", [(1, 7), (2, 7), (31, 33), (33, 7), (65, 33), (130, 7)])
+def test_cosine_cross_and_diagonal_gradient_passes_match_oracle(env, n, M):
+    """HipEngine.kernel_grads_vfe (W_fu rectangular, W_uu symmetric, wdiag) with a cosine in the structure against the oracle's explicit
+    derivative matrices, to 1e-6 of the largest component (the gradient tolerance of tests/test_spectral_gpu.py); the `rest` products
+    mix the cosine with EQ, RQ, Matern and periodic-embedded factors.  The diagonal pass alone: a cosine's scales receive exactly 0."""
+    torch, hip, dev, to_dev = env
+    from gpar_amd.engine import HipEngine
+    from gpar_amd.kernels import compile_kernel
+    from oracle.engine import OracleEngine
+
+    eng, ora = HipEngine(), OracleEngine()
+    rng = np.random.default_rng(100 * n + M)
+    x, z = rng.uniform(0, 1, (n, _COSINE_WIDTH)), rng.uniform(0, 1, (M, _COSINE_WIDTH))
+    Wfu, Wuu, wd = rng.standard_normal((n, M)), rng.standard_normal((M, M)), rng.standard_normal(n)
+    Wuu = Wuu + Wuu.T
+    worst = {}
+    for name, k in _cosine_structures().items():
+        ck = compile_kernel(k, _COSINE_WIDTH)
+        got = eng.kernel_grads_vfe(ck, to_dev(x), to_dev(z), to_dev(Wfu), to_dev(np.tril(Wuu) + np.triu(np.full((M, M), np.nan), 1)),
+                                   torch.tensor(wd, device=dev))
+        ref = ora.kernel_grads_vfe(ora.compile(k, _COSINE_WIDTH), torch.tensor(x), torch.tensor(z), torch.tensor(Wfu), torch.tensor(Wuu),
+                                   torch.tensor(wd))
+        g, r = _flat_grads(got), _flat_grads(ref)
+        assert g.shape == r.shape and np.max(np.abs(r)) > 1e-3, name
+        worst[name] = float(np.max(np.abs(g - r)) / (1e-6 * np.max(np.abs(r))))
+        assert np.max(np.abs(g - r)) <= 1e-6 * np.max(np.abs(r)), (name, g, r)
+        diag = eng.kernel_grads_diag(ck, to_dev(x), torch.tensor(wd, device=dev))
+        rdiag = ora.kernel_grads_diag(ora.compile(k, _COSINE_WIDTH), torch.tensor(x), torch.tensor(wd))
+        for t, term in enumerate(k.terms):
+            for fi, f in enumerate(term.factors):
+                if f.type == "cos":
+                    assert np.all(np.asarray(diag["factors"][t][fi]["scales"]) == 0.0), (name, t, fi)
+        gd, rd = _flat_grads(diag), _flat_grads(rdiag)
+        assert np.max(np.abs(gd - rd)) <= 1e-6 * max(np.max(np.abs(rd)), 1e-300), (name, gd, rd)
+    print(f"[spectral] kernel_grads_vfe n={n} M={M}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("n", [1, 2, 31, 33, 65, 130])
+def test_cosine_diagonal_value_and_input_gradients(env, n):
+    """gpar_gram_diag: a cosine factor is exactly 1 on the diagonal, so a term's diagonal is that of its other factors - coef |z|^2 where
+    it multiplies a Linear factor, not 1 - and equals the diagonal of the full Gram matrix.  kernel_diag_input_grads: cosine factors
+    contribute exactly 0 (the gradient with the cosine factors removed from the structure, bit for bit), and the oracle's value."""
+    torch, hip, dev, to_dev = env
+    from gpar_amd.engine import HipEngine
+    from gpar_amd.kernels import Kernel, Term, compile_kernel
+    from oracle import kernels as ok
+    from oracle.engine import OracleEngine
+
+    eng, ora = HipEngine(), OracleEngine()
+    rng = np.random.default_rng(n)
+    x = rng.uniform(0, 1, (n, _COSINE_WIDTH))
+    w = rng.standard_normal(n)
+    for name, k in _cosine_structures().items():
+        ck = compile_kernel(k, _COSINE_WIDTH)
+        spec = ok.spec_to_dict(k.resolve(_COSINE_WIDTH))
+        zf = hip.featurize(ck, to_dev(x))
+        got = hip.gram_diag(ck, zf).cpu().numpy()
+        np.testing.assert_allclose(got, ok.gram_diag(spec, x), rtol=1e-13, atol=1e-14, err_msg=name)
+        np.testing.assert_allclose(got, np.diag(hip.gram(ck, zf, zf).cpu().numpy()), rtol=1e-13, atol=1e-14, err_msg=name)
+        if name == "lin-x-cos":
+            want = 0.9 * ((x[:, 1] * (1.0 / 1.5)) ** 2 + (x[:, 2] * (1.0 / 2.5)) ** 2)
+            np.testing.assert_allclose(got, want, rtol=1e-14, atol=0, err_msg=name)
+            assert not np.allclose(got, 0.9)
+        if name == "cos-nd2":
+            assert np.all(got == 1.3)
+        grads = eng.kernel_diag_input_grads(ck, to_dev(x), torch.tensor(w, device=dev)).cpu().numpy()
+        stripped = Kernel([Term(t.coef, [f for f in t.factors if f.type != "cos"]) for t in k.terms])
+        same = eng.kernel_diag_input_grads(compile_kernel(stripped, _COSINE_WIDTH), to_dev(x), torch.tensor(w, device=dev)).cpu().numpy()
+        assert np.array_equal(grads, same), name
+        ref = ora.kernel_diag_input_grads(ora.compile(k, _COSINE_WIDTH), torch.tensor(x), torch.tensor(w)).numpy()
+        # (the oracle differentiates the diagonal numerically, step 1e-5 on a quadratic: exact to rounding / step ~ 1e-10)
+        np.testing.assert_allclose(grads, ref, rtol=0, atol=1e-8 * max(1.0, np.max(np.abs(ref))), err_msg=name)
+        if name in ("cos-nd2", "matern32+rq-x-cos"):
+            assert np.all(grads == 0.0), name
+
+
+@pytest.mark.parametrize("n", [1, 2, 31, 33, 65, 130])
+def test_cosine_structures_in_the_lockstep_build(env, monkeypatch, n):
+    """gpar_logpdf_lockstep over five layers with a cosine in every structure (LS_CHUNK = 4: a ragged second launch of the fused build):
+    the fused build (lockstep_build_kernel) and the per-layer build (gram_kernel) leave the same bits - factored matrices, solved rows,
+    values, total; the library has no entry point that stops after the fused build, see test_lockstep_logpdf_across_both_chunk_sizes -,
+    each value is gpar_logpdf_dense's and the oracle's, and the per-layer build itself matches the oracle's Gram matrix at rtol 1e-13 /
+    atol 1e-14."""
+    from gpar_amd.kernels import compile_kernel
+    from oracle import gp_ref
+    from oracle import kernels as ok
+
+    torch, hip, dev, to_dev = env
+    zoo = _cosine_structures()
+    names = ["cos-nd2", "eq-x-cos+lin", "matern32+rq-x-cos", "spectral2+per", "lin-x-cos"]
+    rng = np.random.default_rng(7000 + n)
+    x, y, w = rng.uniform(0, 1, (n, _COSINE_WIDTH)), rng.standard_normal((n, 5)), rng.uniform(0.5, 2.0, (n, 5))
+    layers = [(compile_kernel(zoo[name], _COSINE_WIDTH), 0.05 + 0.01 * b, (b + 2) % 5) for b, name in enumerate(names)]
+    assert [ck.dz for ck, _, _ in layers] == [2, 5, 6, 16, 3]   # all within the fused build's 24 dims, neighbours differ
+    dx, dy, dw = to_dev(x), to_dev(y), to_dev(w)
+    fused = _lockstep_call(env, layers, dx, dy, dw)
+    monkeypatch.setenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS", "0")
+    separate = _lockstep_call(env, layers, dx, dy, dw)
+    monkeypatch.delenv("GPAR_LOCKSTEP_FUSED_BUILD_ROWS")
+    assert fused[2] == [0] * 5 and separate[2] == [0] * 5
+    for b in range(5):
+        assert np.array_equal(fused[3][b], separate[3][b]), "factored matrix of layer %d (%s): fused against separate build" % (b, names[b])
+    assert np.array_equal(fused[0], separate[0]) and fused[1] == separate[1]
+    ratios = {}
+    for b, (ck, noise, col) in enumerate(layers):
+        spec = ok.spec_to_dict(zoo[names[b]].resolve(_COSINE_WIDTH))
+        one, _, info1, _ = hip.logpdf_dense(ck, dx, dy[:, col], noise / dw[:, col], _LOCKSTEP_JITTER)
+        assert int(info1.item()) == 0
+        assert abs(fused[0][b] - float(one)) <= 1e-11 * max(1.0, abs(float(one))), (names[b], fused[0][b], float(one))
+        ref = gp_ref.logpdf(spec, x, y[:, col], noise / w[:, col], eps=_LOCKSTEP_JITTER)
+        assert abs(fused[0][b] - ref) <= 1e-10 * abs(ref), (names[b], fused[0][b], ref)
+        zf = hip.featurize(ck, dx)
+        K = to_dev(np.full((n, n), np.nan))
+        hip.gram(ck, zf, None, out=K, lower=True, diag_add=to_dev(noise / w[:, col]), diag_const=_LOCKSTEP_JITTER)
+        il = np.tril_indices(n)
+        want = ok.gram(spec, x, None, noise_diag=noise / w[:, col], jitter=_LOCKSTEP_JITTER)
+        ratios[names[b]] = _ratio(K.cpu().numpy()[il], want[il], 1e-13, 1e-14)
+        assert np.allclose(K.cpu().numpy()[il], want[il], rtol=1e-13, atol=1e-14), names[b]
+    print(f"[spectral] lock-step build n={n}: Gram error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))

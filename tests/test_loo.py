@@ -184,6 +184,34 @@ def test_first_layer_of_the_model_equals_the_numpy_closed_form_with_weights(engi
     np.testing.assert_allclose(var[:, 0], s_ref, rtol=1e-8, atol=1e-10)
 
 
+def _spectral_first_layer(x):
+    """The first layer's kernel of GPARRegressor(scale=0.5, linear=False, nonlinear=False, spectral=2, spectral_period=(0.7, 0.31),
+    spectral_scale=0.8) at its initial values, in numpy: EQ(0.5) + sum_q 1/2 EQ(0.8) cos(2 pi sum_d (x_d - x'_d) / T_q)."""
+    d = x[:, None, :] - x[None, :, :]
+    K = np.exp(-0.5 * (d**2).sum(-1) / 0.5**2)
+    return K + sum(0.5 * np.exp(-0.5 * (d**2).sum(-1) / 0.8**2) * np.cos(2.0 * np.pi * d.sum(-1) / t) for t in (0.7, 0.31))
+
+
+_SPECTRAL_KW = dict(scale=0.5, linear=False, nonlinear=False, noise=0.05, normalise_y=False, spectral=2, spectral_period=(0.7, 0.31), spectral_scale=0.8)
+
+
+def test_first_layer_of_a_spectral_model_equals_the_closed_form_and_the_brute_force_with_weights(engine):
+    """`test_first_layer_of_the_model_equals_the_numpy_closed_form_with_weights` for a spectral model: the VALUE of loo, its means and
+    variances against the dense restatement (closed form and one deletion per row)."""
+    x, y = _data(30, 1, seed=4)
+    w = np.random.default_rng(4).uniform(0.5, 2.0, y.shape)
+    value, mean, var = GPARRegressor(**_SPECTRAL_KW).loo(x, y, w)
+    K = _spectral_first_layer(x) + np.diag(0.05 / w[:, 0]) + engine.epsilon * np.eye(len(x))
+    v_ref, m_ref, s_ref, _, _ = _closed_form(K, y[:, 0])
+    v_brute, m_brute, s_brute = _brute_force(K, y[:, 0])
+    assert abs(v_ref - v_brute) <= 1e-12 * abs(v_brute)
+    assert abs(float(value) - v_brute) <= 1e-10 * abs(v_brute)
+    np.testing.assert_allclose(mean[:, 0], m_brute, rtol=1e-8, atol=1e-10)
+    np.testing.assert_allclose(var[:, 0], s_brute, rtol=1e-8, atol=1e-10)
+    plain = GPARRegressor(scale=0.5, linear=False, nonlinear=False, noise=0.05, normalise_y=False).loo(x, y, w)[0]
+    assert abs(float(plain) - v_brute) > 1e-3 * abs(v_brute)
+
+
 # ---- gradient ----------------------------------------------------------------------------------------------------------------
 def _fd(f, vector, rel_step=1e-3):
     """Fourth-order central differences, entry by entry (the helper of tests/test_matern_gpu.py)."""
@@ -199,11 +227,12 @@ def _fd(f, vector, rel_step=1e-3):
     return grad
 
 
-@pytest.mark.parametrize("matern", [None, 1.5], ids=["eq", "matern32"])
-def test_autograd_gradient_of_the_loo_value_against_central_differences(engine, matern):
+@pytest.mark.parametrize("matern,spectral", [(None, None), (1.5, None), (None, 2)], ids=["eq", "matern32", "spectral2"])
+def test_autograd_gradient_of_the_loo_value_against_central_differences(engine, matern, spectral):
     x, y = _data(40, 2, seed=5)
     w = np.random.default_rng(5).uniform(0.5, 2.0, y.shape)
-    reg = GPARRegressor(matern=matern, **_KW)
+    # (spectral: two components at periods 0.7 and 0.31 with short envelopes - periods, envelope scales and variances are differentiated)
+    reg = GPARRegressor(matern=matern, **_KW, **({} if spectral is None else dict(spectral=spectral, spectral_period=(0.7, 0.31), spectral_scale=0.8)))
 
     def value():
         return _construct_gpar(reg, reg.vs, 2, 2).loo(x, y, w)[0]
@@ -222,9 +251,12 @@ def test_autograd_gradient_of_the_loo_value_against_central_differences(engine, 
         with torch.no_grad():
             return float(value())
 
-    want = _fd(f, x0)
+    # The stencil's step is relative to the optimiser's variable, ~ -10 for a value of 0.3 between the bounds 1e-4 and 1e4, where
+    # d log(value) / d variable ~ 1: the default 1e-3 moves a period by 1 % and the phase 2 pi |x - x'| / T ~ 20 by h k = 0.2, a truncation
+    # error (h k)^4 / 30 ~ 5e-5 of that component - above the tolerance below.  A tenth of the step: 5e-9; rounding 1e-16 |L| / h ~ 1e-11.
+    want = _fd(f, x0, rel_step=1e-3 if spectral is None else 1e-4)
     reg.vs.set_vector(x0, names)
-    print(f"matern={matern}: {got.size} variables, largest |fd| {np.max(np.abs(want)):.3e}, max error {np.max(np.abs(got - want)):.2e}")
+    print(f"matern={matern} spectral={spectral}: {got.size} variables, largest |fd| {np.max(np.abs(want)):.3e}, max error {np.max(np.abs(got - want)):.2e}")
     assert np.max(np.abs(want)) > 1e-2
     np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6 * np.max(np.abs(want)))
 

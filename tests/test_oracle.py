@@ -472,3 +472,262 @@ def test_matern_config_is_not_silently_evaluated_as_eq(name, oracle_engine):
     assert abs(got - ref) <= 1e-9 * abs(ref), (got, ref)
     as_eq = gpar_ref.gpar_logpdf(x, y, w, case["hypers"], {k: v for k, v in reg.model_config.items() if k != "matern"}, **kw)
     assert abs(as_eq - ref) > 1e-3 * abs(ref), (as_eq, ref)
+
+
+# ---- the cosine factor (include/gpar_hip.h: GPAR_K_COS) and the spectral mixture of GPARRegressor(spectral=Q) -----------------------
+
+def test_cosine_closed_forms_and_argument_errors():
+    """cos(2 pi sigma) of the SUM of the scaled differences; 1 on the diagonal exactly; the phase survives large time stamps (2 sigma is
+    reduced before pi enters); periods, or no features, are refused everywhere."""
+    from oracle import mp_ref
+
+    x = np.array([[0.0, 1.0], [3.0, 5.0]])
+    cos = {"terms": [{"coef": 2.0, "factors": [_f("cos", [0, 1], [4.0, 16.0])]}]}
+    # sigma = -3/4 - 4/16 = -1: a whole period;  with scales (4, 8): sigma = -5/4, a quarter period: exactly 0
+    np.testing.assert_array_equal(ok.gram(cos, x), [[2.0, 2.0], [2.0, 2.0]])
+    quarter = {"terms": [{"coef": 2.0, "factors": [_f("cos", [0, 1], [4.0, 8.0])]}]}
+    # (the zero is that of cos(pi / 2) with pi rounded to long double: 1e-19, or 1e-16 where long double is float64)
+    np.testing.assert_allclose(ok.gram(quarter, x), [[2.0, 0.0], [0.0, 2.0]], rtol=0, atol=2.5e-16)
+    np.testing.assert_array_equal(ok.gram_diag(cos, x), [2.0, 2.0])
+    eighth = {"terms": [{"coef": 1.0, "factors": [_f("cos", [0], [24.0])]}]}
+    np.testing.assert_allclose(ok.gram(eighth, x)[0, 1], np.sqrt(0.5), rtol=1e-15)
+    # a Linear factor beside it keeps |z|^2 on the diagonal
+    lin = {"terms": [{"coef": 0.5, "factors": [_f("cos", [0], [0.3]), _f("linear", [1], [2.0])]}]}
+    np.testing.assert_allclose(ok.gram_diag(lin, x), [0.5 * 0.25, 0.5 * 6.25], rtol=1e-15)
+    np.testing.assert_allclose(np.diag(ok.gram(lin, x)), ok.gram_diag(lin, x), rtol=1e-15)
+    # time stamps of 2^40 + quarters over the period 1: float64 holds them exactly, and so must the phase be
+    t = np.array([[2.0 ** 40], [2.0 ** 40 + 0.25], [2.0 ** 40 + 0.5]])
+    unit = {"terms": [{"coef": 1.0, "factors": [_f("cos", [0], [1.0])]}]}
+    np.testing.assert_allclose(ok.gram(unit, t), [[1.0, 0.0, -1.0], [0.0, 1.0, 0.0], [-1.0, 0.0, 1.0]], rtol=0, atol=1.3e-16)
+    # against 50 digits at a large argument, where cos(2 * pi * sigma) in float64 is off by 2 pi |sigma| 2^-52 ~ 1e-10
+    big = np.array([[123456.789], [0.123]])
+    third = {"terms": [{"coef": 1.0, "factors": [_f("cos", [0], [0.37])]}]}
+    exact = float(mp_ref.gram(third, big.tolist())[0, 1])
+    z = big[:, 0] * (1.0 / 0.37)        # (the features as both compute them: x times the rounded reciprocal)
+    import mpmath as mp
+
+    exact_of_rounded = float(mp.cos(2 * mp.pi * (mp.mpf(float(z[0])) - mp.mpf(float(z[1])))))
+    assert abs(ok.gram(third, big)[0, 1] - exact_of_rounded) < 1e-15 + 2 * np.pi * abs(z[0]) * 2.0 ** -53 * 1.01   # one rounding of sigma
+    assert abs(exact - exact_of_rounded) < 1e-9   # (what dividing by the scale in 50 digits instead changes: not the oracle's error)
+    for bad in ({"terms": [{"coef": 1.0, "factors": [_f("cos", [0], [0.7, 1.3], periods=[2.0])]}]},
+                {"terms": [{"coef": 1.0, "factors": [_f("cos", [], [])]}]}):
+        W = np.ones((2, 2))
+        for call in (lambda: ok.gram(bad, x), lambda: ok.gram_diag(bad, x), lambda: ok.kernel_grads(bad, x, W),
+                     lambda: ok.kernel_input_grads(bad, x, x, W), lambda: mp_ref.gram(bad, x.tolist())):
+            with pytest.raises(ValueError, match="cosine factor"):
+                call()
+
+
+def test_cosine_equals_linear_on_the_periodic_embedding():
+    """cos(2 pi (x - y) / T) = <phi(x), phi(y)>, phi = [sin(2 pi x / T), cos(2 pi x / T)]: Cosine().stretch(T) is Linear().periodic(T)
+    with unit scales - what the oracle already had.  Pins the sign, the factor of two and the reading of the scale as a period.
+
+    Tolerance: the embedding rounds each row angle a = 2 pi x / T (the product 2 pi / T, then times x: 2 roundings, then the argument
+    reduction of sin / cos inside libm is exact to the rounded a) - an absolute phase error of at most 2 * 2^-53 |a| per row, two rows
+    per entry, |a| <= 2 pi 8 / T - and four roundings of values of size <= 1 in forming the inner product, 4 * 2^-53; the cosine
+    side's own error (one rounding of x / T and of the difference, the evaluation) is below 2 pi * 2 * 2^-53 * 8 / T + 2^-52.  With a
+    factor 2 of slack on the sum."""
+    rng = np.random.default_rng(11)
+    x = rng.uniform(0.0, 8.0, (40, 1))
+
+    def bound(T):
+        amax = 2 * np.pi * 8.0 / T
+        return 2 * (2 * (2 * 2.0 ** -53 * amax) + 4 * 2.0 ** -53 + 2 * np.pi * 2 * 2.0 ** -53 * 8.0 / T + 2.0 ** -52)
+
+    assert bound(0.31) < 2.5e-13 and bound(2.7) < 3e-14
+    for T in (0.31, 1.0, 2.7):
+        cos = {"terms": [{"coef": 1.0, "factors": [_f("cos", [0], [T])]}]}
+        lin = {"terms": [{"coef": 1.0, "factors": [_f("linear", [0], [1.0, 1.0], periods=[T])]}]}
+        tol = bound(T)
+        np.testing.assert_allclose(ok.gram(cos, x), ok.gram(lin, x), rtol=0, atol=tol)
+        y = rng.uniform(0.0, 8.0, (7, 1))
+        np.testing.assert_allclose(ok.gram(cos, x, y), ok.gram(lin, x, y), rtol=0, atol=tol)
+        got = ok.gram(cos, x)
+        assert np.array_equal(got, got.T) and np.all(np.diag(got) == 1.0)
+    # and through the product's own classes: what `spec_to_dict` makes of Cosine().stretch(T)
+    from gpar_amd.kernels import Cosine, Linear
+
+    a = ok.spec_to_dict(Cosine().stretch(np.array([0.8])).resolve(1))
+    b = ok.spec_to_dict(Linear().periodic(np.array([0.8])).resolve(1))
+    assert [f["type"] for f in a["terms"][0]["factors"]] == ["cos"] and b["terms"][0]["factors"][0]["scales"] == [1.0, 1.0]
+    np.testing.assert_allclose(ok.gram(a, x), ok.gram(b, x), rtol=0, atol=bound(0.8))
+
+
+def test_pure_cosine_gram_is_positive_semidefinite_of_rank_two():
+    rng = np.random.default_rng(12)
+    n = 40
+    x = rng.uniform(0.0, 8.0, (n, 2))
+    for scales in ([0.7, 1.9], [0.31, 0.31]):
+        K = ok.gram({"terms": [{"coef": 1.0, "factors": [_f("cos", [0, 1], scales)]}]}, x)
+        ev = np.linalg.eigvalsh(K)
+        assert ev[0] >= -1e-12 * n, ev[0]
+        assert np.sum(ev > 1e-10 * n) <= 2, ev[-4:]
+        assert abs(np.sum(ev) - n) < 1e-10 * n
+
+
+def _cosine_structures():
+    per = _f("eq", [0], [0.9, 1.4], periods=[0.8])
+    return {
+        "cos-nd1": [{"coef": 1.3, "factors": [_f("cos", [1], [0.6])]}],
+        "cos-nd2": [{"coef": 1.3, "factors": [_f("cos", [0, 2], [0.6, 1.7])]}],
+        "cos-nd3": [{"coef": 0.7, "factors": [_f("cos", [0, 1, 2], [0.9, 0.5, 2.3])]}],
+        "eq-x-cos": [{"coef": 0.8, "factors": [_f("eq", [0, 1], [0.7, 1.1]), _f("cos", [0, 1], [0.45, 1.3])]}],
+        "matern32-x-cos": [{"coef": 1.1, "factors": [_f("matern32", [0, 1], [0.7, 1.1]), _f("cos", [0], [0.45])]}],
+        "rq-x-cos": [{"coef": 0.5, "factors": [_f("rq", [1, 2], [0.7, 1.1], alpha=0.8), _f("cos", [0, 1], [0.45, 0.9])]}],
+        "linear-x-cos": [{"coef": 0.9, "factors": [_f("linear", [1, 2], [1.5, 2.5]), _f("cos", [0], [0.45])]}],
+        "cos-beside-locally-periodic": [{"coef": 0.6, "factors": [_f("eq", [0, 1], [2.0, 2.5]), _f("cos", [0, 1], [0.5, 0.7])]},
+                                        {"coef": 1.2, "factors": [per, _f("eq", [0], [3.0])]}],
+    }
+
+
+@pytest.mark.parametrize("name", list(_cosine_structures()))
+def test_cosine_kernel_gradients_match_central_differences(name):
+    """`kernel_grads` (coefficients, scales - and the neighbours' periods and alphas, whose `rest` products now hold a cosine) and
+    `kernel_input_grads`, rectangular and symmetric, against central differences of `gram`.  The cosine has no kink: the stencil needs
+    no distance condition.  Fourth-order stencil, h = 1e-3 relative: truncation ~ h^4 (2 pi / T)^5 / 30 < 1e-7 relative at T >= 0.45
+    on inputs in [-1, 1], rounding 1e-16 / h = 1e-13."""
+    import copy
+
+    rng = np.random.default_rng(19)
+    spec = {"terms": _cosine_structures()[name]}
+    n = 9
+    x = rng.uniform(-1, 1, (n, 3))
+    W = rng.standard_normal((n, n))
+    W = W + W.T
+    grads = ok.kernel_grads(spec, x, W)
+
+    def fd(fn, h):
+        return (-fn(2 * h) + 8 * fn(h) - 8 * fn(-h) + fn(-2 * h)) / (12 * h)
+
+    def value_at(ti, fi, key, idx):
+        def fn(delta):
+            s = copy.deepcopy(spec)
+            if fi is None:
+                s["terms"][ti]["coef"] += delta
+            elif idx is None:
+                s["terms"][ti]["factors"][fi][key] += delta
+            else:
+                s["terms"][ti]["factors"][fi][key][idx] += delta
+            return 0.5 * np.sum(W * ok.gram(s, x))
+        return fn
+
+    checked = 0
+    for ti, term in enumerate(spec["terms"]):
+        want = fd(value_at(ti, None, "coef", None), 1e-3)
+        assert abs(want - grads["coef"][ti]) < 1e-7 * (1 + abs(want)), (ti, want, grads["coef"][ti])
+        for fi, f in enumerate(term["factors"]):
+            g = grads["factors"][ti][fi]
+            if f["type"] == "cos":
+                assert g["periods"] is None and g["alpha"] is None
+            for q, s_q in enumerate(f["scales"]):
+                want = fd(value_at(ti, fi, "scales", q), 1e-3 * s_q)
+                assert abs(want - g["scales"][q]) < 2e-6 * (1 + abs(want)), (ti, fi, q, want, g["scales"][q])
+                checked += 1
+            if f["periods"] is not None:
+                want = fd(value_at(ti, fi, "periods", 0), 1e-3 * f["periods"][0])
+                assert abs(want - g["periods"][0]) < 2e-6 * (1 + abs(want))
+            if f["type"] == "rq":
+                want = fd(value_at(ti, fi, "alpha", None), 1e-3)
+                assert abs(want - g["alpha"]) < 1e-7 * (1 + abs(want))
+    assert checked >= 1
+    # inputs: rectangular, and symmetric as the engine forms it (twice the row sums with the symmetric weights)
+    x2 = rng.uniform(-1, 1, (5, 3))
+    V = rng.standard_normal((n, 5))
+    got = ok.kernel_input_grads(spec, x, x2, V)
+    got_sym = 2.0 * ok.kernel_input_grads(spec, x, x, W)
+    want, want_sym = np.zeros_like(x), np.zeros_like(x)
+    for a in range(n):
+        for c in range(3):
+            def moved(delta):
+                xp = x.copy()
+                xp[a, c] += delta
+                return xp
+            want[a, c] = fd(lambda d: np.sum(V * ok.gram(spec, moved(d), x2)), 1e-3)
+            want_sym[a, c] = fd(lambda d: np.sum(W * ok.gram(spec, moved(d))), 1e-3)
+    big = max(np.max(np.abs(want)), 1.0)
+    np.testing.assert_allclose(got, want, rtol=0, atol=2e-6 * big)
+    np.testing.assert_allclose(got_sym, want_sym, rtol=0, atol=2e-6 * max(np.max(np.abs(want_sym)), 1.0))
+    used = sorted({c for t in spec["terms"] for f in t["factors"] for c in f["cols"]})
+    assert all(np.any(got[:, c] != 0.0) for c in used)
+
+
+def _spectral_hypers(m, p, config, rng):
+    import importlib.util
+
+    s = importlib.util.spec_from_file_location("make_golden", os.path.join(os.path.dirname(GOLDEN), "make_golden.py"))
+    mod = importlib.util.module_from_spec(s)
+    s.loader.exec_module(mod)
+    return mod.hypers_for(m, p, config, rng)
+
+
+def test_layer_spec_follows_the_regressor_for_spectral():
+    """config["spectral"] = Q adds var * EQ(scales) * cos(pers) per component over the input columns, after the locally periodic term;
+    the envelope stays EQ under `matern` / `rq`, `scale_tie` does not tie these - and the variables are those the regressor creates."""
+    from gpar_amd.engine import set_engine
+    from gpar_amd.regression import GPARRegressor
+
+    rng = np.random.default_rng(6)
+    base = dict(linear=True, nonlinear=True, per=True, input_linear=True)
+    for extra, kind in ((dict(), "eq"), (dict(matern=1.5), "matern32"), (dict(rq=True), "rq"), (dict(scale_tie=True), "eq")):
+        cfg = dict(base, spectral=2, **extra)
+        hypers = _spectral_hypers(2, 2, cfg, rng)
+        spec, _ = gpar_ref.layer_spec(hypers, 2, 1, cfg)
+        assert [[f["type"] for f in t["factors"]] for t in spec["terms"]] == [[kind], ["eq", "eq"], ["eq", "cos"], ["eq", "cos"], ["linear"], [],
+                                                                              ["linear"], [kind]]
+        for q in (0, 1):
+            term = spec["terms"][2 + q]
+            assert term["coef"] == hypers[f"1/input/sm{q}/var"] and [f["cols"] for f in term["factors"]] == [[0, 1], [0, 1]]
+            assert term["factors"][0]["scales"] == hypers[f"1/input/sm{q}/scales"] and term["factors"][1]["scales"] == hypers[f"1/input/sm{q}/pers"]
+            assert term["factors"][1]["periods"] is None
+    previous = set_engine(OracleEngine())
+    try:
+        x, y = rng.uniform(0, 1, (12, 2)), rng.standard_normal((12, 2))
+        reg = GPARRegressor(normalise_y=False, spectral=2, spectral_period=(0.7, 0.31), spectral_scale=0.8, **base)
+        got = float(reg.logpdf(x, y))
+        variables = reg.get_variables()
+        assert {k for k in variables if "/sm" in k} == {f"{pi}/input/sm{q}/{v}" for pi in (0, 1) for q in (0, 1) for v in ("var", "scales", "pers")}
+        np.testing.assert_allclose(variables["1/input/sm1/pers"], [0.31, 0.31])
+        np.testing.assert_allclose(variables["0/input/sm0/scales"], [0.8, 0.8])
+        want = gpar_ref.gpar_logpdf(x, y, None, variables, reg.model_config)
+        assert abs(got - want) <= 1e-10 * abs(want)
+    finally:
+        set_engine(previous)
+    for bad in (0, True, 1.5, "2"):
+        with pytest.raises((ValueError, TypeError)):
+            gpar_ref.layer_spec(_spectral_hypers(1, 1, dict(linear=False, spectral=1), rng), 1, 0, dict(linear=False, spectral=bad))
+
+
+@pytest.mark.parametrize("name", ["spectral2-missing-weights", "spectral2-inducing"])
+def test_spectral_config_on_the_engine_equals_the_restatement(name, oracle_engine):
+    """The stand-alone numpy GPAR handed the `model_config` of a spectral regressor equals the product's host algebra on the oracle
+    engine - missing data, weights, `impute`, inducing points - and differs far beyond rounding from the same call without `spectral`."""
+    case = next(c for c in _load_golden()["gpar_logpdf"] if c["name"] == name)
+    x, y = np.array(case["x"]), _nan_array(case["y"])
+    w = None if case["w"] is None else np.array(case["w"])
+    x_ind = None if case.get("x_ind") is None else np.array(case["x_ind"])
+    reg = regressor_from_case(case)
+    assert reg.model_config["spectral"] == case["config"]["spectral"] == 2 and np.isnan(y).any() and case["impute"]
+    kw = dict(impute=case["impute"], replace=case["replace"], x_ind=x_ind)
+    ref = gpar_ref.gpar_logpdf(x, y, w, case["hypers"], reg.model_config, **kw)
+    got = float(reg.logpdf(x, y, w))
+    assert abs(got - ref) <= 1e-9 * abs(ref), (got, ref)
+    assert abs(ref - case["logpdf"]) <= 1e-12 * abs(ref)
+    without = gpar_ref.gpar_logpdf(x, y, w, case["hypers"], {k: v for k, v in reg.model_config.items() if not k.startswith("spectral")}, **kw)
+    assert abs(without - ref) > 1e-3 * abs(ref), (without, ref)
+
+
+def test_spectral_regressor_runs_every_entry_point_on_the_oracle_engine(oracle_engine):
+    """GPARRegressor(spectral=2) through logpdf, condition, predict, loo, cv and ahead on the numpy engine, where the oracle raised
+    `unknown factor type 'cos'` before it knew the factor."""
+    from gpar_amd.regression import GPARRegressor
+
+    rng = np.random.default_rng(21)
+    x = np.linspace(0, 1, 30)[:, None]
+    y = np.stack([np.sin(2 * np.pi * x[:, 0] / 0.5), np.cos(2 * np.pi * x[:, 0] / 0.31)], axis=1) + 0.05 * rng.standard_normal((30, 2))
+    reg = GPARRegressor(spectral=2, spectral_period=(0.5, 0.31), spectral_scale=0.8, replace=True, noise=0.05, normalise_y=False)
+    values = [float(reg.logpdf(x, y)), float(reg.loo(x, y)[0]), float(reg.cv(x, y, folds=3)[0]), float(reg.ahead(x, y)[0])]
+    assert np.all(np.isfinite(values)), values
+    reg.condition(x, y)
+    mean = reg.predict(np.linspace(0, 1, 7)[:, None], num_samples=3)
+    assert np.all(np.isfinite(np.asarray(mean))) and np.asarray(mean).shape == (7, 2)
+    assert np.isfinite(float(reg.logpdf(x, y, posterior=True)))

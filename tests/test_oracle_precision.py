@@ -86,3 +86,68 @@ def test_expanded_versus_explicit_squared_distances(oracle_engine, n, m, p_cols,
     expanded, _, _ = tc.layer_logpdf(spec, torch.as_tensor(x), y, np.full(n, noise))
     rel = abs(expanded - explicit) / abs(explicit)
     assert rel < 1e-10, (explicit, expanded, rel)
+
+
+def _spectral_layer(m, rng):
+    """The regressor's Q = 2 layer kernel over m inputs (EQ + 2 x (EQ x cos)), random hyper-parameters."""
+    from .test_oracle import _spectral_hypers
+
+    config = dict(linear=False, spectral=2)
+    return gpar_ref.layer_spec(_spectral_hypers(m, 1, config, rng), m, 0, config)[0]
+
+
+def test_spectral_structure_against_50_digits():
+    """`gram`, `logpdf`, `posterior` and `vfe_bound` of the fp64 oracle for the spectral structure with Q = 2, against oracle/mp_ref.py
+    at n <= 30, at the bounds this file applies to every other kernel: 5e-13 relative dense, 1e-12 of the scale for the moments, 5e-9
+    with inducing points (K_zz + 1e-12 I)."""
+    from oracle import gp_ref
+    from oracle import kernels as ok
+
+    rng = np.random.default_rng(20261020)
+    rows = lambda a: [[float(v) for v in r] for r in a]
+    n, m = 24, 2
+    spec = _spectral_layer(m, rng)
+    assert [[f["type"] for f in t["factors"]] for t in spec["terms"]] == [["eq"], ["eq", "cos"], ["eq", "cos"]]
+    x, xs = rng.uniform(-1.5, 1.5, (n, m)), rng.uniform(-1.5, 1.5, (6, m))
+    y, noise = rng.standard_normal(n), rng.uniform(0.05, 0.2, n)
+    K = mp_ref.gram(spec, rows(x), rows(xs))
+    K = np.array([[float(K[i, j]) for j in range(K.cols)] for i in range(K.rows)])
+    # entries: each factor's feature z = x * (1 / s) carries 2 roundings (2^-52 |z|), the phase 2 pi sigma hence 2 pi m 2^-52 max|z| - at
+    # scales >= 0.4 and |x| <= 1.5 below 4e-14 - and the envelope's r2 as much again; terms of size <= var <= 2
+    np.testing.assert_allclose(ok.gram(spec, x, xs), K, rtol=0, atol=2e-13)
+    exact = mp_ref.logpdf(spec, rows(x), y, noise)
+    got = gp_ref.logpdf(spec, x, y, noise)
+    assert abs(float((exact - got) / exact)) < 5e-13, (float(exact), got)
+    mean, cov = mp_ref.posterior(spec, rows(x), y, noise, rows(xs))
+    mean = np.array([float(v) for v in mean])
+    cov = np.array([[float(cov[i, j]) for j in range(cov.cols)] for i in range(cov.rows)])
+    got_mean, got_cov = gp_ref.posterior(spec, x, y, noise, xs)
+    np.testing.assert_allclose(got_mean, mean, rtol=0, atol=1e-12 * max(1.0, np.max(np.abs(mean))))
+    np.testing.assert_allclose(got_cov, cov, rtol=0, atol=1e-12 * np.max(np.abs(cov)))
+    # inducing points, one input
+    n, m = 30, 1
+    spec = _spectral_layer(m, rng)
+    x, z = rng.uniform(-2, 2, (n, m)), np.linspace(-2, 2, 9)[:, None]
+    y, noise = np.sin(2 * x[:, 0]) + 0.1 * rng.standard_normal(n), rng.uniform(0.05, 0.1, n)
+    exact = mp_ref.vfe_bound(spec, rows(x), y, noise, rows(z))
+    got = gp_ref.vfe_bound(spec, x, y, noise, z)
+    assert abs(float((exact - got) / exact)) < 5e-9, (float(exact), got)
+
+
+def test_spectral_gpar_logpdf_against_50_digits():
+    """`gpar_ref.gpar_logpdf` with spectral=2 - missing data, weights, impute - against `mp_ref.gpar_logpdf`, at the bound of the
+    golden cases above."""
+    from .test_oracle import _spectral_hypers
+
+    rng = np.random.default_rng(20261021)
+    n, m, p = 18, 1, 3
+    config = dict(linear=True, nonlinear=True, spectral=2)
+    x = rng.uniform(-1.5, 1.5, (n, m))
+    y = rng.standard_normal((n, p))
+    y[rng.random((n, p)) < 0.2] = np.nan
+    y[0] = rng.standard_normal(p)
+    w = rng.random((n, p)) + 0.5
+    hypers = _spectral_hypers(m, p, config, rng)
+    got = gpar_ref.gpar_logpdf(x, y, w, hypers, config, impute=True, replace=False)
+    exact = mp_ref.gpar_logpdf(x, y, w, hypers, config, impute=True, replace=False)
+    assert abs(float((exact - got) / exact)) < 5e-13, (float(exact), got)

@@ -116,13 +116,23 @@ CONFIGS = {
     "matern32-markov2": (dict(scale=0.5, linear=True, nonlinear=True, markov=2, noise=0.1, matern=1.5), 300, 3, 6, 0.0),
     "matern52-inducing": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, matern=2.5, x_ind=np.random.default_rng(9).uniform(0, 1, (48, 4))), 400, 4, 3, 0.0),
     "matern12-missing-impute": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, impute=True, matern=0.5), 257, 2, 3, 0.2),
+    # the spectral mixture (`spectral=Q`, the cosine factor): the same four regimes; Q = 3 with `linear` and `nonlinear` only (6 of the
+    # device's 8 terms); Q = 4 over one input without the linear term - the structure whose Gram build is slower than its count predicts
+    "spectral2-markov2": (dict(scale=0.5, linear=True, nonlinear=True, markov=2, noise=0.1, spectral=2, spectral_period=(0.7, 0.31), spectral_scale=0.8), 300, 3, 6, 0.0),
+    "spectral3-inducing": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, spectral=3, x_ind=np.random.default_rng(9).uniform(0, 1, (48, 4))), 400, 4, 3, 0.0),
+    # (one input: length scales of 0.05 and periods from 0.2 down keep the posterior covariance of the 40 sampled points away from
+    # singular - smallest eigenvalue 4e-6 on the reference, against -4e-15 at scales of 0.5, where a latent sample is determined to the
+    # root of the jitter only, as the C1 case's comment below says; noise 0.2: the value stays away from a zero crossing of the sum)
+    "spectral4-m1": (dict(scale=0.05, linear=False, nonlinear=True, noise=0.2, spectral=4, spectral_period=0.2, spectral_scale=0.05), 300, 1, 3, 0.0),
+    "spectral2-missing-impute": (dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, impute=True, spectral=2, spectral_period=0.5), 257, 2, 3, 0.2),
 }
 
 
 def _report(label, name, **ratios):
-    """The error / tolerance ratios of the Matern cases (pytest -s shows them)."""
-    if "matern" in str(name):
-        print(f"[matern] {label} {name}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
+    """The error / tolerance ratios of the Matern and the spectral cases (pytest -s shows them)."""
+    for block in ("matern", "spectral"):
+        if block in str(name):
+            print(f"[{block}] {label} {name}: error / tolerance = " + ", ".join(f"{k} {v:.3g}" for k, v in ratios.items()))
 
 
 @pytest.mark.parametrize("name", list(CONFIGS))
@@ -172,8 +182,32 @@ def test_logpdf_matches_the_independent_oracle_route(name, hip):
                                 x_ind=kw.get("x_ind"))
     tol = 1e-10 if kw.get("x_ind") is None else 1e-8  # inducing-point chains go through K_zz^-1 (jitter-conditioned)
     _report("independent restatement", name, prior=abs(got - want) / (tol * abs(want)))
-    assert reg.model_config.get("matern") == kw.get("matern")
+    assert reg.model_config.get("matern") == kw.get("matern") and reg.model_config.get("spectral") == kw.get("spectral")
     assert abs(got - want) <= tol * abs(want), (got, want)
+
+
+def test_spectral4_log_density_at_the_default_scales(hip):
+    """The Q = 4, one-input structure of "spectral4-m1" once more with the regressor's default length scales (envelopes of 10, periods
+    1, 1/2, 1/3, 1/4 over inputs in [0, 1]): every entry of the Gram matrix carries its cosines, far from the diagonal too, where the
+    CONFIGS row's envelopes of 0.05 have vanished.  Log-density only (no samples: their covariance is singular at these scales), against
+    the numpy engine and the independent restatement at the tolerance of the tests above; noise 0.2 as in the CONFIGS row."""
+    from gpar_amd.regression import GPARRegressor
+    from oracle import gpar_ref
+
+    x, y = _problem(300, 1, 3, seed=12)
+    kw = dict(linear=False, nonlinear=True, noise=0.2, spectral=4, normalise_y=False)
+
+    def run():
+        reg = GPARRegressor(**kw)
+        return float(reg.logpdf(x, y)), reg.get_variables(), reg.model_config
+
+    got, hypers, config = run()
+    ref = _on("oracle", run)[0]
+    want = gpar_ref.gpar_logpdf(x, y, None, hypers, config, impute=True, replace=False)
+    assert config["spectral"] == 4 and np.ndim(hypers["0/input/sm3/pers"]) == 1 and abs(float(hypers["0/input/sm3/pers"][0]) - 0.25) < 1e-12
+    _report("default scales", "spectral4-m1", engine=abs(got - ref) / (1e-10 * abs(ref)), restatement=abs(got - want) / (1e-10 * abs(want)))
+    assert abs(got - ref) <= 1e-10 * abs(ref), (got, ref)
+    assert abs(got - want) <= 1e-10 * abs(want), (got, want)
 
 
 @pytest.mark.parametrize("kw", [
@@ -184,7 +218,10 @@ def test_logpdf_matches_the_independent_oracle_route(name, hip):
     dict(impute=True, matern=1.5),
     dict(impute=True, replace=True, matern=0.5),
     dict(impute=True, x_ind=np.random.default_rng(4).uniform(0, 1, (40, 2)), matern=2.5),
-], ids=["impute", "no-impute", "replace", "inducing", "matern32-impute", "matern12-replace", "matern52-inducing"])
+    dict(impute=True, spectral=2, spectral_period=(0.7, 0.31)),
+    dict(impute=True, x_ind=np.random.default_rng(4).uniform(0, 1, (40, 2)), spectral=2, spectral_scale=0.8),
+], ids=["impute", "no-impute", "replace", "inducing", "matern32-impute", "matern12-replace", "matern52-inducing", "spectral2-impute",
+        "spectral2-inducing"])
 def test_sampled_imputations_match_the_oracle_on_a_shared_stream(kw):
     """`logpdf(sample_missing=True)` (reference gpar/model.py:229-237) with holes that are NOT closed downwards, n = 300, p = 4:
     the device draws its imputations from Philox stream (seed, call index), which the oracle restates bit for bit - same seed,
@@ -207,9 +244,10 @@ def test_sampled_imputations_match_the_oracle_on_a_shared_stream(kw):
     independent = gpar_ref.gpar_logpdf(x, y, None, hypers, config, impute=kw.get("impute", True), replace=kw.get("replace", False),
                                        x_ind=kw.get("x_ind"), sample_missing=True, seed=41)
     tol = 1e-8 if kw.get("x_ind") is None else 1e-7
-    _report("sampled imputations", "matern" if "matern" in kw else "", nu=kw.get("matern", 0.0), engine=abs(got - ref) / (tol * abs(ref)),
+    _report("sampled imputations", "matern" if "matern" in kw else "spectral" if "spectral" in kw else "", nu=kw.get("matern", 0.0),
+            inducing=float("x_ind" in kw), engine=abs(got - ref) / (tol * abs(ref)),
             restatement=abs(got - independent) / ((tol if kw.get("x_ind") is None else 1e-5) * abs(independent)))
-    assert config.get("matern") == kw.get("matern")
+    assert config.get("matern") == kw.get("matern") and config.get("spectral") == kw.get("spectral")
     assert abs(got - ref) <= tol * abs(ref), (got, ref)
     # (inducing points: the independent route solves against K_zz + 1e-12 I directly, the product through its Cholesky factor -
     # with 40 random inducing inputs at scale 0.5 that matrix is conditioned ~1e9, and the drawn imputations inherit the difference)
@@ -334,11 +372,13 @@ def test_linear_output_dependence_samples_with_one_shared_solve(monkeypatch, kw,
 
 _LOCKSTEP_ONE_CALL = [(700, 4, False, None), (512, 3, True, None), (1300, 5, True, None), (40, 70, True, None), (2100, 2, False, None),
                       (512, 3, True, 1.5), (1300, 4, False, 2.5), (40, 70, True, 0.5), (300, 5, True, 0.5)]
+_LOCKSTEP_ONE_CALL = [row + (None,) for row in _LOCKSTEP_ONE_CALL] + [(512, 3, True, None, 2), (300, 5, True, None, 1)]   # (.., spectral)
 
 
-@pytest.mark.parametrize("n,p,weights,matern", _LOCKSTEP_ONE_CALL,
-                         ids=[f"{n}-{p}-{w}" + ("" if nu is None else f"-matern{nu}") for n, p, w, nu in _LOCKSTEP_ONE_CALL])
-def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, weights, matern):
+@pytest.mark.parametrize("n,p,weights,matern,spectral", _LOCKSTEP_ONE_CALL,
+                         ids=[f"{n}-{p}-{w}" + ("" if nu is None else f"-matern{nu}") + ("" if q is None else f"-spectral{q}")
+                              for n, p, w, nu, q in _LOCKSTEP_ONE_CALL])
+def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, weights, matern, spectral):
     """gpar_logpdf_lockstep (ABI v5): the whole lock-step evaluation in one library call - no design matrix, noise tensor or
     observation object per layer - returns bit for bit what the per-layer build calls return (GPAR_ONE_CALL=0), with weights
     (noise / w divided on the device), with more layers than one launch of the preparing kernel takes (70 > 64), in chunks,
@@ -353,9 +393,11 @@ def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, w
         y = np.concatenate([y] * (p // y.shape[1] + 1), axis=1)[:, :p] + 0.01 * np.random.default_rng(0).standard_normal((n, p))
     w = np.random.default_rng(1).uniform(0.5, 2.0, y.shape) if weights else None
 
+    sp = {} if spectral is None else dict(spectral=spectral, spectral_period=0.7, spectral_scale=0.8)
+
     def run():
         eng = get_engine()
-        kw = dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3 if p > 6 else None, normalise_y=False, matern=matern)
+        kw = dict(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3 if p > 6 else None, normalise_y=False, matern=matern, **sp)
         out = {}
         for mode in ["1", "0"]:
             monkeypatch.setenv("GPAR_ONE_CALL", mode)
@@ -374,8 +416,9 @@ def test_one_call_lockstep_evaluation_returns_the_same_bits(monkeypatch, n, p, w
     assert got["1"] == got["0"] and got["1last"] == got["0last"] and got["1chunks"] == got["0chunks"], got
     if n <= 600:
         ref = _on("oracle", lambda: float(GPARRegressor(scale=0.5, linear=True, nonlinear=True, noise=0.1, markov=3 if p > 6 else None,
-                                                        normalise_y=False, matern=matern).logpdf(x, y, w)))
-        _report("one-call lock-step", f"matern{matern}" if matern else "", n=n, p=p, value=abs(got["1"] - ref) / (1e-9 * abs(ref)))
+                                                        normalise_y=False, matern=matern, **sp).logpdf(x, y, w)))
+        _report("one-call lock-step", f"matern{matern}" if matern else f"spectral{spectral}" if spectral else "", n=n, p=p,
+                value=abs(got["1"] - ref) / (1e-9 * abs(ref)))
         assert abs(got["1"] - ref) <= 1e-9 * abs(ref), (got, ref)
 
 
@@ -657,8 +700,12 @@ def test_gradient_matches_oracle(hip):
     dict(impute=True, replace=True, matern=0.5),
     dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), sparse_method="fitc", matern=2.5),
     dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), sparse_method="dtc", matern=0.5),
+    dict(impute=True, replace=True, spectral=2, spectral_period=(0.7, 0.31), spectral_scale=0.8),
+    dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), spectral=2, spectral_period=0.5),
+    dict(impute=True, replace=True, x_ind=np.linspace(0, 1, 24), sparse_method="fitc", spectral=1, spectral_period=0.31, spectral_scale=0.8),
 ], ids=["impute+replace+inducing", "impute+replace", "impute+replace+fitc", "matern32+impute+replace+inducing", "matern12+impute+replace",
-        "matern52+impute+replace+fitc", "matern12+impute+replace+dtc"])
+        "matern52+impute+replace+fitc", "matern12+impute+replace+dtc", "spectral2+impute+replace", "spectral2+impute+replace+vfe",
+        "spectral1+impute+replace+fitc"])
 def test_joint_gradient_matches_oracle(hip, kw):
     """The JOINT objective of fit(fix=False) (reference gpar/regression.py:447-456) in regimes where posterior means are fed
     forward - imputed AND replaced columns, inducing inputs extended layer by layer: d / d(every hyper-parameter) through
@@ -683,7 +730,8 @@ def test_joint_gradient_matches_oracle(hip, kw):
 
     ref, got = _on("oracle", grads), _on("hip", grads)
     assert np.max(np.abs(ref)) > 1e-2
-    _report("joint gradient", "matern" if "matern" in kw else "", nu=kw.get("matern", 0.0),
+    _report("joint gradient", "matern" if "matern" in kw else f"spectral{kw['spectral']}-{kw.get('sparse_method', 'vfe') if 'x_ind' in kw else 'dense'}"
+            if "spectral" in kw else "", nu=kw.get("matern", 0.0),
             gradient=float(np.max(np.abs(got - ref) / (1e-7 * np.max(np.abs(ref)) + 1e-6 * np.abs(ref)))))
     np.testing.assert_allclose(got, ref, rtol=1e-6, atol=1e-7 * np.max(np.abs(ref)))
 
@@ -909,7 +957,8 @@ def test_nan_pattern_of_device_outputs_is_remembered_until_they_change(hip):
 @pytest.mark.parametrize("kw,n", [(dict(linear=True, nonlinear=True), 500), (dict(per=True, rq=True, linear=True, nonlinear=True), 300),
                                   (dict(linear=True, nonlinear=False, input_linear=True), 1300),
                                   (dict(linear=True, nonlinear=True, matern=0.5), 500), (dict(per=True, linear=True, nonlinear=True, matern=2.5), 300),
-                                  (dict(linear=True, nonlinear=True, input_linear=True, matern=1.5), 1300)])
+                                  (dict(linear=True, nonlinear=True, input_linear=True, matern=1.5), 1300),
+                                  (dict(linear=True, nonlinear=True, spectral=2, spectral_period=(0.7, 0.31), spectral_scale=0.8), 500)])
 def test_one_call_objective_and_gradient_return_the_same_bits(monkeypatch, kw, n):
     """gpar_logpdf_dense_grad (ABI v5): a layer's training objective and the ingredients of its gradient in one library call -
     the launches of the separate entry points in their order, so value and gradient are bit for bit those of the two-step route

@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from gpar_amd import greedy_inducing
-from gpar_amd.kernels import EQ, RQ, Linear, Matern32
+from gpar_amd.kernels import EQ, RQ, Cosine, Linear, Matern32
 from gpar_amd.regression import GPARRegressor
 
 from .conftest import to_np
@@ -69,6 +69,8 @@ def kernels2d():
         "matern32": (1.1 * Matern32().stretch(s)).select([0, 1]),
         "eq*periodic": (1.2 * EQ().stretch(np.array([1.5, 1.65, 1.35, 1.8])).periodic(np.array([0.7, 0.9])) * EQ().stretch(np.array([1.0, 1.2]))).select([0, 1]),
         "eq+linear": (1.0 * EQ().stretch(s) + Linear().stretch(np.array([1.5, 2.5]))).select([0, 1]),
+        # one component of a spectral mixture: the envelope keeps forty pivots apart, the cosine (periods 0.7 and 0.9) changes sign over the box
+        "eq x cos": (1.2 * EQ().stretch(s) * Cosine().stretch(np.array([0.7, 0.9]))).select([0, 1]),
     }
 
 
@@ -141,6 +143,30 @@ def assert_rank3(got):
 def test_rank_stop_on_a_linear_kernel(oracle_engine):
     kernel, x = linear_rank3()
     assert_rank3(greedy_inducing(oracle_engine, oracle_engine.compile(kernel, 3), x, 10))
+
+
+def cosine_rank2():
+    """300 points under a pure cosine kernel over two columns: cos(a - b) = cos a cos b + sin a sin b, a Gram matrix of rank 2."""
+    x = np.random.default_rng(8).uniform(0.0, 1.0, (300, 2))
+    return (1.3 * Cosine().stretch(np.array([0.7, 0.45]))).select([0, 1]), x
+
+
+def assert_rank2(got, K):
+    """As `assert_rank3`; and the residual diagonal after the two pivots is at most 1e-12 everywhere."""
+    Lt, piv, trace, rank = (to_np(t) for t in got)
+    assert int(rank[0]) == 2 and np.all(piv[:2] >= 0) and np.all(piv[2:] == -1)
+    assert np.all(Lt[2:] == 0.0) and np.any(Lt[1] != 0.0)
+    assert trace[2] <= 1e-10 * trace[0]
+    residual = np.diag(K) - np.sum(Lt[:2] ** 2, axis=0)
+    assert np.max(np.abs(residual)) <= 1e-12, np.max(np.abs(residual))
+
+
+def test_rank_stop_on_a_pure_cosine_kernel(oracle_engine):
+    kernel, x = cosine_rank2()
+    K = dense_gram(oracle_engine, kernel, x)
+    ref = _reference(K, 10)
+    assert ref[3] == 2 and np.max(np.abs(np.diag(K) - np.sum(ref[0] ** 2, axis=0))) <= 1e-12   # the reference alone
+    assert_rank2(greedy_inducing(oracle_engine, oracle_engine.compile(kernel, 2), x, 10), K)
 
 
 def test_tol_stop(oracle_engine):

@@ -24,8 +24,8 @@ from gpar_amd.kernels import EQ, Linear
 from gpar_amd.regression import GPARRegressor
 
 from .conftest import make_engine, to_np
-from .test_select_inducing import (FLOOR, GAP, PIVOT_MIN, _reference, assert_rank3, assert_same, bound, dense_gram, kernels2d, linear_rank3,
-                                   points, regression_data)
+from .test_select_inducing import (FLOOR, GAP, PIVOT_MIN, _reference, assert_rank2, assert_rank3, assert_same, bound, cosine_rank2, dense_gram,
+                                   kernels2d, linear_rank3, points, regression_data)
 
 pytestmark = pytest.mark.gpu
 
@@ -145,6 +145,21 @@ def test_two_runs_give_the_same_bits(eng):
     assert int(info.item()) == 0
     for a, b, c in zip(first, second, third):
         assert a.tobytes() == b.tobytes() == c.tobytes()
+
+
+def test_stops_on_the_device_for_a_pure_cosine_kernel(eng):
+    """Rank 2 (tests/test_select_inducing.py: cosine_rank2): the fused route stops after two pivots, with the pivots of the composed
+    route and of the numpy reference, and leaves a residual diagonal of at most 1e-12."""
+    kernel, x = cosine_rank2()
+    K = dense_gram(None, kernel, x)
+    ref = _reference(K, 10)
+    fused, composed = _both_routes(eng, kernel, x, 10)
+    assert_rank2(fused, K)
+    assert_rank2(composed, K)
+    np.testing.assert_array_equal(to_np(fused[1]), to_np(composed[1]))
+    # (the first step is an exact tie, row 0; the second has a clear maximum on the reference)
+    np.testing.assert_array_equal(to_np(fused[1])[:2], ref[1][:2])
+    np.testing.assert_allclose(to_np(fused[0])[:2], ref[0][:2], rtol=0, atol=bound(2, 1.3))
 
 
 def test_stops_on_the_device(eng):

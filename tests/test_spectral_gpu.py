@@ -1,6 +1,7 @@
 """The cosine factor (GPAR_K_COS) and GPARRegressor(spectral=Q) through libgpar_hip.so on the MI355X.
 
-The reference is the numpy restatement below, which imports nothing from gpar_amd (`oracle/` does not know the factor):
+The reference is the numpy restatement below, which imports nothing from gpar_amd - a second statement beside `oracle/kernels.py`, which
+learned the factor later (tests/test_hip_primitives.py, test_parity_gpu.py and test_fuzz_parity_gpu.py compare the device with that one):
 
     z_d = x[col_d] * (1 / scale_d)                            the feature map as include/gpar_hip.h defines it, in float64
     sigma = ((0 + (z_0 - z'_0)) + (z_1 - z'_1)) + ...          float64, in dim order: the definition of the factor's argument
