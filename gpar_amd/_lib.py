@@ -27,6 +27,7 @@ WS_GEMM_SPLITK, WS_GEMV_T, WS_GRAM_GRAD, WS_CHOL_INVERSE, WS_INPUT_GRAD, WS_LOO,
 WS_CV_GAP = 11
 WS_AHEAD_MULTI = 12
 WS_AHEAD_WINDOW = 13
+WS_POSTERIOR_TERMS = 14
 AHEAD_WINDOW_MAX = 64   # GPAR_AHEAD_WINDOW_MAX: the longest window (rows) the fused sliding-window forecast entries take
 AHEAD_MAX_HORIZONS = 8   # GPAR_AHEAD_MAX_HORIZONS: the most horizons the fused multi-horizon rolling-origin entries take
 PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
@@ -35,7 +36,7 @@ SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the sc
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -111,6 +112,17 @@ SIGNATURES = {
          _ptr],
     ),
     "gpar_gram_diag": (_c_int, [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    # (the decomposition by kernel component: `comp` is a HOST array of ints)
+    "gpar_gram_terms": (
+        _c_int,
+        [ctypes.POINTER(KSpec), ctypes.POINTER(_c_int), _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, ctypes.c_longlong, _ptr],
+    ),
+    "gpar_gram_terms_diag": (_c_int, [ctypes.POINTER(KSpec), ctypes.POINTER(_c_int), _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr]),
+    "gpar_posterior_terms": (
+        _c_int,
+        [ctypes.POINTER(KSpec), ctypes.POINTER(_c_int), _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr,
+         _c_int, _ptr, ctypes.c_longlong, _ptr],
+    ),
     "gpar_pivoted_chol": (_c_int, [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "gpar_featurize_dfreq": (_c_int, [ctypes.POINTER(FSpec), _ptr, _c_int, _c_int, _ptr, _c_int, _ptr]),
     "gpar_grad_nacc": (_c_int, []),

@@ -14,6 +14,7 @@
 #include "pivchol.h"
 #include "chol_update.h"
 #include "score.h"   // the scoring rules of the held-out objectives
+#include "gram_terms.h"   // posterior decomposition by kernel component: its kernels and the chain of gpar_posterior_terms
 
 namespace gpar {
 
@@ -1820,6 +1821,49 @@ int gpar_gram_input_grad(const gpar_kspec_t* ks, const double* z1, int n1, int l
     return 0;
 }
 
+// ---- posterior decomposition by kernel component (ABI v18; gram_terms.h) ---------------------------------------------------------------------
+// Argument errors are found before anything is launched: no output is touched.
+int gpar_gram_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* z1, int n1, int ldz1, const double* z2, int n2, int ldz2,
+                    int dz, double* K, int ldk, long long stride_k, void* stream) {
+    GPAR_API_GUARD;
+    TermGroups tg;
+    const int rc = term_groups_check(ks, comp, ncomp, dz, tg);
+    if (rc) return rc;
+    if (n1 < 0 || n2 < 0) return GPAR_ARG_ERROR(5);
+    if (n1 == 0 || n2 == 0) return 0;
+    if (!z1 || !z2 || !K || ldz1 < dz || ldz2 < dz) return GPAR_ARG_ERROR(6);
+    if (ldk < n2 || (ncomp > 1 && stride_k < (long long)(n1 - 1) * ldk + n2)) return GPAR_ARG_ERROR(7);
+    return gram_terms_launch(ks, tg, z1, n1, ldz1, z2, n2, ldz2, dz, K, ldk, stride_k, (hipStream_t)stream);
+}
+
+int gpar_gram_terms_diag(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* z, int n, int ldz, int dz, double* out, int ldo,
+                         void* stream) {
+    GPAR_API_GUARD;
+    TermGroups tg;
+    const int rc = term_groups_check(ks, comp, ncomp, dz, tg);
+    if (rc) return rc;
+    if (n < 0) return GPAR_ARG_ERROR(5);
+    if (n == 0) return 0;
+    if (!z || !out || ldz < dz) return GPAR_ARG_ERROR(6);
+    if (ldo < n) return GPAR_ARG_ERROR(7);
+    return gram_terms_diag_launch(ks, tg, z, n, ldz, out, ldo, nullptr, 0, (hipStream_t)stream);
+}
+
+int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* zs, int ns, int ldzs, const double* z, int n, int ldz,
+                         int dz, const double* alpha, const double* L, int ldl, double* mean, int ldm, double* var, int ldv, double* ws,
+                         long long ws_doubles, void* stream) {
+    GPAR_API_GUARD;
+    TermGroups tg;
+    const int rc = term_groups_check(ks, comp, ncomp, dz, tg);
+    if (rc) return rc;
+    if (n < 0 || ns < 0) return GPAR_ARG_ERROR(5);
+    if (ns == 0) return 0;
+    if (!zs || !mean || ldzs < dz || (n > 0 && (!z || !alpha || ldz < dz || (var && (!L || ldl < n))))) return GPAR_ARG_ERROR(6);
+    if (ldm < ns || (var && ldv < ns)) return GPAR_ARG_ERROR(7);
+    if (!ws || ws_doubles < (long long)ncomp * ns || (var && n > 0 && ws_doubles < pt_row_doubles(n, ncomp))) return GPAR_ARG_ERROR(8);
+    return posterior_terms_run(ks, tg, zs, ns, ldzs, z, n, ldz, dz, alpha, L, ldl, mean, ldm, var, ldv, ws, ws_doubles, (hipStream_t)stream);
+}
+
 int gpar_potrf(double* A, int N, int nf, int lda, double* logdet, int* info, void* stream) {
     GPAR_API_GUARD;
     if (N <= 0 || nf <= 0) return 0;
@@ -1985,6 +2029,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_AHEAD_WINDOW: return aw_workspace_doubles(a, b);                   /* n, with gradient */
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
+        case GPAR_WS_POSTERIOR_TERMS: return pt_workspace_doubles(a, b, c);              /* n, ns, ncomp */
         default: return -1;
     }
 }

@@ -194,6 +194,16 @@ class HipEngine:
     def gram_diag(self, ck, z):
         return hip.gram_diag(ck, z)
 
+    # ---- decomposition by kernel component (gpar_gram_terms, gpar_gram_terms_diag, gpar_posterior_terms) ----------
+    def gram_terms(self, ck, comp, ncomp, z1, z2=None, out=None):
+        return hip.gram_terms(ck, comp, ncomp, z1, z2, out=out)
+
+    def gram_terms_diag(self, ck, comp, ncomp, z):
+        return hip.gram_terms_diag(ck, comp, ncomp, z)
+
+    def posterior_terms(self, ck, comp, ncomp, zs, z, alpha, L, variance=True):
+        return hip.posterior_terms(ck, comp, ncomp, zs, z, alpha, L, variance=variance)
+
     def pivoted_cholesky(self, ck, z, max_rank, tol=0.0, floor=None):
         """Greedy (partially pivoted) Cholesky of k(z, z) on the features z in one library call (gpar_pivoted_chol): (Lt, piv, trace, rank)
         as device tensors - the factor transposed (max_rank x n, zero rows from the rank on), the pivots (-1 beyond the rank), the

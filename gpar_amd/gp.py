@@ -37,7 +37,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import AHEAD_MAX_HORIZONS, AHEAD_WINDOW_MAX, CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD
+from ._lib import AHEAD_MAX_HORIZONS, AHEAD_WINDOW_MAX, CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD, GPAR_MAX_TERMS
 from .engine import get_engine, joining
 from .hip import (fold_offsets, hold_extents, horizon_weight_array, origin_array, origins_array, upload_hold, upload_origin, upload_origins,
                   upload_window, window_arrays)
@@ -54,6 +54,12 @@ def one_call_grad_rows():
     three synchronisations around them.  Above, the host's share of an evaluation is negligible and the two-step form lets the
     factor be reused."""
     return int(os.environ.get("GPAR_ONE_CALL_GRAD_ROWS", "4096"))
+
+
+def fused_terms():
+    """GPAR_FUSED_TERMS=0: the decomposition by kernel component (`Obs.components`) through the composed route - one sub-kernel, Gram
+    matrix and solve per component - on every engine; default: one library call (gpar_posterior_terms) where the engine has it."""
+    return os.environ.get("GPAR_FUSED_TERMS", "1") != "0"
 
 
 def _as_matrix(eng, x):
@@ -702,6 +708,15 @@ class GP:
         if nv is not None:
             var = var + nv
         return self._mean_at(p), var
+
+    def component_moments(self, x, comp, ncomp, variance=True):
+        """(mean, var), each ncomp x n*, of the components of the kernel under the grouping `comp` at x (`Obs.components`), for a process
+        conditioned on dense observations of its prior.  Inducing points: ValueError."""
+        if isinstance(self._obs, PseudoObs):
+            raise ValueError("a decomposition by kernel component needs dense observations: inducing points are not supported")
+        if not self.is_posterior:
+            raise ValueError("a decomposition by kernel component needs a conditioned process")
+        return self._obs.components(self._pts(x), comp, ncomp, variance)
 
     def sample_batch(self, xs, noise=None):
         """One draw of f (+ noise) at each input set in `xs` (a list of n* x D matrices, e.g. the per-sample design
@@ -1381,6 +1396,50 @@ class Obs:
         eng.gemm(V, V, tb=True, alpha=-1.0, beta=1.0, out=block, c_lower=True)
         corr = eng.gemm(V, self.factor().zrow, tb=True)
         return corr if not self.base.is_posterior else mean + corr
+
+    # ---- decomposition by kernel component (dense observations of the prior) -----------------------------
+    def components(self, p, comp, ncomp, variance=True):
+        """(mean, var), each ncomp x n*: the posterior moments at the points `p` of the components k_g = sum_{comp[t] = g} c_t k_t of the
+        kernel k = sum_t c_t k_t - `comp` holds, per term of the kernel, its component 0 .. ncomp - 1 or -1 for none:
+            mean_g = k_g(x*, X) alpha,        var_g = k_g(x*, x*) - |L^-1 k_g(X, x*)|^2        (latent: the noise belongs to no component)
+        with alpha = K^-1 y and L the factor conditioning holds (Rasmussen & Williams 5.4.3).  `var` is None without `variance`.  One
+        library call where the engine has it (`posterior_terms`; GPAR_FUSED_TERMS=0 turns it off), otherwise composed of what every
+        engine has: the sub-kernel of each component, its Gram matrix and diagonal, the triangular solve."""
+        if self.base.is_posterior:
+            raise ValueError("a decomposition by kernel component needs dense observations of a prior process")
+        comp = [int(c) for c in comp]
+        ncomp = int(ncomp)
+        if len(comp) != len(self.base.kernel.terms):
+            raise ValueError(f"the grouping holds {len(comp)} entries for {len(self.base.kernel.terms)} kernel terms")
+        if not 1 <= ncomp <= GPAR_MAX_TERMS or any(not -1 <= c < ncomp for c in comp):
+            raise ValueError(f"components are numbered 0 .. ncomp - 1 (-1: none) with 1 <= ncomp <= {GPAR_MAX_TERMS}")
+        eng, fac = self.eng, self.factor()
+        if self.fdd.n > 0 and p.n > 0 and fused_terms() and hasattr(eng, "posterior_terms"):
+            _, z = self.fdd.features()
+            return eng.posterior_terms(p.ck, comp, ncomp, p.z, z, fac.alpha(), fac.L, variance=variance)
+        return self._components_composed(p, comp, ncomp, variance)
+
+    def _components_composed(self, p, comp, ncomp, variance):
+        eng, fac, n = self.eng, self.factor(), self.fdd.n
+        kernel, width = self.base.kernel, self.fdd.x.shape[1]
+        mean = torch.zeros(ncomp, p.n, dtype=torch.float64, device=p.x.device)
+        var = torch.zeros(ncomp, p.n, dtype=torch.float64, device=p.x.device) if variance else None
+        for g in range(ncomp):
+            terms = [t for t, c in zip(kernel.terms, comp) if c == g]
+            if not terms or p.n == 0:
+                continue   # (a component without a term is zero)
+            ck = eng.compile(Kernel(terms), width)
+            zs = eng.features(ck, p.x)
+            if variance:
+                var[g] = eng.gram_diag(ck, zs)
+            if n == 0:
+                continue
+            Ks = eng.gram(ck, zs, eng.features(ck, self.fdd.x))
+            mean[g] = eng.gemm(Ks, fac.alpha(), tb=True).reshape(-1)
+            if variance:
+                eng.trsm_rlt_(fac.L, Ks)
+                var[g] -= eng.rownorm2(Ks)
+        return mean, var
 
     # ---- batched routines for dense observations of the prior (`fast_dense`) ----------------------------
     def posterior_mean_batch(self, xs):

@@ -747,6 +747,81 @@ def gram_diag(ck, z):
     return out
 
 
+def _comp_array(ck, comp):
+    """The grouping of a compiled kernel's terms as the host int array the library reads (one entry per term)."""
+    comp = [int(c) for c in comp]
+    if len(comp) != int(ck.kspec.nterms):
+        raise ValueError(f"the grouping holds {len(comp)} entries for {int(ck.kspec.nterms)} kernel terms")
+    return (ctypes.c_int * max(len(comp), 1))(*comp)
+
+
+def gram_terms(ck, comp, ncomp, z1, z2=None, out=None):
+    """k_g(z1, z2) for the components of the grouping `comp` (per term of `ck` a component 0 .. ncomp - 1, or -1 for none), stacked by
+    rows - component g in rows g n1 .. (g + 1) n1 of a (ncomp n1) x n2 matrix (`out`, or a new one) -, built in one pass over the pairs
+    (gpar_gram_terms)."""
+    lib = _lib.load()
+    if z2 is None:
+        z2 = z1
+    _check_mat(z1, "z1")
+    _check_mat(z2, "z2")
+    n1, n2 = z1.shape[0], z2.shape[0]
+    stacked = out if out is not None else alloc_matrix(ncomp * n1, n2, z1.device)
+    _check_mat(stacked, "out")
+    if stacked.shape[0] != ncomp * n1 or stacked.shape[1] != n2:
+        raise ValueError("out must be (ncomp n1) x n2")
+    _lib.check(
+        lib.gpar_gram_terms(ctypes.byref(ck.kspec), _comp_array(ck, comp), int(ncomp), z1.data_ptr(), n1, _ld(z1), z2.data_ptr(), n2, _ld(z2),
+                            ck.dz, stacked.data_ptr(), _ld(stacked), n1 * _ld(stacked), stream_ptr(z1.device)),
+        "gpar_gram_terms",
+    )
+    return stacked
+
+
+def gram_terms_diag(ck, comp, ncomp, z):
+    """out[g][a] = k_g(z[a], z[a]): ncomp x n (gpar_gram_terms_diag)."""
+    lib = _lib.load()
+    _check_mat(z, "z")
+    n = z.shape[0]
+    out = torch.empty(ncomp, n, dtype=torch.float64, device=z.device)
+    _lib.check(
+        lib.gpar_gram_terms_diag(ctypes.byref(ck.kspec), _comp_array(ck, comp), int(ncomp), z.data_ptr(), n, _ld(z), ck.dz, out.data_ptr(),
+                                 max(n, 1), stream_ptr(z.device)),
+        "gpar_gram_terms_diag",
+    )
+    return out
+
+
+def posterior_terms(ck, comp, ncomp, zs, z, alpha, L, variance=True, ws_doubles=None):
+    """(mean, var), each ncomp x n*: the posterior moments of every component of the grouping `comp` at the test features `zs`, for the
+    conditioned dense layer with training features `z`, alpha = K^-1 y and factor `L` - one library call (gpar_posterior_terms).  `var` is
+    None without `variance`.  `ws_doubles`: the workspace to bring instead of the recommended one (a small one makes the variance pass
+    take several chunks of test rows)."""
+    lib = _lib.load()
+    _check_mat(zs, "zs")
+    _check_mat(z, "z")
+    _check_mat(L, "L")
+    ns, n = zs.shape[0], z.shape[0]
+    alpha = alpha.reshape(-1).contiguous()
+    if alpha.numel() != n or alpha.dtype != torch.float64 or not alpha.is_cuda:
+        raise ValueError("alpha must hold one fp64 device value per training row")
+    if L.shape[0] != n or L.shape[1] != n:
+        raise ValueError("L must be the n x n factor of the training covariance")
+    if ws_doubles is None:
+        ws_doubles = lib.gpar_workspace_doubles(_lib.WS_POSTERIOR_TERMS, n, ns, int(ncomp))
+    if ws_doubles < 0:
+        raise ValueError(f"no workspace size for n={n}, n*={ns}, ncomp={ncomp}")
+    ws = torch.empty(max(int(ws_doubles), 2), dtype=torch.float64, device=zs.device)
+    mean = torch.empty(ncomp, ns, dtype=torch.float64, device=zs.device)
+    var = torch.empty(ncomp, ns, dtype=torch.float64, device=zs.device) if variance else None
+    _lib.check(
+        lib.gpar_posterior_terms(ctypes.byref(ck.kspec), _comp_array(ck, comp), int(ncomp), zs.data_ptr(), ns, _ld(zs), z.data_ptr(), n, _ld(z),
+                                 ck.dz, alpha.data_ptr(), L.data_ptr(), _ld(L), mean.data_ptr(), max(ns, 1),
+                                 None if var is None else var.data_ptr(), max(ns, 1), ws.data_ptr(), int(ws_doubles), stream_ptr(zs.device)),
+        "gpar_posterior_terms",
+    )
+    return mean, var
+
+
 def pivoted_chol(ck, z, max_rank, tol_trace, floor):
     """Greedy (partially pivoted) Cholesky of k(z, z) on the features z (gpar_pivoted_chol; semantics: include/gpar_hip.h).  Returns
     device tensors and never synchronises: (Lt max_rank x n - the factor transposed, rows from the rank on zero -, piv int32 max_rank

@@ -75,14 +75,25 @@ class Factor:
 
 
 class Term:
-    __slots__ = ("coef", "factors")
+    """One product term.  `label` names the part of a model the term stands for (`Kernel.labelled`); it travels with the term through
+    the algebra into the compiled term order and takes no part in any arithmetic."""
 
-    def __init__(self, coef, factors):
+    __slots__ = ("coef", "factors", "label")
+
+    def __init__(self, coef, factors, label=None):
         self.coef = coef
         self.factors = list(factors)
+        self.label = label
 
     def coef_value(self):
         return float(_value(self.coef))
+
+
+def _joined_label(a, b):
+    """Label of the product of two terms: the one that is given; of two different ones, both."""
+    if a is None or b is None or a == b:
+        return a if a is not None else b
+    return f"{a}*{b}"
 
 
 def _scalar_like(x):
@@ -119,16 +130,20 @@ class Kernel:
     def __mul__(self, other):
         if isinstance(other, Kernel):
             return Kernel(
-                [Term(_times(a.coef, b.coef), a.factors + b.factors) for a in self.terms for b in other.terms]
+                [Term(_times(a.coef, b.coef), a.factors + b.factors, _joined_label(a.label, b.label)) for a in self.terms for b in other.terms]
             )
         if _scalar_like(other):
-            return Kernel([Term(_times(other, t.coef), t.factors) for t in self.terms])
+            return Kernel([Term(_times(other, t.coef), t.factors, t.label) for t in self.terms])
         return NotImplemented
 
     __rmul__ = __mul__
 
     def _map_factors(self, fn):
-        return Kernel([Term(t.coef, [fn(f) for f in t.factors]) for t in self.terms])
+        return Kernel([Term(t.coef, [fn(f) for f in t.factors], t.label) for t in self.terms])
+
+    def labelled(self, label):
+        """The same kernel with every term named `label` (read back from the compiled term order: `CompiledKernel.kernel.terms`)."""
+        return Kernel([Term(t.coef, t.factors, label) for t in self.terms])
 
     def stretch(self, scales):
         """k(x / scales, y / scales)."""

@@ -969,6 +969,37 @@ class GPAR:
                 x = torch.cat([x, mean.reshape(-1, 1)], dim=1)
         return torch.cat(means, dim=1), torch.cat(variances, dim=1)
 
+    def decompose(self, x, comps, variance=True):
+        """Per layer (mean, var), each G_i x n*: the latent posterior moments at x of the components of layer i's kernel under the grouping
+        comps[i] = (comp, ncomp) - per term of the kernel its component 0 .. ncomp - 1, or -1 for none (`GP.component_moments`; ncomp = 0:
+        no component, 0 x n* results).  The PLUG-IN decomposition: the layers are visited as `moments` visits them, the inputs of layer
+        i + 1 are [x_i, latent posterior mean of layer i] - nothing is sampled, so either `replace` is served; with `replace=True` the
+        components of a layer that uses every term sum to the latent mean `moments` returns.  `var` is None without `variance`.  For a
+        conditioned model with dense layers: inducing points are a ValueError.  [an addition: the reference shows only the sum]"""
+        if self.sparse:
+            raise ValueError("a decomposition by kernel component needs dense layers: inducing points are not supported")
+        if len(comps) != len(self.layers):
+            raise ValueError(f"{len(comps)} groupings for {len(self.layers)} layers")
+        return _retry_unfused(lambda: self._decompose(x, comps, variance), self.layers, (x,))
+
+    def _decompose(self, x, comps, variance):
+        eng = get_engine()
+        x = eng.tensor(x)
+        if x.dim() == 1:
+            x = x[:, None]
+        out = []
+        with torch.no_grad():
+            for (is_last, model), (comp, ncomp) in zip(last(self.layers), comps):
+                f, _ = model()
+                if ncomp:
+                    out.append(f.component_moments(x, comp, ncomp, variance))
+                else:
+                    empty = torch.zeros(0, x.shape[0], dtype=torch.float64, device=x.device)
+                    out.append((empty, empty.clone() if variance else None))
+                if not is_last:
+                    x = torch.cat([x, f.mean(x).reshape(-1, 1)], dim=1)
+        return out
+
     # ---- helpers -----------------------------------------------------------------------------------
     @staticmethod
     def _noise_over(noise, w):

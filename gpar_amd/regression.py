@@ -8,6 +8,8 @@ to one fused device kernel, and every Gram / Cholesky / solve runs in libgpar_hi
 Hyper-parameter names, initialisations and bounds follow reference regression.py:92-180 exactly (table in
 SURVEY.md Appendix C), so `get_variables()` dictionaries are interchangeable.
 """
+import collections
+import fnmatch
 import os
 
 import numpy as np
@@ -21,7 +23,7 @@ from .model import GPAR, check_gap, check_window, host_index, host_masks, per_ou
 from .optimise import minimise_l_bfgs_b
 from .vars import Vars
 
-__all__ = ["GPARRegressor", "log_transform", "squishing_transform"]
+__all__ = ["GPARRegressor", "Decomposition", "log_transform", "squishing_transform"]
 
 
 def _xp(x):
@@ -147,7 +149,8 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
         # nonlinear kernel over the inputs
         var = vs.bnd(name=f"{pi}/input/var", init=1.0)
         scales = vs.bnd(name=f"{0 if scale_tie else pi}/input/scales", init=_vector_from_init(scale, m))
-        k_in = k_in + var * nonlinear_kernel(f"{pi}/input").stretch(scales)
+        # (every term is named after the variables it comes from: `GPARRegressor.decompose` reads the names off the compiled term order)
+        k_in = k_in + (var * nonlinear_kernel(f"{pi}/input").stretch(scales)).labelled("input/nonlin")
 
         # locally periodic kernel over the inputs
         if per:
@@ -155,7 +158,7 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
             scales = vs.bnd(name=f"{pi}/input/per/scales", init=_vector_from_init(per_scale, 2 * m))
             periods = vs.bnd(name=f"{pi}/input/per/pers", init=_vector_from_init(per_period, m))
             decays = vs.bnd(name=f"{pi}/input/per/decay", init=_vector_from_init(per_decay, m))
-            k_in = k_in + var * EQ().stretch(scales).periodic(periods) * EQ().stretch(decays)
+            k_in = k_in + (var * EQ().stretch(scales).periodic(periods) * EQ().stretch(decays)).labelled("input/per")
 
         # spectral mixture over the inputs (Wilson & Adams 2013): Q Gaussian-windowed cosines of a SUM over the inputs, periods learned.
         # The envelope stays EQ under `matern` / `rq` (as the locally periodic term's factors do); `scale_tie` does not tie these.
@@ -164,30 +167,53 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
                 var = vs.bnd(name=f"{pi}/input/sm{q}/var", init=1.0 / spectral)
                 scales = vs.bnd(name=f"{pi}/input/sm{q}/scales", init=_vector_from_init(spectral_scale, m))
                 periods = vs.bnd(name=f"{pi}/input/sm{q}/pers", init=_vector_from_init(period, m))
-                k_in = k_in + var * EQ().stretch(scales) * Cosine().stretch(periods)
+                k_in = k_in + (var * EQ().stretch(scales) * Cosine().stretch(periods)).labelled(f"input/sm{q}")
 
         # linear kernel (plus constant) over the inputs
         if input_linear:
             scales = vs.bnd(name=f"{pi}/input/lin/scales", init=_vector_from_init(input_linear_scale, m))
             const = vs.get(name=f"{pi}/input/lin/const", init=1.0)
-            k_in = k_in + (Linear().stretch(scales) + const)
+            k_in = k_in + (Linear().stretch(scales).labelled("input/lin") + (ZeroKernel() + const).labelled("input/const"))
 
         # linear dependencies on the previous outputs
         if linear and pi > 0:
             scales = vs.bnd(name=f"{pi}/output/lin/scales", init=_vector_from_init(linear_scale, p_num))
-            k_out = k_out + Linear().stretch(scales)
+            k_out = k_out + Linear().stretch(scales).labelled("output/lin")
 
         # nonlinear dependencies on the previous outputs
         if nonlinear and pi > 0:
             var = vs.bnd(name=f"{pi}/output/nonlin/var", init=1.0)
             scales = vs.bnd(name=f"{pi}/output/nonlin/scales", init=_vector_from_init(nonlinear_scale, p_num))
-            k_out = k_out + var * nonlinear_kernel(f"{pi}/output/nonlin").stretch(scales)
+            k_out = k_out + (var * nonlinear_kernel(f"{pi}/output/nonlin").stretch(scales)).labelled("output/nonlin")
 
         noise_variance = vs.bnd(name=f"{pi}/noise", init=_vector_from_init(noise, pi + 1)[pi], lower=1e-8)
         f = GP(k_in.select(m_inds) + k_out.select(p_inds), measure=Measure())
         return f, noise_variance
 
     return model
+
+
+#: What `GPARRegressor.decompose` returns: per output a tuple of component names, a G_i x n* array of means, one of variances (or None
+#: for `var`), and the p normalisation shifts.
+Decomposition = collections.namedtuple("Decomposition", "names mean var offset")
+
+
+def _group_terms(labels, components):
+    """(names, comp) of one layer whose kernel terms are named `labels`: the names of its components and, per term, the index of its
+    component among them (-1: none).  `components` None: one component per term; a dict {name: patterns}: a term belongs to the
+    component one of whose patterns its name matches (`fnmatch`, case-sensitive), to none where no pattern does - two components
+    matching one term is a ValueError -, and a component without a term here is not among the names."""
+    if components is None:
+        return tuple(labels), list(range(len(labels)))
+    owner = []
+    for label in labels:
+        hits = [name for name, patterns in components.items()
+                if any(fnmatch.fnmatchcase(str(label), pat) for pat in ([patterns] if isinstance(patterns, str) else patterns))]
+        if len(hits) > 1:
+            raise ValueError(f"kernel term {label!r} is matched by the components {hits}: a term belongs to one component")
+        owner.append(hits[0] if hits else None)
+    names = tuple(name for name in components if name in owner)
+    return names, [names.index(o) if o is not None else -1 for o in owner]
 
 
 def update_drop_fraction():
@@ -1038,9 +1064,7 @@ class GPARRegressor:
             raise RuntimeError("Must condition or fit model before predicting.")
         if not self.replace:
             raise ValueError("closed-form predictive moments need replace=True")
-        probe = torch.tensor([-1.5, 0.25, 3.0], dtype=torch.float64)
-        if not torch.equal(self._untransform_y(probe), probe):
-            raise ValueError("closed-form predictive moments need the identity output transform (a non-linear map of a Gaussian is not Gaussian)")
+        self._check_identity_transform()
         x = _uprank(_to_engine(x))
         w = _default_weights(x.shape[0], self.p) if w is None else _uprank(_to_torch(w))
         gpar = _conditioned
@@ -1058,6 +1082,51 @@ class GPARRegressor:
             mean = self._unnormalise_y(mean)
             var = var * slope ** 2
         return mean.cpu().numpy(), var.cpu().numpy()
+
+    def _check_identity_transform(self):
+        probe = torch.tensor([-1.5, 0.25, 3.0], dtype=torch.float64)
+        if not torch.equal(self._untransform_y(probe), probe):
+            raise ValueError("closed-form predictive moments need the identity output transform (a non-linear map of a Gaussian is not Gaussian)")
+
+    def decompose(self, x, components=None, variance=True):
+        """What each part of the trained kernel explains at x - an addition; the reference shows only the sum.  A layer's kernel is a
+        sum of named terms - `input/nonlin`, `input/per`, `input/sm0` .. , `input/lin`, `input/const`, `output/lin`, `output/nonlin`,
+        named after the variables they come from - and its latent posterior is the sum of one Gaussian process per term (Rasmussen &
+        Williams 5.4.3): `decompose` returns their means and marginal variances, for time series the trend and the seasonal part, for
+        GPAR how much of an output comes from the inputs and how much from the outputs before it.
+
+        `components` None: one component per term.  A dict {name: [patterns]}: the terms whose name matches a pattern (`fnmatch`) form
+        the component; terms no pattern matches are left out, a term matched by two components is a ValueError, a component without a
+        term in a layer is absent from that layer's names.
+
+        Returns `Decomposition(names, mean, var, offset)`: per output i a tuple of names, a G_i x n* array of means and one of variances
+        (`var` is None without `variance`), in the units of y - means times the output's normalisation slope, variances times its
+        square - and the p normalisation shifts `offset`.  The layers see [x, latent posterior means of the outputs before them] (the
+        plug-in decomposition, `GPAR.decompose`): with `replace=True` and every term used, offset[i] + mean[i].sum(0) is
+        `predict_moments(x, latent=True)[0][:, i]`.  RuntimeError: not conditioned; ValueError: a non-identity `transform_y`, inducing
+        points."""
+        if not self.is_conditioned:
+            raise RuntimeError("Must condition or fit model before decomposing.")
+        self._check_identity_transform()
+        if self.sparse:
+            raise ValueError("a decomposition by kernel component needs dense layers: inducing points are not supported")
+        x = _uprank(_to_engine(x))
+        gpar = self._stream_posterior() if getattr(self, "_stream_cache", None) is not None else None
+        if gpar is None:
+            gpar = _construct_gpar(self, self.vs, self.m, self.p) | (self.x, self.y, self.w)
+        names, comps = [], []
+        for model in gpar.layers:
+            layer_names, comp = _group_terms([t.label for t in model()[0].kernel.terms], components)
+            names.append(layer_names)
+            comps.append((comp, len(layer_names)))
+        with torch.no_grad():
+            parts = gpar.decompose(x, comps, variance=variance)
+            zero = torch.zeros(1, self.p, dtype=torch.float64, device=x.device)
+            shift = self._unnormalise_y(zero)
+            slope = self._unnormalise_y(torch.ones_like(zero)) - shift   # (un-normalisation is affine, as in predict_moments)
+            mean = [(m * slope[0, i]).cpu().numpy() for i, (m, _) in enumerate(parts)]
+            var = [(v * slope[0, i] ** 2).cpu().numpy() for i, (_, v) in enumerate(parts)] if variance else None
+        return Decomposition(tuple(names), mean, var, shift.reshape(-1).cpu().numpy())
 
     def sample(self, x, w=None, p=None, posterior=False, num_samples=1, latent=False, _conditioned=None):
         """Draw samples from the prior or the posterior at inputs x; a single ndarray for num_samples=1, otherwise

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 17
+#define GPAR_ABI_VERSION 18
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -184,6 +184,40 @@ int gpar_gram_batch(const gpar_kspec_t* ks, const double* z, int n, int ldz, lon
 
 /* out[a] = k(z[a], z[a])   [kernel diagonal; VFE trace term, posterior marginal variances] */
 int gpar_gram_diag(const gpar_kspec_t* ks, const double* z, int n, int ldz, int dz, double* out, void* stream);
+
+/* Posterior decomposition by kernel component (ABI v18): the additive decomposition of a GP whose kernel is a sum (Rasmussen & Williams
+ * 5.4.3; Duvenaud et al. 2013).  A layer kernel is k = sum_t c_t k_t over its nterms product terms; a GROUPING comp (HOST array of nterms
+ * ints, each -1 .. ncomp - 1) sends term t to component comp[t], -1 to none, and k_g = sum_{comp[t] = g} c_t k_t.  1 <= ncomp <= GPAR_MAX_TERMS.
+ *
+ * gpar_gram_terms       K_g[a][b] = k_g(z1[a], z2[b]) for every g in ONE pass over the pairs: component g's n1 x n2 block (leading dimension
+ *                       ldk >= n2) starts at K + g * stride_k (blocks must not overlap).  The arguments of gpar_gram otherwise, without
+ *                       flags, diagonal add and row scale: always the full rectangle.  A component without a term is written as zeros.  A
+ *                       term has the bits it has in gpar_gram's interpreter kernel: one component holding every term is that kernel's result
+ *                       bit for bit, and the blocks of any grouping that uses every term once sum to it to rounding.
+ * gpar_gram_terms_diag  out[g * ldo + a] = k_g(z[a], z[a]) (ldo >= n), the arithmetic of gpar_gram_diag.
+ * gpar_posterior_terms  for ONE conditioned dense layer - training features z (n x dz), alpha = K^-1 y (n values) and the factor L (n x n,
+ *                       ldl) of K = k(X, X) + D + eps I - and test features zs (ns x dz):
+ *                           mean[g * ldm + a] = k_g(zs[a], X) alpha            var[g * ldv + a] = k_g(zs[a], zs[a]) - |L^-1 k_g(X, zs[a])|^2
+ *                       (latent: the noise belongs to no component).  Over a grouping that uses every term once the means sum to the layer's
+ *                       posterior mean; one component holding every term has the layer's posterior variance.  var == NULL skips the
+ *                       variances (and L is not read).  The means are a fused Gram-times-vector pass - no ns x n matrix is written -, split
+ *                       over n and summed in a fixed order; the variances compose gpar_gram_terms (the (ncomp c) x n stack of a chunk of c
+ *                       test rows), ONE gpar_trsm_rlt over the stack, gpar_rownorm2 and gpar_gram_terms_diag.
+ *                       ws: ws_doubles doubles, 16-byte aligned; gpar_workspace_doubles(GPAR_WS_POSTERIOR_TERMS, n, ns, ncomp) is the size
+ *                       to bring.  Any size from max(ncomp ns, ncomp (n + 3)) doubles is taken: a smaller workspace means fewer splits
+ *                       of the mean pass and smaller chunks of test rows (the means' last bits depend on the number of splits, so on
+ *                       ws_doubles; for given arguments a call returns the same bits every time).
+ * Argument errors - ncomp outside 1 .. GPAR_MAX_TERMS, a comp entry outside -1 .. ncomp - 1, a negative n / ns / n1 / n2, dz outside
+ * 0 .. GPAR_MAX_DIMS or a factor reaching past it, leading dimensions or a workspace too small - are found before the first launch: a
+ * negative status, no output touched.  No floating-point atomics anywhere.   [no reference counterpart: the reference's todo.tasks asks for
+ * an "overview of trained hyperparameters"; this is what each trained part of the kernel explains] */
+int gpar_gram_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* z1, int n1, int ldz1, const double* z2, int n2,
+                    int ldz2, int dz, double* K, int ldk, long long stride_k, void* stream);
+int gpar_gram_terms_diag(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* z, int n, int ldz, int dz, double* out, int ldo,
+                         void* stream);
+int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* zs, int ns, int ldzs, const double* z, int n,
+                         int ldz, int dz, const double* alpha, const double* L, int ldl, double* mean, int ldm, double* var, int ldv,
+                         double* ws, long long ws_doubles, void* stream);
 
 /* Greedy (partially pivoted) Cholesky of k(Z, Z) (ABI v10): the selection of inducing points by largest conditional variance (Fine &
  * Scheinberg 2001; the initialisation Burt et al. 2019 recommend for sparse variational GPs).  z: n x dz features as gpar_featurize
@@ -705,7 +739,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_PIVOTED_CHOL (n, -, -)        gpar_pivoted_chol
  *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading
  *   GPAR_WS_AHEAD_MULTI  (n, grad, nh)    the `vec` of gpar_ahead_multi_dense (grad = 0) / gpar_ahead_multi_dense_grad[_finish] (grad = 1)
- *   GPAR_WS_AHEAD_WINDOW (n, grad, -)     the `vec` of gpar_ahead_window_dense (grad = 0) / gpar_ahead_window_dense_grad (grad = 1) */
+ *   GPAR_WS_AHEAD_WINDOW (n, grad, -)     the `vec` of gpar_ahead_window_dense (grad = 0) / gpar_ahead_window_dense_grad (grad = 1)
+ *   GPAR_WS_POSTERIOR_TERMS (n, ns, ncomp)  gpar_posterior_terms (the recommended size; see there for the least) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -719,6 +754,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_CV_GAP 11
 #define GPAR_WS_AHEAD_MULTI 12
 #define GPAR_WS_AHEAD_WINDOW 13
+#define GPAR_WS_POSTERIOR_TERMS 14
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
