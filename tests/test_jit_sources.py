@@ -59,6 +59,31 @@ def test_every_layer_structure_compiles_for_gfx950():
     assert len(sizes) >= 10 and len(set(sizes)) > 3 and wide >= 1   # different structures, different code
 
 
+def test_structures_of_the_geometry_tests_compile_for_gfx950():
+    """The six structures tests/test_generated_kernels_gpu.py drives at the edges of the generated kernels' geometry, in every kind it
+    launches: 0 Gram (strip kernel, and the wide form at 23 dims), 1 / 11 parameter-gradient pass with symmetric / rectangular weights,
+    2 / 12 input-gradient pass (rectangular / symmetric), and 21 / 31 - the passes with frequency derivatives - where the structure is
+    periodic."""
+    from gpar_amd import _lib
+    from gpar_amd.kernels import compile_kernel
+
+    from .test_generated_kernels_gpu import _DIMS, structures
+
+    lib = _lib.load()
+    log = ctypes.create_string_buffer(1 << 16)
+    seen = set()
+    for name, kernel, width in structures():
+        ck = compile_kernel(kernel, width)
+        assert ck.dz == _DIMS[name], (name, ck.dz)
+        periodic = any(f.periods is not None for t in ck.kernel.terms for f in t.factors)
+        kinds = [0, 1, 11, 2, 12] + ([21, 31] if periodic else [])   # (2 / 12 compile at 0 and 23 dims too; the launch never asks for them)
+        for kind in kinds:
+            size = lib.gpar_jit_compile_check(kind, ctypes.byref(ck.kspec), ck.dz, b"gfx950", log, len(log))
+            assert size > 0, (name, kind, log.value.decode()[:4000])
+        seen.add((ck.dz, periodic))
+    assert {dz for dz, _ in seen} == {0, 7, 8, 10, 12, 23} and any(p for _, p in seen)
+
+
 def test_bad_arguments_are_refused():
     from gpar_amd import _lib
 
