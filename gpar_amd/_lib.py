@@ -36,7 +36,7 @@ SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the sc
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -123,6 +123,7 @@ SIGNATURES = {
         [ctypes.POINTER(KSpec), ctypes.POINTER(_c_int), _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr,
          _c_int, _ptr, ctypes.c_longlong, _ptr],
     ),
+    "gpar_periodogram": (_c_int, [_ptr, _c_int, _c_dbl, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr]),
     "gpar_pivoted_chol": (_c_int, [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "gpar_featurize_dfreq": (_c_int, [ctypes.POINTER(FSpec), _ptr, _c_int, _c_int, _ptr, _c_int, _ptr]),
     "gpar_grad_nacc": (_c_int, []),

@@ -14,6 +14,7 @@
 #include "pivchol.h"
 #include "chol_update.h"
 #include "score.h"   // the scoring rules of the held-out objectives
+#include "periodogram.h"   // generalised Lomb-Scargle periodogram (gpar_periodogram)
 #include "gram_terms.h"   // posterior decomposition by kernel component: its kernels and the chain of gpar_posterior_terms
 
 namespace gpar {
@@ -1862,6 +1863,13 @@ int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, con
     if (ldm < ns || (var && ldv < ns)) return GPAR_ARG_ERROR(7);
     if (!ws || ws_doubles < (long long)ncomp * ns || (var && n > 0 && ws_doubles < pt_row_doubles(n, ncomp))) return GPAR_ARG_ERROR(8);
     return posterior_terms_run(ks, tg, zs, ns, ldzs, z, n, ldz, dz, alpha, L, ldl, mean, ldm, var, ldv, ws, ws_doubles, (hipStream_t)stream);
+}
+
+// ---- generalised Lomb-Scargle periodogram (ABI v19; periodogram.h) ------------------------------------------------------------------------------
+int gpar_periodogram(const double* t, int n, double t0, const double* y, int ldy, const double* omega, int ldo, int p, const double* freq, int nf,
+                     double* power, int ldp, void* stream) {
+    GPAR_API_GUARD;
+    return periodogram_launch(t, n, t0, y, ldy, omega, ldo, p, freq, nf, power, ldp, (hipStream_t)stream);
 }
 
 int gpar_potrf(double* A, int N, int nf, int lda, double* logdet, int* info, void* stream) {

@@ -204,6 +204,15 @@ class HipEngine:
     def posterior_terms(self, ck, comp, ncomp, zs, z, alpha, L, variance=True):
         return hip.posterior_terms(ck, comp, ncomp, zs, z, alpha, L, variance=variance)
 
+    # ---- generalised Lomb-Scargle periodogram (gpar_periodogram) ----------------------------------------------------
+    def periodogram(self, t, y, omega, freq, t0=None):
+        """power (p x F, a device tensor) of the p columns of y (n x p) with weights omega (0 = unobserved) at the time stamps t and
+        the frequencies freq; the phases are counted from t0 (default: min t, read from the device)."""
+        t, y, omega, freq = self.tensor(t), self.tensor(y), self.tensor(omega), self.tensor(freq)
+        if t0 is None:
+            t0 = float(t.min().item()) if t.numel() else 0.0
+        return hip.periodogram(t, y, omega, freq, t0)
+
     def pivoted_cholesky(self, ck, z, max_rank, tol=0.0, floor=None):
         """Greedy (partially pivoted) Cholesky of k(z, z) on the features z in one library call (gpar_pivoted_chol): (Lt, piv, trace, rank)
         as device tensors - the factor transposed (max_rank x n, zero rows from the rank on), the pivots (-1 beyond the rank), the

@@ -552,7 +552,7 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     its origins (`model.rolling_window_starts`) and uploaded with them; None where a window holds more than `_lib.AHEAD_WINDOW_MAX` rows."""
     from .gp import one_call_grad_rows
     from .model import contiguous_folds, host_index, purged_folds, rolling_origins, rolling_window_starts
-    from .regression import _model_generator
+    from .regression import _model_generator, layer_config
 
     on_device = cls is None   # (the CPU tests of the host logic hand in a class with its own device side)
     cls = DenseLayerObjective if cls is None else cls
@@ -615,7 +615,7 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
         if int((origin - lo)[origin >= 0].max(initial=0)) > _lib.AHEAD_WINDOW_MAX:
             return None   # (a window longer than the library call takes: the general route trains the layer)
     tracer = _TracingVars(vs)
-    f, noise = _model_generator(tracer, reg.m, pi, **reg.model_config)()
+    f, noise = _model_generator(tracer, reg.m, pi, **layer_config(reg, reg.m, pi))()
     kernel = f.kernel
     if not isinstance(kernel, Kernel) or f.is_posterior or _slots(kernel) is None:
         return None

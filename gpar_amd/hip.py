@@ -19,6 +19,7 @@ __all__ = [
     "featurize",
     "gram",
     "gram_diag",
+    "periodogram",
     "pivoted_chol",
     "chol_drop_leading",
     "chol_append_",
@@ -820,6 +821,25 @@ def posterior_terms(ck, comp, ncomp, zs, z, alpha, L, variance=True, ws_doubles=
         "gpar_posterior_terms",
     )
     return mean, var
+
+
+def periodogram(t, y, omega, freq, t0):
+    """power (p x F): the generalised Lomb-Scargle periodogram of the p columns of y (n x p; weights omega, 0 = unobserved) at the time
+    stamps t (n) and frequencies freq (F), phases counted from the host number t0 (gpar_periodogram; semantics: include/gpar_hip.h)."""
+    lib = _lib.load()
+    for a, name in ((t, "t"), (y, "y"), (omega, "omega"), (freq, "freq")):
+        _check_mat(a, name)
+    t, freq = t.reshape(-1).contiguous(), freq.reshape(-1).contiguous()
+    if y.dim() != 2 or tuple(omega.shape) != tuple(y.shape) or y.shape[0] != t.numel():
+        raise ValueError("y and omega must be n x p, one row per time stamp")
+    n, p, nf = int(y.shape[0]), int(y.shape[1]), int(freq.numel())
+    power = torch.zeros(p, nf, dtype=torch.float64, device=y.device)
+    _lib.check(
+        lib.gpar_periodogram(t.data_ptr(), n, float(t0), y.data_ptr(), _ld(y), omega.data_ptr(), _ld(omega), p, freq.data_ptr(), nf,
+                             power.data_ptr(), max(nf, 1), stream_ptr(y.device)),
+        "gpar_periodogram",
+    )
+    return power
 
 
 def pivoted_chol(ck, z, max_rank, tol_trace, floor):

@@ -210,6 +210,14 @@ def _tag_host_nan(reg, y_dev):
         y_dev._host_nan, y_dev._host_nan_version = torch.isnan(reg.y).numpy(), y_dev._version
 
 
+def _refuse_auto_periods(reg):
+    """`spectral_period="auto"` reads a periodogram off the device engine; the ranks of a sharded driver may run on engines without one
+    and would have to agree on the picks: refused, with the way out."""
+    if reg.model_config.get("spectral_period") == "auto":
+        raise ValueError('spectral_period="auto" is not available in the sharded drivers (their ranks may have no periodogram): pick the '
+                         "periods once (GPARRegressor.periodogram, spectral_peaks) and pass spectral_period=(...)")
+
+
 def sharded_fit(reg, x, y, w=None, group=None, fix=True, **kw_args):
     """`GPARRegressor.fit(x, y, w, fix=fix)` over the ranks of `group`; every rank ends up with the same hyper-parameters.
     Returns what it did:
@@ -220,6 +228,7 @@ def sharded_fit(reg, x, y, w=None, group=None, fix=True, **kw_args):
                         sequential, every rank runs the serial `fit`."""
     from .regression import _construct_gpar
 
+    _refuse_auto_periods(reg)
     rank, size = world(group)
     eng = get_engine()
     reg.condition(x, y, w)
@@ -367,6 +376,7 @@ def sharded_condition(reg, group=None):
     from .model import _retry_unfused
     from .regression import _construct_gpar
 
+    _refuse_auto_periods(reg)
     rank, size = world(group)
     eng = get_engine()
     gpar = _construct_gpar(reg, reg.vs, reg.m, reg.p)
@@ -415,6 +425,7 @@ def _sharded_sample_stack(reg, x, w, num_samples, latent, group, marginal=False)
     """(S x n* x p device tensor holding every rank's draws, in rank order; the per-rank counts): the conditioning is
     layer-parallel (`sharded_condition`), each rank draws its share with its own Philox stream, and the device-resident stacks
     are all-gathered ONCE - no sample visits the host."""
+    _refuse_auto_periods(reg)
     rank, size = world(group)
     eng = get_engine()
     counts = [num_samples // size + (1 if r < num_samples % size else 0) for r in range(size)]

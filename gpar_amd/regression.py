@@ -21,9 +21,10 @@ from .gp import GP, Measure, check_score, greedy_inducing
 from .kernels import EQ, RQ, Cosine, Linear, Matern12, Matern32, Matern52, ZeroKernel
 from .model import GPAR, check_gap, check_window, host_index, host_masks, per_output
 from .optimise import minimise_l_bfgs_b
+from .spectrum import Periodogram, periodogram_grid, periodogram_inputs, spectral_peaks
 from .vars import Vars
 
-__all__ = ["GPARRegressor", "Decomposition", "log_transform", "squishing_transform"]
+__all__ = ["GPARRegressor", "Decomposition", "Periodogram", "spectral_peaks", "log_transform", "squishing_transform"]
 
 
 def _xp(x):
@@ -227,6 +228,22 @@ def update_drop_fraction():
     return float(os.environ.get("GPAR_UPDATE_DROP_FRACTION", "0"))
 
 
+def layer_config(reg, m, pi):
+    """The keywords `_model_generator` builds layer `pi` of `reg` from: the regressor's `model_config`, and where periods were picked from
+    a periodogram (`spectral_period="auto"`, `init_spectral`) the layer's own Q of them as its `spectral_period` - given where a user
+    would have given them, so names, bounds, every other initial value and the rule that an existing variable is not overwritten are
+    the constructor's."""
+    config = reg.model_config
+    picked = getattr(reg, "_spectral_auto", None)   # p x Q
+    if picked is None:
+        if config.get("spectral_period") == "auto":
+            raise RuntimeError('spectral_period="auto" takes the initial periods from data: call fit, condition or init_spectral first')
+        return config
+    if m != 1 or pi >= picked.shape[0]:
+        raise ValueError(f"the spectral periods were picked for one input and {picked.shape[0]} outputs; this model has {m} inputs and a layer {pi}")
+    return {**config, "spectral_period": tuple(float(v) for v in picked[pi])}
+
+
 def _construct_gpar(reg, vs, m, p):
     x_ind = reg.x_ind
     if x_ind is not None and getattr(reg, "_x_ind_trainable", False):
@@ -236,7 +253,7 @@ def _construct_gpar(reg, vs, m, p):
     if reg.model_config.get("spectral") is not None:   # (the feature dims grow with m and p, which the constructor did not know)
         _check_layer_kernel_size(reg.model_config, m, p)
     for pi in range(p):
-        gpar = gpar.add_layer(_model_generator(vs, m, pi, **reg.model_config))
+        gpar = gpar.add_layer(_model_generator(vs, m, pi, **layer_config(reg, m, pi)))
     return gpar
 
 
@@ -442,13 +459,23 @@ class GPARRegressor:
             if isinstance(spectral, (bool, np.bool_)) or not isinstance(spectral, (int, np.integer)) or spectral < 1:
                 raise ValueError("spectral must be None or an integer >= 1 (the number of spectral-mixture components)")
             spectral = int(spectral)
-            spectral_period = float(spectral_period) if np.ndim(spectral_period) == 0 else tuple(float(v) for v in np.reshape(spectral_period, -1))
+            if isinstance(spectral_period, str):
+                # "auto": the periods are picked from the generalised Lomb-Scargle periodogram of the data the model is first built on
+                # (`init_spectral`; Wilson & Adams 2013 initialise from the empirical spectrum) - one input column, the device engine
+                if spectral_period != "auto":
+                    raise ValueError(f'spectral_period={spectral_period!r}: a number, {spectral} numbers or "auto"')
+            else:
+                spectral_period = float(spectral_period) if np.ndim(spectral_period) == 0 else tuple(float(v) for v in np.reshape(spectral_period, -1))
             spectral_scale = float(spectral_scale) if np.ndim(spectral_scale) == 0 else tuple(float(v) for v in np.reshape(spectral_scale, -1))
-            _spectral_periods(spectral, spectral_period)
+            if spectral_period != "auto":
+                _spectral_periods(spectral, spectral_period)
             self.model_config.update(spectral=spectral, spectral_period=spectral_period, spectral_scale=spectral_scale)
             # terms and factors of the widest layer (one with previous outputs) are known now; its feature dims once m and p are
             _check_layer_kernel_size(self.model_config, 1, 2)
+        elif isinstance(spectral_period, str):
+            raise ValueError(f"spectral_period={spectral_period!r} belongs to spectral=Q")
         self.spectral = spectral
+        self._spectral_auto = None   # p x Q periods picked from a periodogram, once there are any
         self.vs = Vars(dtype=torch.float64)
         self.is_conditioned = False
         self.x = self.y = self.w = None
@@ -495,6 +522,9 @@ class GPARRegressor:
 
             self._normalise_y, self._unnormalise_y = normalise_y, unnormalise_y
             self.y = torch.from_numpy((y_np - means) / stds)
+        if self.model_config.get("spectral_period") == "auto" and (self._spectral_auto is None or self._spectral_auto.shape[0] < self.p):
+            # the first data the model is built on: the periods every layer's components start at (later calls keep them)
+            self._spectral_auto = self._pick_periods(self.x.numpy(), self.y.numpy(), self.w.numpy())
         self.is_conditioned = True
 
     def fit(self, x, y, w=None, greedy=False, fix=True, optimise_x_ind=False, objective="mll", folds=None, horizon=None, start=None,
@@ -685,6 +715,9 @@ class GPARRegressor:
         `condition`."""
         from .vars import Vars
 
+        if self.model_config.get("spectral_period") == "auto":
+            raise ValueError('spectral_period="auto" picks layer i\'s periods from output i\'s periodogram, and greedy_order decides which '
+                             "output layer i models: pick the periods yourself (periodogram, spectral_peaks) and pass spectral_period=(...)")
         self.condition(x, y, w)
         eng = get_engine()
         x_host, y_host, w_host = self.x, self.y, self.w
@@ -750,7 +783,7 @@ class GPARRegressor:
             raise ValueError(f"x has {m} columns, the model has {self.m} inputs")
         eng = get_engine()
         with torch.no_grad():
-            kernel = _model_generator(self.vs, m, 0, **self.model_config)()[0].kernel
+            kernel = _model_generator(self.vs, m, 0, **layer_config(self, m, 0))()[0].kernel
             with eng.defer_checks():
                 _, piv, trace, rank = greedy_inducing(eng, eng.compile(kernel, m), eng.tensor(x_np), num, tol=tol)
         rank = int(rank.item())
@@ -852,6 +885,68 @@ class GPARRegressor:
         self._stream_cache = (self._stream_key(), gpar)
         self.last_update_incremental_ = bool(incremental)
         return self
+
+    # ---- periodogram and the initial periods of spectral-mixture layers --------------------------------------------------
+    def _periodogram(self, t, y, omega, freq=None, oversample=5, nyquist=1.0):
+        """`periodogram` for prepared arrays (`spectrum.periodogram_inputs`): every ValueError first, then the engine."""
+        span = float(t.max() - t.min())
+        n_obs = int((omega > 0).sum(axis=0).max())
+        if freq is None:
+            freq = periodogram_grid(span, n_obs, oversample, nyquist)
+        else:
+            freq = np.asarray(freq, dtype=np.float64).reshape(-1)
+            if not span > 0:
+                raise ValueError("the time stamps must span a positive range: a periodogram of one instant has no frequencies")
+            if freq.size == 0 or not np.all(np.isfinite(freq)) or np.any(freq <= 0):
+                raise ValueError("freq must hold positive, finite frequencies (cycles per unit of x)")
+        eng = get_engine()
+        if not hasattr(eng, "periodogram"):
+            raise NotImplementedError(f"{type(eng).__name__} has no periodogram: the generalised Lomb-Scargle periodogram is a device kernel "
+                                      "(HipEngine.periodogram, gpar_periodogram) and has no CPU fallback")
+        power = eng.periodogram(t, y, omega, freq, t0=float(t.min()))
+        return Periodogram(freq, power.cpu().numpy())
+
+    def periodogram(self, x, y, w=None, freq=None, oversample=5, nyquist=1.0):
+        """Generalised Lomb-Scargle periodogram (Zechmeister & Kuerster 2009: floating mean, weights) of every output - an addition, and
+        where `spectral_period="auto"` takes its periods from.  x: n x 1 or 1-D, in any order (more than one input column: ValueError);
+        y: n x p, NaN = missing, taken through `transform_y` as the model sees it (the power is invariant under affine maps of y, so the
+        normalisation plays no part); w: the observation weights of `fit`.  Returns `Periodogram(freq, power)`: F frequencies in cycles
+        per unit of x and the p x F powers in [0, 1] - the share of the output's weighted variance a sinusoid of that frequency explains;
+        exactly 0 for an output with fewer than 3 observed rows or constant values.  `freq`: the frequencies to use, or None for the grid
+        k / (oversample span), k = 1, 2, ... up to nyquist n_obs / (2 span), with span = max x - min x and n_obs the observed rows of the
+        best-observed output (`spectrum.periodogram_grid`).  ValueError: span = 0, fewer than 3 rows.  One device call
+        (`gpar_periodogram`); NotImplementedError on an engine without it."""
+        y = np.asarray(self._transform_y(_uprank(_to_torch(y))).detach().cpu().numpy(), dtype=np.float64)
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+        w = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w
+        return self._periodogram(*periodogram_inputs(x, y, w), freq=freq, oversample=oversample, nyquist=nyquist)
+
+    def _pick_periods(self, x, y, w, **grid):
+        """p x Q periods, strongest first: 1 / `spectral_peaks` of each output's periodogram, inside the variables' bounds."""
+        if self.spectral is None:
+            raise ValueError("initial periods belong to spectral=Q")
+        t, y, omega = periodogram_inputs(x, y, w)   # (more than one input column is refused here)
+        pg = self._periodogram(t, y, omega, **grid)
+        span = float(t.max() - t.min())
+        return np.stack([np.clip(1.0 / spectral_peaks(pg.freq, row, self.spectral, span), 1e-4, 1e4) for row in pg.power])
+
+    def init_spectral(self, x, y, w=None, **grid):
+        """Pick the initial periods of the spectral-mixture components from the data's periodogram, now: layer i's `{i}/input/sm{q}/pers`
+        become 1 / the q-th strongest peak (`spectral_peaks`) of output i's periodogram (`periodogram(x, y, w, **grid)`).  What
+        `spectral_period="auto"` does at the first `fit` / `condition`, on demand and for any `spectral_period` - and where "auto" leaves a
+        variable that already exists alone, this OVERWRITES it.  Returns the p x Q periods."""
+        y_t = np.asarray(self._transform_y(_uprank(_to_torch(y))).detach().cpu().numpy(), dtype=np.float64)
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x
+        w = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w
+        periods = self._pick_periods(x, y_t, w, **grid)
+        self._spectral_auto = periods
+        self._stream_cache = None
+        for pi in range(periods.shape[0]):
+            for q in range(self.spectral):
+                name = f"{pi}/input/sm{q}/pers"
+                if name in self.vs:
+                    self.vs.assign(name, _vector_from_init(periods[pi, q], 1))
+        return periods.copy()
 
     def loo(self, x, y, w=None, score="log"):
         """Layer-wise leave-one-out cross-validation under the prior model (`GPAR.loo`): `(value, mean, var)`.  `value` is the sum

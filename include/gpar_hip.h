@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 18
+#define GPAR_ABI_VERSION 19
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -218,6 +218,30 @@ int gpar_gram_terms_diag(const gpar_kspec_t* ks, const int* comp, int ncomp, con
 int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* zs, int ns, int ldzs, const double* z, int n,
                          int ldz, int dz, const double* alpha, const double* L, int ldl, double* mean, int ldm, double* var, int ldv,
                          double* ws, long long ws_doubles, void* stream);
+
+/* Generalised Lomb-Scargle periodogram (ABI v19; Zechmeister & Kuerster 2009: floating mean, weights) of p irregularly sampled series
+ * that share their time stamps - where a spectral-mixture layer's periods should start (Wilson & Adams 2013 initialise from the
+ * empirical spectrum).  t: n time stamps in any order, duplicates allowed.  y, omega: n x p row-major (ldy, ldo >= p); omega >= 0 are the
+ * observation weights and omega == 0 marks an unobserved entry, whose y is never read.  freq: nf frequencies > 0 in cycles per unit of t.
+ * power: p x nf row-major (ldp >= nf), power[j * ldp + k] in [0, 1].  For output j and frequency f, with w = omega / sum(omega) over the
+ * column and phi_i = 2 pi f (t_i - t0):
+ *     C = sum w cos phi   S = sum w sin phi   Y = sum w y   YY = sum w y^2 - Y^2   YC = sum w y cos phi - Y C   YS = sum w y sin phi - Y S
+ *     CC = sum w cos^2 phi - C^2   SS = (1 - sum w cos^2 phi) - S^2   CS = sum w cos phi sin phi - C S   D = CC SS - CS^2
+ *     power = (SS YC^2 + CC YS^2 - 2 CS YC YS) / (YY D)
+ * The phase is formed as t_i - t0 first, then 2 f (t_i - t0), and evaluated with sincospi (its reduction to half periods is exact): pass
+ * t0 = min t and time stamps like 1e6 lose nothing beyond the rounding of t_i - t0.  Every (row, frequency) pair has its own sincospi
+ * - no recurrence along the grid -, shared by up to 4 outputs (more outputs: chunks of 4, each repeating it).  y enters centred by the
+ * column's weighted mean (the power is invariant under affine maps of y).
+ * Degenerate cases give power exactly 0, never NaN or Inf.  With tiny = 16 n 2^-52 (the sums are of magnitude 1 once the weights are
+ * normalised, and carry about n 2^-53 of rounding): fewer than 3 observed rows; YY <= tiny^2 mean^2 (constant y); D <= tiny; a frequency
+ * that is not a positive finite number.
+ * The sum over the rows has a fixed order that depends on n alone (csrc/periodogram.h): two calls return the same bits, and the power
+ * at a frequency has the same bits computed alone or inside any grid.  No atomics, no allocation, no synchronisation.
+ * n == 0 or nf == 0: nothing is done, 0 is returned (power untouched).  Argument errors - n or nf negative, p < 1, ldy or ldo < p,
+ * ldp < nf, t0 not finite, a NULL array with n, nf > 0 - are found before the launch: a negative status, power untouched.
+ * [no reference counterpart; in Python: GPARRegressor.periodogram, spectral_period="auto"] */
+int gpar_periodogram(const double* t, int n, double t0, const double* y, int ldy, const double* omega, int ldo, int p, const double* freq,
+                     int nf, double* power, int ldp, void* stream);
 
 /* Greedy (partially pivoted) Cholesky of k(Z, Z) (ABI v10): the selection of inducing points by largest conditional variance (Fine &
  * Scheinberg 2001; the initialisation Burt et al. 2019 recommend for sparse variational GPs).  z: n x dz features as gpar_featurize
