@@ -28,6 +28,7 @@ WS_CV_GAP = 11
 WS_AHEAD_MULTI = 12
 WS_AHEAD_WINDOW = 13
 WS_POSTERIOR_TERMS = 14
+WS_GRAM_APPLY = 15
 AHEAD_WINDOW_MAX = 64   # GPAR_AHEAD_WINDOW_MAX: the longest window (rows) the fused sliding-window forecast entries take
 AHEAD_MAX_HORIZONS = 8   # GPAR_AHEAD_MAX_HORIZONS: the most horizons the fused multi-horizon rolling-origin entries take
 PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
@@ -36,7 +37,7 @@ SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the sc
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -122,6 +123,13 @@ SIGNATURES = {
         _c_int,
         [ctypes.POINTER(KSpec), ctypes.POINTER(_c_int), _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr,
          _c_int, _ptr, ctypes.c_longlong, _ptr],
+    ),
+    # (pathwise posterior sampling: the random Fourier prior and the fused cross-Gram-times-vector, rows in groups)
+    "gpar_rff_apply": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr]),
+    "gpar_gram_apply_groups": (
+        _c_int,
+        [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, ctypes.c_longlong,
+         _ptr],
     ),
     "gpar_periodogram": (_c_int, [_ptr, _c_int, _c_dbl, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr]),
     "gpar_pivoted_chol": (_c_int, [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),

@@ -16,6 +16,7 @@
 #include "score.h"   // the scoring rules of the held-out objectives
 #include "periodogram.h"   // generalised Lomb-Scargle periodogram (gpar_periodogram)
 #include "gram_terms.h"   // posterior decomposition by kernel component: its kernels and the chain of gpar_posterior_terms
+#include "pathwise.h"   // pathwise posterior sampling: gpar_rff_apply, gpar_gram_apply_groups
 
 namespace gpar {
 
@@ -1872,6 +1873,32 @@ int gpar_periodogram(const double* t, int n, double t0, const double* y, int ldy
     return periodogram_launch(t, n, t0, y, ldy, omega, ldo, p, freq, nf, power, ldp, (hipStream_t)stream);
 }
 
+// ---- pathwise posterior sampling (ABI v20; pathwise.h) --------------------------------------------------------------------------------------------
+// Argument errors are found before anything is launched: no output is touched.
+int gpar_rff_apply(const double* z, int rows, int ldz, int dz, const double* shift, const double* omega, int ldw, int nfreq, const double* thc,
+                   const double* ths, int ldt, int count, int group_rows, double* out, int ldo, void* stream) {
+    GPAR_API_GUARD;
+    return rff_apply_launch(z, rows, ldz, dz, shift, omega, ldw, nfreq, thc, ths, ldt, count, group_rows, out, ldo, (hipStream_t)stream);
+}
+
+int gpar_gram_apply_groups(const gpar_kspec_t* ks, const double* zs, int rows, int ldzs, const double* z, int n, int ldz, int dz, const double* vt,
+                           int ldv, int count, int group_rows, double* out, int ldo, double* ws, long long ws_doubles, void* stream) {
+    GPAR_API_GUARD;
+    TermGroups tg;
+    const int every[GPAR_MAX_TERMS] = {0, 0, 0, 0, 0, 0, 0, 0};   // one component holding every term
+    static_assert(GPAR_MAX_TERMS == 8, "the grouping above names every term");
+    const int rc = term_groups_check(ks, every, 1, dz, tg);
+    if (rc) return rc;
+    if (n < 0 || rows < 0 || count < 0 || group_rows < 0) return GPAR_ARG_ERROR(5);
+    if (group_rows > 0 && (long long)group_rows * count != rows) return GPAR_ARG_ERROR(5);
+    if (rows == 0 || count == 0) return 0;
+    if (!zs || !out || ldzs < dz || (n > 0 && (!z || !vt || ldz < dz || ldv < n))) return GPAR_ARG_ERROR(6);
+    if (group_rows == 0 && ldo < count) return GPAR_ARG_ERROR(7);
+    if (!ws || ws_doubles < (long long)rows * (group_rows > 0 ? 1 : count)) return GPAR_ARG_ERROR(8);
+    return gram_apply_groups_run(ks, tg, zs, rows, ldzs, z, n, ldz, dz, vt, ldv, count, group_rows, out, group_rows > 0 ? 1 : ldo, ws, ws_doubles,
+                                 (hipStream_t)stream);
+}
+
 int gpar_potrf(double* A, int N, int nf, int lda, double* logdet, int* info, void* stream) {
     GPAR_API_GUARD;
     if (N <= 0 || nf <= 0) return 0;
@@ -2038,6 +2065,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_PIVOTED_CHOL: return pc_workspace_doubles(a);                       /* n */
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         case GPAR_WS_POSTERIOR_TERMS: return pt_workspace_doubles(a, b, c);              /* n, ns, ncomp */
+        case GPAR_WS_GRAM_APPLY: return ga_workspace_doubles(a, b, c);                   /* n, rows, output columns (1 with groups) */
         default: return -1;
     }
 }

@@ -213,6 +213,16 @@ class HipEngine:
             t0 = float(t.min().item()) if t.numel() else 0.0
         return hip.periodogram(t, y, omega, freq, t0)
 
+    # ---- pathwise posterior sampling (gpar_rff_apply, gpar_gram_apply_groups) ----------------------------------------
+    def rff_apply(self, z, dz, shift, omega, thc, ths, group_rows=0):
+        """The random Fourier prior at the feature rows z: a vector (rows in groups of `group_rows`, one weight column each) or, with
+        group_rows = 0, rows x S (every row meets every column)."""
+        return hip.rff_apply(self._mat(z), dz, shift, self._mat(omega), self._mat(thc), self._mat(ths), group_rows=group_rows)
+
+    def gram_apply_groups(self, ck, zs, z, vt, group_rows=0):
+        """sum_a k(zs_r, z_a) vt[g(r), a] in one fused pass (no rows x n matrix): a vector with groups, rows x S without."""
+        return hip.gram_apply_groups(ck, self._mat(zs), self._mat(z), self._mat(vt), group_rows=group_rows)
+
     def pivoted_cholesky(self, ck, z, max_rank, tol=0.0, floor=None):
         """Greedy (partially pivoted) Cholesky of k(z, z) on the features z in one library call (gpar_pivoted_chol): (Lt, piv, trace, rank)
         as device tensors - the factor transposed (max_rank x n, zero rows from the rank on), the pivots (-1 beyond the rank), the

@@ -62,6 +62,13 @@ def fused_terms():
     return os.environ.get("GPAR_FUSED_TERMS", "1") != "0"
 
 
+def fused_pathwise():
+    """GPAR_FUSED_PATHWISE=0: pathwise sampling (`Obs.pathwise_sample_batch`) through the composed route - `pathwise.feature_map`, torch
+    cos / sin, `eng.gram` + `eng.gemm` in chunks - on every engine; default: the two library calls (gpar_rff_apply,
+    gpar_gram_apply_groups) where the engine has them."""
+    return os.environ.get("GPAR_FUSED_PATHWISE", "1") != "0"
+
+
 def _as_matrix(eng, x):
     """Engine tensor of rank 2 (`B.uprank`: a vector becomes a column)."""
     t = eng.tensor(x)
@@ -1618,6 +1625,93 @@ class Obs:
                         eng.check_info(info)
                         draw = eng.trmv_lower(cov, zr[:, s0 + k : s0 + k + 1])
                         out[:, s0 + k : s0 + k + 1] = draw if mean is None else draw + mean
+        return out
+
+    # ---- pathwise sampling (Matheron's rule; dense observations of the prior) ----------------------------------------
+    def _pathwise_prior(self, basis, zf, theta, group_rows, fused):
+        """The prior draws Phi(z) theta at the feature rows zf: rows x S (group_rows = 0: every row meets every column) or a vector
+        (rows in groups of group_rows, group g uses column g).  Fused: the Fourier part in one library call, the few exact features by
+        torch; composed: Phi in chunks of rows by torch."""
+        eng, F = self.eng, basis.num_frequencies
+        rows, S = int(zf.shape[0]), int(theta.shape[1])
+
+        def apply(phi, tht, r0):
+            if not group_rows:
+                return phi @ tht
+            col = torch.arange(r0, r0 + phi.shape[0], device=phi.device) // group_rows
+            return (phi * tht.index_select(1, col).T).sum(dim=1)
+
+        if fused:
+            omega, amp, shift, _, _, _ = basis.on(zf)
+            out = eng.rff_apply(zf, basis.dz, shift, omega, theta[:F] * amp[:, None], theta[F : 2 * F] * amp[:, None], group_rows=group_rows)
+            if basis.num_weights > 2 * F:
+                out = out + apply(basis.exact_phi(zf), theta[2 * F :], 0)
+            return out
+        out = torch.empty((rows,) if group_rows else (rows, S), dtype=torch.float64, device=zf.device)
+        step = max(1, int(2 ** 27 // max(1, basis.num_weights)))   # (Phi of a chunk: at most 1 GiB)
+        for r0 in range(0, rows, step):
+            out[r0 : r0 + step] = apply(basis.phi(zf[r0 : r0 + step]), theta, r0)
+        return out
+
+    def pathwise_sample_batch(self, xs, noise, basis, S, draws=None):
+        """S posterior draws by pathwise conditioning (Wilson et al., ICML 2020), n* x S:
+
+            f*_s(.) = f_s(.) + k(., X) (K + D + eps I)^-1 (y - f_s(X) - e_s),      f_s = Phi theta_s,  e_s ~ N(0, D)
+
+        with Phi the `pathwise.Basis` of this layer's kernel (shared by the S draws, which are independent given it), D the observation
+        noise and (K + D + eps I) the factor conditioning holds (eps: the engine's jitter).  `xs`: a `Stacked` of S design matrices
+        (group s is draw s's) or one matrix all draws share.  `noise`: added to the draws as N(0, noise) when not None.  Per draw what
+        remains is an n-vector solve, a fused cross-Gram-times-vector over n* n pairs and a fused feature evaluation over n* F pairs: no
+        n* x n* matrix exists, and the fused route writes no n* x n matrix either.  `draws`: (theta, e, xi) standard normals to use
+        instead of the engine's (num_weights x S, n x S, n* x S) - for tests.  A posterior base process: ValueError."""
+        from .pathwise import feature_map
+
+        if self.base.is_posterior:
+            raise ValueError("pathwise sampling needs dense observations of a prior process")
+        eng, fac, n = self.eng, self.factor(), self.fdd.n
+        ck, z = self.fdd.features()
+        grouped = isinstance(xs, Stacked)
+        if grouped and len(xs) != S:
+            raise ValueError(f"{len(xs)} stacked design matrices for {S} draws")
+        xmat = _as_matrix(eng, xs.matrix if grouped else xs)
+        ns = xs.rows if grouped else int(xmat.shape[0])
+        group_rows = ns if grouped else 0
+        if ns == 0 or S == 0:
+            return torch.empty(ns, S, dtype=torch.float64, device=xmat.device)
+        fused = fused_pathwise() and hasattr(eng, "rff_apply") and hasattr(eng, "gram_apply_groups")
+        zs = eng.features(ck, xmat)   # what the Gram passes read (the oracle engine: the design matrix itself)
+        zf_train, zf_test = (z, zs) if fused else (feature_map(ck.kernel, self.fdd.x), feature_map(ck.kernel, xmat))
+        if basis.shift is None:
+            basis = basis.with_shift(zf_train)
+        theta, e, xi = draws if draws is not None else (None, None, None)
+        theta = eng.randn(basis.num_weights, S) if theta is None else eng.tensor(theta)
+        out = self._pathwise_prior(basis, zf_test, theta, group_rows, fused)
+        if n > 0:
+            R = self.y - self._pathwise_prior(basis, zf_train, theta, 0, fused)
+            if self.fdd.noise is not None:
+                R = R - torch.sqrt(self.fdd.noise)[:, None] * (eng.randn(n, S) if e is None else eng.tensor(e))
+            Vt = eng.new_matrix(S, n)   # v_s^T = R_s^T L^-T L^-1, row s
+            Vt.copy_(R.T)
+            eng.trsm_rlt_(fac.L, Vt)
+            eng.trsm_rln_(fac.L, Vt)
+            if fused:
+                out = out + eng.gram_apply_groups(ck, zs, z, Vt, group_rows=group_rows)
+            elif grouped:
+                chunk = self._chunk(ns)
+                for s0 in range(0, S, chunk):
+                    s1 = min(S, s0 + chunk)
+                    Ks = eng.gram(ck, zs[s0 * ns : s1 * ns], z)
+                    for k in range(s1 - s0):
+                        out[(s0 + k) * ns : (s0 + k + 1) * ns] += eng.gemm(Ks[k * ns : (k + 1) * ns], Vt[s0 + k : s0 + k + 1], tb=True).reshape(-1)
+            else:
+                step = max(1, int(2e9 // (8 * n)))
+                for r0 in range(0, ns, step):
+                    out[r0 : r0 + step] += eng.gemm(eng.gram(ck, zs[r0 : r0 + step], z), Vt, tb=True)
+        if grouped:
+            out = out.reshape(S, ns).T
+        nv = _noise_vector(eng, noise, ns)
+        if nv is not None:
+            out = out + torch.sqrt(nv)[:, None] * (eng.randn(ns, S) if xi is None else eng.tensor(xi))
         return out
 
 

@@ -20,6 +20,8 @@ __all__ = [
     "gram",
     "gram_diag",
     "periodogram",
+    "rff_apply",
+    "gram_apply_groups",
     "pivoted_chol",
     "chol_drop_leading",
     "chol_append_",
@@ -840,6 +842,51 @@ def periodogram(t, y, omega, freq, t0):
         "gpar_periodogram",
     )
     return power
+
+
+def rff_apply(z, dz, shift, omega, thc, ths, group_rows=0):
+    """The random Fourier prior of pathwise sampling at the feature rows z (gpar_rff_apply; semantics: include/gpar_hip.h):
+    sum_j thc[j, c] cos(2 pi omega_j . (z_r - shift)) + ths[j, c] sin(...).  group_rows > 0: z holds S = thc.shape[1] groups of group_rows
+    rows, row r uses column r // group_rows, a vector of z.shape[0] values comes back; group_rows = 0: every row meets every column,
+    rows x S."""
+    lib = _lib.load()
+    for a, name in ((z, "z"), (shift, "shift"), (omega, "omega"), (thc, "thc"), (ths, "ths")):
+        _check_mat(a, name)
+    rows, nfreq, count = int(z.shape[0]), int(omega.shape[0]), int(thc.shape[1])
+    shift, thc, ths = shift.reshape(-1).contiguous(), thc.contiguous(), ths.contiguous()   # (one leading dimension for both weight matrices)
+    if tuple(ths.shape) != tuple(thc.shape) or thc.shape[0] != nfreq or shift.numel() < dz or (nfreq and omega.shape[1] < dz) or (dz and z.shape[1] < dz):
+        raise ValueError("rff_apply: omega must be F x dz, thc and ths F x S, shift dz long, z rows x dz")
+    out = torch.empty(rows, dtype=torch.float64, device=z.device) if group_rows else torch.empty(rows, max(count, 1), dtype=torch.float64, device=z.device)
+    _lib.check(
+        lib.gpar_rff_apply(z.data_ptr(), rows, _ld(z), int(dz), shift.data_ptr(), omega.data_ptr(), _ld(omega), nfreq, thc.data_ptr(),
+                           ths.data_ptr(), max(count, 1), count, int(group_rows), out.data_ptr(), max(count, 1),
+                           stream_ptr(z.device)),
+        "gpar_rff_apply",
+    )
+    return out if group_rows else out[:, :count]
+
+
+def gram_apply_groups(ck, zs, z, vt, group_rows=0, ws_doubles=None):
+    """sum_a k(zs_r, z_a) vt[c, a] without the rows x n matrix (gpar_gram_apply_groups): vt is S x n.  group_rows > 0: zs holds S groups of
+    group_rows rows, row r uses vt[r // group_rows], a vector comes back; group_rows = 0: every row meets every vector, rows x S.
+    `ws_doubles`: the workspace to bring instead of the recommended one (a small one allows fewer splits of the training rows)."""
+    lib = _lib.load()
+    for a, name in ((zs, "zs"), (z, "z"), (vt, "vt")):
+        _check_mat(a, name)
+    rows, n, count = int(zs.shape[0]), int(z.shape[0]), int(vt.shape[0])
+    if vt.dim() != 2 or vt.shape[1] != n:
+        raise ValueError("vt must be S x n: one vector per row")
+    ncols = 1 if group_rows else count
+    if ws_doubles is None:
+        ws_doubles = lib.gpar_workspace_doubles(_lib.WS_GRAM_APPLY, n, rows, max(ncols, 1))
+    ws = torch.empty(max(int(ws_doubles), 2), dtype=torch.float64, device=zs.device)
+    out = torch.empty(rows, dtype=torch.float64, device=zs.device) if group_rows else torch.empty(rows, max(count, 1), dtype=torch.float64, device=zs.device)
+    _lib.check(
+        lib.gpar_gram_apply_groups(ctypes.byref(ck.kspec), zs.data_ptr(), rows, _ld(zs), z.data_ptr(), n, _ld(z), ck.dz, vt.data_ptr(), _ld(vt),
+                                   count, int(group_rows), out.data_ptr(), max(count, 1), ws.data_ptr(), int(ws_doubles), stream_ptr(zs.device)),
+        "gpar_gram_apply_groups",
+    )
+    return out if group_rows else out[:, :count]
 
 
 def pivoted_chol(ck, z, max_rank, tol_trace, floor):

@@ -885,7 +885,7 @@ class GPAR:
             return torch.zeros(x.shape[0], 0, dtype=torch.float64, device=x.device)
         return torch.cat(columns, dim=1)
 
-    def sample_many(self, x, w, num_samples, latent=False, marginal=False):
+    def sample_many(self, x, w, num_samples, latent=False, marginal=False, sampler="exact", features=2048):
         """`num_samples` independent ancestral samples (the loop of reference regression.py:559-563), computed layer by
         layer for all samples at once.  While every sample still sees the same design matrix (always at layer 0;
         at every layer when `replace` feeds posterior means forward) one factorisation serves all draws; once the
@@ -894,7 +894,24 @@ class GPAR:
         `marginal` (not in the reference; off by default): within a layer every point is drawn from its own marginal
         N(mean_j, var_j) instead of the joint law over the n* points.  Per-point predictive statistics (what `predict`
         reports: means and marginal percentiles) have the same distribution; the joint law of one sample across points
-        does not, so `sample` keeps the joint sampler.  No n* x n* covariance is built or factored."""
+        does not, so `sample` keeps the joint sampler.  No n* x n* covariance is built or factored.
+
+        `sampler` (an addition): "exact", the above, or "pathwise" - every layer's draws by pathwise conditioning
+        (`Obs.pathwise_sample_batch`: a prior draw through a random Fourier basis of `features` frequencies per stationary kernel
+        term plus one exact update from the factor the layer holds): per draw and layer an n-vector solve and two fused passes instead
+        of an n* x n solve, a rank-n downdate and an n* x n* factorisation, and no limit on n*.  One basis per layer and call, seeded
+        from the engine's seed and shared by the draws, which are independent given it.  For a conditioned model with dense layers;
+        inducing points, `marginal` and a kernel term without a basis (`pathwise.draw_basis`) are a ValueError."""
+        if sampler not in ("exact", "pathwise"):
+            raise ValueError(f'sampler must be "exact" or "pathwise" (got {sampler!r})')
+        if int(features) < 1:
+            raise ValueError(f"features must be at least 1 (got {features})")
+        if sampler == "pathwise":
+            if self.sparse:
+                raise ValueError('sampler="pathwise" needs dense layers: inducing points are not supported')
+            if marginal:
+                raise ValueError('sampler="pathwise" draws jointly over the points already: marginal=True does not apply')
+            return _retry_unfused(lambda: self._sample_many_pathwise(x, w, num_samples, latent, int(features)), self.layers, (x, w), rewind=True)
         if num_samples == 1 and not marginal:
             return [self.sample(x, w, latent=latent)]
         return _retry_unfused(lambda: self._sample_many(x, w, num_samples, latent, marginal), self.layers, (x, w), rewind=True)
@@ -941,6 +958,47 @@ class GPAR:
             else:
                 xs = xs.with_columns(fed)
         # one stack (n* x S x p) and S views of it, instead of S stacks of p columns each
+        return list(torch.stack(columns, dim=2).permute(1, 0, 2).unbind(0))
+
+    def _sample_many_pathwise(self, x, w, num_samples, latent, features):
+        """`_sample_many` with every layer's draws made by `Obs.pathwise_sample_batch`; what is fed forward is what `_sample_many` feeds."""
+        from .pathwise import draw_basis
+
+        eng = get_engine()
+        x = eng.tensor(x)
+        if x.dim() == 1:
+            x = x[:, None]
+        w = eng.tensor(w)
+        S, ns = num_samples, x.shape[0]
+        seed, calls = int(getattr(eng, "_seed", 0)), int(getattr(eng, "_calls", 0))
+        shared, xs = True, None
+        columns = []  # per layer: n* x S
+        for i, (is_last, model) in enumerate(last(self.layers)):
+            f, noise = model()
+            obs = getattr(f, "_obs", None)
+            if not isinstance(obs, Obs) or obs.base.is_posterior:
+                raise ValueError('sampler="pathwise" needs a conditioned model: every layer must hold dense observations of its prior')
+            width = int(x.shape[1]) if shared else int(xs.matrix.shape[1])
+            basis = draw_basis(eng.compile(f.kernel, width).kernel, features, np.random.default_rng([seed % 2 ** 63, calls, i]))
+            obs_noise = None if latent else self._noise_over(noise, w[:, i])
+            draws = obs.pathwise_sample_batch(x if shared else xs, obs_noise, basis, S)
+            columns.append(draws)
+            if is_last:
+                break
+            if latent:
+                fed = draws + torch.sqrt(self._noise_over(noise, w[:, i : i + 1])) * eng.randn(ns, S)
+            else:
+                fed = draws
+            if self.replace:
+                if shared:
+                    x = torch.cat([x, f.mean(x)], dim=1)
+                else:
+                    xs = xs.with_columns(torch.cat(list(f.mean_batch(xs)), dim=0))
+            elif shared:
+                xs = Stacked.repeat(x, S).with_columns(fed)
+                shared = False
+            else:
+                xs = xs.with_columns(fed)
         return list(torch.stack(columns, dim=2).permute(1, 0, 2).unbind(0))
 
     def moments(self, x, w, latent=False):

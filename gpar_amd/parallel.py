@@ -443,18 +443,27 @@ def _sharded_sample_stack(reg, x, w, num_samples, latent, group, marginal=False)
     return torch.cat([gathered[r][: counts[r]] for r in range(size)], dim=0), counts
 
 
-def sharded_sample(reg, x, w=None, num_samples=100, latent=False, group=None):
+def _refuse_pathwise(sampler):
+    """The sharded drivers keep the exact sampler: a pathwise basis would have to be agreed on by the ranks."""
+    if sampler != "exact":
+        raise ValueError(f'the sharded drivers keep the exact sampler (got sampler={sampler!r}): use GPARRegressor.predict / sample for '
+                         'sampler="pathwise"')
+
+
+def sharded_sample(reg, x, w=None, num_samples=100, latent=False, group=None, sampler="exact"):
     """Posterior samples split over ranks (`_sharded_sample_stack`).  Returns the full list of `num_samples` arrays on every
-    rank (the reference's return type: host arrays, regression.py:564)."""
+    rank (the reference's return type: host arrays, regression.py:564).  `sampler`: "exact" only (ValueError otherwise)."""
+    _refuse_pathwise(sampler)
     stack, _ = _sharded_sample_stack(reg, x, w, num_samples, latent, group)
     host = stack.cpu().numpy()
     return [host[k] for k in range(host.shape[0])]
 
 
-def sharded_predict(reg, x, w=None, num_samples=100, latent=False, credible_bounds=False, marginal=False, group=None):
+def sharded_predict(reg, x, w=None, num_samples=100, latent=False, credible_bounds=False, marginal=False, group=None, sampler="exact"):
     """`GPARRegressor.predict` with the samples drawn across the ranks and the Monte-Carlo reduction (mean, central 95 %
     bounds; reference regression.py:589-595) done on the device by `gpar_sample_stats` over the gathered stack - only the
-    n* x p results cross to the host.  Every rank returns the same arrays."""
+    n* x p results cross to the host.  Every rank returns the same arrays.  `sampler`: "exact" only (ValueError otherwise)."""
+    _refuse_pathwise(sampler)
     stack, _ = _sharded_sample_stack(reg, x, w, num_samples, latent, group, marginal=marginal)
     eng = get_engine()
     if num_samples == 1:

@@ -1126,8 +1126,10 @@ class GPARRegressor:
             value = value.detach().cpu().numpy()
         return value
 
-    def _sample_device(self, x, w, p, posterior, num_samples, latent, conditioned=None, marginal=False):
+    def _sample_device(self, x, w, p, posterior, num_samples, latent, conditioned=None, marginal=False, sampler="exact", features=2048):
         """The samples of `sample` as engine tensors (n* x p each), output transforms undone."""
+        if sampler == "pathwise" and not posterior:
+            raise ValueError('sampler="pathwise" conditions prior draws on the data: it needs posterior=True')
         x = _uprank(_to_engine(x))
         if posterior and not self.is_conditioned:
             raise RuntimeError("Must condition or fit model before sampling from the posterior.")
@@ -1147,7 +1149,7 @@ class GPARRegressor:
         else:
             gpar = _construct_gpar(self, self.vs, x.shape[1], p)
         return [self._untransform_y(self._unnormalise_y(s)).detach()
-                for s in gpar.sample_many(x, w, num_samples, latent=latent, marginal=marginal)]
+                for s in gpar.sample_many(x, w, num_samples, latent=latent, marginal=marginal, sampler=sampler, features=features)]
 
     def predict_moments(self, x, w=None, latent=False, _conditioned=None):
         """Predictive means and variances (two n* x p arrays) of the conditioned model at x in CLOSED FORM - for `replace=True`,
@@ -1223,14 +1225,15 @@ class GPARRegressor:
             var = [(v * slope[0, i] ** 2).cpu().numpy() for i, (_, v) in enumerate(parts)] if variance else None
         return Decomposition(tuple(names), mean, var, shift.reshape(-1).cpu().numpy())
 
-    def sample(self, x, w=None, p=None, posterior=False, num_samples=1, latent=False, _conditioned=None):
+    def sample(self, x, w=None, p=None, posterior=False, num_samples=1, latent=False, _conditioned=None, sampler="exact", features=2048):
         """Draw samples from the prior or the posterior at inputs x; a single ndarray for num_samples=1, otherwise
         a list (reference regression.py:508-564).  (`_conditioned`: an already conditioned GPAR, used by the
-        multi-GPU path.)"""
-        samples = [s.cpu().numpy() for s in self._sample_device(x, w, p, posterior, num_samples, latent, _conditioned)]
+        multi-GPU path.)  `sampler`, `features`: as in `predict`; "pathwise" needs `posterior=True`."""
+        samples = [s.cpu().numpy() for s in self._sample_device(x, w, p, posterior, num_samples, latent, _conditioned, sampler=sampler,
+                                                                 features=features)]
         return samples[0] if num_samples == 1 else samples
 
-    def predict(self, x, w=None, num_samples=100, latent=False, credible_bounds=False, marginal=False):
+    def predict(self, x, w=None, num_samples=100, latent=False, credible_bounds=False, marginal=False, sampler="exact", features=2048):
         """Monte-Carlo predictive mean (and central 95% marginal bounds) from posterior samples
         (reference regression.py:566-597).  The reduction over the sample axis runs on the device
         (`gpar_sample_stats`: sequential mean, numpy-"linear" percentiles); only the n* x p results cross PCIe.
@@ -1238,8 +1241,16 @@ class GPARRegressor:
         `marginal=True` (an addition, off by default; reference todo.tasks:5): the statistics returned here only involve
         per-point marginals, so within each layer the points may be drawn from their marginals N(mean_j, var_j)
         instead of jointly - same distribution of every returned number, no n* x n* covariance, SYRK downdate or
-        factorisation per sample (`GPAR.sample_many`)."""
-        samples = self._sample_device(x, w, None, True, num_samples, latent, marginal=marginal)
+        factorisation per sample (`GPAR.sample_many`).
+
+        `sampler="pathwise"` (an addition; the default "exact" is the path above, unchanged): the samples are drawn by pathwise
+        conditioning (Matheron's rule; Wilson et al., ICML 2020) - a prior draw through a random Fourier basis of `features`
+        frequencies per stationary kernel term, corrected by one exact update from the factor conditioning holds.  Joint draws over
+        the n* points without any n* x n* matrix: the cost per sample and layer falls from n^2 n* to n n* + n* `features`, and n* is
+        bounded by the output alone.  The prior part is an approximation that improves with `features` (DESIGN 3.23 tabulates it); the
+        update is exact.  One basis per layer and call, seeded from the engine's seed.  ValueError: inducing points, `marginal=True`,
+        a kernel term without a basis (a linear factor times another), an unknown sampler, `features < 1`."""
+        samples = self._sample_device(x, w, None, True, num_samples, latent, marginal=marginal, sampler=sampler, features=features)
         if num_samples == 1:
             # the reference hands np.mean a single (n*, p) array here, so axis 0 is the input axis; keep that
             samples = samples[0].cpu().numpy()

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 19
+#define GPAR_ABI_VERSION 20
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -242,6 +242,35 @@ int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, con
  * [no reference counterpart; in Python: GPARRegressor.periodogram, spectral_period="auto"] */
 int gpar_periodogram(const double* t, int n, double t0, const double* y, int ldy, const double* omega, int ldo, int p, const double* freq,
                      int nf, double* power, int ldp, void* stream);
+
+/* Pathwise posterior sampling (ABI v20; Matheron's rule - Wilson et al., ICML 2020): a posterior draw is a prior draw through a random
+ * Fourier basis plus one exact data-dependent update,
+ *     f*_s(.) = f_s(.) + k(., X) v_s,    v_s = (K + D)^-1 (y - f_s(X) - eps_s),    f_s(z) = sum_j thc[j, s] cos(phi_j) + ths[j, s] sin(phi_j),
+ * phi_j = 2 pi omega_j . (z - shift).  The two entries below are its two device passes; the solve for v_s uses the factor conditioning
+ * holds.  Rows come in GROUPS - group_rows > 0: rows = count * group_rows, rows g group_rows .. (g + 1) group_rows - 1 use weight column g
+ * (the stacked per-sample design matrices of ancestral sampling), out is a vector of `rows` values - or, group_rows == 0, as one set of
+ * rows that meets every one of the `count` columns: out is rows x count row-major (ldo >= count).  No n* x n, rows x F or n* x n* matrix
+ * is written.  No atomics: every sum has a fixed order that depends on the sizes alone (csrc/pathwise.h), two calls return the same bits,
+ * and a row's value has the same bits whatever other rows, groups or columns the call holds (gpar_gram_apply_groups: among calls that
+ * split the training rows alike - the number of splits follows n, the total number of rows and the workspace).
+ *
+ * gpar_rff_apply: z rows x dz features as gpar_featurize writes them (ldz >= dz), shift dz doubles, omega nfreq x dz in cycles per unit of
+ * z (ldw >= dz), thc / ths nfreq x count (ldt >= count), all DEVICE arrays.  The phase is formed as z - shift first, the dot product by
+ * fma in ascending dims, then sincospi(2 dot) - one per (row, frequency) pair, shared by the columns.  nfreq == 0: zeros.
+ *
+ * gpar_gram_apply_groups: out[r] = sum_a k(zs_r, z_a) vt[g(r) * ldv + a] - the vectors TRANSPOSED, count x n (ldv >= n), as the two
+ * triangular solves leave them.  It is the mean pass of gpar_posterior_terms with one component holding every term: a pair has the bits
+ * gpar_gram gives it.  ws: gpar_workspace_doubles(GPAR_WS_GRAM_APPLY, n, rows, output columns - 1 with groups, count without) doubles
+ * are recommended; any ws_doubles >= rows * (output columns) is taken (fewer splits of the training rows).  n == 0: zeros.
+ *
+ * rows == 0 or count == 0: nothing is done.  Argument errors - a negative size, rows != count * group_rows, dz outside 0 .. GPAR_MAX_DIMS
+ * or a factor reaching past it, leading dimensions or the workspace too small, a NULL array that would be read - are found before the
+ * first launch: a negative status, out untouched.
+ * [no reference counterpart; in Python: predict / sample (sampler="pathwise")] */
+int gpar_rff_apply(const double* z, int rows, int ldz, int dz, const double* shift, const double* omega, int ldw, int nfreq, const double* thc,
+                   const double* ths, int ldt, int count, int group_rows, double* out, int ldo, void* stream);
+int gpar_gram_apply_groups(const gpar_kspec_t* ks, const double* zs, int rows, int ldzs, const double* z, int n, int ldz, int dz, const double* vt,
+                           int ldv, int count, int group_rows, double* out, int ldo, double* ws, long long ws_doubles, void* stream);
 
 /* Greedy (partially pivoted) Cholesky of k(Z, Z) (ABI v10): the selection of inducing points by largest conditional variance (Fine &
  * Scheinberg 2001; the initialisation Burt et al. 2019 recommend for sparse variational GPs).  z: n x dz features as gpar_featurize
@@ -779,6 +808,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_AHEAD_MULTI 12
 #define GPAR_WS_AHEAD_WINDOW 13
 #define GPAR_WS_POSTERIOR_TERMS 14
+#define GPAR_WS_GRAM_APPLY 15   /* (n, rows, output columns)  gpar_gram_apply_groups */
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
