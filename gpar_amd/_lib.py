@@ -29,6 +29,7 @@ WS_AHEAD_MULTI = 12
 WS_AHEAD_WINDOW = 13
 WS_POSTERIOR_TERMS = 14
 WS_GRAM_APPLY = 15
+WS_POSTERIOR_DERIV = 16
 AHEAD_WINDOW_MAX = 64   # GPAR_AHEAD_WINDOW_MAX: the longest window (rows) the fused sliding-window forecast entries take
 AHEAD_MAX_HORIZONS = 8   # GPAR_AHEAD_MAX_HORIZONS: the most horizons the fused multi-horizon rolling-origin entries take
 PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
@@ -37,7 +38,7 @@ SCORES = {"log": 0, "crps": 1, "se": 2}   # GPAR_SCORE_LOG / _CRPS / _SE: the sc
 CV_MAX_FOLD = 64   # GPAR_CV_MAX_FOLD: the largest fold (purged forms: fold and purged rows together) the fused cross-validation entries take
 GRAD_NACC = GPAR_MAX_TERMS + GPAR_MAX_FACTORS + 2 * GPAR_MAX_DIMS
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 LIB_NAME = "libgpar_hip.so"
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -123,6 +124,12 @@ SIGNATURES = {
         _c_int,
         [ctypes.POINTER(KSpec), ctypes.POINTER(_c_int), _c_int, _ptr, _c_int, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr,
          _c_int, _ptr, ctypes.c_longlong, _ptr],
+    ),
+    # (posterior derivatives: zs, J with its leading dimension and per-direction stride, ndir, then the arguments of gpar_posterior_terms)
+    "gpar_posterior_deriv": (
+        _c_int,
+        [ctypes.POINTER(KSpec), _ptr, _c_int, _c_int, _ptr, _c_int, ctypes.c_longlong, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int,
+         _ptr, _c_int, _ptr, _c_int, _ptr, ctypes.c_longlong, _ptr],
     ),
     # (pathwise posterior sampling: the random Fourier prior and the fused cross-Gram-times-vector, rows in groups)
     "gpar_rff_apply": (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr]),

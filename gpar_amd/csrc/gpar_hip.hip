@@ -16,6 +16,7 @@
 #include "score.h"   // the scoring rules of the held-out objectives
 #include "periodogram.h"   // generalised Lomb-Scargle periodogram (gpar_periodogram)
 #include "gram_terms.h"   // posterior decomposition by kernel component: its kernels and the chain of gpar_posterior_terms
+#include "gram_deriv.h"   // posterior derivatives: the kernels and the chain of gpar_posterior_deriv
 #include "pathwise.h"   // pathwise posterior sampling: gpar_rff_apply, gpar_gram_apply_groups
 
 namespace gpar {
@@ -1866,6 +1867,26 @@ int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, con
     return posterior_terms_run(ks, tg, zs, ns, ldzs, z, n, ldz, dz, alpha, L, ldl, mean, ldm, var, ldv, ws, ws_doubles, (hipStream_t)stream);
 }
 
+// ---- posterior derivatives (ABI v21; gram_deriv.h) ----------------------------------------------------------------------------------------------
+// Argument errors are found before anything is launched: no output is touched.
+int gpar_posterior_deriv(const gpar_kspec_t* ks, const double* zs, int ns, int ldzs, const double* J, int ldj, long long stride_j, int ndir,
+                         const double* z, int n, int ldz, int dz, const double* alpha, const double* L, int ldl, double* mean, int ldm, double* var,
+                         int ldv, double* ws, long long ws_doubles, void* stream) {
+    GPAR_API_GUARD;
+    DerivPlan pl;
+    const int rc = deriv_check(ks, ndir, dz, pl);
+    if (rc) return rc;
+    if (n < 0 || ns < 0) return GPAR_ARG_ERROR(5);
+    if (ns == 0) return 0;
+    if (!zs || !mean || ldzs < dz || (dz > 0 && (!J || ldj < dz || (ndir > 1 && stride_j < (long long)(ns - 1) * ldj + dz)))) return GPAR_ARG_ERROR(6);
+    if (n > 0 && (!z || !alpha || ldz < dz || (var && (!L || ldl < n)))) return GPAR_ARG_ERROR(6);
+    if (ldm < ns || (var && ldv < ns)) return GPAR_ARG_ERROR(7);
+    if (!ws || ws_doubles < (long long)ndir * ns || (var && n > 0 && ws_doubles < pt_row_doubles(n, ndir))) return GPAR_ARG_ERROR(8);
+    if (pd_lds_bytes(dz, ndir, true) > PD_MAX_LDS) return GPAR_ARG_ERROR(9);   // the tiles of features and directions must fit the LDS
+    return posterior_deriv_run(ks, pl, zs, ns, ldzs, J, ldj, stride_j, ndir, z, n, ldz, dz, alpha, L, ldl, mean, ldm, var, ldv, ws, ws_doubles,
+                               (hipStream_t)stream);
+}
+
 // ---- generalised Lomb-Scargle periodogram (ABI v19; periodogram.h) ------------------------------------------------------------------------------
 int gpar_periodogram(const double* t, int n, double t0, const double* y, int ldy, const double* omega, int ldo, int p, const double* freq, int nf,
                      double* power, int ldp, void* stream) {
@@ -2066,6 +2087,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_CHOL_UPDATE: return cu_workspace_doubles(a, b);                     /* n, k */
         case GPAR_WS_POSTERIOR_TERMS: return pt_workspace_doubles(a, b, c);              /* n, ns, ncomp */
         case GPAR_WS_GRAM_APPLY: return ga_workspace_doubles(a, b, c);                   /* n, rows, output columns (1 with groups) */
+        case GPAR_WS_POSTERIOR_DERIV: return pt_workspace_doubles(a, b, c);              /* n, ns, ndir */
         default: return -1;
     }
 }

@@ -204,6 +204,15 @@ class HipEngine:
     def posterior_terms(self, ck, comp, ncomp, zs, z, alpha, L, variance=True):
         return hip.posterior_terms(ck, comp, ncomp, zs, z, alpha, L, variance=variance)
 
+    # ---- posterior derivatives (gpar_posterior_deriv) -------------------------------------------------------------------
+    def feature_directions(self, ck, xs, U):
+        """J (ndir x n* x dz) from design-space directions U at the design rows xs (hip.feature_directions)."""
+        return hip.feature_directions(ck, self._mat(xs), U)
+
+    def posterior_deriv(self, ck, zs, J, z, alpha, L, variance=True):
+        """(dmean, dvar), each ndir x n*, of one conditioned dense layer along the feature-space directions J - one library call."""
+        return hip.posterior_deriv(ck, zs, J, z, alpha, L, variance=variance)
+
     # ---- generalised Lomb-Scargle periodogram (gpar_periodogram) ----------------------------------------------------
     def periodogram(self, t, y, omega, freq, t0=None):
         """power (p x F, a device tensor) of the p columns of y (n x p) with weights omega (0 = unobserved) at the time stamps t and

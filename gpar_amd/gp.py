@@ -725,6 +725,15 @@ class GP:
             raise ValueError("a decomposition by kernel component needs a conditioned process")
         return self._obs.components(self._pts(x), comp, ncomp, variance)
 
+    def derivative_moments(self, x, U, variance=True):
+        """(dmean, dvar), each ndir x n*, of the directional derivatives of the process at x along the design-space directions U
+        (`Obs.derivatives`), for a process conditioned on dense observations of its prior.  Inducing points: ValueError."""
+        if isinstance(self._obs, PseudoObs):
+            raise ValueError("posterior derivatives need dense observations: inducing points are not supported")
+        if not self.is_posterior:
+            raise ValueError("posterior derivatives need a conditioned process")
+        return self._obs.derivatives(self._pts(x), U, variance)
+
     def sample_batch(self, xs, noise=None):
         """One draw of f (+ noise) at each input set in `xs` (a list of n* x D matrices, e.g. the per-sample design
         matrices of ancestral sampling): returns an n* x len(xs) matrix.  For a dense posterior the expensive step -
@@ -1425,6 +1434,36 @@ class Obs:
             _, z = self.fdd.features()
             return eng.posterior_terms(p.ck, comp, ncomp, p.z, z, fac.alpha(), fac.L, variance=variance)
         return self._components_composed(p, comp, ncomp, variance)
+
+    # ---- posterior derivatives (dense observations of the prior) -----------------------------------------
+    def derivatives(self, p, U, variance=True):
+        """(dmean, dvar), each ndir x n*: mean and latent variance of the directional derivatives of the posterior at the points `p` along
+        the design-space directions `U` (n* x width: one direction per row; or ndir x n* x width) - the derivative of a Gaussian process
+        is a Gaussian process (Rasmussen & Williams 9.4):
+            dmean = u . grad_x k(x*, X) alpha,        dvar = u^T [grad_x grad_x'^T k](x*, x*) u - |L^-1 (u . grad_x k(x*, X))^T|^2
+        with alpha = K^-1 y and L the factor conditioning holds.  One library call (`posterior_deriv`: no n* x n matrix for the means, one
+        triangular solve for all variances); an engine without it raises NotImplementedError.  `dvar` is None without `variance`.
+        ValueError: observations of a posterior process, a Matern 1/2 factor (its process is not differentiable)."""
+        if self.base.is_posterior:
+            raise ValueError("posterior derivatives need dense observations of a prior process")
+        if any(f.type == "matern12" for t in self.base.kernel.terms for f in t.factors):
+            raise ValueError("a Matern 1/2 process is not differentiable: no posterior derivatives")
+        eng = self.eng
+        if not hasattr(eng, "posterior_deriv"):
+            raise NotImplementedError(f"{type(eng).__name__} has no posterior_deriv: posterior derivatives are a device kernel "
+                                      "(gpar_posterior_deriv); run them on the HIP engine")
+        U = eng.tensor(U)
+        if U.dim() == 2:
+            U = U[None]
+        if U.dim() != 3 or tuple(U.shape[1:]) != tuple(p.x.shape) or not 1 <= U.shape[0] <= GPAR_MAX_TERMS:
+            raise ValueError(f"directions must be n* x width or ndir x n* x width with 1 <= ndir <= {GPAR_MAX_TERMS}, one row per point")
+        if p.n == 0:
+            empty = torch.zeros(U.shape[0], 0, dtype=torch.float64, device=p.x.device)
+            return empty, (empty.clone() if variance else None)
+        fac = self.factor()
+        _, z = self.fdd.features()
+        J = eng.feature_directions(p.ck, p.x, U)
+        return eng.posterior_deriv(p.ck, p.z, J, z, fac.alpha(), fac.L, variance=variance)
 
     def _components_composed(self, p, comp, ncomp, variance):
         eng, fac, n = self.eng, self.factor(), self.fdd.n

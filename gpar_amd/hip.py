@@ -825,6 +825,63 @@ def posterior_terms(ck, comp, ncomp, zs, z, alpha, L, variance=True, ws_doubles=
     return mean, var
 
 
+def feature_directions(ck, xs, U):
+    """J (ndir x n* x dz): the feature-space image of the design-space directions `U` (n* x width, or ndir x n* x width) at the design
+    rows `xs` under the feature map of the compiled kernel `ck`:
+        J[c][a][q] = U[c][a][col[q]] * d embed_q / d x (xs[a][col[q]]) * inv_scale[q],
+    d embed / d x = 1 (identity), freq cos(freq x) (sin dim), -freq sin(freq x) (cos dim) - what gpar_posterior_deriv takes for J.  torch
+    on the device of `xs`: the feature map's few numbers go over as kernel arguments' data, nothing comes back."""
+    fs, dz = ck.fspec, int(ck.dz)
+    U3 = U if U.dim() == 3 else U[None]
+    if xs.dim() != 2 or U3.shape[1] != xs.shape[0] or U3.shape[2] != xs.shape[1] or xs.shape[1] != ck.width:
+        raise ValueError(f"directions must be n* x width (or ndir x n* x width) over design rows of width {ck.width}")
+    if dz == 0:
+        return torch.zeros(U3.shape[0], xs.shape[0], 0, dtype=torch.float64, device=xs.device)
+    col = torch.tensor([int(fs.col[q]) for q in range(dz)], dtype=torch.long).to(xs.device, non_blocking=True)
+    spec = torch.tensor([[float(fs.inv_scale[q]) for q in range(dz)], [float(fs.freq[q]) for q in range(dz)],
+                         [float(fs.embed[q]) for q in range(dz)]], dtype=torch.float64).to(xs.device, non_blocking=True)
+    inv_scale, freq, embed = spec[0], spec[1], spec[2]
+    phase = xs.index_select(1, col) * freq
+    slope = torch.where(embed == float(_lib.EMBED_SIN), freq * torch.cos(phase),
+                        torch.where(embed == float(_lib.EMBED_COS), -freq * torch.sin(phase), torch.ones_like(phase)))
+    return (U3.index_select(2, col) * (slope * inv_scale)[None]).contiguous()
+
+
+def posterior_deriv(ck, zs, J, z, alpha, L, variance=True, ws_doubles=None):
+    """(dmean, dvar), each ndir x n*: mean and latent variance of the directional derivatives of the conditioned dense layer with training
+    features `z`, alpha = K^-1 y and factor `L`, at the test features `zs` along the feature-space directions `J` (ndir x n* x dz,
+    `feature_directions`) - one library call (gpar_posterior_deriv).  `dvar` is None without `variance`.  `ws_doubles`: the workspace to
+    bring instead of the recommended one (a small one means fewer splits of the mean pass and several chunks of test rows)."""
+    lib = _lib.load()
+    _check_mat(zs, "zs")
+    _check_mat(z, "z")
+    _check_mat(L, "L")
+    ns, n = zs.shape[0], z.shape[0]
+    if J.dim() != 3 or J.shape[1] != ns or J.shape[2] != ck.dz or J.dtype != torch.float64 or not J.is_cuda:
+        raise ValueError("J must be an ndir x n* x dz fp64 device tensor")
+    J = J.contiguous()
+    ndir = int(J.shape[0])
+    alpha = alpha.reshape(-1).contiguous()
+    if alpha.numel() != n or alpha.dtype != torch.float64 or not alpha.is_cuda:
+        raise ValueError("alpha must hold one fp64 device value per training row")
+    if L.shape[0] != n or L.shape[1] != n:
+        raise ValueError("L must be the n x n factor of the training covariance")
+    if ws_doubles is None:
+        ws_doubles = lib.gpar_workspace_doubles(_lib.WS_POSTERIOR_DERIV, n, ns, ndir)
+    if ws_doubles < 0:
+        raise ValueError(f"no workspace size for n={n}, n*={ns}, ndir={ndir}")
+    ws = torch.empty(max(int(ws_doubles), 2), dtype=torch.float64, device=zs.device)
+    mean = torch.empty(ndir, ns, dtype=torch.float64, device=zs.device)
+    var = torch.empty(ndir, ns, dtype=torch.float64, device=zs.device) if variance else None
+    _lib.check(
+        lib.gpar_posterior_deriv(ctypes.byref(ck.kspec), zs.data_ptr(), ns, _ld(zs), J.data_ptr(), max(ck.dz, 1), ns * max(ck.dz, 1), ndir,
+                                 z.data_ptr(), n, _ld(z), ck.dz, alpha.data_ptr(), L.data_ptr(), _ld(L), mean.data_ptr(), max(ns, 1),
+                                 None if var is None else var.data_ptr(), max(ns, 1), ws.data_ptr(), int(ws_doubles), stream_ptr(zs.device)),
+        "gpar_posterior_deriv",
+    )
+    return mean, var
+
+
 def periodogram(t, y, omega, freq, t0):
     """power (p x F): the generalised Lomb-Scargle periodogram of the p columns of y (n x p; weights omega, 0 = unobserved) at the time
     stamps t (n) and frequencies freq (F), phases counted from the host number t0 (gpar_periodogram; semantics: include/gpar_hip.h)."""

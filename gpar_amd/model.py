@@ -1058,6 +1058,41 @@ class GPAR:
                     x = torch.cat([x, f.mean(x).reshape(-1, 1)], dim=1)
         return out
 
+    def derivative(self, x, wrt, variance=True):
+        """(dmean, dvar), each n* x p: the derivative of every layer's latent posterior with respect to input column `wrt` at x, along the
+        PLUG-IN path `decompose` walks: layer i sees [x, mu_0(x) .. mu_{i-1}(x)] (latent posterior means) and is differentiated along
+        u = (e_wrt, d mu_0 / d x_wrt, .., d mu_{i-1} / d x_wrt) per row - its feature map keeps the columns the layer selects.  So dmean[:, i]
+        is the TOTAL derivative of the plug-in mean path by the chain rule (with `replace=True`: of the latent mean `moments` returns), and
+        dvar[:, i] the variance of layer i's latent derivative along that direction, the means of the layers before it held as given.
+        `dvar` is None without `variance`.  For a conditioned model with dense layers: inducing points are a ValueError; an engine without
+        `posterior_deriv` raises NotImplementedError.  [an addition: the reference has no derivatives]"""
+        if self.sparse:
+            raise ValueError("posterior derivatives need dense layers: inducing points are not supported")
+        return _retry_unfused(lambda: self._derivative(x, wrt, variance), self.layers, (x,))
+
+    def _derivative(self, x, wrt, variance):
+        eng = get_engine()
+        x = eng.tensor(x)
+        if x.dim() == 1:
+            x = x[:, None]
+        wrt = int(wrt)
+        if not 0 <= wrt < x.shape[1]:
+            raise ValueError(f"wrt={wrt}: the inputs have columns 0 .. {x.shape[1] - 1}")
+        U = torch.zeros_like(x)
+        U[:, wrt] = 1.0
+        means, variances = [], []
+        with torch.no_grad():
+            for is_last, model in last(self.layers):
+                f, _ = model()
+                dmean, dvar = f.derivative_moments(x, U, variance)
+                means.append(dmean.reshape(-1, 1))
+                if variance:
+                    variances.append(dvar.reshape(-1, 1))
+                if not is_last:
+                    x = torch.cat([x, f.mean(x).reshape(-1, 1)], dim=1)
+                    U = torch.cat([U, dmean.reshape(-1, 1)], dim=1)
+        return torch.cat(means, dim=1), (torch.cat(variances, dim=1) if variance else None)
+
     # ---- helpers -----------------------------------------------------------------------------------
     @staticmethod
     def _noise_over(noise, w):

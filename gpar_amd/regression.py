@@ -1225,6 +1225,41 @@ class GPARRegressor:
             var = [(v * slope[0, i] ** 2).cpu().numpy() for i, (_, v) in enumerate(parts)] if variance else None
         return Decomposition(tuple(names), mean, var, shift.reshape(-1).cpu().numpy())
 
+    def derivative(self, x, wrt=0, variance=True):
+        """How fast every output changes with input column `wrt` at x, and how certain that is - an addition; the reference has no
+        derivatives.  The derivative of a Gaussian process is a Gaussian process (Rasmussen & Williams 9.4): returns `(mean, var)`, two
+        n* x p arrays in the units of y per unit of x - means times the output's normalisation slope, variances times its square; `var`
+        is None without `variance`.  A slope is significant where |mean| exceeds about two sqrt(var).
+
+        The layers are visited along the plug-in path of `decompose` (`GPAR.derivative`): layer i sees [x, latent posterior means of the
+        outputs before it] and is differentiated along (e_wrt, the derivatives of those means), so mean[:, i] is the TOTAL derivative of
+        output i's plug-in mean - with `replace=True` exactly d / d x_wrt of `predict_moments(x, latent=True)[0][:, i]` - and var[:, i]
+        the latent variance of layer i's derivative along that direction, the earlier outputs' means held as given.  After `update()` the
+        kept factors are used, as in `decompose`.  On the device one library call per layer (`gpar_posterior_deriv`); an engine without
+        it raises NotImplementedError.  RuntimeError: not conditioned; ValueError: a non-identity `transform_y`, inducing points, `wrt`
+        outside 0 .. m - 1, `matern=0.5` (not differentiable)."""
+        if not self.is_conditioned:
+            raise RuntimeError("Must condition or fit model before differentiating.")
+        self._check_identity_transform()
+        if self.sparse:
+            raise ValueError("posterior derivatives need dense layers: inducing points are not supported")
+        if self.model_config.get("matern") == 0.5:
+            raise ValueError("matern=0.5: the Matern 1/2 process is not differentiable")
+        wrt = int(wrt)
+        if not 0 <= wrt < self.m:
+            raise ValueError(f"wrt={wrt}: the model has inputs 0 .. {self.m - 1}")
+        x = _uprank(_to_engine(x))
+        gpar = self._stream_posterior() if getattr(self, "_stream_cache", None) is not None else None
+        if gpar is None:
+            gpar = _construct_gpar(self, self.vs, self.m, self.p) | (self.x, self.y, self.w)
+        with torch.no_grad():
+            mean, var = gpar.derivative(x, wrt, variance=variance)
+            zero = torch.zeros(1, self.p, dtype=torch.float64, device=x.device)
+            slope = self._unnormalise_y(torch.ones_like(zero)) - self._unnormalise_y(zero)   # (un-normalisation is affine, as in predict_moments)
+            mean = (mean * slope).cpu().numpy()
+            var = (var * slope ** 2).cpu().numpy() if variance else None
+        return mean, var
+
     def sample(self, x, w=None, p=None, posterior=False, num_samples=1, latent=False, _conditioned=None, sampler="exact", features=2048):
         """Draw samples from the prior or the posterior at inputs x; a single ndarray for num_samples=1, otherwise
         a list (reference regression.py:508-564).  (`_conditioned`: an already conditioned GPAR, used by the

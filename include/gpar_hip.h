@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define GPAR_ABI_VERSION 20
+#define GPAR_ABI_VERSION 21
 
 /* ---- kernel specification -------------------------------------------------------------------
  * A GPAR layer kernel (gpar/regression.py:92-180) is a sum of products of elementary kernels applied
@@ -218,6 +218,36 @@ int gpar_gram_terms_diag(const gpar_kspec_t* ks, const int* comp, int ncomp, con
 int gpar_posterior_terms(const gpar_kspec_t* ks, const int* comp, int ncomp, const double* zs, int ns, int ldzs, const double* z, int n,
                          int ldz, int dz, const double* alpha, const double* L, int ldl, double* mean, int ldm, double* var, int ldv,
                          double* ws, long long ws_doubles, void* stream);
+
+/* Posterior derivatives (ABI v21): the derivative of a Gaussian process is a Gaussian process (Rasmussen & Williams 9.4) - the slope of a
+ * trend with its error bar, the sensitivity of an output to an input.  For ONE conditioned dense layer - training features z (n x dz),
+ * alpha = K^-1 y and the factor L (n x n, ldl) of K = k(X, X) + D + eps I, as gpar_posterior_terms takes them - test features zs (ns x dz)
+ * and ndir DIRECTION FIELDS J (device; direction c's ns x dz rows, leading dimension ldj >= dz, start at J + c * stride_j; fields must not
+ * overlap): J[c][a][:] is the feature-space direction of test row a, i.e. d z / d x applied to a direction of the design space - the
+ * CALLER chains 1 / scale and the derivative of the periodic embedding, by the convention of gpar_gram_input_grad.  With
+ *     d_c,a[b] = J[c][a] . grad_z k(zs[a], z[b])                                      (never stored for the means)
+ *     mean[c * ldm + a] = sum_b d_c,a[b] alpha[b]
+ *     var[c * ldv + a]  = J[c][a]^T H(zs[a]) J[c][a] - |L^-1 d_c,a|^2,     H = grad_z grad_z'^T k at z = z' = zs[a]
+ * (latent: the noise has no derivative).  var == NULL skips the variances (and L is not read).  The means are a fused pass over the pairs
+ * - no ns x n matrix is written; per pair each term's factor values and gradient multipliers are evaluated once and every direction's dot
+ * product is formed from them -, split over n and summed in a fixed order; the variances build the (ndir c) x n stack of d for a chunk of c
+ * test rows with the same per-pair arithmetic, then ONE gpar_trsm_rlt over the stack, gpar_rownorm2 and the prior term J^T H J per row (per
+ * factor on its dims: EQ, RQ I; Matern 3/2 3 I; Matern 5/2 5/3 I; cosine 4 pi^2 1 1^T; linear I, and between two linear factors of one
+ * term the cross terms of the product rule - csrc/gram_deriv.h).  1 <= ndir <= GPAR_MAX_TERMS; at most 4 factors per product term (as
+ * in gpar_gram_input_grad); the factor values use libm's exp (gpar_gram uses tables: agreement to rounding).
+ * ws: ws_doubles doubles, 16-byte aligned; gpar_workspace_doubles(GPAR_WS_POSTERIOR_DERIV, n, ns, ndir) is the size to bring.  Any size
+ * from max(ndir ns, ndir (n + 3)) doubles is taken (without variances: ndir ns): a smaller workspace means fewer splits of the mean pass
+ * and smaller chunks of test rows (the means' last bits depend on the number of splits, so on ws_doubles; for given arguments a call
+ * returns the same bits every time).  No floating-point atomics anywhere.
+ * n == 0: means 0, variances the prior term.  ns == 0: nothing is done.  A zero direction gives mean 0 and variance 0.
+ * Argument errors - a GPAR_K_MATERN12 factor (its process is not mean-square differentiable), ndir outside 1 .. GPAR_MAX_TERMS, a negative
+ * n / ns, dz outside 0 .. GPAR_MAX_DIMS or a factor reaching past it, more than 4 factors in a term, leading dimensions, stride_j or the
+ * workspace too small, a NULL array that would be read, (2 + ndir) dz too large for the tiles to fit 160 KiB of LDS ((2 + ndir) max(dz, 1)
+ * 68 + 68 + 64 ndir doubles) - are found before the first launch: a negative status, no output touched.
+ * [no reference counterpart; in Python: Obs.derivatives, GPAR.derivative, GPARRegressor.derivative] */
+int gpar_posterior_deriv(const gpar_kspec_t* ks, const double* zs, int ns, int ldzs, const double* J, int ldj, long long stride_j, int ndir,
+                         const double* z, int n, int ldz, int dz, const double* alpha, const double* L, int ldl, double* mean, int ldm,
+                         double* var, int ldv, double* ws, long long ws_doubles, void* stream);
 
 /* Generalised Lomb-Scargle periodogram (ABI v19; Zechmeister & Kuerster 2009: floating mean, weights) of p irregularly sampled series
  * that share their time stamps - where a spectral-mixture layer's periods should start (Wilson & Adams 2013 initialise from the
@@ -793,7 +823,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_CHOL_UPDATE  (n, k, -)        gpar_chol_drop_leading
  *   GPAR_WS_AHEAD_MULTI  (n, grad, nh)    the `vec` of gpar_ahead_multi_dense (grad = 0) / gpar_ahead_multi_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_AHEAD_WINDOW (n, grad, -)     the `vec` of gpar_ahead_window_dense (grad = 0) / gpar_ahead_window_dense_grad (grad = 1)
- *   GPAR_WS_POSTERIOR_TERMS (n, ns, ncomp)  gpar_posterior_terms (the recommended size; see there for the least) */
+ *   GPAR_WS_POSTERIOR_TERMS (n, ns, ncomp)  gpar_posterior_terms (the recommended size; see there for the least)
+ *   GPAR_WS_POSTERIOR_DERIV (n, ns, ndir)   gpar_posterior_deriv (likewise) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -809,6 +840,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_AHEAD_WINDOW 13
 #define GPAR_WS_POSTERIOR_TERMS 14
 #define GPAR_WS_GRAM_APPLY 15   /* (n, rows, output columns)  gpar_gram_apply_groups */
+#define GPAR_WS_POSTERIOR_DERIV 16   /* (n, ns, ndir)  gpar_posterior_deriv (the recommended size; see there for the least) */
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
