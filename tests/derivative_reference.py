@@ -115,6 +115,27 @@ def layer_derivative(spec, x, y, noise_diag, xs, U, variance=True):
     return dmean, prior_term(spec, xs, U) - (half ** 2).sum(axis=0), mean
 
 
+def layer_derivatives(spec, x, y, noise_diag, xs, U):
+    """(dmean, dvar, prior), each ndir x n*: `layer_derivative` for a stack of directions U (ndir x n* x width) - the same formulas from the
+    same helpers, with what does not depend on the direction (the factorisation, the gradients of k(x*_a, x_b) with respect to the design
+    columns, the matrix of `prior_hessian` per test row) formed once.  `prior` is the term u^T [grad grad'^T k] u alone."""
+    x, y, xs, U = (np.asarray(a, dtype=np.float64) for a in (x, y, xs, U))
+    n, ns = x.shape[0], xs.shape[0]
+    K = ok.gram(spec, x) + np.diag(np.broadcast_to(np.asarray(noise_diag, dtype=np.float64), (n,)) + EPS)
+    L = np.linalg.cholesky(K)
+    alpha = scipy.linalg.cho_solve((L, True), y)
+    one = np.ones((ns, 1))
+    G = np.stack([ok.kernel_input_grads(spec, xs, x[b:b + 1], one) for b in range(n)], axis=1)   # n* x n x width
+    H = [prior_hessian(spec, xs[a]) for a in range(ns)]
+    dmean, dvar, prior = np.zeros(U.shape[:2]), np.zeros(U.shape[:2]), np.zeros(U.shape[:2])
+    for c in range(U.shape[0]):
+        d = np.einsum("aw,abw->ab", U[c], G)
+        dmean[c] = d @ alpha
+        prior[c] = [U[c, a] @ H[a] @ U[c, a] for a in range(ns)]
+        dvar[c] = prior[c] - (scipy.linalg.solve_triangular(L, d.T, lower=True) ** 2).sum(axis=0)
+    return dmean, dvar, prior
+
+
 def model_derivative(x, y, hypers, config, xs, wrt, impute, replace, variance=True, normalise_y=False):
     """(dmean, dvar), each n* x p, in the units of y: GPAR.derivative restated.  Conditioning as oracle.gpar_ref.gpar_predict_moments
     (rows kept per layer, the next input column = observed values, imputed / replaced by posterior means); prediction along the plug-in
