@@ -60,6 +60,49 @@ def _reference(K, num, tol=0.0, floor=FLOOR):
     return Lt, piv, trace, rank, gap, smallest
 
 
+def _reference_matrix_free(column, diag, num, tol=0.0, floor=FLOOR, ties="first"):
+    """The matrix-free twin of `_reference`, for candidate sets whose Gram matrix cannot be held: `column(p)` returns column p of K and
+    `diag` its diagonal, both in np.longdouble; only d and the `num` rows of Lt are kept.  The same tuple, Lt and the traces rounded to
+    float64 at the end.  `ties`: "first" - the smallest row among equal maxima, the rule - or "last" (tests only: the tie cases must
+    tell the two apart)."""
+    n = len(diag)
+    d, Lt, piv, trace = np.array(diag, dtype=np.longdouble), np.zeros((num, n), dtype=np.longdouble), np.full(num, -1), np.zeros(num + 1, dtype=np.longdouble)
+    rank, gap, smallest = num, np.inf, np.inf
+    for j in range(num + 1):
+        trace[j] = d.sum()
+        if j == num:
+            break
+        p = int(np.argmax(d)) if ties == "first" else n - 1 - int(np.argmax(d[::-1]))
+        if d[p] <= floor or trace[j] <= tol * trace[0] or not np.isfinite(d[p]):
+            rank = j
+            break
+        if n > 1 and not np.all(d == d[0]):
+            gap = min(gap, float((d[p] - np.partition(d, -2)[-2]) / d[p]))
+        smallest = min(smallest, float(d[p]))
+        col = (column(p) - Lt[:j].T @ Lt[:j, p]) / np.sqrt(d[p])
+        col[p] = np.sqrt(d[p])
+        Lt[j], piv[j] = col, p
+        d = d - col**2
+        d[p] = 0.0
+    return Lt.astype(float), piv, trace.astype(float), rank, gap, smallest
+
+
+def columns2d(name, x):
+    """(column, diag) of kernels2d()[name] over the rows of x in np.longdouble, written out from the kernels' definitions: "eq" -
+    1.3 exp(-1/2 sum_d ((x_d - x'_d) / s_d)^2) - and "eq+linear" - that with coefficient 1 plus sum_d (x_d / t_d) (x'_d / t_d),
+    s = (0.3, 0.36), t = (1.5, 2.5)."""
+    ld = np.longdouble
+    xs, xt = x.astype(ld) / np.array([0.3, 0.36], dtype=ld), x.astype(ld) / np.array([1.5, 2.5], dtype=ld)
+    coef = ld(13) / ld(10) if name == "eq" else ld(1)
+
+    def column(p):
+        col = coef * np.exp(-0.5 * np.sum((xs - xs[p]) ** 2, axis=1))
+        return col + xt @ xt[p] if name == "eq+linear" else col
+
+    diag = np.full(len(x), coef) + (np.sum(xt * xt, axis=1) if name == "eq+linear" else 0)
+    return column, diag
+
+
 def kernels2d():
     """The kernels of the comparisons, over two input columns (the choice of scales: module docstring)."""
     s = np.array([0.3, 0.36])
@@ -109,6 +152,29 @@ def test_composed_route_matches_the_numpy_reference(oracle_engine, name):
     assert ref[3] == 40 and ref[5] > PIVOT_MIN
     got = greedy_inducing(oracle_engine, oracle_engine.compile(kernel, 2), x, 40)
     assert_same(got, ref, np.max(np.diag(K)))
+
+
+@pytest.mark.parametrize("name", ["eq", "eq+linear"])
+def test_matrix_free_reference_equals_the_dense_one(name):
+    x = points(600)
+    K = dense_gram(None, kernels2d()[name], x)
+    ref = _reference(K, 40)
+    assert ref[4] > GAP and ref[3] == 40 and ref[5] > PIVOT_MIN
+    free = _reference_matrix_free(*columns2d(name, x), 40)
+    assert free[3] == 40 and free[4] > GAP and free[5] > PIVOT_MIN
+    np.testing.assert_array_equal(free[1], ref[1])
+    b = bound(40, np.max(np.diag(K)))
+    err_l, err_t = np.max(np.abs(free[0] - ref[0])), np.max(np.abs(free[2] - ref[2]))
+    print(f"{name}: matrix-free longdouble against dense float64: |Lt| {err_l:.3g}, |trace| {err_t:.3g} (bound {b:.3g})")
+    assert err_l <= b and err_t <= b
+    # the tie rule is part of the twin: on exact ties (a stationary kernel: every d_i the same number) the smallest row, and a twin
+    # that breaks ties towards the larger row is told apart by the cases that rest on it
+    column, diag = columns2d("eq", x)
+    assert _reference_matrix_free(column, diag, 1)[1][0] == 0 and _reference_matrix_free(column, diag, 1, ties="last")[1][0] == 599
+    x[41] = x[17] = [1.5, 1.5]
+    column, diag = columns2d("eq+linear", x)
+    first, last = _reference_matrix_free(column, diag, 8), _reference_matrix_free(column, diag, 8, ties="last")
+    assert first[1][0] == 17 and 41 not in first[1] and last[1][0] == 41
 
 
 def test_tie_goes_to_the_smaller_row_and_the_twin_is_never_picked(oracle_engine):

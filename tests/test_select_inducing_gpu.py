@@ -12,6 +12,13 @@ to against the oracle - the fused column kernel uses libm's exp, gpar_gram its t
 k = 40, kmax = 1.3 (EQ): 1.2e-12;  k = 64, kmax = 1.60 (EQ + linear, n = 600): 1.4e-12;  k = 96, kmax = 1: 9.7e-13.  `Lt` and the traces
 of the two routes are held to it; only where a trace is RECOMPUTED here as a sum of n residuals, each of them held to the bound (the
 invariants test), is it held to n times the bound.
+
+Past one workgroup's reach: every launch opens by reducing the previous launch's partials with `for (w = tid; w < nwg; w += 256)`, which
+takes a second iteration only from 257 workgroups on - n = 65793 (257 full workgroups and one row, 258 partials) against the matrix-free
+longdouble reference of tests/test_select_inducing.py, with a planted maximum and exact ties in workgroup 256 -, and the pivot's row
+of the factor is staged with `for (t = tid; t < j; t += 256)`, which takes a second pass from step 257 on - 300 steps at n = 300, 264
+at n = 600, under an EQ kernel over six columns (length scales 0.5) that keeps the reference's pivots above 1e-4 and its gaps above
+1e-6.  bound(6, 2.36) = 2.0e-12, bound(300, 1) = 1.2e-12.
 """
 import numpy as np
 import pytest
@@ -24,8 +31,8 @@ from gpar_amd.kernels import EQ, Linear
 from gpar_amd.regression import GPARRegressor
 
 from .conftest import make_engine, to_np
-from .test_select_inducing import (FLOOR, GAP, PIVOT_MIN, _reference, assert_rank2, assert_rank3, assert_same, bound, cosine_rank2, dense_gram,
-                                   kernels2d, linear_rank3, points, regression_data)
+from .test_select_inducing import (FLOOR, GAP, PIVOT_MIN, _reference, _reference_matrix_free, assert_rank2, assert_rank3, assert_same, bound,
+                                   columns2d, cosine_rank2, dense_gram, kernels2d, linear_rank3, points, regression_data)
 
 pytestmark = pytest.mark.gpu
 
@@ -204,3 +211,155 @@ def test_select_inducing_to_a_trained_sparse_model(eng):
     assert np.isfinite(float(reg.logpdf(x, y)))
     mean, var = reg.predict_moments(x[:50])
     assert mean.shape == (50, 2) and np.all(np.isfinite(mean)) and np.all(var > 0.0)
+
+
+# ---- past one workgroup's reach: more than 256 workgroups, more than 256 steps, the raw entry's corners -----------------------------------
+MANY = 65793   # 257 full workgroups and one row: 258 partials, thread 0 of the reduction reads workgroups 0 and 256, thread 1 reads 1 and 257
+
+
+def _fused_raw(eng, kernel, x, num, floor=None):
+    from gpar_amd import hip
+
+    ck = eng.compile(kernel, x.shape[1])
+    z = eng.features(ck, eng.tensor(x))
+    out = hip.pivoted_chol(ck, z, num, 0.0, eng.epsilon if floor is None else floor)
+    torch.cuda.synchronize()
+    return [to_np(t).copy() for t in out]   # Lt, piv, trace, rank, info, d
+
+
+def _against_matrix_free(got, ref, kmax, n):
+    """Lt, piv, trace of `hip.pivoted_chol` against the matrix-free reference: the preconditions on the reference first."""
+    Lt, piv, trace, rank, info, _ = got
+    num = len(piv)
+    assert ref[4] > GAP, f"the pivot order is not comparable between two roundings: smallest gap {ref[4]:.3g}"
+    assert ref[3] == num and ref[5] > PIVOT_MIN
+    assert int(info[0]) == 0 and int(rank[0]) == num
+    np.testing.assert_array_equal(piv, ref[1])
+    b = bound(num, kmax)
+    err_l, err_t = np.max(np.abs(Lt - ref[0])), np.max(np.abs(trace - ref[2]))
+    print(f"n = {n}, {num} steps: |Lt - ref| {err_l:.3g} (bound {b:.3g}), |trace - ref| {err_t:.3g} (n bound {n * b:.3g})")
+    assert err_l <= b
+    assert err_t <= n * b   # (each trace is a sum of n residuals, every one of them within the bound: the invariants test's rule)
+
+
+def test_a_planted_maximum_in_workgroup_256_is_found_through_the_second_pass_over_the_partials(eng):
+    n = MANY
+    x = points(n)
+    x[65600] = [1.5, 1.5]   # the largest norm: the largest prior variance under EQ + linear; 65600 = 256 * 256 + 64
+    column, diag = columns2d("eq+linear", x)
+    ref = _reference_matrix_free(column, diag, 6)
+    got = _fused_raw(eng, kernels2d()["eq+linear"], x, 6)
+    assert ref[1][0] == 65600 and got[1][0] == 65600
+    groups = ref[1] // 256
+    assert (groups < 256).any() and (groups >= 256).any()
+    _against_matrix_free(got, ref, float(np.max(diag)), n)
+    again = _fused_raw(eng, kernels2d()["eq+linear"], x, 6)
+    for a, b in zip(got, again):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_exact_ties_across_the_two_passes_over_the_partials_go_to_the_smaller_row(eng):
+    n = MANY
+    x = points(n)
+    # a stationary kernel: every d_i is the same number, in every workgroup's partial - thread 0 meets the rows 0 and 65536
+    Lt, piv, trace, rank, info, _ = _fused_raw(eng, kernels2d()["eq"], x, 2)
+    ref = _reference_matrix_free(*columns2d("eq", x), 2)
+    assert int(info[0]) == 0 and int(rank[0]) == 2 and piv[0] == 0 and ref[1][0] == 0
+    assert abs(trace[0] - ref[2][0]) <= n * bound(2, 1.3)
+    # two bit-identical points of largest norm, rows 300 (workgroup 1) and 65700 (workgroup 256)
+    x[300] = x[65700] = [1.5, 1.5]
+    column, diag = columns2d("eq+linear", x)
+    ref = _reference_matrix_free(column, diag, 6)
+    got = _fused_raw(eng, kernels2d()["eq+linear"], x, 6)
+    assert ref[1][0] == 300 and 65700 not in ref[1] and ref[5] > PIVOT_MIN
+    assert got[1][0] == 300 and 65700 not in got[1] and int(got[3][0]) == 6
+    np.testing.assert_array_equal(got[1], ref[1])
+    b = bound(6, float(np.max(diag)))
+    assert np.max(np.abs(got[0] - ref[0])) <= b and abs(got[2][0] - ref[2][0]) <= n * b
+
+
+def long_run(n):
+    """EQ over six columns, length scales 0.5, on n uniform points: full rank far above the floor (the module docstring)."""
+    cols = list(range(6))
+    return (1.0 * EQ().stretch(np.full(6, 0.5))).select(cols), np.random.default_rng(77 + n).uniform(0.0, 1.0, (n, 6))
+
+
+@pytest.mark.parametrize("n,num", [(300, 300), (600, 264)])
+def test_more_than_256_steps_against_the_dense_reference(eng, n, num):
+    kernel, x = long_run(n)
+    K = dense_gram(None, kernel, x)
+    ref = _reference(K, num)
+    assert ref[3] == num and ref[5] > 1e3 * FLOOR   # the residual stays above the floor for all the steps ...
+    assert ref[4] > GAP and ref[5] > PIVOT_MIN      # ... and the pivot order is comparable between two roundings
+    got = greedy_inducing(eng, eng.compile(kernel, 6), x, num)
+    assert_same(got, ref, 1.0)
+    if n == num:
+        Lt = to_np(got[0])
+        err = np.max(np.abs(Lt.T @ Lt - K))
+        print(f"full rank at {n}: |Lt^T Lt - K| {err:.3g} (bound {bound(n, 1.0):.3g})")
+        assert sorted(to_np(got[1]).tolist()) == list(range(n)) and err <= bound(n, 1.0)
+
+
+@pytest.mark.parametrize("n,max_rank", [(2, 5), (257, 300)])
+def test_more_steps_than_rows_stop_at_rank_n(eng, n, max_rank):
+    kernel, x = long_run(300)
+    x = x[:n]
+    ref = _reference(dense_gram(None, kernel, x), n)
+    assert ref[3] == n and ref[5] > PIVOT_MIN
+    Lt, piv, trace, rank, info, d = _fused_raw(eng, kernel, x, max_rank)
+    assert int(rank[0]) == n and int(info[0]) == 0
+    assert sorted(piv[:n].tolist()) == list(range(n)) and np.all(piv[n:] == -1)
+    assert np.all(Lt[n:] == 0.0) and np.all(trace[n + 1:] == 0.0)
+    assert np.all(d <= 0.0) and d.min() >= -bound(n, 1.0)   # (every row was picked: 0 then, and below it only by later steps' rounding)
+    np.testing.assert_array_equal(piv[:n], ref[1])
+    assert np.max(np.abs(Lt[:n] - ref[0])) <= bound(n, 1.0)
+
+
+def _raw_call(eng, ck, z, n, max_rank, ldz, ldl, tol=0.0, floor=FLOOR):
+    """gpar_pivoted_chol with every buffer allocated here and prefilled with -7: (status, z buffer, Lt buffer, piv, trace, words)."""
+    import ctypes
+
+    from gpar_amd import _lib
+    from gpar_amd import hip
+
+    lib, dev = _lib.load(), z.device
+    zb = torch.full((n, ldz), -7.0, dtype=torch.float64, device=dev)
+    zb[:, : z.shape[1]] = z
+    Lb = torch.full((max_rank, max(ldl, 1)), -7.0, dtype=torch.float64, device=dev)
+    piv = torch.full((max_rank,), -7, dtype=torch.int32, device=dev)
+    trace = torch.full((max_rank + 1,), -7.0, dtype=torch.float64, device=dev)
+    words = torch.full((2,), -7, dtype=torch.int32, device=dev)
+    ws = torch.empty(lib.gpar_workspace_doubles(_lib.WS_PIVOTED_CHOL, n, 0, 0), dtype=torch.float64, device=dev)
+    rc = lib.gpar_pivoted_chol(ctypes.byref(ck.kspec), zb.data_ptr(), n, ldz, ck.dz, max_rank, float(tol), float(floor), Lb.data_ptr(), ldl,
+                               piv.data_ptr(), trace.data_ptr(), words.data_ptr(), words[1:].data_ptr(), ws.data_ptr(), hip.stream_ptr(dev))
+    torch.cuda.synchronize()
+    return rc, zb, Lb, piv, trace, words
+
+
+def test_padded_leading_dimensions_give_the_same_bits_and_leave_the_padding(eng):
+    n, num = 257, 40
+    kernel, x = kernels2d()["eq+linear"], points(n)
+    ck = eng.compile(kernel, 2)
+    z = eng.features(ck, eng.tensor(x))
+    dz = ck.dz
+    assert z.shape[1] == dz
+    rc, _, Lt, piv, trace, words = _raw_call(eng, ck, z, n, num, dz, n)
+    assert rc == 0 and words.tolist() == [num, 0]
+    rc, zp, Lp, pivp, tracep, wordsp = _raw_call(eng, ck, z, n, num, dz + 3, n + 5)
+    assert rc == 0 and wordsp.tolist() == [num, 0]
+    assert torch.equal(Lp[:, :n], Lt) and torch.equal(pivp, piv) and torch.equal(tracep, trace)
+    assert bool((Lp[:, n:] == -7.0).all()) and bool((zp[:, dz:] == -7.0).all()) and torch.equal(zp[:, :dz], z)
+
+
+def test_argument_errors_of_the_raw_entry_touch_nothing(eng):
+    n = 257
+    kernel, x = kernels2d()["eq+linear"], points(n)
+    ck = eng.compile(kernel, 2)
+    z = eng.features(ck, eng.tensor(x))
+    for told in (dict(max_rank=4097), dict(ldl=n - 1), dict(floor=-1e-12)):
+        args = dict(max_rank=8, ldz=ck.dz, ldl=n, floor=FLOOR)
+        args.update(told)
+        rc, _, Lt, piv, trace, words = _raw_call(eng, ck, z, n, **args)
+        assert -1100 < rc <= -1001, (told, rc)   # (an argument error: -(1000 + the argument group))
+        assert words.tolist() == [-7, -7], told
+        assert bool((Lt == -7.0).all()) and bool((piv == -7).all()) and bool((trace == -7.0).all()), told
