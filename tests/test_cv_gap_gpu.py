@@ -197,6 +197,28 @@ def test_malformed_extents_are_reported_in_the_info_word(hip):
             lib.cv_gap_dense(ck, x, y, noise, 1e-12, [0, 40, 90, 130], hold)
 
 
+def test_malformed_extents_at_257_rows_are_reported_by_the_fold_behind_column_256(hip):
+    """The malformed extents of the test above at n = 257, in the last of six folds - rows 250 ... 256, so the fold that reports holds the
+    one column of the second 256-column block of loo_rank2_kernel: info = n + 1 + 5 from the value-only, the one-call and the finish
+    form.  The fold that reports is skipped whole: its rows of the means and the variances come back as the sentinel they went in
+    with, as do the padding of every buffer and every word behind n.  (The other folds have written theirs, and include/gpar_hip.h
+    promises nothing for W, 1/2 diag W and the value behind a set info word: "Results are garbage then" - so those are not held.)"""
+    from .test_cv_large_gpu import SENTINEL, case, padding_untouched, raw_call
+
+    n, fold = 257, 5
+    c = dict(case("loo", None, n), family="cv_gap")   # (the inputs of the large cases at 257 rows)
+    starts = [0, 50, 100, 150, 200, 250, 257]
+    for lo, hi in (([0, 45, 95, 145, 192, 192], [55, 105, 155, 205, 250, 257]),     # fold 5: rows 192 ... 256, 65 of them
+                   ([0, 45, 95, 145, 192, 252], [55, 105, 155, 205, 250, 257]),     # fold 5 begins at row 250, its block at row 252
+                   ([0, 45, 95, 145, 200, 199], [55, 105, 155, 205, 250, 257]),     # hold_lo decreases at fold 5
+                   ([0, 45, 95, 145, 192, 240], [55, 105, 155, 205, 250, 258])):    # a block beyond the last row
+        for mode in ("value", "grad", "finish"):
+            got = raw_call(hip, c, mode, pad=3, extents=(starts, lo, hi, 64))
+            assert got["rc"] == 0 and got["info"][1 if mode == "finish" else 0] == n + 1 + fold, (lo, hi, mode, got["info"])
+            assert bool((got["mean"][250:] == SENTINEL).all()) and bool((got["var"][250:] == SENTINEL).all()), (lo, hi, mode)
+            assert padding_untouched(got), (lo, hi, mode)
+
+
 def test_regressor_cv_and_fit_with_a_gap_against_the_composed_route_on_the_same_engine(hip, monkeypatch):
     from gpar_amd.engine import HipEngine
     from gpar_amd.regression import GPARRegressor
