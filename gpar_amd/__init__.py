@@ -11,10 +11,10 @@ __version__ = "0.2.0"
 # queues - 4 by default - and streams that share a queue serialise; `HipEngine` asks for 8 when it is created before the
 # process has touched the GPU and otherwise works with what the runtime already has: see engine._hardware_queues.)
 
-from .regression import Decomposition, GPARRegressor, log_transform, squishing_transform  # noqa: F401
+from .regression import Decomposition, GPARRegressor, HyperPosterior, log_transform, squishing_transform  # noqa: F401
 from .spectrum import Periodogram, spectral_peaks  # noqa: F401
 from .model import GPAR  # noqa: F401
 from .kernels import Cosine, Matern12, Matern32, Matern52  # noqa: F401
 from .gp import greedy_inducing  # noqa: F401
 
-__all__ = ["GPARRegressor", "Decomposition", "Periodogram", "spectral_peaks", "GPAR", "log_transform", "squishing_transform", "Matern12", "Matern32", "Matern52", "Cosine", "greedy_inducing"]
+__all__ = ["GPARRegressor", "Decomposition", "HyperPosterior", "Periodogram", "spectral_peaks", "GPAR", "log_transform", "squishing_transform", "Matern12", "Matern32", "Matern52", "Cosine", "greedy_inducing"]

@@ -30,6 +30,7 @@ WS_AHEAD_WINDOW = 13
 WS_POSTERIOR_TERMS = 14
 WS_GRAM_APPLY = 15
 WS_POSTERIOR_DERIV = 16
+WS_GRAM_GRAD_ROWS = 17
 AHEAD_WINDOW_MAX = 64   # GPAR_AHEAD_WINDOW_MAX: the longest window (rows) the fused sliding-window forecast entries take
 AHEAD_MAX_HORIZONS = 8   # GPAR_AHEAD_MAX_HORIZONS: the most horizons the fused multi-horizon rolling-origin entries take
 PIVCHOL_MAX_RANK = 4096   # GPAR_PIVCHOL_MAX_RANK: the most steps gpar_pivoted_chol takes
@@ -150,6 +151,11 @@ SIGNATURES = {
         _c_int,
         [ctypes.POINTER(KSpec), _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _c_int, _c_int, _ptr, _c_int,
          _ptr, _ptr],
+    ),
+    # (the same sums per row of z1: z1, zd1, n1, ldz1, z2, zd2, n2, ldz2, dz, the n2 weights, out with its leading dimension, workspace)
+    "gpar_gram_grad_rows": (
+        _c_int,
+        [ctypes.POINTER(KSpec), _ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, ctypes.c_longlong, _ptr],
     ),
     "gpar_gram_input_grad": (
         _c_int,

@@ -18,6 +18,7 @@
 #include "gram_terms.h"   // posterior decomposition by kernel component: its kernels and the chain of gpar_posterior_terms
 #include "gram_deriv.h"   // posterior derivatives: the kernels and the chain of gpar_posterior_deriv
 #include "pathwise.h"   // pathwise posterior sampling: gpar_rff_apply, gpar_gram_apply_groups
+#include "gram_grad_rows.h"   // per-row gradient moment sums: the kernels and the chain of gpar_gram_grad_rows
 
 namespace gpar {
 
@@ -1887,6 +1888,25 @@ int gpar_posterior_deriv(const gpar_kspec_t* ks, const double* zs, int ns, int l
                                (hipStream_t)stream);
 }
 
+// ---- per-row gradient moment sums (gram_grad_rows.h) --------------------------------------------------------------------------------------------
+// Argument errors are found before anything is launched: no output is touched.
+int gpar_gram_grad_rows(const gpar_kspec_t* ks, const double* z1, const double* zd1, int n1, int ldz1, const double* z2, const double* zd2, int n2,
+                        int ldz2, int dz, const double* v, double* out, int ldo, double* ws, long long ws_doubles, void* stream) {
+    GPAR_API_GUARD;
+    if (n1 < 0 || n2 < 0) return GPAR_ARG_ERROR(5);
+    RowsPlan pl;
+    const int rc = rows_check(ks, dz, zd1 != nullptr, pl);
+    if (rc) return rc;
+    if (n1 == 0) return 0;
+    // (the rule of gpar_gram_grad_cross: both, for P_q, or neither - where there are rows of z2 to read)
+    if (n2 > 0 && (zd1 == nullptr) != (zd2 == nullptr)) return GPAR_ARG_ERROR(8);
+    if (ldo < GRAD_NACC || ldz1 < dz || ldz2 < dz) return GPAR_ARG_ERROR(7);
+    if (!out || (dz > 0 && !z1) || (n2 > 0 && (!v || (dz > 0 && !z2)))) return GPAR_ARG_ERROR(6);
+    if (!ws || ws_doubles < (long long)n1 * GRAD_NACC) return GPAR_ARG_ERROR(9);
+    if (rows_lds_bytes(dz, zd1 != nullptr, pl.nused) > ROWS_MAX_LDS) return GPAR_ARG_ERROR(10);   // the tiles and accumulators must fit the LDS
+    return gram_grad_rows_run(ks, pl, z1, zd1, n1, ldz1, z2, zd2, n2, ldz2, dz, v, out, ldo, ws, ws_doubles, (hipStream_t)stream);
+}
+
 // ---- generalised Lomb-Scargle periodogram (ABI v19; periodogram.h) ------------------------------------------------------------------------------
 int gpar_periodogram(const double* t, int n, double t0, const double* y, int ldy, const double* omega, int ldo, int p, const double* freq, int nf,
                      double* power, int ldp, void* stream) {
@@ -2088,6 +2108,7 @@ long long gpar_workspace_doubles(int op, int a, int b, int c) {
         case GPAR_WS_POSTERIOR_TERMS: return pt_workspace_doubles(a, b, c);              /* n, ns, ncomp */
         case GPAR_WS_GRAM_APPLY: return ga_workspace_doubles(a, b, c);                   /* n, rows, output columns (1 with groups) */
         case GPAR_WS_POSTERIOR_DERIV: return pt_workspace_doubles(a, b, c);              /* n, ns, ndir */
+        case GPAR_WS_GRAM_GRAD_ROWS: return rows_workspace_doubles(a, b);                /* n2, n1 */
         default: return -1;
     }
 }

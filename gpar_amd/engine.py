@@ -213,6 +213,15 @@ class HipEngine:
         """(dmean, dvar), each ndir x n*, of one conditioned dense layer along the feature-space directions J - one library call."""
         return hip.posterior_deriv(ck, zs, J, z, alpha, L, variance=variance)
 
+    # ---- per-row gradient moment sums (gpar_gram_grad_rows) ----------------------------------------------------------------
+    def gram_grad_rows(self, ck, z1, z2, v, zd1=None, zd2=None):
+        """n1 x GRAD_NACC raw moment sums, row a over the pairs (z1_a, z2_b) weighted by v[b] - one library call, no n1 x n2 matrix."""
+        return hip.gram_grad_rows(ck, self._mat(z1), self._mat(z2), v, zd1=zd1, zd2=zd2)
+
+    def featurize_dfreq(self, ck, x):
+        """d features / d freq at the design rows x (zero for non-periodic features): the zd of the period sums."""
+        return hip.featurize_dfreq(ck, self._mat(x))
+
     # ---- generalised Lomb-Scargle periodogram (gpar_periodogram) ----------------------------------------------------
     def periodogram(self, t, y, omega, freq, t0=None):
         """power (p x F, a device tensor) of the p columns of y (n x p) with weights omega (0 = unobserved) at the time stamps t and

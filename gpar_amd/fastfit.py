@@ -33,7 +33,7 @@ import torch
 from . import _lib, hip, optimise
 from .kernels import Kernel, compile_kernel
 
-__all__ = ["build", "DenseLayerObjective", "LockstepFactor", "lockstep_rows"]
+__all__ = ["build", "DenseLayerObjective", "LayerChain", "layer_chain", "hessian_of", "LockstepFactor", "lockstep_rows"]
 
 log = logging.getLogger(__name__)
 
@@ -520,6 +520,82 @@ class DenseLayerObjective:
             grad[sl] = -g
         return -value, grad
 
+    # ---- curvature and the chain rule as a matrix (GPARRegressor.laplace, predict_moments_hyper) -----------------------------------
+    def hessian(self, x):
+        """The Hessian of the objective at the latent vector x: the central difference of the analytic gradient `fg`, 2 P evaluations with
+        the step h = eps^(1/3) max(1, |x_i|) per coordinate (eps: the double-precision unit round-off), symmetrised as (H + H^T) / 2.
+        The "mll" objective only.  The holders are left at x."""
+        if self.objective != "mll":
+            raise ValueError('hessian: the objective "mll" only')
+        H = hessian_of(self.fg, x)
+        self._write_values(np.asarray(x, dtype=np.float64))
+        return H
+
+    def _chain(self, grads, noise_grad, sig):
+        """The chain rule of `fg` for any parameter gradients (`HipEngine._grads_from_moments`) and noise derivative: the derivative with
+        respect to the latent variables, without fg's change of sign."""
+        by_name = {}
+
+        def add(holder, val):
+            val = np.asarray(val, dtype=np.float64)
+            if val.size != holder.size:
+                val = val.sum()
+            prev = by_name.get(holder.gpar_name)
+            val = np.asarray(val, dtype=np.float64).reshape(holder.shape)
+            by_name[holder.gpar_name] = val if prev is None else prev + val
+
+        for kind, ti, fi, holder in self.slots:
+            add(holder, grads["coef"][ti] if kind == "coef" else grads["factors"][ti][fi][kind])
+        if isinstance(self.noise, _Holder) and self.noise.gpar_name is not None:
+            add(self.noise, noise_grad)
+        out = np.zeros(self.size)
+        for name, kind, lower, upper, sl, shape in self.layout:
+            g = by_name.get(name)
+            if g is None:
+                continue
+            g = g.reshape(-1)
+            if kind == "bnd":
+                s = sig[sl]
+                g = ((g * (upper - lower)) * (1.0 - s)) * s
+            elif kind == "pos":
+                g = g * sig[sl]
+            out[sl] = g
+        return out
+
+    def chain_matrix(self, x):
+        """(M, noise_col) at the latent vector x: the raw-slot -> variable chain rule of `fg` as a matrix - M (P x GRAD_NACC) maps FULL moment
+        sums (no factor 1/2: a row of `gram_grad_rows`) to derivatives with respect to the P latent variables, noise_col (P) is the
+        derivative per unit derivative with respect to the noise variance.  The chain rule is linear in the sums, so M is `_chain` applied
+        to the unit vectors.  The holders are left at x."""
+        x = np.asarray(x, dtype=np.float64)
+        sig = self._write_values(x)
+        ck = compile_kernel(self.kernel, self.width)
+        nacc = _lib.GRAD_NACC
+        M = np.zeros((self.size, nacc))
+        unit = np.zeros(nacc)
+        for s in range(nacc):
+            unit[s] = 1.0
+            M[:, s] = self._chain(self.eng._grads_from_moments(ck, unit, 1.0), 0.0, sig)
+            unit[s] = 0.0
+        noise_col = self._chain(self.eng._grads_from_moments(ck, unit, 1.0), 1.0, sig)
+        return M, noise_col
+
+    def natural(self, x):
+        """(values, slopes) of the P variables at the latent vector x: the natural (bounded) values and d value / d latent - the delta
+        method's factor between a standard error in the optimiser's coordinates and one in natural units."""
+        x = np.asarray(x, dtype=np.float64)
+        sig = self._write_values(x).copy()
+        value, slope = np.zeros(self.size), np.ones(self.size)
+        for name, kind, lower, upper, sl, shape in self.layout:
+            if kind == "bnd":
+                value[sl] = lower + (upper - lower) * sig[sl]
+                slope[sl] = (upper - lower) * sig[sl] * (1.0 - sig[sl])
+            elif kind == "pos":
+                value[sl] = slope[sl] = sig[sl]
+            else:
+                value[sl] = x[sl]
+        return value, slope
+
     # ---- the optimisation ----------------------------------------------------------------------------------------------------
     def minimise(self, iters=1000, f_calls=10000, trace=False):
         """L-BFGS-B over the selected latents (as optimise.minimise_l_bfgs_b); the optimum is written back into the store."""
@@ -534,6 +610,62 @@ class DenseLayerObjective:
         x_opt, val, _ = scipy.optimize.fmin_l_bfgs_b(fg, x0, maxiter=iters, maxfun=f_calls)
         self.vs.set_vector(x_opt, self.names)
         return val
+
+
+def hessian_of(fg, x):
+    """The Hessian at x of a function whose `fg(x)` returns (value, analytic gradient): the central difference of the gradient, 2 P
+    evaluations, step h = eps^(1/3) max(1, |x_i|) per coordinate (eps: the double-precision unit round-off), symmetrised as (H + H^T) / 2."""
+    x = np.asarray(x, dtype=np.float64).copy()
+    H = np.zeros((x.size, x.size))
+    eps = np.finfo(np.float64).eps
+    for i in range(x.size):
+        h = eps ** (1.0 / 3.0) * max(1.0, abs(x[i]))
+        xp, xm = x.copy(), x.copy()
+        xp[i] += h
+        xm[i] -= h
+        H[:, i] = (np.asarray(fg(xp)[1]) - np.asarray(fg(xm)[1])) / (xp[i] - xm[i])
+    return 0.5 * (H + H.T)
+
+
+class LayerChain:
+    """The host side of a layer's chain rule WITHOUT the objective: the layer's kernel over value holders, the layout of its variables in
+    the optimiser's coordinates and `DenseLayerObjective`'s own `chain_matrix` / `natural` (the same functions: one text).  Needs no
+    data and no device buffer, so it serves a layer of any number of rows."""
+
+    _write_values = DenseLayerObjective._write_values
+    _chain = DenseLayerObjective._chain
+    chain_matrix = DenseLayerObjective.chain_matrix
+    natural = DenseLayerObjective.natural
+
+    def __init__(self, eng, vs, names, kernel, noise_holder, holders, width):
+        self.eng, self.vs, self.names = eng, vs, list(names)
+        self.kernel, self.noise, self.holders, self.width = kernel, noise_holder, holders, int(width)
+        self.layout, at = [], 0
+        for name in self.names:
+            var = vs._vars[name]
+            size = int(var.latent.numel())
+            self.layout.append((name, var.kind, var.lower, var.upper, slice(at, at + size), tuple(var.latent.shape)))
+            at += size
+        self.size = at
+        self.slots = _slots(kernel)
+
+
+def layer_chain(reg, eng, vs, pi, names):
+    """The `LayerChain` of layer `pi` of regressor `reg` (its design rows are m + pi wide), or None where the layer's kernel holds a
+    parameter whose origin is unknown (`_slots`) or the engine has no moment-sum chain rule."""
+    from .regression import _model_generator, layer_config
+
+    if not hasattr(eng, "_grads_from_moments"):
+        return None
+    tracer = _TracingVars(vs)
+    f, noise = _model_generator(tracer, reg.m, pi, **layer_config(reg, reg.m, pi))()
+    kernel = f.kernel
+    if not isinstance(kernel, Kernel) or f.is_posterior or _slots(kernel) is None or not isinstance(noise, _Holder):
+        return None
+    names = vs.match(names)
+    if not names:
+        return None
+    return LayerChain(eng, vs, names, kernel, noise, tracer.holders, reg.m + pi)
 
 
 def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, group=None, lane=None, objective="mll", folds=None, ahead=None,

@@ -1465,6 +1465,56 @@ class Obs:
         J = eng.feature_directions(p.ck, p.x, U)
         return eng.posterior_deriv(p.ck, p.z, J, z, fac.alpha(), fac.L, variance=variance)
 
+    # ---- sensitivity of the posterior mean to the hyperparameters (dense observations of the prior) ---------
+    def mean_sensitivity(self, p, M, noise_col, noise_value):
+        """The n* x P Jacobian of the latent posterior mean at the points `p` with respect to the layer's P trainable variables in the
+        optimiser's unconstrained coordinates (those `fastfit.DenseLayerObjective.fg` differentiates in):
+            J[a, theta] = sum_b alpha_b d k(z*_a, z_b) / d theta - k*_a^T K^-1 (dK / d theta) alpha,        alpha = K^-1 y.
+        `M` (P x GRAD_NACC) and `noise_col` (P) are that objective's chain rule as a matrix (`chain_matrix`): raw moment sums ->
+        variables, and the noise variance -> variables; `noise_value` the noise variance itself (dK / d noise = diag(noise_i) / noise,
+        the inverse weights).  Computed as R* = gram_grad_rows(z*, Z, alpha) and R = gram_grad_rows(Z, Z, alpha) = (dK / d raw) alpha
+        column by column - one fused pass each, rows unreduced -, T = K^-1 R for the slot columns M uses by the two triangular solves
+        with the factor conditioning holds, the second term by `gram_apply_groups`, then the chain rule.  No n* x n matrix is written.
+        The noise does not appear in k: only the second term contributes.  An engine without `gram_grad_rows` raises
+        NotImplementedError.  ValueError: observations of a posterior process."""
+        if self.base.is_posterior:
+            raise ValueError("the sensitivity of the posterior mean needs dense observations of a prior process")
+        eng = self.eng
+        if not hasattr(eng, "gram_grad_rows"):
+            raise NotImplementedError(f"{type(eng).__name__} has no gram_grad_rows: per-row gradient sums are a device kernel "
+                                      "(gpar_gram_grad_rows); run them on the HIP engine")
+        M = np.asarray(M, dtype=np.float64)
+        noise_col = np.asarray(noise_col, dtype=np.float64).reshape(-1)
+        P, n = M.shape[0], self.fdd.n
+        dev = p.x.device
+        if p.n == 0 or n == 0 or P == 0:
+            return torch.zeros(p.n, P, dtype=torch.float64, device=dev)
+        fac, pts = self.factor(), self.fdd.pts()
+        ck, z = pts.ck, pts.z
+        alpha = fac.alpha().reshape(-1).contiguous()
+        zd = zds = None
+        if eng._periodic(ck):
+            zd, zds = eng.featurize_dfreq(ck, pts.x), eng.featurize_dfreq(p.ck, p.x)
+        used = [int(s) for s in np.flatnonzero(np.any(M != 0.0, axis=0))]
+        with_noise = bool(np.any(noise_col != 0.0))
+        at = torch.tensor(used, dtype=torch.long).to(dev)
+        Rs = eng.gram_grad_rows(p.ck, p.z, z, alpha, zd1=zds, zd2=zd).index_select(1, at)   # n* x U
+        R = eng.gram_grad_rows(ck, z, z, alpha, zd1=zd, zd2=zd).index_select(1, at)         # n x U: (dK / d raw) alpha
+        rows = [R.T]
+        if with_noise:
+            rows.append((alpha * (self.fdd.noise / float(noise_value)))[None])
+        Tt = torch.cat(rows, dim=0).contiguous()   # (U [+ 1]) x n: rows b^T -> b^T K^-1 = b^T L^-T L^-1
+        if Tt.shape[0] == 0:
+            return torch.zeros(p.n, P, dtype=torch.float64, device=dev)
+        eng.trsm_rlt_(fac.L, Tt)
+        eng.trsm_rln_(fac.L, Tt)
+        second = eng.gram_apply_groups(p.ck, p.z, z, Tt)   # n* x (U [+ 1]): k*^T K^-1 (dK / d .) alpha
+        Mt = torch.from_numpy(np.ascontiguousarray(M[:, used].T)).to(dev)   # U x P
+        J = (Rs - second[:, :len(used)]) @ Mt if used else torch.zeros(p.n, P, dtype=torch.float64, device=dev)
+        if with_noise:
+            J = J - second[:, len(used):] * torch.from_numpy(noise_col).to(dev)[None]
+        return J
+
     def _components_composed(self, p, comp, ncomp, variance):
         eng, fac, n = self.eng, self.factor(), self.fdd.n
         kernel, width = self.base.kernel, self.fdd.x.shape[1]

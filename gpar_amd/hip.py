@@ -39,6 +39,7 @@ __all__ = [
     "trmv_lower",
     "gram_grad",
     "gram_grad_cross",
+    "gram_grad_rows",
     "gram_input_grad",
     "chol_inverse",
 ]
@@ -1394,6 +1395,36 @@ def gram_grad_cross(ck, z1, zd1, z2, zd2, W, mode, nblocks=None):
             out.data_ptr(), stream_ptr(z1.device),
         ),
         "gpar_gram_grad_cross",
+    )
+    return out
+
+
+def gram_grad_rows(ck, z1, z2, v, zd1=None, zd2=None, ws_doubles=None):
+    """Raw moment sums PER ROW of z1 (n1 x GRAD_NACC, device tensor): row a holds sum_b v[b] (moment of the pair (z1_a, z2_b)), what
+    `gram_grad_cross(GRAD_RECT)` returns for z1 = z1[a], W = v^T - one library call (gpar_gram_grad_rows), no n1 x n2 matrix.  zd1 / zd2:
+    both or neither (the period sums).  `ws_doubles`: the workspace to bring instead of the recommended one (a small one means fewer
+    splits of the rows of z2; from n1 * GRAD_NACC)."""
+    lib = _lib.load()
+    _check_mat(z1, "z1")
+    _check_mat(z2, "z2")
+    n1, n2 = int(z1.shape[0]), int(z2.shape[0])
+    v = v.reshape(-1).contiguous()
+    if v.numel() != n2 or v.dtype != torch.float64 or not v.is_cuda:
+        raise ValueError("v must hold one fp64 device weight per row of z2")
+    for a, b in ((zd1, z1), (zd2, z2)):
+        if a is not None:
+            _check_mat(a, "zd")
+            if _ld(a) != _ld(b) or a.shape[0] != b.shape[0]:
+                raise ValueError("features and their frequency derivatives must share rows and a leading dimension")
+    if ws_doubles is None:
+        ws_doubles = lib.gpar_workspace_doubles(_lib.WS_GRAM_GRAD_ROWS, n2, n1, 0)
+    ws = torch.empty(max(int(ws_doubles), 2), dtype=torch.float64, device=z1.device)
+    out = torch.empty(n1, _lib.GRAD_NACC, dtype=torch.float64, device=z1.device)
+    _lib.check(
+        lib.gpar_gram_grad_rows(ctypes.byref(ck.kspec), z1.data_ptr(), None if zd1 is None else zd1.data_ptr(), n1, _ld(z1), z2.data_ptr(),
+                                None if zd2 is None else zd2.data_ptr(), n2, _ld(z2), ck.dz, v.data_ptr(), out.data_ptr(), _lib.GRAD_NACC,
+                                ws.data_ptr(), int(ws_doubles), stream_ptr(z1.device)),
+        "gpar_gram_grad_rows",
     )
     return out
 

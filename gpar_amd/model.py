@@ -16,6 +16,7 @@ import collections
 import numpy as np
 import torch
 
+from ._lib import GPAR_MAX_TERMS
 from .engine import get_engine
 from .engine import joining as _joining
 from .gp import Obs, PseudoObs, PseudoObsDTC, PseudoObsFITC, Stacked, _score_rows, check_score
@@ -1092,6 +1093,55 @@ class GPAR:
                     x = torch.cat([x, f.mean(x).reshape(-1, 1)], dim=1)
                     U = torch.cat([U, dmean.reshape(-1, 1)], dim=1)
         return torch.cat(means, dim=1), (torch.cat(variances, dim=1) if variance else None)
+
+    def hyper_jacobian(self, x, chains):
+        """Per layer i an n* x P matrix: the TOTAL Jacobian of the plug-in latent mean mean[:, i] at x with respect to ALL layers'
+        trainable variables (P = sum of the layers' P_j, layer by layer, in the optimiser's unconstrained coordinates).  `chains[j]` =
+        (M_j, noise_col_j): layer j's chain rule as a matrix (`fastfit.DenseLayerObjective.chain_matrix`).  The layers are visited along
+        the plug-in path of `decompose` / `derivative` - layer i sees [x, latent means before it]:
+            with respect to its own variables        `Obs.mean_sensitivity`;
+            with respect to an earlier layer j's      sum_{k < i} d m_i / d (input column of output k) * d m_k / d theta_j,
+        the first factor from `derivative_moments` with unit direction fields.  The TRAINING inputs are held as given, exactly as
+        `fit(fix=True)` holds them: under `replace=True` the dependence of the replaced training inputs on earlier layers' variables is
+        ignored.  Inducing points: ValueError; an engine without `gram_grad_rows` raises NotImplementedError.  A Matern 1/2 layer after
+        the first has no input derivative (`derivative_moments`: ValueError).  [an addition: the reference has no such Jacobian]"""
+        if self.sparse:
+            raise ValueError("the hyperparameter Jacobian needs dense layers: inducing points are not supported")
+        if len(chains) != len(self.layers):
+            raise ValueError(f"{len(chains)} chain rules for {len(self.layers)} layers")
+        return _retry_unfused(lambda: self._hyper_jacobian(x, chains), self.layers, (x,))
+
+    def _hyper_jacobian(self, x, chains):
+        eng = get_engine()
+        x = eng.tensor(x)
+        if x.dim() == 1:
+            x = x[:, None]
+        m, ns = int(x.shape[1]), int(x.shape[0])
+        sizes = [int(np.asarray(M).shape[0]) for M, _ in chains]
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+        total = int(starts[-1])
+        out = []
+        with torch.no_grad():
+            for i, (is_last, model) in enumerate(last(self.layers)):
+                f, noise = model()
+                obs = getattr(f, "_obs", None)
+                if not isinstance(obs, Obs) or obs.base.is_posterior:
+                    raise ValueError("the hyperparameter Jacobian needs a conditioned model: every layer must hold dense observations of its prior")
+                noise_value = float(noise.detach()) if _is_torch(noise) else float(noise)
+                J = torch.zeros(ns, total, dtype=torch.float64, device=x.device)
+                J[:, starts[i]:starts[i + 1]] = obs.mean_sensitivity(f._pts(x), chains[i][0], chains[i][1], noise_value)
+                for k0 in range(0, i, GPAR_MAX_TERMS):   # (the derivative pass takes GPAR_MAX_TERMS directions a call)
+                    ks = list(range(k0, min(i, k0 + GPAR_MAX_TERMS)))
+                    U = torch.zeros(len(ks), ns, int(x.shape[1]), dtype=torch.float64, device=x.device)
+                    for c, k in enumerate(ks):
+                        U[c, :, m + k] = 1.0
+                    dmean, _ = f.derivative_moments(x, U, variance=False)
+                    for c, k in enumerate(ks):
+                        J += dmean[c].reshape(-1, 1) * out[k]
+                out.append(J)
+                if not is_last:
+                    x = torch.cat([x, f.mean(x).reshape(-1, 1)], dim=1)
+        return out
 
     # ---- helpers -----------------------------------------------------------------------------------
     @staticmethod

@@ -11,6 +11,7 @@ SURVEY.md Appendix C), so `get_variables()` dictionaries are interchangeable.
 import collections
 import fnmatch
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -24,7 +25,7 @@ from .optimise import minimise_l_bfgs_b
 from .spectrum import Periodogram, periodogram_grid, periodogram_inputs, spectral_peaks
 from .vars import Vars
 
-__all__ = ["GPARRegressor", "Decomposition", "Periodogram", "spectral_peaks", "log_transform", "squishing_transform"]
+__all__ = ["GPARRegressor", "Decomposition", "HyperPosterior", "Periodogram", "spectral_peaks", "log_transform", "squishing_transform"]
 
 
 def _xp(x):
@@ -197,6 +198,38 @@ def _model_generator(vs, m, pi, scale, scale_tie, per, per_period, per_scale, pe
 #: What `GPARRegressor.decompose` returns: per output a tuple of component names, a G_i x n* array of means, one of variances (or None
 #: for `var`), and the p normalisation shifts.
 Decomposition = collections.namedtuple("Decomposition", "names mean var offset")
+
+# What `laplace` returns: `names` the trained variables layer by layer, `value` / `stderr` one array per name in natural units, `cov` the
+# P x P covariance in the optimiser's unconstrained coordinates (block diagonal over layers), `flat` the dropped directions per layer;
+# `slices` (per name) and `layers` (per layer) locate them among the P coordinates.
+HyperPosterior = collections.namedtuple("HyperPosterior", "names value stderr cov flat slices layers")
+
+FLAT_RELATIVE = 1e-10   # eigenvalues of a layer's Hessian at or below this fraction of the largest (or <= 0) are flat directions
+
+
+def laplace_block(H, relative=FLAT_RELATIVE):
+    """(Sigma, flat, support) of one layer from the Hessian H of its negative log marginal likelihood: the pseudo-inverse over the
+    eigen-directions with eigenvalue > max(relative * lambda_max, 0) - the others are FLAT (not at a mode, or pinned at a bound), are left
+    out and counted in `flat`; `support[i]` = the squared length of coordinate i within the kept directions (0: the variable lies wholly
+    in flat directions and has no finite standard error)."""
+    H = np.asarray(H, dtype=np.float64)
+    if H.size == 0:
+        return np.zeros((0, 0)), 0, np.zeros(0)
+    lam, V = np.linalg.eigh(0.5 * (H + H.T))
+    keep = lam > max(relative * lam.max(), 0.0)
+    Vk = V[:, keep]
+    return (Vk / lam[keep]) @ Vk.T, int((~keep).sum()), (Vk ** 2).sum(axis=1)
+
+
+def block_diagonal(blocks):
+    """The blocks on the diagonal of one matrix, in order."""
+    sizes = [int(b.shape[0]) for b in blocks]
+    out = np.zeros((sum(sizes), sum(sizes)))
+    at = 0
+    for b, s in zip(blocks, sizes):
+        out[at:at + s, at:at + s] = b
+        at += s
+    return out
 
 
 def _group_terms(labels, components):
@@ -1259,6 +1292,150 @@ class GPARRegressor:
             mean = (mean * slope).cpu().numpy()
             var = (var * slope ** 2).cpu().numpy() if variance else None
         return mean, var
+
+    # ---- hyperparameter uncertainty: Laplace at the trained values, delta method for the forecast -------------------------------------
+    def _layer_chains(self):
+        """Every layer's chain rule as an object (`fastfit.LayerChain`): the layer's kernel over value holders and the layout of its
+        variables.  Host work only - no data, no device buffer, any number of rows."""
+        from . import fastfit
+
+        if self.sparse:
+            raise ValueError("hyperparameter uncertainty needs dense layers: inducing points are not supported")
+        eng = get_engine()
+        if not hasattr(eng, "gram_grad_rows"):
+            raise NotImplementedError(f"{type(eng).__name__} has no gram_grad_rows: per-row gradient sums are a device kernel "
+                                      "(gpar_gram_grad_rows); run them on the HIP engine")
+        out = []
+        for pi in range(self.p):
+            chain = fastfit.layer_chain(self, eng, self.vs, pi, [f"{pi}/*"])
+            if chain is None:
+                raise ValueError(f"layer {pi}: a kernel parameter is not one variable of the store; its chain rule cannot be traced")
+            out.append(chain)
+        return out
+
+    def _layer_objectives(self):
+        """Per layer (chain, fg) on the conditioned data: the chain rule (`_layer_chains`; the prepared objective itself where there is
+        one) and `fg(u)` -> (negative log marginal likelihood, gradient) in the optimiser's coordinates - the prepared objective of
+        `fit(fix=True)` (fastfit.build) where it applies, above `one_call_grad_rows()` rows (or wherever else it does not) the general
+        route's objective and back-propagated gradient, exactly what `fit` itself trains such a layer through."""
+        from . import fastfit
+        from .optimise import objective_and_gradient
+
+        chains = self._layer_chains()
+        eng = get_engine()
+        x_dev, y_dev, w_dev = eng.tensor(self.x), eng.tensor(self.y), eng.tensor(self.w)
+        if host_masks():
+            if y_dev is self.y:
+                y_dev = y_dev.view(y_dev.shape)
+            y_dev._host_nan, y_dev._host_nan_version = torch.isnan(self.y).numpy(), y_dev._version
+        y_cached = {k: list(per_output(y_dev, w_dev, keep=k)) for k in [True, False]}
+        self._prepare_kernels(self.m, self.p, self.n, training=True, inputs=False)
+        out = []
+        for pi, chain in enumerate(chains):
+            with torch.no_grad():
+                gpar = _construct_gpar(self, self.vs, self.m, pi + 1)
+                fixed_x, _ = gpar.logpdf(x_dev, y_cached, None, only_last_layer=True, outputs=list(range(pi)), return_inputs=True)
+            obj = fastfit.build(self, eng, self.vs, pi, [f"{pi}/*"], fixed_x, y_cached[bool(self.impute)][pi]) if self.fast_fit else None
+            if obj is not None and obj.names == chain.names:
+                out.append((obj, obj.fg))
+                continue
+
+            def neg_value(vs, pi=pi, fixed_x=fixed_x):
+                return -_construct_gpar(self, vs, self.m, pi + 1).logpdf(fixed_x, y_cached, None, only_last_layer=True, outputs=[pi])
+
+            out.append((chain, objective_and_gradient(neg_value, self.vs, chain.names)[0]))
+        return out
+
+    def laplace(self, x, y, w=None):
+        """How sure the trained values are - an addition; the reference's todo.tasks asks for an "overview of trained hyperparameters".
+        The Laplace approximation at the current values, layer by layer (layers train independently under `fit(fix=True)`: no
+        cross-layer blocks): H = the Hessian of the layer's negative log marginal likelihood on (x, y, w) in the optimiser's
+        unconstrained coordinates (`fastfit.hessian_of`: a central difference of the analytic gradient, 2 P evaluations - of the
+        prepared objective where `fit(fix=True)` trains the layer through it, of the general route's back-propagated gradient above
+        `one_call_grad_rows()` rows),
+        Sigma = its pseudo-inverse over the directions with eigenvalue > 1e-10 lambda_max.  The others are FLAT - the values are not at
+        a mode there, or a variable is pinned at a bound -, are left out and counted; any flat direction issues ONE warning.
+
+        Returns `HyperPosterior(names, value, stderr, cov, flat, slices, layers)`: the trained variables' names layer by layer, per name
+        the value and the standard error in natural units (delta method through the variable's transform: |d value / d u| sqrt(cov_uu);
+        inf for a variable lying wholly in flat directions), `cov` (P x P, block diagonal over layers, unconstrained coordinates),
+        `flat` per layer; `slices[k]` / `layers[i]` locate name k / layer i among the P coordinates.  The data are conditioned on, as
+        `fit` does.  RuntimeError: neither fitted nor conditioned; ValueError: inducing points; NotImplementedError: an engine without
+        `gram_grad_rows` (the forecast's side of this needs it: `predict_moments_hyper`)."""
+        if not self.is_conditioned:
+            raise RuntimeError("Must condition or fit model before the Laplace approximation.")
+        if self.sparse:
+            raise ValueError("hyperparameter uncertainty needs dense layers: inducing points are not supported")
+        self.condition(x, y, w)
+        names, values, errors, slices, layers, blocks, flats = [], [], [], [], [], [], []
+        at = 0
+        from .fastfit import hessian_of
+
+        for obj, fg in self._layer_objectives():
+            u = self.vs.get_vector(obj.names)
+            try:
+                sigma, flat, support = laplace_block(hessian_of(fg, u))
+            finally:
+                self.vs.set_vector(u, obj.names)   # (the general route's evaluations write the store)
+            value, slope = obj.natural(u)
+            sd = np.where(support > 1e-12, np.abs(slope) * np.sqrt(np.maximum(np.diag(sigma), 0.0)), np.inf)
+            for name, kind, lower, upper, sl, shape in obj.layout:
+                names.append(name)
+                values.append(value[sl].reshape(shape))
+                errors.append(sd[sl].reshape(shape))
+                slices.append(slice(at + sl.start, at + sl.stop))
+            layers.append(slice(at, at + obj.size))
+            at += obj.size
+            blocks.append(sigma)
+            flats.append(flat)
+        if any(flats):
+            warnings.warn(f"laplace: {sum(flats)} flat direction(s) of the training objective (per layer: {tuple(flats)}) - not at a mode, or a "
+                          "variable pinned at a bound; they are left out of the covariance", stacklevel=2)
+        return HyperPosterior(tuple(names), tuple(values), tuple(errors), block_diagonal(blocks), tuple(flats), tuple(slices), tuple(layers))
+
+    def predict_moments_hyper(self, x, hp, w=None, latent=False):
+        """What the uncertainty of the trained values does to the forecast - an addition.  Returns `(mean, var, var_hyper)`, three n* x p
+        arrays: `mean` and `var` are `predict_moments(x, w, latent)` (that call), and, to first order (Laplace at the mode, delta method),
+            var_hyper[:, i] = diag(J_i Sigma J_i^T)        in the units of y,
+        J_i the TOTAL Jacobian of output i's plug-in latent mean over all layers' variables (`GPAR.hyper_jacobian`: per layer one fused
+        device pass with the row index unreduced, `gpar_gram_grad_rows`, and the chain rule through the test-time inputs) and Sigma =
+        `hp.cov` from `laplace`.  The first-order total variance is var + var_hyper; the sensitivity of `var` itself to the
+        hyperparameters is second order and left out, and so is, under `replace=True`, the dependence of the replaced TRAINING inputs on
+        earlier layers' variables (they are held as given, as `fit(fix=True)` holds them).  `matern=0.5` is served for a model with ONE output (the
+        parameter gradient takes the r = 0 multiplier as 0, as in training); with more outputs it is refused up front (ValueError): a
+        Matern 1/2 layer after the first has no input derivative for the chain rule.  Any number of rows: the chain rule is traced
+        on the host (`fastfit.LayerChain`) and needs none of the training objective's buffers.  ValueError: inducing points, a non-identity
+        `transform_y`, `replace=False` (`predict_moments`), an `hp` of another model; NotImplementedError: an engine without
+        `gram_grad_rows`."""
+        if not self.is_conditioned:
+            raise RuntimeError("Must condition or fit model before predicting.")
+        if self.sparse:
+            raise ValueError("hyperparameter uncertainty needs dense layers: inducing points are not supported")
+        self._check_identity_transform()
+        if self.model_config.get("matern") == 0.5 and self.p > 1:
+            raise ValueError("matern=0.5 with more than one output: a Matern 1/2 layer after the first has no input derivative for the "
+                             "chain rule through the earlier outputs (its process is not differentiable)")
+        eng = get_engine()
+        if not hasattr(eng, "gram_grad_rows"):
+            raise NotImplementedError(f"{type(eng).__name__} has no gram_grad_rows: per-row gradient sums are a device kernel "
+                                      "(gpar_gram_grad_rows); run them on the HIP engine")
+        mean, var = self.predict_moments(x, w, latent)
+        objectives = self._layer_chains()
+        cov = np.asarray(hp.cov, dtype=np.float64)
+        if tuple(n for obj in objectives for n in obj.names) != tuple(hp.names) or cov.shape[0] != sum(obj.size for obj in objectives):
+            raise ValueError("hp does not belong to this model: its names are not the trained variables of the layers")
+        chains = [obj.chain_matrix(self.vs.get_vector(obj.names)) for obj in objectives]
+        x = _uprank(_to_engine(x))
+        gpar = self._stream_posterior() if getattr(self, "_stream_cache", None) is not None else None
+        if gpar is None:
+            gpar = _construct_gpar(self, self.vs, self.m, self.p) | (self.x, self.y, self.w)
+        with torch.no_grad():
+            jac = gpar.hyper_jacobian(x, chains)
+            sigma = torch.from_numpy(cov).to(x.device)
+            zero = torch.zeros(1, self.p, dtype=torch.float64, device=x.device)
+            slope = self._unnormalise_y(torch.ones_like(zero)) - self._unnormalise_y(zero)
+            extra = torch.stack([((J @ sigma) * J).sum(dim=1) for J in jac], dim=1) * slope ** 2
+        return mean, var, extra.cpu().numpy()
 
     def sample(self, x, w=None, p=None, posterior=False, num_samples=1, latent=False, _conditioned=None, sampler="exact", features=2048):
         """Draw samples from the prior or the posterior at inputs x; a single ndarray for num_samples=1, otherwise

@@ -628,6 +628,28 @@ int gpar_gram_grad_cross(const gpar_kspec_t* ks, const double* z1, const double*
                          const double* zd2, int n2, int ldz2, int dz, const double* W, int ldw, int mode, double* workspace,
                          int nblocks, double* out, void* stream);
 
+/* The same moment sums with the ROW index left unreduced (an addition within ABI v21: no existing entry changes):
+ *     out[a * ldo + s] = sum_{b < n2} v[b] * (moment s of the pair (z1_a, z2_b)),   a < n1, s < GPAR_GRAD_NACC,
+ * slots, order and conventions those of gpar_gram_grad_cross(GPAR_GRAD_RECT) - C_t, Al_f, A_q, P_q; full sums; d/dscale = -2 A / scale;
+ * the Matern-1/2 multiplier 0 at r = 0; the cosine convention of ABI v17 - so that row a is what that call returns for n1 = 1,
+ * z1 = z1[a], W = v^T, and the host's raw-slot -> variable chain rule applies to a row unchanged.  With v = alpha = K^-1 y these are the
+ * sums behind d mean(x*_a) / d theta of a conditioned layer.  One fused pass (csrc/gram_grad_rows.h): a workgroup owns 64 rows of z1,
+ * the rows of z2 are staged through LDS and split over the grid, the splits' partial sums are added in a fixed order.  Only the slots
+ * the structure uses are accumulated; every other slot is written as 0.  The per-pair arithmetic is the interpreted gradient pass's.
+ * zd1 / zd2: both NULL (no P_q: those slots are 0) or both given, the rule of gpar_gram_grad_cross.  ldo >= GPAR_GRAD_NACC.
+ * ws: ws_doubles doubles; gpar_workspace_doubles(GPAR_WS_GRAM_GRAD_ROWS, n2, n1, 0) is the size to bring.  Any size from
+ * n1 * GPAR_GRAD_NACC doubles is taken, at the cost of fewer splits (a split keeps n1 * GPAR_GRAD_NACC doubles; the last bits depend on
+ * the number of splits, so on ws_doubles).  No floating-point atomics: for given arguments a call returns the same bits every time, and a
+ * row's bits do not depend on the other rows of the call, among calls that split n2 alike.
+ * n1 == 0: nothing is done.  n2 == 0: zeros.
+ * Argument errors - a negative n1 / n2, dz outside 0 .. GPAR_MAX_DIMS or a factor reaching past it, more than 4 factors in a term, ldo,
+ * ldz1, ldz2 or the workspace too small, a NULL array that would be read, one of zd1 / zd2 NULL and the other not, tiles and accumulators
+ * that do not fit 160 KiB of LDS ((2, with zd 4) max(dz, 1) 68 + 68 + 64 used slots doubles + GPAR_GRAD_NACC ints: without zd dz <= 95
+ * always fits, with zd dz <= 47) - are found before the first launch: a negative status, `out` untouched.
+ * [no reference counterpart; in Python: Obs.mean_sensitivity, GPAR.hyper_jacobian, GPARRegressor.predict_moments_hyper] */
+int gpar_gram_grad_rows(const gpar_kspec_t* ks, const double* z1, const double* zd1, int n1, int ldz1, const double* z2, const double* zd2,
+                        int n2, int ldz2, int dz, const double* v, double* out, int ldo, double* ws, long long ws_doubles, void* stream);
+
 /* Gradient with respect to the inputs, in feature space:  out[a][q] = sum_b W(a, b) d k(z1_a, z2_b) / d z1_a[q]  for the
  * pair weights W (GPAR_GRAD_RECT: n1 x n2;  GPAR_GRAD_SYM: z2 == z1, W symmetric, lower triangle read).  out: n1 x dz (ldo);
  * workspace: gpar_workspace_doubles(GPAR_WS_INPUT_GRAD, n1, dz, nsplit) doubles; nsplit >= 1 column splits (summed in order).
@@ -824,7 +846,8 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
  *   GPAR_WS_AHEAD_MULTI  (n, grad, nh)    the `vec` of gpar_ahead_multi_dense (grad = 0) / gpar_ahead_multi_dense_grad[_finish] (grad = 1)
  *   GPAR_WS_AHEAD_WINDOW (n, grad, -)     the `vec` of gpar_ahead_window_dense (grad = 0) / gpar_ahead_window_dense_grad (grad = 1)
  *   GPAR_WS_POSTERIOR_TERMS (n, ns, ncomp)  gpar_posterior_terms (the recommended size; see there for the least)
- *   GPAR_WS_POSTERIOR_DERIV (n, ns, ndir)   gpar_posterior_deriv (likewise) */
+ *   GPAR_WS_POSTERIOR_DERIV (n, ns, ndir)   gpar_posterior_deriv (likewise)
+ *   GPAR_WS_GRAM_GRAD_ROWS  (n2, n1, -)     gpar_gram_grad_rows (likewise) */
 #define GPAR_WS_GEMM_SPLITK 1
 #define GPAR_WS_GEMV_T 2
 #define GPAR_WS_GRAM_GRAD 3
@@ -841,6 +864,7 @@ int gpar_unpack_lower(const double* in, int n, double* A, int lda, void* stream)
 #define GPAR_WS_POSTERIOR_TERMS 14
 #define GPAR_WS_GRAM_APPLY 15   /* (n, rows, output columns)  gpar_gram_apply_groups */
 #define GPAR_WS_POSTERIOR_DERIV 16   /* (n, ns, ndir)  gpar_posterior_deriv (the recommended size; see there for the least) */
+#define GPAR_WS_GRAM_GRAD_ROWS 17   /* (n2, n1, -)  gpar_gram_grad_rows (the recommended size; see there for the least) */
 long long gpar_workspace_doubles(int op, int a, int b, int c);
 /* Standard normals from Philox-4x32-10 + Box-Muller: out[r][c], element index = r*cols + c in the stream
  * identified by (seed, offset).   [B.randn in Normal.sample] */
