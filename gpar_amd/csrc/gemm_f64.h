@@ -189,36 +189,148 @@ __device__ __forceinline__ void gemm_mainloop(const GemmArgs& p, double* smem, g
     }
 }
 
+// Build-time switches of the fast K loop's instruction stream (same arithmetic in every setting):
+//   ADDR_ONCE    operand addresses are formed once per tile (GemmSrc) instead of per load
+//   FRAG_AHEAD   the LDS fragments of sub-step k4 + 1 are read before the MFMAs of sub-step k4
+//   SPLIT_STORE  the LDS stores of the next stage sit inside the last two MFMA groups instead of behind the MFMA phase
+#ifndef GPAR_GEMM_ADDR_ONCE
+#define GPAR_GEMM_ADDR_ONCE 1
+#endif
+#ifndef GPAR_GEMM_FRAG_AHEAD
+#define GPAR_GEMM_FRAG_AHEAD 1
+#endif
+#ifndef GPAR_GEMM_SPLIT_STORE
+#define GPAR_GEMM_SPLIT_STORE 1
+#endif
+// The fast K loop addresses an operand tile with 32-bit byte offsets from the tile's first element (GemmSrc): 128 rows of
+// a k-contiguous operand, 16 of the other kind.  Tiles of operands with a longer leading dimension take the general loop.
+constexpr int GEMM_FAST_LD_MAX = 1 << 21;
+
+// Where the 16-byte chunks of one thread lie in a FAST operand tile (see gemm_gload): a wave-uniform base - the tile's
+// first row (KC) or first column (MC), in scalar registers - plus 32-bit byte offsets that stay the same for the whole
+// tile, so a stage's loads are `base + k + voff` with a wave-uniform k: no vector address arithmetic in the K loop.
+// FAST == 1: chunk q lies q * qstep bytes (wave-uniform) behind chunk 0; FAST == 2: every chunk has its clamped row's offset.
+template <bool KC, int FAST, int ROWS>
+struct GemmSrc {
+    const char* base;
+    size_t kstep;   // bytes per unit of k
+    unsigned qstep;
+    unsigned voff[FAST == 2 ? ROWS / 32 : 1];
+};
+
+template <bool KC, int FAST, int ROWS>
+__device__ __forceinline__ GemmSrc<KC, FAST, ROWS> gemm_src(const double* __restrict__ g, int ld, int r0, int rmax, int t) {
+    static_assert(FAST != 0, "branch-free loads only");
+    GemmSrc<KC, FAST, ROWS> s;
+    r0 = __builtin_amdgcn_readfirstlane(r0);
+    // (the lower half tile of an overhanging tile row can lie wholly behind the last row - 129 rows: the half that starts at row
+    // 192 -: every one of its rows is the last valid one, and the offsets below are differences of clamped rows, never negative)
+    if (FAST == 2) r0 = min(r0, rmax - 1);
+    if (KC) {
+        const int r = t >> 3, kk = (t & 7) * 2;
+        s.base = reinterpret_cast<const char*>(g + (size_t)r0 * ld);
+        s.kstep = 8;
+        s.qstep = 32u * (unsigned)ld * 8u;
+        if (FAST == 2) {
+#pragma unroll
+            for (int q = 0; q < ROWS / 32; ++q) s.voff[q] = ((unsigned)(min(r0 + r + 32 * q, rmax - 1) - r0) * (unsigned)ld + (unsigned)kk) * 8u;
+        } else {
+            s.voff[0] = ((unsigned)r * (unsigned)ld + (unsigned)kk) * 8u;
+        }
+    } else {
+        const int kk = t / (ROWS / 2), r = (t % (ROWS / 2)) * 2;
+        s.base = reinterpret_cast<const char*>(g + r0);
+        s.kstep = (size_t)ld * 8;
+        s.qstep = (unsigned)(512 / ROWS) * (unsigned)ld * 8u;
+        s.voff[0] = ((unsigned)kk * (unsigned)ld + (unsigned)r) * 8u;
+        if (FAST == 2) {   // (never run: the clamp is for k-contiguous operands; kept consistent with gemm_gload_src)
+#pragma unroll
+            for (int q = 1; q < ROWS / 32; ++q) s.voff[q] = s.voff[0] + q * s.qstep;
+        }
+    }
+    return s;
+}
+
+// A wave-uniform address of global memory, in scalar registers.  (The address space is spelled out: a pointer rebuilt from
+// integers is a generic one to the compiler, whose flat loads count on the LDS counter as well.)
+typedef const __attribute__((address_space(1))) char* gpar_gptr;
+typedef const __attribute__((address_space(1))) gpar_d2* gpar_gptr_d2;
+__device__ __forceinline__ gpar_gptr gemm_uniform(const char* ptr) {
+    const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return (gpar_gptr)(((unsigned long long)hi << 32) | lo);
+}
+
+// The loads of gemm_gload<KC, FAST, ROWS>(g, ld, r0, rmax, k0, ...) from a prepared source; k0 is wave-uniform.
+template <bool KC, int FAST, int ROWS>
+__device__ __forceinline__ void gemm_gload_src(const GemmSrc<KC, FAST, ROWS>& s, int k0, gpar_d2 (&reg)[ROWS / 32]) {
+    const char* sb = s.base + (size_t)k0 * s.kstep;
+#pragma unroll
+    for (int q = 0; q < ROWS / 32; ++q) {
+        // (the scalar part is named as such, or hipcc folds it into a 64-bit vector sum per chunk and adds that to the lane offset with
+        // vector ALU; the empty asm keeps the offset's zero extension beside the load, where instruction selection folds both into the
+        // scalar-base form of the load - hoisted out of the K loop, the extension costs a 64-bit vector add per load instead)
+        unsigned vo = s.voff[FAST == 2 ? q : 0];
+        asm volatile("" : "+v"(vo));
+        reg[q] = *(gpar_gptr_d2)(gemm_uniform(sb + (FAST == 2 ? (size_t)0 : (size_t)q * s.qstep)) + vo);
+    }
+}
+
+// LDS fragments of the 4-deep sub-step k4 of a stage: lane l holds row / column l & 15 of each 16-wide block at k = 4 k4 + (l >> 4).
+template <bool A_KC, bool B_KC, int BM>
+__device__ __forceinline__ void gemm_frag(const double* __restrict__ As, const double* __restrict__ Bs, int k4, int l15, int lk,
+                                          int wm, int wn, double (&af)[BM / 32], double (&bf)[4]) {
+    const int kk = k4 * 4 + lk;
+#pragma unroll
+    for (int mi = 0; mi < BM / 32; ++mi) {
+        const int r = wm * (BM / 2) + 16 * mi + l15;
+        af[mi] = A_KC ? As[r * GEMM_LDKC + kk] : As[kk * GEMM_LDMC + r];
+    }
+#pragma unroll
+    for (int nj = 0; nj < 4; ++nj) {
+        const int c = wn * 64 + 16 * nj + l15;
+        bf[nj] = B_KC ? Bs[c * GEMM_LDKC + kk] : Bs[kk * GEMM_LDMC + c];
+    }
+}
+
 // One 16-deep stage of the K loop out of LDS images As / Bs; after the first quarter of its MFMAs the global loads of a
 // LATER stage (k offset `knext`) are issued into (ra, rb).
+// FRAG_AHEAD: (af, bf)[0] arrive holding the fragments of sub-step 0 (read by the caller right behind the barrier); the
+// reads of sub-step k4 + 1 are issued in front of the MFMAs of sub-step k4, so the wait in front of an MFMA group is for
+// reads that have had a whole group's issue time to return.  Set 0 is free again when the stage ends.
+// SPLIT_STORE: (sa, sb), the operands of the NEXT stage (requested a stage ago), go to its LDS images An / Bn inside the last
+// two MFMA groups; nothing reads those images between the barriers on either side of this stage.
+// Every accumulator receives its MFMAs in the order k4 = 0, 1, 2, 3 whatever the switches say.
 template <bool A_KC, bool B_KC, int FAST, int BM>
 __device__ __forceinline__ void gemm_stage(const GemmArgs& p, const double* __restrict__ As, const double* __restrict__ Bs,
-                                           gpar_d4 (&acc)[BM / 32][4], int m0, int n0, int knext, int kend, int t, int l15, int lk,
-                                           int wm, int wn, gpar_d2 (&ra)[BM / 32], gpar_d2 (&rb)[4]) {
+                                           gpar_d4 (&acc)[BM / 32][4], const GemmSrc<A_KC, FAST, BM>& srcA,
+                                           const GemmSrc<B_KC, FAST, 128>& srcB, int m0, int n0, int knext, int kend, int t, int l15, int lk,
+                                           int wm, int wn, double (&af)[2][BM / 32], double (&bf)[2][4], gpar_d2 (&ra)[BM / 32],
+                                           gpar_d2 (&rb)[4], double* __restrict__ An, double* __restrict__ Bn, const gpar_d2 (&sa)[BM / 32],
+                                           const gpar_d2 (&sb)[4]) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int k4 = 0; k4 < 4; ++k4) {
-        const int kk = k4 * 4 + lk;
-        double af[BM / 32], bf[4];
+        const int cur = GPAR_GEMM_FRAG_AHEAD ? (k4 & 1) : 0;
+        if (!GPAR_GEMM_FRAG_AHEAD) gemm_frag<A_KC, B_KC, BM>(As, Bs, k4, l15, lk, wm, wn, af[0], bf[0]);
+        else if (k4 < 3) gemm_frag<A_KC, B_KC, BM>(As, Bs, k4 + 1, l15, lk, wm, wn, af[cur ^ 1], bf[cur ^ 1]);
 #pragma unroll
         for (int mi = 0; mi < BM / 32; ++mi) {
-            const int r = wm * (BM / 2) + 16 * mi + l15;
-            af[mi] = A_KC ? As[r * GEMM_LDKC + kk] : As[kk * GEMM_LDMC + r];
-        }
-#pragma unroll
-        for (int nj = 0; nj < 4; ++nj) {
-            const int c = wn * 64 + 16 * nj + l15;
-            bf[nj] = B_KC ? Bs[c * GEMM_LDKC + kk] : Bs[kk * GEMM_LDMC + c];
-        }
-#pragma unroll
-        for (int mi = 0; mi < BM / 32; ++mi)
 #pragma unroll
             for (int nj = 0; nj < 4; ++nj) {
-                acc[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[mi], bf[nj], acc[mi][nj], 0, 0, 0);
+                acc[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[cur][mi], bf[cur][nj], acc[mi][nj], 0, 0, 0);
             }
+            if (GPAR_GEMM_SPLIT_STORE && mi == 0 && k4 == 2) gemm_sstore<A_KC, BM>(An, t, sa);
+            if (GPAR_GEMM_SPLIT_STORE && mi == 0 && k4 == 3) gemm_sstore<B_KC>(Bn, t, sb);
+        }
         if (k4 == 0) {
+#if GPAR_GEMM_ADDR_ONCE
+            gemm_gload_src<A_KC, FAST, BM>(srcA, knext, ra);
+            gemm_gload_src<B_KC, FAST, 128>(srcB, knext, rb);
+#else
             gemm_gload<A_KC, FAST, BM>(p.A, p.lda, m0, p.m, knext, kend, false, t, ra);
             gemm_gload<B_KC, FAST>(p.B, p.ldb, n0, p.n, knext, kend, false, t, rb);
+#endif
         }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -243,10 +355,19 @@ __device__ __forceinline__ void gemm_mainloop_pf2(const GemmArgs& p, double* sme
     double* buf0 = smem;
     double* buf1 = smem + 2 * GEMM_TILE;
     const int klast = kbeg + (nk - 1) * GEMM_BK;
+    const GemmSrc<A_KC, FAST, BM> srcA = gemm_src<A_KC, FAST, BM>(p.A, p.lda, m0, p.m, t);
+    const GemmSrc<B_KC, FAST, 128> srcB = gemm_src<B_KC, FAST, 128>(p.B, p.ldb, n0, p.n, t);
+#if GPAR_GEMM_ADDR_ONCE
+    gemm_gload_src<A_KC, FAST, BM>(srcA, kbeg, ra0);
+    gemm_gload_src<B_KC, FAST, 128>(srcB, kbeg, rb0);
+    gemm_gload_src<A_KC, FAST, BM>(srcA, min(kbeg + GEMM_BK, klast), ra1);
+    gemm_gload_src<B_KC, FAST, 128>(srcB, min(kbeg + GEMM_BK, klast), rb1);
+#else
     gemm_gload<A_KC, FAST, BM>(p.A, p.lda, m0, p.m, kbeg, kend, false, t, ra0);
     gemm_gload<B_KC, FAST>(p.B, p.ldb, n0, p.n, kbeg, kend, false, t, rb0);
     gemm_gload<A_KC, FAST, BM>(p.A, p.lda, m0, p.m, min(kbeg + GEMM_BK, klast), kend, false, t, ra1);
     gemm_gload<B_KC, FAST>(p.B, p.ldb, n0, p.n, min(kbeg + GEMM_BK, klast), kend, false, t, rb1);
+#endif
     if (PRELOAD) {
         // wave-uniform base (scalar registers) + one 32-bit lane offset: no per-row address registers beside the accumulators
         const int wmu = __builtin_amdgcn_readfirstlane(wm), wnu = __builtin_amdgcn_readfirstlane(wn);
@@ -266,6 +387,8 @@ __device__ __forceinline__ void gemm_mainloop_pf2(const GemmArgs& p, double* sme
     gemm_sstore<B_KC>(buf0 + GEMM_TILE, t, rb0);
     __syncthreads();
     const int l15 = lane & 15, lk = lane >> 4;
+    double af[2][BM / 32], bf[2][4];
+    if (GPAR_GEMM_FRAG_AHEAD) gemm_frag<A_KC, B_KC, BM>(buf0, buf0 + GEMM_TILE, 0, l15, lk, wm, wn, af[0], bf[0]);
 #ifdef GPAR_GEMM_STAGE_STAMPS
 #define GEMM_STAGE_STAMP(stage, which)                                                                                     \
     do {                                                                                                                   \
@@ -276,29 +399,46 @@ __device__ __forceinline__ void gemm_mainloop_pf2(const GemmArgs& p, double* sme
 #else
 #define GEMM_STAGE_STAMP(stage, which) do {} while (0)
 #endif
-    for (int kt = 0; kt < nk; kt += 2) {
+    // The loop runs whole PAIRS of stages and leaves in one place; an odd stage count ends in one more stage behind it.  (With an
+    // exit in the middle of the pair, the compiler's flow graph carried an edge from that exit back to the loop's head, and its
+    // counter bookkeeping then assumed at the head that the loads just requested into (ra0, rb0) might be the ones in flight:
+    // every even stage opened with vmcnt(0), i.e. waited for the loads of the stage before it - half of the two-stage distance.)
+    int kt = 0;
+    for (; kt + 2 <= nk; kt += 2) {
         // even stage: compute buf0; (ra1, rb1) carry stage kt + 1; stage kt + 2 is requested into (ra0, rb0)
         GEMM_STAGE_STAMP(kt, 0);
-        gemm_stage<A_KC, B_KC, FAST, BM>(p, buf0, buf0 + GEMM_TILE, acc, m0, n0, min(kbeg + (kt + 2) * GEMM_BK, klast), kend, t, l15,
-                                     lk, wm, wn, ra0, rb0);
+        gemm_stage<A_KC, B_KC, FAST, BM>(p, buf0, buf0 + GEMM_TILE, acc, srcA, srcB, m0, n0, min(kbeg + (kt + 2) * GEMM_BK, klast), kend,
+                                         t, l15, lk, wm, wn, af, bf, ra0, rb0, buf1, buf1 + GEMM_TILE, ra1, rb1);
         GEMM_STAGE_STAMP(kt, 1);
-        if (kt + 1 >= nk) break;
-        gemm_sstore<A_KC, BM>(buf1, t, ra1);
-        gemm_sstore<B_KC>(buf1 + GEMM_TILE, t, rb1);
+        if (!GPAR_GEMM_SPLIT_STORE) {
+            gemm_sstore<A_KC, BM>(buf1, t, ra1);
+            gemm_sstore<B_KC>(buf1 + GEMM_TILE, t, rb1);
+        }
         GEMM_STAGE_STAMP(kt, 2);
         __syncthreads();
+        if (GPAR_GEMM_FRAG_AHEAD) gemm_frag<A_KC, B_KC, BM>(buf1, buf1 + GEMM_TILE, 0, l15, lk, wm, wn, af[0], bf[0]);
         // odd stage: compute buf1; (ra0, rb0) carry stage kt + 2; stage kt + 3 is requested into (ra1, rb1)
         GEMM_STAGE_STAMP(kt + 1, 0);
-        gemm_stage<A_KC, B_KC, FAST, BM>(p, buf1, buf1 + GEMM_TILE, acc, m0, n0, min(kbeg + (kt + 3) * GEMM_BK, klast), kend, t, l15,
-                                     lk, wm, wn, ra1, rb1);
+        gemm_stage<A_KC, B_KC, FAST, BM>(p, buf1, buf1 + GEMM_TILE, acc, srcA, srcB, m0, n0, min(kbeg + (kt + 3) * GEMM_BK, klast), kend,
+                                         t, l15, lk, wm, wn, af, bf, ra1, rb1, buf0, buf0 + GEMM_TILE, ra0, rb0);
         GEMM_STAGE_STAMP(kt + 1, 1);
-        if (kt + 2 >= nk) break;
-        gemm_sstore<A_KC, BM>(buf0, t, ra0);
-        gemm_sstore<B_KC>(buf0 + GEMM_TILE, t, rb0);
+        // (behind the last pair of an even stage count this stores a second copy of the last stage, which nothing reads, and its
+        // barrier is the one the epilogue needs)
+        if (!GPAR_GEMM_SPLIT_STORE) {
+            gemm_sstore<A_KC, BM>(buf0, t, ra0);
+            gemm_sstore<B_KC>(buf0 + GEMM_TILE, t, rb0);
+        }
         GEMM_STAGE_STAMP(kt + 1, 2);
         __syncthreads();
+        if (GPAR_GEMM_FRAG_AHEAD) gemm_frag<A_KC, B_KC, BM>(buf0, buf0 + GEMM_TILE, 0, l15, lk, wm, wn, af[0], bf[0]);
     }
-    __syncthreads();   // the epilogue reuses the stage buffers
+    if (kt < nk) {
+        GEMM_STAGE_STAMP(kt, 0);
+        gemm_stage<A_KC, B_KC, FAST, BM>(p, buf0, buf0 + GEMM_TILE, acc, srcA, srcB, m0, n0, klast, kend, t, l15, lk, wm, wn, af, bf, ra0,
+                                         rb0, buf1, buf1 + GEMM_TILE, ra1, rb1);
+        GEMM_STAGE_STAMP(kt, 1);
+        __syncthreads();   // the epilogue reuses the stage buffers
+    }
 }
 
 // Epilogue of an interior tile with a 16-byte aligned C: the accumulators go through LDS (the operand stages are dead after
@@ -428,7 +568,7 @@ __device__ __forceinline__ void gemm_tile_body(GemmArgs& p, double* smem, const 
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = gpar_d4{0.0, 0.0, 0.0, 0.0};
 
-    const bool fastk = p.fastA && p.fastB && !a_lower && ((kend - kbeg) % GEMM_BK == 0);
+    const bool fastk = p.fastA && p.fastB && !a_lower && ((kend - kbeg) % GEMM_BK == 0) && p.lda <= GEMM_FAST_LD_MAX && p.ldb <= GEMM_FAST_LD_MAX;
     const bool inner = (m0 + BM <= p.m) && (n0 + GEMM_BN <= p.n);
     // (see PRELOAD above; not with split-K, whose slabs are partial sums, nor for diagonal tiles of a lower-triangular C)
     const bool c_lower = (p.flags & GPAR_GEMM_C_LOWER) != 0;

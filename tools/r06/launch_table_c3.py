@@ -30,7 +30,11 @@ lib.gpar_profile_read(ctypes.byref(l), ctypes.byref(ms), ctypes.byref(busy), cty
 print(f"== C3 lock-step evaluation: {e0.elapsed_time(e1):.2f} ms; {l.value} update launches, sum {ms.value:.2f} ms, union {busy.value:.2f} ms, "
       f"{fl.value / (busy.value * 1e-3) * 1e-12:.1f} TF over the union")
 print("   start_ms    dur_us     rows   cols  Kxbatch   tiles(x8)  rounds   TFLOP/s(own duration)")
+TAIL = 1   # rows of the augmented matrix below the factored part: y^T
 def tiles(rows, cols):
+    # the hook reports the update's full row count; the tile launch of a lock-step batch stops TAIL rows earlier when that removes
+    # a tile row (potrf_tail_split, gpar_amd/csrc/potrf_schedule.h), and potrf_tail_update_kernel updates those rows
+    if -(-(rows - TAIL) // 128) < -(-rows // 128): rows -= TAIL
     tm, tn = -(-rows // 128), -(-cols // 128); tn = min(tn, tm)
     return tn * (tn + 1) // 2 + (tm - tn) * tn
 for line in open(dump):

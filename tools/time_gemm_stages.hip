@@ -10,17 +10,20 @@
 using namespace gpar;
 int main(int argc, char** argv) {
     const int n = 16384, K = argc > 1 ? atoi(argv[1]) : 512;
+    const int ldp = K > 1024 ? K : 1024;   // the panel holds all K columns (K = 1536: the rest update)
+    // argv[2] = 1: one workgroup per compute unit (the LDS request leaves no room for a second)
+    const int lds = (argc > 2 && atoi(argv[2]) == 1) ? 96 * 1024 : GEMM_LDS_BYTES;
     double *C, *P; long long* st;
-    (void)hipMalloc(&C, sizeof(double) * (size_t)n * n); (void)hipMalloc(&P, sizeof(double) * (size_t)n * 1024);
-    (void)hipMemset(C, 0, sizeof(double) * (size_t)n * n); (void)hipMemset(P, 0, sizeof(double) * (size_t)n * 1024);
-    GemmArgs p{}; p.A = P; p.B = P; p.C = C; p.m = n; p.n = n; p.k = K; p.lda = 1024; p.ldb = 1024; p.ldc = n;
+    (void)hipMalloc(&C, sizeof(double) * (size_t)n * n); (void)hipMalloc(&P, sizeof(double) * (size_t)n * ldp);
+    (void)hipMemset(C, 0, sizeof(double) * (size_t)n * n); (void)hipMemset(P, 0, sizeof(double) * (size_t)n * ldp);
+    GemmArgs p{}; p.A = P; p.B = P; p.C = C; p.m = n; p.n = n; p.k = K; p.lda = ldp; p.ldb = ldp; p.ldc = n;
     p.alpha = -1; p.beta = 1; p.flags = GPAR_GEMM_C_LOWER; p.tiles_m = n / 128; p.tiles_n = n / 128; p.fastA = p.fastB = p.fastC = 1;
     const int ntiles = gemm_num_tiles(p.tiles_m, p.tiles_n, p.flags);
     (void)hipMalloc(&st, sizeof(long long) * 64 * 40 * 3); (void)hipMemset(st, 0, sizeof(long long) * 64 * 40 * 3);
     p.stage_stamps = st;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f64_kernel<false, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     for (int rep = 0; rep < 2; ++rep) {
-        hipLaunchKernelGGL((gemm_f64_kernel<false, true, 1>), dim3(ntiles), dim3(256), GEMM_LDS_BYTES, 0, p);
+        hipLaunchKernelGGL((gemm_f64_kernel<false, true, 1>), dim3(ntiles), dim3(256), lds, 0, p);
         (void)hipDeviceSynchronize();
     }
     std::vector<long long> h(64 * 40 * 3);
