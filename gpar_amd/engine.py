@@ -309,81 +309,64 @@ class HipEngine:
         out, half_diag, info, A = hip.logpdf_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), **self._factor_flags())
         return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2])
 
+    def _held_out_dense(self, scheme, ck, x, y, noise_diag, jitter, grad, score="log"):
+        """One dense layer's value under a held-out scheme (`heldout`) in one library call.  The value form: (value as a 0-d device
+        tensor, info word, means, variances).  With `grad`, the conventions of `logpdf_dense_grad`: (value, info word, a function
+        returning (1/2 diag(W) on the device, kernel-parameter gradients), (factor buffer, log-determinant word) - not for a window, which
+        forms no factor -, means, variances).  K horizons: K x n means and variances, and the K unweighted values behind them."""
+        r = hip.held_out_dense(scheme, ck, self._mat(x), y, noise_diag, jitter, grad=grad, periodic=grad and self._periodic(ck), score=score,
+                               **self._factor_flags())
+        moments = (r["mean"], r["var"], *((r["values"],) if scheme.horizons else ()))
+        if not grad:
+            return (r["out"][0], r["info"], *moments)
+        factor = ((r["A"], r["out"][1:2]),) if scheme.factored else ()
+        return (r["out"][0], r["info"], self._gradients_of(ck, r["out"], r["half"]), *factor, *moments)
+
+    # The schemes by name, value form and gradient form (what `gp.Obs` looks up): each builds its scheme from the loose arguments - host
+    # arrays, what `hip.upload_*` returned, or the scheme itself - and forwards.  `score`: the scoring rule ("log", "crps", "se").
     def loo_dense(self, ck, x, y, noise_diag, jitter, score="log"):
-        """One dense layer's leave-one-out value, predictive means and variances in one library call: (value as a 0-d device
-        tensor, info word, means, variances).  `score`: the scoring rule ("log", "crps", "se")."""
-        out, mean, var, info = hip.loo_dense(ck, self._mat(x), y, noise_diag, jitter, score=score, **self._factor_flags())
-        return out[0], info, mean, var
+        """Leave-one-out."""
+        return self._held_out_dense(hip.Loo(), ck, x, y, noise_diag, jitter, False, score)
 
     def loo_dense_grad(self, ck, x, y, noise_diag, jitter, score="log"):
-        """The leave-one-out counterpart of `logpdf_dense_grad`, same conventions: (value, info word, a function returning (1/2 diag(W)
-        on the device, kernel-parameter gradients), (factor buffer, log-determinant word)), then the predictive means and variances."""
-        out, half_diag, mean, var, info, A, _ = hip.loo_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
-                                                                   score=score, **self._factor_flags())
-        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
+        return self._held_out_dense(hip.Loo(), ck, x, y, noise_diag, jitter, True, score)
 
     def cv_dense(self, ck, x, y, noise_diag, jitter, fold_start):
-        """One dense layer's blocked cross-validation value, predictive means and marginal variances in one library call, for contiguous
-        folds of at most `_lib.CV_MAX_FOLD` rows given by their nfolds + 1 row offsets: (value as a 0-d device tensor, info word, means,
-        variances)."""
-        out, mean, var, info = hip.cv_dense(ck, self._mat(x), y, noise_diag, jitter, fold_start, **self._factor_flags())
-        return out[0], info, mean, var
+        """Blocked cross-validation over contiguous folds of at most `_lib.CV_MAX_FOLD` rows, given by their nfolds + 1 row offsets."""
+        return self._held_out_dense(hip.Folds.of(fold_start, x.shape[0]), ck, x, y, noise_diag, jitter, False)
 
     def cv_dense_grad(self, ck, x, y, noise_diag, jitter, fold_start):
-        """The blocked cross-validation counterpart of `loo_dense_grad`, same conventions and return values."""
-        out, half_diag, mean, var, info, A, _ = hip.cv_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), fold_start,
-                                                                  **self._factor_flags())
-        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
+        return self._held_out_dense(hip.Folds.of(fold_start, x.shape[0]), ck, x, y, noise_diag, jitter, True)
 
     def cv_gap_dense(self, ck, x, y, noise_diag, jitter, fold_start, hold):
         """`cv_dense` with purged rows: `hold` = (hold_lo, hold_hi), per fold the block of at most `_lib.CV_MAX_FOLD` rows - the fold and
         the purged rows on either side of it - that it is not predicted from (checked on the host: `hip.hold_extents`)."""
-        out, mean, var, info = hip.cv_gap_dense(ck, self._mat(x), y, noise_diag, jitter, fold_start, hold, **self._factor_flags())
-        return out[0], info, mean, var
+        return self._held_out_dense(hip.Purged.of(fold_start, hold, x.shape[0]), ck, x, y, noise_diag, jitter, False)
 
     def cv_gap_dense_grad(self, ck, x, y, noise_diag, jitter, fold_start, hold):
-        """The purged counterpart of `cv_dense_grad`, same conventions and return values."""
-        out, half_diag, mean, var, info, A, _ = hip.cv_gap_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), fold_start, hold,
-                                                                      **self._factor_flags())
-        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
+        return self._held_out_dense(hip.Purged.of(fold_start, hold, x.shape[0]), ck, x, y, noise_diag, jitter, True)
 
     def ahead_dense(self, ck, x, y, noise_diag, jitter, origin, score="log"):
-        """One dense layer's rolling-origin forecast value, predictive means and variances in one library call, row r predicted from rows
-        0 ... origin[r] - 1 (-1: not scored, NaN in its mean and variance): (value as a 0-d device tensor, info word, means, variances)."""
-        out, mean, var, info = hip.ahead_dense(ck, self._mat(x), y, noise_diag, jitter, origin, score=score, **self._factor_flags())
-        return out[0], info, mean, var
+        """Rolling-origin forecasts: row r predicted from rows 0 ... origin[r] - 1 (-1: not scored, NaN in its mean and variance)."""
+        return self._held_out_dense(hip.Origins.of(origin, x.shape[0]), ck, x, y, noise_diag, jitter, False, score)
 
     def ahead_dense_grad(self, ck, x, y, noise_diag, jitter, origin, score="log"):
-        """The rolling-origin counterpart of `loo_dense_grad`, same conventions and return values."""
-        out, half_diag, mean, var, info, A, _ = hip.ahead_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), origin,
-                                                                     score=score, **self._factor_flags())
-        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var
+        return self._held_out_dense(hip.Origins.of(origin, x.shape[0]), ck, x, y, noise_diag, jitter, True, score)
 
     def ahead_multi_dense(self, ck, x, y, noise_diag, jitter, origins, weights=None, score="log"):
-        """`ahead_dense` at K horizons in one library call (`origins`: K x n, `weights`: K positive numbers): (weighted value as a 0-d
-        device tensor, info word, K x n means, K x n variances, the K unweighted values)."""
-        out, values, mean, var, info = hip.ahead_multi_dense(ck, self._mat(x), y, noise_diag, jitter, origins, weights, score=score,
-                                                             **self._factor_flags())
-        return out[0], info, mean, var, values
+        """`ahead_dense` at K horizons (`origins`: K x n, `weights`: K positive numbers): the weighted value."""
+        return self._held_out_dense(hip.Origins.of(origins, x.shape[0], weights, multi=True), ck, x, y, noise_diag, jitter, False, score)
 
     def ahead_multi_dense_grad(self, ck, x, y, noise_diag, jitter, origins, weights=None, score="log"):
-        """The multi-horizon counterpart of `ahead_dense_grad`: its return values, then the K unweighted values."""
-        out, values, half_diag, mean, var, info, A, _ = hip.ahead_multi_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck),
-                                                                                  origins, weights, score=score, **self._factor_flags())
-        return out[0], info, self._gradients_of(ck, out, half_diag), (A, out[1:2]), mean, var, values
+        return self._held_out_dense(hip.Origins.of(origins, x.shape[0], weights, multi=True), ck, x, y, noise_diag, jitter, True, score)
 
     def ahead_window_dense(self, ck, x, y, noise_diag, jitter, lo, origin, score="log"):
-        """`ahead_dense` from a window: row r predicted from rows lo[r] ... origin[r] - 1 alone (at most `_lib.AHEAD_WINDOW_MAX` of them),
-        in one library call that factors no n x n matrix: (value as a 0-d device tensor, info word, means, variances)."""
-        out, mean, var, info = hip.ahead_window_dense(ck, self._mat(x), y, noise_diag, jitter, lo, origin, score=score)
-        return out[0], info, mean, var
+        """`ahead_dense` from a window: row r predicted from rows lo[r] ... origin[r] - 1 alone (at most `_lib.AHEAD_WINDOW_MAX` of them);
+        no n x n matrix is factored."""
+        return self._held_out_dense(hip.Window.of(lo, origin, x.shape[0]), ck, x, y, noise_diag, jitter, False, score)
 
     def ahead_window_dense_grad(self, ck, x, y, noise_diag, jitter, lo, origin, score="log"):
-        """The sliding-window counterpart of `ahead_dense_grad`: (value, info word, a function returning (1/2 diag(W) on the device,
-        kernel-parameter gradients), means, variances) - no factor: the call forms none."""
-        out, half_diag, mean, var, info, _ = hip.ahead_window_dense_grad(ck, self._mat(x), y, noise_diag, jitter, self._periodic(ck), lo, origin,
-                                                                         score=score)
-        return out[0], info, self._gradients_of(ck, out, half_diag), mean, var
+        return self._held_out_dense(hip.Window.of(lo, origin, x.shape[0]), ck, x, y, noise_diag, jitter, True, score)
 
     def logpdf_lockstep(self, layers, x, y, w, jitter):
         """The whole lock-step evaluation in one library call: (values, their sum in layer order, info words)."""

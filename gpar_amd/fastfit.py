@@ -30,7 +30,7 @@ import numpy as np
 import scipy.optimize
 import torch
 
-from . import _lib, hip, optimise
+from . import _lib, heldout, hip, optimise
 from .kernels import Kernel, compile_kernel
 
 __all__ = ["build", "DenseLayerObjective", "LayerChain", "layer_chain", "hessian_of", "LockstepFactor", "lockstep_rows"]
@@ -262,50 +262,27 @@ class LockstepFactor:
 
 
 class DenseLayerObjective:
-    """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or, with `objective="loo"`, minus the leave-one-out predictive
-    log-density under the same covariance (gpar_loo_dense_grad), or, with `objective="cv"`, minus the blocked cross-validation value
-    over the contiguous folds of the rows given by the offsets `fold_start` (gpar_cv_dense_grad; with `hold` = (hold_lo, hold_hi), the
-    blocks the folds are not predicted from, its purged form: gpar_cv_gap_dense_grad), or, with `objective="ahead"`, minus the
-    rolling-origin forecast score for the per-row origins `origin` (gpar_ahead_dense_grad; a K x n `origin` with `weights`: the weighted
-    sum over K horizons in one pass, gpar_ahead_multi_dense_grad); `score` ("log", "crps", "se") is the rule "loo"
-    and "ahead" score their held-out entries by (the *_score forms of their library calls) - and its gradient with respect to
-    the latent (unconstrained) variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are
-    device tensors that do not change during the optimisation."""
+    """-log N(y; 0, K_theta(X) + noise / w + eps I) of layer `pi` - or minus a held-out score under the same covariance: `objective`
+    "loo" (leave-one-out), "cv" (blocked cross-validation over the contiguous folds with the row offsets `fold_start`; with `hold` =
+    (hold_lo, hold_hi), the blocks the folds are not predicted from, its purged form) or "ahead" (the rolling-origin forecast score for
+    the per-row origins `origin`; a K x n `origin` with `weights`: the weighted sum over K horizons in one pass; with `lo`: the sliding
+    window), or the `heldout` scheme itself as `scheme` - what `heldout.scheme_of` makes of those keywords.  `score` ("log", "crps", "se")
+    is the rule "loo" and "ahead" score their held-out entries by.  And its gradient with respect to the latent (unconstrained)
+    variables `names` of `vs`, evaluated as described in the module docstring.  X (n x width), y, w (n) are device tensors that do not
+    change during the optimisation."""
+
+    fold_start = property(lambda self: getattr(self.scheme, "starts", None))   # (host offsets of the folds, where the scheme has folds)
 
     def __init__(self, eng, vs, names, kernel, noise_holder, holders, X, y, w, general_fg=None, group=None, lane=None, objective="mll",
-                 fold_start=None, origin=None, score="log", hold=None, weights=None, lo=None):
-        if objective not in ("mll", "loo", "cv", "ahead"):
-            raise ValueError('objective must be "mll", "loo", "cv" or "ahead"')
-        self.score = hip.score_code(score)
+                 fold_start=None, origin=None, score="log", hold=None, weights=None, lo=None, scheme=None):
+        # which library call `_device_eval` makes: everything behind it is shared (host arrays; their device copy is made once, with the buffers)
+        self.scheme = heldout.scheme_of(objective, fold_start, hold, origin, weights, lo) if scheme is None else scheme
+        hip.score_code(score)
         if score != "log" and objective not in ("loo", "ahead"):
             raise ValueError('score belongs to objective="loo" and "ahead"')
-        if (objective == "cv") != (fold_start is not None):
-            raise ValueError('fold_start belongs to objective="cv"')
-        if (objective == "ahead") != (origin is not None):
-            raise ValueError('origin belongs to objective="ahead"')
-        if hold is not None and objective != "cv":
-            raise ValueError('hold belongs to objective="cv"')
-        # (host origins of the rows; their device copy is made once, with the other buffers)
-        # (a K x n origin array: K horizons in one pass, the multi-horizon call with `weights`, K positive numbers, default all 1)
-        self.origin = None if origin is None else np.asarray(origin, dtype=np.int64)
-        self.multi = self.origin is not None and self.origin.ndim == 2
-        if self.origin is not None and not self.multi:
-            self.origin = self.origin.reshape(-1)
-        if weights is not None and not self.multi:
-            raise ValueError("weights belong to a K x n origin array")
-        # (a sliding window: the first row of every scored row's window beside its origin - gpar_ahead_window_dense_grad in the call's place)
-        if lo is not None and (self.origin is None or self.multi):
-            raise ValueError("lo belongs to one array of origins")
-        self.lo = None if lo is None else np.asarray(lo, dtype=np.int64).reshape(-1)
-        self.weights = hip.horizon_weight_array(weights, self.origin.shape[0]) if self.multi else None
+        self.score = score
         self.eng, self.vs, self.names = eng, vs, list(names)
-        self.objective = objective   # which library call `_device_eval` makes: everything behind it is shared
-        # (host offsets of the folds; their device copy is made once, with the other buffers)
-        self.fold_start = None if fold_start is None else np.asarray(fold_start, dtype=np.int64).reshape(-1)
-        self.hold = None if hold is None else tuple(np.asarray(h, dtype=np.int64).reshape(-1) for h in hold)   # (purged folds: block extents)
-        self.call = "cv_gap" if self.hold is not None else objective   # (the library call's family: `hip.objective_vec_doubles`)
-        if self.lo is not None:
-            self.call = "ahead_window"
+        self.objective = objective
         if objective != "mll":
             group = lane = None      # (cross-validation lanes take no part in the lock-step rendezvous)
         self.group, self.lane = group, lane   # a LockstepFactor and this objective's slot in it, or None
@@ -349,25 +326,15 @@ class DenseLayerObjective:
         nt = (n + 63) // 64
         self.nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
         nacc = _lib.GRAD_NACC
-        # gradient partials, alpha; for the cross-validation objectives their vectors, the predictive means and variances behind them
-        self.folds = hip.upload_folds(self.fold_start, n, dev) if self.objective == "cv" else ()   # (device offsets, number of folds, largest fold)
-        if self.hold is not None:
-            self.folds = hip.upload_hold(self.fold_start, self.hold, n, dev)   # (device offsets and block extents, number of folds, largest block)
-        if self.objective == "ahead" and not self.multi:
-            self.folds = (hip.upload_origin(self.origin, n, dev),)   # (the one argument the entry takes in the folds' place)
-        if self.lo is not None:
-            self.folds = hip.upload_window(self.lo, self.origin, n, dev)   # (lo and origin on the device)
-        nmom = n   # (doubles of the held-out means, and of the variances)
-        if self.multi:   # origins (K x n, uploaded once), K, the weights (host), the K values (device): what the multi call takes in the origin's place
-            k = int(self.origin.shape[0])
-            self.values = torch.zeros(k, dtype=torch.float64, device=dev)
-            self.folds = (hip.upload_origins(self.origin, n, dev), k, (ctypes.c_double * k)(*self.weights), self.values)
-            nmom = k * n
-            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 1, k)) + 2 * nmom
-        elif self.lo is not None:
-            nloo = int(self.lib.gpar_workspace_doubles(_lib.WS_AHEAD_WINDOW, n, 1, 0)) + 2 * n
-        else:
-            nloo = 0 if self.objective == "mll" else hip.objective_vec_doubles(self.lib, self.call, n, 1, self.folds) + 2 * n
+        # gradient partials, alpha; for a held-out scheme its vector workspace, the predictive means and variances (K x n each for K horizons,
+        # whose K values stay on the device) behind it
+        scheme = self.scheme
+        k = scheme.horizons if scheme is not None else None
+        nmom = (k or 1) * n
+        self.values = torch.zeros(k, dtype=torch.float64, device=dev) if k else None
+        # (the scheme's arrays are uploaded here, once - beyond what the call takes a ValueError - and stay with the scheme)
+        self._trailing = () if scheme is None else hip.held_out_trailing(scheme, n, dev, self.values, self.score)
+        nloo = 0 if scheme is None else scheme.workspace(self.lib, n, 1) + 2 * nmom
         nalpha = n + (n & 1)   # (the vectors start at an even offset: "ahead" keeps a matrix among them)
         self.work = torch.empty(self.nblocks * nacc + nalpha + nloo, dtype=torch.float64, device=dev)
         # [value, log det, moment sums (nacc), 1/2 diag W (n), info word (int32 in the last 8 bytes)]
@@ -386,14 +353,14 @@ class DenseLayerObjective:
             alpha=self.work[self.nblocks * nacc:].data_ptr(), work=self.work.data_ptr(), out=self.res.data_ptr(),
             half=self.res[2 + nacc:].data_ptr(), info=self.res[2 + nacc + n:].data_ptr(),
         )
-        if self.objective != "mll":
+        if scheme is not None:
             at = self.nblocks * nacc + nalpha
-            self._ptrs.update(vec=self.work[at:].data_ptr(), loo_mean=self.work[at + nloo - 2 * nmom:].data_ptr(),
-                              loo_var=self.work[at + nloo - nmom:].data_ptr())
+            self._ptrs.update(vec=self.work[at:].data_ptr(), mean=self.work[at + nloo - 2 * nmom:].data_ptr(),
+                              var=self.work[at + nloo - nmom:].data_ptr())
 
     def _device_eval(self, ck, noise):
-        """One library call + one device-to-host copy: (the objective - log marginal likelihood, leave-one-out or blocked cross-
-        validation value -, kernel-parameter gradients of it, 1/2 diag W as a host vector), or None when the factorisation reported a failure."""
+        """One library call + one device-to-host copy: (the objective - the log marginal likelihood, or the value under the held-out
+        scheme -, kernel-parameter gradients of it, 1/2 diag W as a host vector), or None when the factorisation reported a failure."""
         dev = self.X.device
         stream = torch.cuda.current_stream(dev)
         if self.unit_weights:
@@ -401,32 +368,13 @@ class DenseLayerObjective:
         else:
             # the correctly rounded quotient of two tensors, as model.GPAR._noise_over forms it
             torch.true_divide(self.noise_num.fill_(noise), self.w, out=self.noise_vec)
-        p = self._ptrs
-        fs, ks, eps = ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), float(self.eng.epsilon)
-        # what every one-call entry takes ahead of its own arguments, and behind them
-        head = (fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["zd"], p["ldz"], p["A"], p["lda"], p["X"], p["ldxw"],
-                p["W"], p["ldw"], p["alpha"])
-        tail = (p["info"], self.flags, stream.cuda_stream)
-        if self.call == "ahead_window":   # (nothing is factored whole: no X, no alpha, no factorisation flags)
-            rc = self.lib.gpar_ahead_window_dense_grad(fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["zd"], p["ldz"],
-                                                       p["A"], p["lda"], p["W"], p["ldw"], p["vec"], p["work"], self.nblocks, p["out"], p["half"],
-                                                       p["loo_mean"], p["loo_var"], *hip._fold_args(self.folds), self.score, p["info"],
-                                                       stream.cuda_stream)
-            _lib.check(rc, "gpar_ahead_window_dense_grad")
-        elif self.objective != "mll":
-            name = {"loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad", "cv_gap": "gpar_cv_gap_dense_grad",
-                    "ahead": "gpar_ahead_multi_dense_grad" if self.multi else "gpar_ahead_dense_grad_score"}[self.call]
-            fold_args = hip._fold_args(self.folds)
-            rule = () if self.objective == "cv" else (self.score,)   # (the blocked form scores a fold's joint density: no rule to take)
-            rc = getattr(self.lib, name)(*head, p["vec"], p["work"], self.nblocks, p["out"], p["half"], p["loo_mean"], p["loo_var"], *fold_args, *rule,
-                                         *tail)
-            _lib.check(rc, name)
-        elif self.group is None:
-            rc = self.lib.gpar_logpdf_dense_grad(*head, p["work"], self.nblocks, p["out"], p["half"], *tail)
-            _lib.check(rc, "gpar_logpdf_dense_grad")
+        p, eps = self._ptrs, float(self.eng.epsilon)
+        if self.group is None:   # (the scheme's entry - or the log marginal likelihood's -, its arguments assembled where `hip.held_out_dense` does)
+            hip.held_out_call(self.lib, self.scheme, True, ck, p, self.n, eps, self.nblocks, self._trailing, self.flags, stream.cuda_stream)
         else:
             # build into this lane's slot, factor with the round, finish on this stream (LockstepFactor)
             g = self.group
+            fs, ks = ctypes.byref(ck.fspec), ctypes.byref(ck.kspec)
             a, ld, info = g.slot(self.lane)
             rc = self.lib.gpar_logpdf_dense_build(fs, ks, p["x"], self.n, p["ldx"], p["y"], p["incy"], p["noise"], eps, p["z"], p["ldz"], a, g.lda, ld,
                                                   info, stream.cuda_stream)
@@ -715,37 +663,32 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
         if not isinstance(mask, slice) and n_missing:
             observed = observed[host_index(keep)]
         fold_start, hold = purged_folds(folds, observed, gap)
-        if int((hold[1] - hold[0]).max()) > _lib.CV_MAX_FOLD:
-            return None
     elif objective == "cv":
         labels = np.asarray(folds).reshape(-1)[host_index(mask)]
         if not isinstance(mask, slice) and n_missing:
             labels = labels[host_index(keep)]
         perm, fold_start = contiguous_folds(labels)
-        if int(np.diff(fold_start).max()) > _lib.CV_MAX_FOLD:
-            return None
         if perm is not None:
             at = torch.as_tensor(perm, dtype=torch.long, device=X.device)
             X, yi, wi = X.index_select(0, at), yi.index_select(0, at), wi.index_select(0, at)
-    origin = None
+    origin = lo = weights = None
     if objective == "ahead":
-        horizon, start, rows, *weights = ahead   # (`horizon` a tuple: K origin arrays, with the horizons' weights behind `rows`)
+        horizon, start, rows, *rest = ahead   # (`horizon` a tuple: K origin arrays, with the horizons' weights behind `rows`)
         observed = np.asarray(rows, dtype=np.int64).reshape(-1)[host_index(mask)]
         if not isinstance(mask, slice) and n_missing:
             observed = observed[host_index(keep)]
         if isinstance(horizon, tuple):
-            if len(horizon) > _lib.AHEAD_MAX_HORIZONS:
-                return None   # (more horizons than the library call takes: the general route trains it)
             origin = np.stack([rolling_origins(observed, h, start) for h in horizon])
+            weights = rest[0] if rest else None
         else:
             origin = rolling_origins(observed, horizon, start)
-    lo = None
     if window is not None:
         if origin is None or origin.ndim != 1:
             raise ValueError('window belongs to objective="ahead" with one horizon')
         lo = rolling_window_starts(observed, horizon, window)
-        if int((origin - lo)[origin >= 0].max(initial=0)) > _lib.AHEAD_WINDOW_MAX:
-            return None   # (a window longer than the library call takes: the general route trains the layer)
+    scheme = heldout.scheme_of(objective, fold_start, hold, origin, weights, lo)
+    if scheme is not None and not scheme.fits():
+        return None   # (a fold, a block or a window larger, or more horizons, than the library call takes: the general route trains the layer)
     tracer = _TracingVars(vs)
     f, noise = _model_generator(tracer, reg.m, pi, **layer_config(reg, reg.m, pi))()
     kernel = f.kernel
@@ -759,7 +702,4 @@ def build(reg, eng, vs, pi, names, fixed_x, item, general_fg=None, cls=None, gro
     if group is not None and (group.n != n or not on_device or objective != "mll"):
         group = None
     return cls(eng, vs, names, kernel, noise, tracer.holders, X, yi, wi.reshape(-1), general_fg=general_fg, group=group,
-               lane=lane if group is not None else None, objective=objective, **({} if fold_start is None else {"fold_start": fold_start}),
-               **({} if origin is None else {"origin": origin}), **({} if score == "log" else {"score": score}),
-               **({"weights": weights[0]} if origin is not None and origin.ndim == 2 and weights else {}),
-               **({} if hold is None else {"hold": hold}), **({} if lo is None else {"lo": lo}))
+               lane=lane if group is not None else None, objective=objective, score=score, scheme=scheme)

@@ -37,10 +37,10 @@ import math
 import numpy as np
 import torch
 
-from ._lib import AHEAD_MAX_HORIZONS, AHEAD_WINDOW_MAX, CHOL_UPDATE_MAX_RANK, CV_MAX_FOLD, GPAR_MAX_TERMS
+from ._lib import CHOL_UPDATE_MAX_RANK, GPAR_MAX_TERMS
 from .engine import get_engine, joining
-from .hip import (fold_offsets, hold_extents, horizon_weight_array, origin_array, origins_array, upload_hold, upload_origin, upload_origins,
-                  upload_window, window_arrays)
+from .heldout import (Folds, Loo, Origins, Purged, Window, fold_offsets, hold_extents, horizon_weight_array, origin_array, origins_array,
+                      window_arrays)
 from .kernels import Kernel
 
 __all__ = ["Measure", "GP", "FDD", "Obs", "PseudoObs", "PseudoObsVFE", "PseudoObsFITC", "PseudoObsDTC", "SparseObs", "greedy_inducing"]
@@ -306,18 +306,18 @@ class _LogMarginal(torch.autograd.Function):
 
 class _HeldOutValue(torch.autograd.Function):
     """A cross-validation value of dense observations of a prior process as a differentiable function of the kernel parameters and the
-    noise vector: with `starts` None the leave-one-out predictive log-density sum_i log N(y_i; mean_-i, var_-i) (Rasmussen & Williams
-    5.4.2), otherwise the blocked value sum_F log N(y_F; mean_-F, cov_-F) over the contiguous folds F with those row offsets.  Forward:
+    noise vector, under a held-out `scheme` (`heldout`): leave-one-out, sum_i log N(y_i; mean_-i, var_-i) (Rasmussen & Williams 5.4.2),
+    the blocked value sum_F log N(y_F; mean_-F, cov_-F) over contiguous folds F, or a forecast score over rolling origins.  Forward:
     `Obs._held_out_eval`; `score` is the rule the held-out entries are scored by (`_score_rows`).  Backward: the same weighted-sum pass as `_LogMarginal`, on other weights - d/dtheta = 1/2 sum_ab W_ab
     dK_ab/dtheta with W = alpha u^T + u alpha^T - 2 K^-1 C K^-1, C diagonal or block-diagonal (`Obs._held_out_gradients`).  The inputs are
     not differentiated."""
 
     @staticmethod
-    def forward(ctx, obs, starts, score, noise, *tensors):
+    def forward(ctx, obs, scheme, score, noise, *tensors):
         ctx.obs = obs
         ctx.noise_shape = None if noise is None else tuple(noise.shape)
         ctx.shapes = [tuple(t.shape) for t in tensors]
-        return obs._held_out_eval(starts, want_grad=True, score=score)
+        return obs._held_out_eval(scheme, want_grad=True, score=score)
 
     @staticmethod
     def backward(ctx, g):
@@ -414,14 +414,6 @@ def _cv_algebra(eng, Kinv, alpha, starts):
     return value, b, b, var, fill
 
 
-class _Purged:
-    """The fourth held-out scheme: contiguous folds, each predicted from the rows outside a block that contains it (`Obs.cv(..., hold)`)."""
-
-    def __init__(self, starts, lo, hi):
-        self.starts, self.lo, self.hi = starts, lo, hi   # checked host arrays (int64): nfolds + 1 offsets, nfolds block extents
-        self.device = None                               # the uploaded copy, made at the first fused call
-
-
 class _DenseC:
     """What `_cv_gap_algebra` hands the gradient in the place of a function filling S: C itself, which is indefinite - no S S^T."""
 
@@ -470,17 +462,28 @@ def _cv_gap_algebra(eng, Kinv, alpha, purged):
     return value, err, b, var, _DenseC(C)
 
 
-class _Origins:
-    """The third held-out scheme beside `None` (leave-one-out) and fold offsets: rolling origins, one per row (`Obs.ahead`)."""
-
-    def __init__(self, origin, weights=None):
-        self.origin = origin   # checked host array (int64), -1: not scored; K x n for K horizons scored in one pass
-        self.weights = weights   # K horizons: their K positive weights (host array)
-        self.device = None     # the uploaded copy, made at the first fused call
-
-    @property
-    def multi(self):
-        return self.origin.ndim == 2
+def _rank_two_weights(eng, Kinv, alpha, b, fill):
+    """W = alpha u^T + u alpha^T - 2 K^-1 C K^-1 on its lower triangle, u = K^-1 b, from what `_loo_algebra`, `_cv_algebra` or
+    `_cv_gap_algebra` returned: S with C = R R^T, K^-1 C K^-1 = S S^T - or C itself -, then the rank-two update."""
+    n = alpha.numel()
+    u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
+    S = eng.new_matrix(n, n)
+    W = eng.new_matrix(n, n)
+    if isinstance(fill, _DenseC):   # purged folds: C is indefinite and banded, not block-diagonal R R^T:  K^-1 C K^-1 as K^-1 (C K^-1)
+        P, Cm = eng.new_matrix(n, n), eng.new_matrix(n, n)
+        P.copy_(Kinv)
+        Cm.copy_(fill.C)
+        eng.gemm(Cm, P, out=S)
+        eng.gemm(P, S, alpha=-2.0, out=W, c_lower=True)
+        del P, Cm
+    else:
+        fill(S)
+        eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
+    left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
+    left.copy_(torch.stack([alpha, u]))
+    right.copy_(torch.stack([u, alpha]))
+    eng.gemm(left, right, ta=True, alpha=1.0, beta=1.0, out=W, c_lower=True)
+    return W
 
 
 def _ahead_algebra(eng, L, a, origin, score="log"):
@@ -517,17 +520,6 @@ def _ahead_algebra(eng, L, a, origin, score="log"):
         return W
 
     return value, e, torch.where(scored, v, nan), scored, weights
-
-
-class _Window:
-    """The fifth held-out scheme: rolling origins with a window - row r predicted from rows lo[r] ... origin[r] - 1 alone (`Obs.ahead(origin,
-    lo=...)`)."""
-
-    def __init__(self, lo, origin):
-        self.lo, self.origin = lo, origin   # checked host arrays (int64); origin -1: not scored
-        scored = origin >= 0
-        self.longest = int((origin - lo)[scored].max()) if scored.any() else 0
-        self.device = None                  # the uploaded pair, made at the first fused call
 
 
 def _ahead_window_algebra(eng, K, y, lo, origin, score="log"):
@@ -986,7 +978,7 @@ class Obs:
         noise where they require one (observations of a prior process; Rasmussen & Williams 5.4.2).  `score`: the rule each held-out
         entry is scored by - "log" as above, "crps": value = -sum_i CRPS(N(mean_-i, var_-i), y_i), "se": value = -sum_i (y_i - mean_-i)^2
         (minus PRESS); mean and var are the same under every rule, and the value is always one to maximise."""
-        return self._held_out(None, "leave-one-out", check_score(score))
+        return self._held_out(Loo(), "leave-one-out", check_score(score))
 
     def cv(self, fold_start, hold=None):
         """(value, mean, var) of blocked (leave-fold-out) cross-validation over contiguous folds of the observations, given by their
@@ -998,10 +990,13 @@ class Obs:
         order) - the pair (hold_lo, hold_hi), one int per fold: fold f is predicted from the rows OUTSIDE hold_lo[f] ... hold_hi[f] - 1, a
         block that contains the fold (`hip.hold_extents`); its other rows are neither scored nor conditioned on.  With G = H without F the
         formulas above hold for Dt = P_FF - P_FG P_GG^-1 P_GF and at = alpha_F - P_FG P_GG^-1 alpha_G in the place of D_F and alpha_F.
-        None: the blocks are the folds themselves, today's route."""
+        None: the blocks are the folds themselves, today's route.  (`fold_start` may be a `heldout.Folds` or `Purged` made earlier: its
+        uploaded arrays are shared.)"""
+        if isinstance(fold_start, Folds):
+            return self._held_out(fold_start, "cross-validation")
         if hold is None:
-            return self._held_out(fold_offsets(fold_start, self.fdd.n), "cross-validation")
-        return self._held_out(_Purged(*hold_extents(fold_start, hold, self.fdd.n)), "cross-validation")
+            return self._held_out(Folds(fold_offsets(fold_start, self.fdd.n)), "cross-validation")
+        return self._held_out(Purged(*hold_extents(fold_start, hold, self.fdd.n)), "cross-validation")
 
     def ahead(self, origin, score="log", weights=None, lo=None):
         """(value, mean, var) of rolling-origin forecasts, the observations in the order given (the time order): row r is predicted from
@@ -1020,31 +1015,34 @@ class Obs:
         origin[r]; lo[r] = origin[r]: from the prior; neither array may decrease over the scored rows).  Nothing n x n is factored: every
         scored row conditions on its own block of the covariance.  One library call where `logpdf` would take one and no window exceeds
         `_lib.AHEAD_WINDOW_MAX` rows; otherwise composed of the Gram matrix and batched block algebra (`_ahead_window_algebra`) - any
-        length.  lo = 0 everywhere gives the values above (by other arithmetic).  None: today's evaluation, untouched."""
+        length.  lo = 0 everywhere gives the values above (by other arithmetic).  None: today's evaluation, untouched.  (`origin` may be
+        a `heldout.Origins` or `Window` made earlier: its uploaded arrays are shared.)"""
         check_score(score)
         if self.base.is_posterior:
             raise NotImplementedError("rolling-origin forecasts are those of a prior process")
+        if isinstance(origin, (Origins, Window)):
+            return self._held_out(origin, "rolling-origin forecast" if origin.factored else "sliding-window forecast", score)
         if lo is not None:
             if np.ndim(origin.cpu() if isinstance(origin, torch.Tensor) else origin) != 1 or weights is not None:
                 raise ValueError("a window belongs to one horizon: lo and origin hold one integer per row each, without weights")
-            return self._held_out(_Window(*window_arrays(lo, origin, self.fdd.n)), "sliding-window forecast", score)
+            return self._held_out(Window(*window_arrays(lo, origin, self.fdd.n)), "sliding-window forecast", score)
         shaped = origin.cpu() if isinstance(origin, torch.Tensor) else origin
         if np.ndim(shaped) == 2:
             origins = origins_array(shaped, self.fdd.n)
-            return self._held_out(_Origins(origins, horizon_weight_array(weights, origins.shape[0])), "rolling-origin forecast", score)
+            return self._held_out(Origins(origins, horizon_weight_array(weights, origins.shape[0])), "rolling-origin forecast", score)
         if weights is not None:
             raise ValueError("weights belong to a K x n origin array: one horizon has nothing to weigh against")
-        return self._held_out(_Origins(origin_array(origin, self.fdd.n)), "rolling-origin forecast", score)
+        return self._held_out(Origins(origin_array(origin, self.fdd.n)), "rolling-origin forecast", score)
 
     def ahead_gradients(self):
         """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the rolling-origin value, with W = L^-T (P + P^T) L^-1,
         P = Phi(L^T B - abar a^T) (`_ahead_algebra`)."""
         return self._held_out_gradients()
 
-    def _held_out(self, starts, what, score="log"):
-        """`loo` (`starts` None) and `cv`: through `_HeldOutValue` where a kernel parameter or the noise needs a gradient.  The two share
-        one set of pending-gradient state on the observations (`_fused_held_out_gradients`, `_held_out_parts`): a second `loo()` or `cv()`
-        with gradients on the same `Obs` replaces what the first left, so run each value's backward pass before evaluating the next."""
+    def _held_out(self, scheme, what, score="log"):
+        """`loo`, `cv` and `ahead`: through `_HeldOutValue` where a kernel parameter or the noise needs a gradient.  They share one set
+        of pending-gradient state on the observations (`_fused_held_out_gradients`, `_held_out_parts`): a second evaluation with gradients
+        on the same `Obs` replaces what the first left, so run each value's backward pass before evaluating the next."""
         if torch.is_grad_enabled():
             params = kernel_parameters(self.base.kernel)
             noise = self.fdd.noise_arg if _needs_grad(self.fdd.noise_arg) else None
@@ -1053,194 +1051,118 @@ class Obs:
                     raise NotImplementedError(f"the {what} gradient covers kernel parameters and noise of a prior process")
                 self._params = params
                 self._noise_device = None if noise is None else noise.device
-                value = _HeldOutValue.apply(self, starts, score, noise, *[p[3] for p in params])
+                value = _HeldOutValue.apply(self, scheme, score, noise, *[p[3] for p in params])
                 return value, self._held_out_mean, self._held_out_var
-        value = self._held_out_eval(starts, score=score)
+        value = self._held_out_eval(scheme, score=score)
         return value, self._held_out_mean, self._held_out_var
 
-    def _held_out_eval(self, starts, want_grad=False, score="log"):
-        """The value (detached; the means and variances are left in `_held_out_mean` / `_held_out_var`).  One library call where the
-        engine has one, `_value_only` / `_fusable_grad` would let `logpdf` take it and no fold exceeds the call's limit; otherwise composed
-        of engine primitives (the factor, K^-1) and the objective's block algebra (`_loo_algebra`, `_cv_algebra`: folds of any size).
-        `score`: the scoring rule of `loo` and `ahead` (blocked cross-validation scores a fold's joint density: "log" alone)."""
+    def _held_out_eval(self, scheme, want_grad=False, score="log"):
+        """The value under `scheme` (detached; the means and variances are left in `_held_out_mean` / `_held_out_var`, K x n for K horizons,
+        whose K unweighted values are left in `_held_out_values`).  One library call - the engine's method named after the scheme's family,
+        looked up now - where the engine has it, `_value_only` / `_fusable_grad` would let `logpdf` take one and `scheme.fits()`; otherwise
+        composed of engine primitives and the scheme's block algebra, without those limits.  `score`: the scoring rule of `loo` and `ahead`
+        (blocked cross-validation scores a fold's joint density: "log" alone)."""
         eng, n = self.eng, self.fdd.n
         dev = self.y.device
-        ahead, purged = isinstance(starts, _Origins), isinstance(starts, _Purged)
+        self._fused_held_out_gradients = self._held_out_parts = self._held_out_values = None   # (what an earlier evaluation left pending)
+        K = scheme.horizons
         if n == 0:
-            shape = (starts.origin.shape[0], 0) if ahead and starts.multi else (0,)
-            self._held_out_mean = self._held_out_var = torch.zeros(shape, dtype=torch.float64, device=dev)
-            self._held_out_values = torch.zeros(shape[0], dtype=torch.float64, device=dev) if len(shape) == 2 else None
-            self._held_out_parts = None
+            self._held_out_mean = self._held_out_var = torch.zeros((K, 0) if K else (0,), dtype=torch.float64, device=dev)
+            if K:
+                self._held_out_values = torch.zeros(K, dtype=torch.float64, device=dev)
             return torch.zeros((), dtype=torch.float64, device=dev)
-        if ahead and starts.multi:
-            return self._ahead_multi_eval(starts, want_grad, score)
-        if isinstance(starts, _Window):
-            return self._ahead_window_eval(starts, want_grad, score)
-        call = "ahead_dense" if ahead else "cv_gap_dense" if purged else "loo_dense" if starts is None else "cv_dense"
-        folds = () if starts is None else (starts,)
-        rule = {} if score == "log" else {"score": score}   # (an engine's one-call forms take the rule by keyword)
-        if purged:   # (the fused calls hold a fold AND its purged rows in one tile)
-            fits = int((starts.hi - starts.lo).max()) <= CV_MAX_FOLD
-            if fits and hasattr(eng, call) and (self._fusable_grad() if want_grad else self._value_only()):
-                if starts.device is None:
-                    starts.device = upload_hold(starts.starts, (starts.lo, starts.hi), n, dev)
-                folds = (starts.device, None)
-        else:
-            fits = starts is None or ahead or int(np.diff(starts).max()) <= CV_MAX_FOLD
-        if ahead and fits and hasattr(eng, call) and (self._fusable_grad() if want_grad else self._value_only()):
-            if starts.device is None:
-                starts.device = upload_origin(starts.origin, n, dev)
-            folds = (starts.device,)
-        if want_grad and fits and hasattr(eng, call + "_grad") and self._fusable_grad():
+        name = scheme.family + ("_dense_grad" if want_grad else "_dense")
+        if scheme.fits() and hasattr(eng, name) and (self._fusable_grad() if want_grad else self._value_only()):
             ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._fused_held_out_gradients, (A, logdet), self._held_out_mean, self._held_out_var = getattr(eng, call + "_grad")(
-                ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, *folds, **rule)
+            rule = {} if score == "log" else {"score": score}   # (an engine's one-call forms take the rule by keyword)
+            value, info, *rest = getattr(eng, name)(ck, self.fdd.x.detach() if want_grad else self.fdd.x, self.y, self.fdd.noise, eng.epsilon,
+                                                    *scheme.args, **rule)
             eng.check_info(info)
-            self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
+            if want_grad:
+                self._fused_held_out_gradients = rest.pop(0)
+                if scheme.factored:   # (the call leaves the factor behind, as logpdf_dense_grad does)
+                    self._fac = _Factor.from_batch(eng, n, *rest.pop(0))
+            self._held_out_mean, self._held_out_var, *values = rest
+            if K:
+                self._held_out_values, = values
             return value.detach()
-        if not want_grad and fits and hasattr(eng, call) and self._value_only():
-            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            value, info, self._held_out_mean, self._held_out_var = getattr(eng, call)(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, *folds, **rule)
-            eng.check_info(info)
-            return value.detach()
-        if ahead:
-            fac = self.factor()
-            value, e, var, scored, weights = _ahead_algebra(eng, fac.L.detach(), fac.zrow.reshape(-1).detach(), starts.origin, score)
-            self._held_out_mean = torch.where(scored, self.y.reshape(-1).detach() - e, var)
-            self._held_out_var = var
-            self._held_out_parts = (fac, weights) if want_grad else None
-            return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
-        fac = self.factor()
+        compose = self._composed_inverse if scheme.inverse else self._composed_ahead if scheme.factored else self._composed_window
+        value, self._held_out_mean, self._held_out_var, pending = compose(scheme, score)
+        self._held_out_parts = pending if want_grad else None   # (a function returning the weights W on their lower triangle)
+        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+
+    def _composed_inverse(self, scheme, score):
+        """Leave-one-out and folds, purged or not, of any size: K^-1 and alpha, then the scheme's block algebra (`_loo_algebra`,
+        `_cv_algebra`, `_cv_gap_algebra`).  (value, means, variances, a function returning W)."""
+        eng, fac = self.eng, self.factor()
         low = torch.tril(eng.chol_inverse(fac.L))   # (only the lower triangle is defined)
         Kinv = low + torch.tril(low, -1).T
         alpha = fac.alpha().reshape(-1).detach()
-        if purged:
-            value, e, b, var, fill = _cv_gap_algebra(eng, Kinv, alpha, starts)
+        if scheme.family == "loo":
+            value, e, b, var, fill = _loo_algebra(Kinv, alpha, score)
+        elif scheme.family == "cv":
+            value, e, b, var, fill = _cv_algebra(eng, Kinv, alpha, scheme.starts)
         else:
-            value, e, b, var, fill = _loo_algebra(Kinv, alpha, score) if starts is None else _cv_algebra(eng, Kinv, alpha, starts)
-        y = self.y.reshape(-1).detach()
-        self._held_out_mean, self._held_out_var = y - e, var
-        self._held_out_parts = (Kinv, alpha, b, fill) if want_grad else None
+            value, e, b, var, fill = _cv_gap_algebra(eng, Kinv, alpha, scheme)
         if score == "log":
-            value = value - 0.5 * n * _LOG_2PI
-        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+            value = value - 0.5 * self.fdd.n * _LOG_2PI
+        return value, self.y.reshape(-1).detach() - e, var, lambda: _rank_two_weights(eng, Kinv, alpha, b, fill)
 
-    def _ahead_multi_eval(self, starts, want_grad, score):
-        """`_held_out_eval` for K horizons (`starts.origin` K x n): the weighted value; K x n means and variances and the K unweighted
-        values are left in `_held_out_mean` / `_held_out_var` / `_held_out_values`."""
-        eng, n = self.eng, self.fdd.n
-        dev = self.y.device
-        K, w = starts.origin.shape[0], starts.weights
-        rule = {} if score == "log" else {"score": score}
-        if K <= AHEAD_MAX_HORIZONS and hasattr(eng, "ahead_multi_dense") and (self._fusable_grad() if want_grad else self._value_only()):
-            if starts.device is None:
-                starts.device = upload_origins(starts.origin, n, dev)
-            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            if want_grad:
-                value, info, self._fused_held_out_gradients, (A, logdet), mean, var, values = eng.ahead_multi_dense_grad(
-                    ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, starts.device, w, **rule)
-                eng.check_info(info)
-                self._fac = _Factor.from_batch(eng, n, A, logdet)   # (the call leaves the factor behind, as logpdf_dense_grad does)
-            else:
-                value, info, mean, var, values = eng.ahead_multi_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon, starts.device, w, **rule)
-                eng.check_info(info)
-            self._held_out_mean, self._held_out_var, self._held_out_values = mean, var, values
-            return value.detach()
-        fac = self.factor()
+    def _composed_ahead(self, scheme, score):
+        """Rolling origins at one horizon or K of them (any K): `_ahead_algebra`'s terms and weights per horizon from the one factor, summed
+        with the horizons' weights.  (value, means, variances, a function returning W); the K unweighted values go to `_held_out_values`."""
+        eng, n, fac = self.eng, self.fdd.n, self.factor()
         L, a, y = fac.L.detach(), fac.zrow.reshape(-1).detach(), self.y.reshape(-1).detach()
+        w = scheme.weights   # (None: one horizon, nothing to weigh)
         total, means, variances, values, parts = None, [], [], [], []
-        for k in range(K):
-            value, e, var, scored, weights = _ahead_algebra(eng, L, a, starts.origin[k], score)
+        for k, origin in enumerate(scheme.origin if scheme.horizons else scheme.origin[None]):
+            value, e, var, scored, weights = _ahead_algebra(eng, L, a, origin, score)
             means.append(torch.where(scored, y - e, var))
             variances.append(var)
             values.append(value.detach())
             parts.append(weights)
-            total = float(w[k]) * value if total is None else total + float(w[k]) * value
-        self._held_out_mean, self._held_out_var, self._held_out_values = torch.stack(means), torch.stack(variances), torch.stack(values)
+            term = value if w is None else float(w[k]) * value
+            total = term if total is None else total + term
 
-        def summed(Kinv):   # W is linear in the horizons' (q, s): the weighted sum of their W
+        def pending():   # K^-1, then the horizons' W - not of the rank-two form; linear in the horizons' (q, s): their weighted sum
+            low = torch.tril(eng.chol_inverse(fac.L))
+            Kinv = eng.new_matrix(n, n)
+            Kinv.copy_(low + torch.tril(low, -1).T)
             W = parts[0](Kinv)
-            W.mul_(float(w[0]))
-            for k in range(1, K):
-                W.add_(parts[k](Kinv), alpha=float(w[k]))
+            if w is not None:
+                W.mul_(float(w[0]))
+                for k in range(1, len(parts)):
+                    W.add_(parts[k](Kinv), alpha=float(w[k]))
             return W
 
-        self._held_out_parts = (fac, summed) if want_grad else None
-        return total.detach() if getattr(eng, "_deferred", None) is not None else total.detach().cpu()
+        if not scheme.horizons:
+            return total, means[0], variances[0], pending
+        self._held_out_values = torch.stack(values)
+        return total, torch.stack(means), torch.stack(variances), pending
 
-    def _ahead_window_eval(self, starts, want_grad, score):
-        """`_held_out_eval` for a sliding window (`starts` a `_Window`): the fused calls where `_value_only` / `_fusable_grad` allow and every
-        window holds at most `AHEAD_WINDOW_MAX` rows, `_ahead_window_algebra` on the covariance otherwise.  No factor is formed or kept."""
+    def _composed_window(self, scheme, score):
+        """A sliding window of any length: `_ahead_window_algebra` on the covariance itself - no factor is formed or kept, no K^-1 anywhere.
+        (value, means, variances, a function returning W from the rows' blocks)."""
         eng, n = self.eng, self.fdd.n
-        rule = {} if score == "log" else {"score": score}
-        if starts.longest <= AHEAD_WINDOW_MAX and hasattr(eng, "ahead_window_dense") and (self._fusable_grad() if want_grad else self._value_only()):
-            if starts.device is None:
-                starts.device = upload_window(starts.lo, starts.origin, n, self.y.device)
-            ck = eng.compile(self.base.kernel, self.fdd.x.shape[1])
-            if want_grad:
-                value, info, self._fused_held_out_gradients, self._held_out_mean, self._held_out_var = eng.ahead_window_dense_grad(
-                    ck, self.fdd.x.detach(), self.y, self.fdd.noise, eng.epsilon, *starts.device, **rule)
-            else:
-                value, info, self._held_out_mean, self._held_out_var = eng.ahead_window_dense(ck, self.fdd.x, self.y, self.fdd.noise, eng.epsilon,
-                                                                                              *starts.device, **rule)
-            eng.check_info(info)
-            return value.detach()
         block = eng.new_matrix(n, n)
         with torch.no_grad():
             self.fdd._fill_cov(block, eng.epsilon)   # (a prior process: the mean is zero)
             low = torch.tril(block)
             y = self.y.reshape(-1).detach()
-            value, e, var, scored, weights = _ahead_window_algebra(eng, low + torch.tril(low, -1).T, y, starts.lo, starts.origin, score)
-        self._held_out_mean = torch.where(scored, y - e, var)
-        self._held_out_var = var
-        self._held_out_parts = (weights,) if want_grad else None
-        return value.detach() if getattr(eng, "_deferred", None) is not None else value.detach().cpu()
+            value, e, var, scored, weights = _ahead_window_algebra(eng, low + torch.tril(low, -1).T, y, scheme.lo, scheme.origin, score)
+        return value, torch.where(scored, y - e, var), var, weights
 
     def _held_out_gradients(self):
-        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the value `_held_out_eval(want_grad=True)` has just formed, with
-        W = alpha u^T + u alpha^T - 2 S S^T,  u = K^-1 b,  S from the objective's block algebra."""
+        """(1/2 diag(W) as a device vector, kernel-parameter gradients) of the value `_held_out_eval(want_grad=True)` has just formed: from
+        the fused call's sums, or from the weights W the composed route left pending."""
         fused = getattr(self, "_fused_held_out_gradients", None)
         if fused is not None:
             self._fused_held_out_gradients = None
             return fused()
-        eng, n = self.eng, self.fdd.n
-        if len(self._held_out_parts) == 1:   # a sliding window: W from the rows' blocks, no K^-1 anywhere
-            W = self._held_out_parts[0]()
-            self._held_out_parts = None
-            ck, _ = self.fdd.features()
-            grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
-            return 0.5 * torch.diagonal(W).clone(), grads
-        if len(self._held_out_parts) == 2:   # rolling origins: W is not of the form below; its algebra returns it whole
-            fac, weights = self._held_out_parts
-            self._held_out_parts = None
-            low = torch.tril(eng.chol_inverse(fac.L))
-            Kinv = eng.new_matrix(n, n)
-            Kinv.copy_(low + torch.tril(low, -1).T)
-            W = weights(Kinv)
-            ck, _ = self.fdd.features()
-            grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
-            return 0.5 * torch.diagonal(W).clone(), grads
-        Kinv, alpha, b, fill = self._held_out_parts
-        self._held_out_parts = None
-        u = eng.gemv_t(Kinv, b).reshape(-1)   # K^-1 b (K^-1 is symmetric)
-        S = eng.new_matrix(n, n)
-        W = eng.new_matrix(n, n)
-        if isinstance(fill, _DenseC):   # purged folds: C is indefinite and banded, not block-diagonal R R^T:  K^-1 C K^-1 as K^-1 (C K^-1)
-            P, Cm = eng.new_matrix(n, n), eng.new_matrix(n, n)
-            P.copy_(Kinv)
-            Cm.copy_(fill.C)
-            eng.gemm(Cm, P, out=S)
-            eng.gemm(P, S, alpha=-2.0, out=W, c_lower=True)
-            del P, Cm
-        else:
-            fill(S)
-            eng.gemm(S, S, tb=True, alpha=-2.0, out=W, c_lower=True)
-        left, right = eng.new_matrix(2, n), eng.new_matrix(2, n)
-        left.copy_(torch.stack([alpha, u]))
-        right.copy_(torch.stack([u, alpha]))
-        eng.gemm(left, right, ta=True, alpha=1.0, beta=1.0, out=W, c_lower=True)
+        pending, self._held_out_parts = self._held_out_parts, None
+        W = pending()
         ck, _ = self.fdd.features()
-        grads = eng.kernel_grads(ck, self.fdd.x.detach(), W)
+        grads = self.eng.kernel_grads(ck, self.fdd.x.detach(), W)
         return 0.5 * torch.diagonal(W).clone(), grads
 
     def loo_gradients(self):

@@ -12,6 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .heldout import (Folds, Loo, Origins, Purged, Window, fold_offsets, hold_extents, horizon_weight_array, origin_array,  # noqa: F401
+                      origins_array, upload_folds, upload_hold, upload_origin, upload_origins, upload_window, window_arrays)
 
 __all__ = [
     "stream_ptr",
@@ -129,34 +131,6 @@ def logpdf_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True):
     return words[0], words[1:], info, A
 
 
-def _folds_of(objective, fold_start, n, dev):
-    """() for "mll" and "loo"; for "cv" the (device offsets, nfolds, largest fold) triple, uploaded unless it is one already; for "ahead"
-    the one-element tuple of the device origins (`fold_start` holds them), uploaded unless they are a device tensor already."""
-    if objective == "ahead":
-        return (fold_start if isinstance(fold_start, torch.Tensor) and fold_start.is_cuda else upload_origin(fold_start, n, dev),)
-    if objective == "cv_gap":   # (`fold_start`: the pair (offsets, (hold_lo, hold_hi)), or the five-tuple `upload_hold` returns)
-        return fold_start if len(fold_start) == 5 else upload_hold(fold_start[0], fold_start[1], n, dev)
-    if objective != "cv":
-        return ()
-    return fold_start if isinstance(fold_start, tuple) else upload_folds(fold_start, n, dev)
-
-
-def _fold_args(folds):
-    """The folds of `_folds_of` as the arguments an entry takes: device arrays by their pointers, counts as they are."""
-    return tuple(f.data_ptr() if isinstance(f, torch.Tensor) else f for f in folds)
-
-
-def objective_vec_doubles(lib, objective, n, grad, folds):
-    """Doubles of the objective's vector workspace ("mll" has none)."""
-    if objective == "mll":
-        return 0
-    if objective == "ahead":
-        return int(lib.gpar_workspace_doubles(_lib.WS_AHEAD, n, grad, 0))
-    if objective == "cv_gap":
-        return int(lib.gpar_workspace_doubles(_lib.WS_CV_GAP, n, grad, folds[4]))
-    return int(lib.gpar_workspace_doubles(_lib.WS_CV, n, grad, folds[2]) if objective == "cv" else lib.gpar_workspace_doubles(_lib.WS_LOO, n, grad, 0))
-
-
 def score_code(score):
     """GPAR_SCORE_* of a scoring rule's name ("log", "crps", "se"); anything else is a ValueError."""
     if score not in _lib.SCORES:
@@ -164,264 +138,166 @@ def score_code(score):
     return _lib.SCORES[score]
 
 
-def _dense_grad(objective, ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused, score="log"):
-    """One dense layer's objective ("mll", "loo", "cv" or "ahead") AND its gradient ingredients in one library call (gpar_logpdf_dense_grad,
-    gpar_loo_dense_grad_score, gpar_cv_dense_grad, gpar_ahead_dense_grad_score): allocation and marshalling for the four.  `score`: the scoring
-    rule of "loo" and "ahead".  Returns (out, vectors, info, A, W): out = [value,
-    logdet, GRAD_NACC moment sums], vectors = 1/2 diag(W) and - but for "mll" - the held-out means and variances in its rows."""
-    lib = _lib.load()
-    rule = (score_code(score),) if objective in ("loo", "ahead") else ()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    folds = _folds_of(objective, fold_start, n, dev)
-    fold_args = _fold_args(folds)
-    dz = max(ck.dz, 1)
-    z = alloc_matrix(n, dz, dev)
-    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
-    A = alloc_matrix(n + 1, n + 1, dev)
-    X = alloc_matrix(n, n, dev)
-    W = alloc_matrix(n, n, dev)
-    nt = (n + 63) // 64
-    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
-    nacc = _lib.GRAD_NACC
-    # gradient partials, alpha, the objective's vector workspace (at an even offset: "ahead" keeps a matrix in it)
-    nalpha = n + (n & 1)
-    work = torch.empty(nblocks * nacc + nalpha + objective_vec_doubles(lib, objective, n, 1, folds), dtype=torch.float64, device=dev)
-    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
-    vectors = torch.empty(1 if objective == "mll" else 3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    head = (ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
-            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr())
-    tail = (info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev))
-    if objective == "mll":
-        rc = lib.gpar_logpdf_dense_grad(*head, work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(), *tail)
+def held_out_trailing(scheme, n, dev, values, score):
+    """What a scheme's entries take between the variances and the info word: the scheme's uploaded arrays by their pointers and its
+    counts as they are (`scheme.device`), the K unweighted `values` where it scores K horizons, the scoring rule where it takes one."""
+    args = tuple(a.data_ptr() if isinstance(a, torch.Tensor) else a for a in scheme.device(n, dev))
+    if scheme.horizons:
+        args += (values.data_ptr(),)
+    return args + ((score_code(score),) if scheme.takes_score else ())
+
+
+def held_out_call(lib, scheme, grad, ck, p, n, jitter, nblocks, trailing, flags, stream):
+    """The ONE place a dense layer's objective entry is called - `scheme` None: gpar_logpdf_dense_grad; otherwise `scheme.entry(grad)` -
+    and its argument list assembled, from the table `p` of pointers and leading dimensions (x ldx y incy noise z ldz A lda out info; mean
+    var vec with a scheme; zd X ldxw W ldw alpha work half with `grad`; X ldxw T ldt for a value form on K^-1), `trailing`
+    (`held_out_trailing`), the factorisation `flags` (not passed where nothing is factored whole) and the raw `stream`."""
+    name = "gpar_logpdf_dense_grad" if scheme is None else scheme.entry(grad)
+    factored = scheme is None or scheme.factored
+    head = (ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), p["x"], n, p["ldx"], p["y"], p["incy"], p["noise"], jitter, p["z"])
+    vec = () if scheme is None else (p["vec"],)
+    tail = (*(() if scheme is None else (p["mean"], p["var"], *trailing)), p["info"], *((flags,) if factored else ()), stream)
+    if grad:
+        mats = (p["X"], p["ldxw"], p["W"], p["ldw"], p["alpha"]) if factored else (p["W"], p["ldw"])
+        args = (*head, p["zd"], p["ldz"], p["A"], p["lda"], *mats, *vec, p["work"], nblocks, p["out"], p["half"], *tail)
     else:
-        entry = {"loo": lib.gpar_loo_dense_grad_score, "cv": lib.gpar_cv_dense_grad, "cv_gap": lib.gpar_cv_gap_dense_grad,
-                 "ahead": lib.gpar_ahead_dense_grad_score}[objective]
-        rc = entry(*head, work[nblocks * nacc + nalpha:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), vectors[0].data_ptr(),
-                   vectors[1].data_ptr(), vectors[2].data_ptr(), *fold_args, *rule, *tail)
-    _lib.check(rc, {"mll": "gpar_logpdf_dense_grad", "loo": "gpar_loo_dense_grad_score", "cv": "gpar_cv_dense_grad",
-                    "cv_gap": "gpar_cv_gap_dense_grad", "ahead": "gpar_ahead_dense_grad_score"}[objective])
-    return out, vectors, info, A, W
+        mats = (p["X"], p["ldxw"], p["T"], p["ldt"]) if scheme.inverse else ()
+        args = (*head, p["ldz"], p["A"], p["lda"], *mats, *vec, p["out"], *tail)
+    _lib.check(getattr(lib, name)(*args), name)
 
 
-def _dense_value(objective, ck, x, y, noise_diag, jitter, fold_start, lookahead, fused, score="log"):
-    """Value, held-out means and variances of one dense layer for "loo", "cv" or "ahead" in one library call (gpar_loo_dense_score,
-    gpar_cv_dense, gpar_ahead_dense_score; `score`: the scoring rule of "loo" and "ahead").  Returns (out, mean, var, info): out = [value,
-    logdet] (device), the n predictive means and variances (device), info word."""
+def held_out_dense(scheme, ck, x, y, noise_diag, jitter, *, grad, periodic=False, score="log", lookahead=True, fused=True):
+    """One dense layer's objective under a held-out scheme (`heldout`; None: the log marginal likelihood, `grad` alone) in one library
+    call: all allocation and the one call for every family, the value form and - `grad` - the one that leaves the gradient's ingredients
+    too.  `score`: the scoring rule of the families that take one.  Returns a dict: out = [value, logdet] and with `grad` the GRAD_NACC
+    moment sums behind them; mean, var (n, or K x n for K horizons) and values (the K unweighted values, else None); info; with `grad`
+    half = 1/2 diag(W), W (lower triangle) and A, the (n + 1) x (n + 1) factor buffer (a window factors nothing whole: no factor)."""
     lib = _lib.load()
-    rule = (score_code(score),) if objective in ("loo", "ahead") else ()
     n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    folds = _folds_of(objective, fold_start, n, dev)
-    fold_args = _fold_args(folds)
-    z = alloc_matrix(n, max(ck.dz, 1), dev)
+    k = None if scheme is None else scheme.horizons
+    factored = scheme is None or scheme.factored
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)   # noqa: E731
+    dz, nacc = max(ck.dz, 1), _lib.GRAD_NACC
+    z = alloc_matrix(n, dz, dev)
     A = alloc_matrix(n + 1, n + 1, dev)
-    if objective == "ahead":   # the factor and its augmented row are all the entry reads: no X, no scratch matrix
-        vec = torch.empty(objective_vec_doubles(lib, objective, n, 0, folds), dtype=torch.float64, device=dev)
-        out = torch.empty(2, dtype=torch.float64, device=dev)
-        moments = torch.empty(2, n, dtype=torch.float64, device=dev)
-        info = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.check(
-            lib.gpar_ahead_dense_score(
-                ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-                None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
-                out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), *fold_args, *rule, info.data_ptr(), _potrf_flags(lookahead, fused),
-                stream_ptr(dev),
-            ),
-            "gpar_ahead_dense_score",
-        )
-        return out, moments[0], moments[1], info
-    X = alloc_matrix(n, n, dev)
-    T = alloc_matrix(n, n, dev)
-    vec = torch.empty(objective_vec_doubles(lib, objective, n, 0, folds), dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
+    out = new(2 + nacc if grad else 2)
+    values = new(k) if k else None
+    trailing = () if scheme is None else held_out_trailing(scheme, n, dev, values, score)   # (uploads: beyond `fits()` the ValueError, first)
     info = torch.empty(1, dtype=torch.int32, device=dev)
-    name = {"cv": "gpar_cv_dense", "cv_gap": "gpar_cv_gap_dense"}.get(objective, "gpar_loo_dense_score")
-    entry = getattr(lib, name)
-    _lib.check(
-        entry(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), X.data_ptr(), _ld(X),
-            T.data_ptr(), _ld(T), vec.data_ptr(), out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(),
-            *fold_args, *rule, info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
-        ),
-        name,
-    )
-    return out, moments[0], moments[1], info
+    if grad and not k:   # 1/2 diag W and - but for "mll" - the means and variances: the rows of one buffer
+        half, mean, var = (*new(1, n), None, None) if scheme is None else new(3, n)
+    else:                # the moments (K x n each for K horizons), 1/2 diag W apart from them
+        half, (mean, var) = new(n) if grad else None, new(2, *((k, n) if k else (n,)))
+    p = dict(x=x.data_ptr(), ldx=_ld(x), y=y.data_ptr(), incy=int(y.stride(0)), noise=None if noise_diag is None else noise_diag.data_ptr(),
+             z=z.data_ptr(), ldz=_ld(z), A=A.data_ptr(), lda=_ld(A), out=out.data_ptr(), info=info.data_ptr())
+    if scheme is not None:
+        p.update(mean=mean.data_ptr(), var=var.data_ptr())
+    W, nblocks = None, 0
+    if grad:
+        zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
+        W = alloc_matrix(n, n, dev)
+        nt = (n + 63) // 64
+        nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
+        # gradient partials, alpha, the scheme's vector workspace (at an even offset: "ahead" keeps a matrix in it; a window has no alpha)
+        nalpha = n + (n & 1) if factored else 0
+        work = new(nblocks * nacc + nalpha + (0 if scheme is None else scheme.workspace(lib, n, 1)))
+        p.update(zd=None if zd is None else zd.data_ptr(), W=W.data_ptr(), ldw=_ld(W), alpha=work[nblocks * nacc:].data_ptr(),
+                 vec=work[nblocks * nacc + nalpha:].data_ptr(), work=work.data_ptr(), half=half.data_ptr())
+    else:
+        vec = new(scheme.workspace(lib, n, 0))
+        p.update(vec=vec.data_ptr())
+    if factored and (grad or scheme.inverse):   # K^-1; the value forms that work on it take a scratch matrix beside it
+        X = alloc_matrix(n, n, dev)
+        p.update(X=X.data_ptr(), ldxw=_ld(X))
+        if not grad:
+            T = alloc_matrix(n, n, dev)
+            p.update(T=T.data_ptr(), ldt=_ld(T))
+    held_out_call(lib, scheme, grad, ck, p, n, float(jitter), nblocks, trailing, _potrf_flags(lookahead, fused), stream_ptr(dev))
+    return dict(out=out, values=values, half=half, mean=mean, var=var, info=info, A=A, W=W)
 
 
 def logpdf_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True):
     """One dense layer's log marginal likelihood AND its gradient ingredients in one library call (gpar_logpdf_dense_grad).
     Returns (out, half_diag, info, A): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W) (device, n),
     info word, the (n + 1) x (n + 1) factor buffer."""
-    out, vectors, info, A, _ = _dense_grad("mll", ck, x, y, noise_diag, jitter, periodic, None, lookahead, fused)
-    return out, vectors[0], info, A
+    r = held_out_dense(None, ck, x, y, noise_diag, jitter, grad=True, periodic=periodic, lookahead=lookahead, fused=fused)
+    return r["out"], r["half"], r["info"], r["A"]
+
+
+def _value_form(scheme, ck, x, y, noise_diag, jitter, **kw):
+    """(out, [the K values,] mean, var, info) of a scheme's value entry."""
+    r = held_out_dense(scheme, ck, x, y, noise_diag, jitter, grad=False, **kw)
+    return (r["out"], *((r["values"],) if scheme.horizons else ()), r["mean"], r["var"], r["info"])
+
+
+def _grad_form(scheme, ck, x, y, noise_diag, jitter, periodic, **kw):
+    """(out, [the K values,] half_diag, mean, var, info, [A,] W) of a scheme's gradient entry."""
+    r = held_out_dense(scheme, ck, x, y, noise_diag, jitter, grad=True, periodic=periodic, **kw)
+    return (r["out"], *((r["values"],) if scheme.horizons else ()), r["half"], r["mean"], r["var"], r["info"],
+            *((r["A"],) if scheme.factored else ()), r["W"])
 
 
 def loo_dense(ck, x, y, noise_diag, jitter, lookahead=True, fused=True, score="log"):
     """Leave-one-out value, means and variances of one dense layer in one library call (gpar_loo_dense_score; no inverse is formed).
     `score`: "log", "crps" or "se" - the rule every held-out entry is scored by; the value is one to maximise under each.
     Returns (out, loo_mean, loo_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
-    return _dense_value("loo", ck, x, y, noise_diag, jitter, None, lookahead, fused, score)
+    return _value_form(Loo(), ck, x, y, noise_diag, jitter, lookahead=lookahead, fused=fused, score=score)
 
 
 def loo_dense_grad(ck, x, y, noise_diag, jitter, periodic, lookahead=True, fused=True, score="log"):
     """One dense layer's leave-one-out value AND its gradient ingredients in one library call (gpar_loo_dense_grad_score).  Returns
     (out, half_diag, loo_mean, loo_var, info, A, W): out = [value, logdet, GRAD_NACC moment sums] (device), half_diag = 1/2 diag(W),
     the n predictive means and variances, info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
-    out, vectors, info, A, W = _dense_grad("loo", ck, x, y, noise_diag, jitter, periodic, None, lookahead, fused, score)
-    return out, vectors[0], vectors[1], vectors[2], info, A, W
+    return _grad_form(Loo(), ck, x, y, noise_diag, jitter, periodic, lookahead=lookahead, fused=fused, score=score)
 
 
-def fold_offsets(fold_start, n):
-    """The nfolds + 1 row offsets of contiguous folds over n rows as a checked host array (int64): ascending strictly from 0 to n
-    (no rows: the single offset 0).  The one check of fold offsets: `gp.Obs.cv` and `upload_folds` both go through it."""
-    starts = np.asarray(fold_start.cpu() if isinstance(fold_start, torch.Tensor) else fold_start, dtype=np.int64).reshape(-1)
-    if n == 0 and starts.size <= 1:
-        return np.zeros(1, dtype=np.int64)
-    if starts.size < 2 or starts[0] != 0 or starts[-1] != n or np.any(np.diff(starts) < 1):
-        raise ValueError("fold_start must ascend strictly from 0 to the number of rows")
-    return starts
+def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=True):
+    """Blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_dense).
+    `fold_start`: the nfolds + 1 row offsets of the contiguous folds (host sequence, the triple `upload_folds` returns, or a `Folds`).
+    Returns (out, cv_mean, cv_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
+    return _value_form(Folds.of(fold_start, x.shape[0]), ck, x, y, noise_diag, jitter, lookahead=lookahead, fused=fused)
 
 
-def upload_folds(fold_start, n, device):
-    """(device int32 array of the nfolds + 1 row offsets, nfolds, largest fold): what the fused cross-validation entries take, from
-    offsets checked by `fold_offsets`; a fold larger than GPAR_CV_MAX_FOLD is a ValueError."""
-    starts = fold_offsets(fold_start, n)
-    sizes = np.diff(starts)
-    if sizes.size == 0 or int(sizes.max()) > _lib.CV_MAX_FOLD:
-        raise ValueError(f"the fused cross-validation takes 1 to {_lib.CV_MAX_FOLD} rows per fold")
-    return torch.tensor(starts, dtype=torch.int32, device=device), int(sizes.size), int(sizes.max())
+def cv_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead=True, fused=True):
+    """One dense layer's blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_dense_grad).
+    `fold_start` as for `cv_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
+    return _grad_form(Folds.of(fold_start, x.shape[0]), ck, x, y, noise_diag, jitter, periodic, lookahead=lookahead, fused=fused)
 
 
-def hold_extents(fold_start, hold, n):
-    """(offsets, hold_lo, hold_hi) of purged cross-validation as checked host arrays (int64): the offsets as `fold_offsets` checks them, and
-    per fold the block [hold_lo[f], hold_hi[f]) it is not predicted from - inside 0 ... n, containing the fold, neither end decreasing from
-    one fold to the next.  The one check of these extents: `gp.Obs.cv` and `upload_hold` both go through it."""
-    starts = fold_offsets(fold_start, n)
-    if not isinstance(hold, (tuple, list)) or len(hold) != 2:
-        raise ValueError("hold must be the pair (hold_lo, hold_hi)")
-    lo, hi = (np.asarray(h.cpu() if isinstance(h, torch.Tensor) else h) for h in hold)
-    nfolds = starts.size - 1
-    for h in (lo, hi):
-        if h.ndim != 1 or h.size != nfolds or (h.size and not np.issubdtype(h.dtype, np.integer)):
-            raise ValueError("hold_lo and hold_hi must hold one integer per fold")
-    lo, hi = lo.astype(np.int64), hi.astype(np.int64)
-    if nfolds and (np.any(lo < 0) or np.any(hi > n) or np.any(lo > starts[:-1]) or np.any(hi < starts[1:]) or np.any(np.diff(lo) < 0)
-                   or np.any(np.diff(hi) < 0)):
-        raise ValueError("every block hold_lo[f] ... hold_hi[f] must lie in 0 ... n and contain its fold, neither end decreasing along the folds")
-    return starts, lo, hi
+def cv_gap_dense(ck, x, y, noise_diag, jitter, fold_start, hold, lookahead=True, fused=True):
+    """Purged blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_gap_dense).
+    `fold_start`: the offsets of the scored folds; `hold`: the pair (hold_lo, hold_hi) of the blocks the folds are not predicted from
+    (`hold_extents`); or `fold_start` the five-tuple `upload_hold` returns (or a `Purged`) and `hold` None.  Returns what `cv_dense` returns."""
+    return _value_form(Purged.of(fold_start, hold, x.shape[0]), ck, x, y, noise_diag, jitter, lookahead=lookahead, fused=fused)
 
 
-def upload_hold(fold_start, hold, n, device):
-    """(device int32 offsets, hold_lo, hold_hi, nfolds, largest block): what the fused purged cross-validation entries take, from extents
-    checked by `hold_extents`; a block of more than GPAR_CV_MAX_FOLD rows is a ValueError."""
-    starts, lo, hi = hold_extents(fold_start, hold, n)
-    if lo.size == 0 or int((hi - lo).max()) > _lib.CV_MAX_FOLD:
-        raise ValueError(f"the fused purged cross-validation takes 1 to {_lib.CV_MAX_FOLD} rows per fold, its purged rows included")
-    up = lambda a: torch.tensor(a, dtype=torch.int32, device=device)   # noqa: E731
-    return up(starts), up(lo), up(hi), int(lo.size), int((hi - lo).max())
-
-
-def origin_array(origin, n):
-    """The n origins of a rolling-origin evaluation as a checked host array (int64): -1 (not scored) or 0 ... r for row r.  The one check
-    of origins: `gp.Obs.ahead` and `upload_origin` both go through it."""
-    o = np.asarray(origin.cpu() if isinstance(origin, torch.Tensor) else origin)
-    if o.ndim != 1 or o.size != n or (o.size and not np.issubdtype(o.dtype, np.integer)):
-        raise ValueError("origin must hold one integer per row")
-    o = o.astype(np.int64)
-    if np.any(o < -1) or np.any(o > np.arange(n)):
-        raise ValueError("origin[r] must be -1 (not scored) or lie in 0 ... r")
-    return o
-
-
-def upload_origin(origin, n, device):
-    """Device int32 array of the n origins the fused rolling-origin entries take, checked by `origin_array`."""
-    return torch.tensor(origin_array(origin, n), dtype=torch.int32, device=device)
+def cv_gap_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, hold, lookahead=True, fused=True):
+    """One dense layer's purged blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_gap_dense_grad).
+    `fold_start`, `hold` as for `cv_gap_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
+    return _grad_form(Purged.of(fold_start, hold, x.shape[0]), ck, x, y, noise_diag, jitter, periodic, lookahead=lookahead, fused=fused)
 
 
 def ahead_dense(ck, x, y, noise_diag, jitter, origin, lookahead=True, fused=True, score="log"):
     """Rolling-origin forecast value, means and variances of one dense layer in one library call (gpar_ahead_dense_score): row r predicted from
-    rows 0 ... origin[r] - 1, origin[r] = -1 not scored (NaN in its mean and variance).  `origin`: a host sequence of n ints or the device
-    tensor `upload_origin` returns.  Returns (out, mean, var, info): out = [value, logdet] (device), means and variances (device), info."""
-    return _dense_value("ahead", ck, x, y, noise_diag, jitter, origin, lookahead, fused, score)
+    rows 0 ... origin[r] - 1, origin[r] = -1 not scored (NaN in its mean and variance).  `origin`: a host sequence of n ints, the device
+    tensor `upload_origin` returns, or an `Origins`.  Returns (out, mean, var, info): out = [value, logdet] (device), means and variances
+    (device), info."""
+    return _value_form(Origins.of(origin, x.shape[0]), ck, x, y, noise_diag, jitter, lookahead=lookahead, fused=fused, score=score)
 
 
 def ahead_dense_grad(ck, x, y, noise_diag, jitter, periodic, origin, lookahead=True, fused=True, score="log"):
     """One dense layer's rolling-origin forecast value AND its gradient ingredients in one library call (gpar_ahead_dense_grad_score).  `origin`
     and `score` as for `ahead_dense`.  Returns (out, half_diag, mean, var, info, A, W), laid out as `loo_dense_grad` returns them."""
-    out, vectors, info, A, W = _dense_grad("ahead", ck, x, y, noise_diag, jitter, periodic, origin, lookahead, fused, score)
-    return out, vectors[0], vectors[1], vectors[2], info, A, W
-
-
-def origins_array(origins, n):
-    """The K x n origins of a multi-horizon rolling-origin evaluation as a checked host array (int64), every row as `origin_array` checks
-    it.  The one check of such origins: `gp.Obs.ahead` and `upload_origins` both go through it."""
-    o = np.asarray(origins.cpu() if isinstance(origins, torch.Tensor) else origins)
-    if o.ndim != 2 or o.shape[0] < 1:
-        raise ValueError("origins must hold one row of n integers per horizon")
-    return np.stack([origin_array(row, n) for row in o])
-
-
-def upload_origins(origins, n, device):
-    """Device int32 array of the K x n origins the fused multi-horizon entries take, checked by `origins_array`; more than
-    GPAR_AHEAD_MAX_HORIZONS rows are a ValueError."""
-    o = origins_array(origins, n)
-    if o.shape[0] > _lib.AHEAD_MAX_HORIZONS:
-        raise ValueError(f"the fused multi-horizon entries take 1 to {_lib.AHEAD_MAX_HORIZONS} horizons")
-    return torch.tensor(o, dtype=torch.int32, device=device)
-
-
-def horizon_weight_array(weights, k):
-    """The k weights of a multi-horizon evaluation as a checked host array (float64): positive and finite; None: all 1."""
-    if weights is None:
-        return np.ones(k)
-    if isinstance(weights, (str, bytes)) or np.ndim(weights) != 1:
-        raise ValueError(f"the horizons' weights must be {k} positive finite numbers")
-    try:
-        w = np.array([float(v) for v in weights], dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"the horizons' weights must be {k} positive finite numbers") from None
-    if w.size != k or not np.all(np.isfinite(w)) or np.any(w <= 0.0):
-        raise ValueError(f"the horizons' weights must be {k} positive finite numbers")
-    return w
-
-
-def _multi_args(origins, weights, n, dev):
-    """(device origins, K, the weights as the host array of doubles the entries take)"""
-    dev_origins = origins if isinstance(origins, torch.Tensor) and origins.is_cuda else upload_origins(origins, n, dev)
-    if dev_origins.dim() != 2 or dev_origins.shape[1] != n or dev_origins.dtype != torch.int32 or not dev_origins.is_contiguous():
-        raise ValueError("device origins must be a contiguous K x n int32 tensor (upload_origins)")
-    k = int(dev_origins.shape[0])
-    w = horizon_weight_array(weights, k)
-    return dev_origins, k, (ctypes.c_double * k)(*w)
+    return _grad_form(Origins.of(origin, x.shape[0]), ck, x, y, noise_diag, jitter, periodic, lookahead=lookahead, fused=fused, score=score)
 
 
 def ahead_multi_dense(ck, x, y, noise_diag, jitter, origins, weights=None, lookahead=True, fused=True, score="log"):
     """Rolling-origin forecast values, means and variances of one dense layer at K horizons in one library call (gpar_ahead_multi_dense):
-    `origins` a K x n host array or the device tensor `upload_origins` returns, `weights` K positive numbers (None: all 1).  Returns
-    (out, values, mean, var, info): out = [weighted value, logdet] (device), the K unweighted values (device), K x n means and variances."""
-    lib = _lib.load()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    og, k, w = _multi_args(origins, weights, n, dev)
-    z = alloc_matrix(n, max(ck.dz, 1), dev)
-    A = alloc_matrix(n + 1, n + 1, dev)
-    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 0, k)), dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    values = torch.empty(k, dtype=torch.float64, device=dev)
-    moments = torch.empty(2, k, n, dtype=torch.float64, device=dev)
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(
-        lib.gpar_ahead_multi_dense(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
-            out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), og.data_ptr(), k, w, values.data_ptr(), score_code(score),
-            info.data_ptr(), _potrf_flags(lookahead, fused), stream_ptr(dev),
-        ),
-        "gpar_ahead_multi_dense",
-    )
-    return out, values, moments[0], moments[1], info
+    `origins` a K x n host array, the device tensor `upload_origins` returns or an `Origins`, `weights` K positive numbers (None: all 1).
+    Returns (out, values, mean, var, info): out = [weighted value, logdet] (device), the K unweighted values (device), K x n means and
+    variances."""
+    scheme = Origins.of(origins, x.shape[0], weights, multi=True)
+    return _value_form(scheme, ck, x, y, noise_diag, jitter, lookahead=lookahead, fused=fused, score=score)
 
 
 def ahead_multi_dense_grad(ck, x, y, noise_diag, jitter, periodic, origins, weights=None, lookahead=True, fused=True, score="log"):
@@ -429,159 +305,23 @@ def ahead_multi_dense_grad(ck, x, y, noise_diag, jitter, periodic, origins, weig
     (gpar_ahead_multi_dense_grad); `origins`, `weights` and `score` as for `ahead_multi_dense`.  Returns (out, values, half_diag, mean, var,
     info, A, W): out = [weighted value, logdet, GRAD_NACC moment sums], the K unweighted values, 1/2 diag(W), K x n means and variances,
     info word, the (n + 1) x (n + 1) factor buffer, the weights W (lower triangle)."""
-    lib = _lib.load()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    og, k, w = _multi_args(origins, weights, n, dev)
-    dz = max(ck.dz, 1)
-    z = alloc_matrix(n, dz, dev)
-    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
-    A = alloc_matrix(n + 1, n + 1, dev)
-    X = alloc_matrix(n, n, dev)
-    W = alloc_matrix(n, n, dev)
-    nt = (n + 63) // 64
-    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
-    nacc = _lib.GRAD_NACC
-    nalpha = n + (n & 1)   # (the vector workspace starts at an even offset: it keeps a matrix)
-    work = torch.empty(nblocks * nacc + nalpha + int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_MULTI, n, 1, k)), dtype=torch.float64, device=dev)
-    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
-    values = torch.empty(k, dtype=torch.float64, device=dev)
-    half_diag = torch.empty(n, dtype=torch.float64, device=dev)
-    moments = torch.empty(2, k, n, dtype=torch.float64, device=dev)
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(
-        lib.gpar_ahead_multi_dense_grad(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
-            A.data_ptr(), _ld(A), X.data_ptr(), _ld(X), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(),
-            work[nblocks * nacc + nalpha:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(), half_diag.data_ptr(), moments[0].data_ptr(),
-            moments[1].data_ptr(), og.data_ptr(), k, w, values.data_ptr(), score_code(score), info.data_ptr(), _potrf_flags(lookahead, fused),
-            stream_ptr(dev),
-        ),
-        "gpar_ahead_multi_dense_grad",
-    )
-    return out, values, half_diag, moments[0], moments[1], info, A, W
-
-
-def window_arrays(lo, origin, n):
-    """(lo, origin) of a sliding-window forecast evaluation as checked host arrays (int64): origin as `origin_array` checks it, and on every
-    scored row 0 <= lo[r] <= origin[r] - row r is predicted from rows lo[r] ... origin[r] - 1 -, neither array decreasing over the scored
-    rows.  The one check of these arrays: `gp.Obs.ahead` and `upload_window` both go through it."""
-    o = origin_array(origin, n)
-    l = np.asarray(lo.cpu() if isinstance(lo, torch.Tensor) else lo)
-    if l.ndim != 1 or l.size != n or (l.size and not np.issubdtype(l.dtype, np.integer)):
-        raise ValueError("lo must hold one integer per row")
-    l = l.astype(np.int64)
-    scored = o >= 0
-    if np.any(l[scored] < 0) or np.any(l[scored] > o[scored]):
-        raise ValueError("lo[r] must lie in 0 ... origin[r] on every scored row")
-    if np.any(np.diff(l[scored]) < 0) or np.any(np.diff(o[scored]) < 0):
-        raise ValueError("lo and origin must not decrease over the scored rows: a window slides forward")
-    return l, o
-
-
-def upload_window(lo, origin, n, device):
-    """(device int32 lo, device int32 origin): what the fused sliding-window entries take, from arrays checked by `window_arrays`; a window
-    of more than GPAR_AHEAD_WINDOW_MAX rows is a ValueError."""
-    l, o = window_arrays(lo, origin, n)
-    if l.size and int((o - l)[o >= 0].max(initial=0)) > _lib.AHEAD_WINDOW_MAX:
-        raise ValueError(f"the fused sliding-window entries take windows of at most {_lib.AHEAD_WINDOW_MAX} rows")
-    return torch.tensor(l, dtype=torch.int32, device=device), torch.tensor(o, dtype=torch.int32, device=device)
-
-
-def _window_args(lo, origin, n, dev):
-    if isinstance(lo, torch.Tensor) and lo.is_cuda and isinstance(origin, torch.Tensor) and origin.is_cuda:
-        for a in (lo, origin):
-            if a.dim() != 1 or a.numel() != n or a.dtype != torch.int32 or not a.is_contiguous():
-                raise ValueError("device lo and origin must be contiguous int32 tensors of n entries (upload_window)")
-        return lo, origin
-    return upload_window(lo, origin, n, dev)
+    scheme = Origins.of(origins, x.shape[0], weights, multi=True)
+    return _grad_form(scheme, ck, x, y, noise_diag, jitter, periodic, lookahead=lookahead, fused=fused, score=score)
 
 
 def ahead_window_dense(ck, x, y, noise_diag, jitter, lo, origin, score="log"):
     """Sliding-window forecast value, means and variances of one dense layer in one library call (gpar_ahead_window_dense): row r predicted
     from rows lo[r] ... origin[r] - 1 alone, origin[r] = -1 not scored (NaN in its mean and variance).  `lo`, `origin`: host sequences of n
-    ints or the device tensors `upload_window` returns.  Returns (out, mean, var, info): out = [value, 0] (device; nothing is factored
-    whole, so there is no log-determinant), means and variances (device), info word."""
-    lib = _lib.load()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    lo_dev, og = _window_args(lo, origin, n, dev)
-    z = alloc_matrix(n, max(ck.dz, 1), dev)
-    A = alloc_matrix(n + 1, n + 1, dev)
-    vec = torch.empty(int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_WINDOW, n, 0, 0)), dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    moments = torch.empty(2, n, dtype=torch.float64, device=dev)
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(
-        lib.gpar_ahead_window_dense(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), _ld(z), A.data_ptr(), _ld(A), vec.data_ptr(),
-            out.data_ptr(), moments[0].data_ptr(), moments[1].data_ptr(), lo_dev.data_ptr(), og.data_ptr(), score_code(score), info.data_ptr(),
-            stream_ptr(dev),
-        ),
-        "gpar_ahead_window_dense",
-    )
-    return out, moments[0], moments[1], info
+    ints or the device tensors `upload_window` returns (or `lo` a `Window`).  Returns (out, mean, var, info): out = [value, 0] (device;
+    nothing is factored whole, so there is no log-determinant), means and variances (device), info word."""
+    return _value_form(Window.of(lo, origin, x.shape[0]), ck, x, y, noise_diag, jitter, score=score)
 
 
 def ahead_window_dense_grad(ck, x, y, noise_diag, jitter, periodic, lo, origin, score="log"):
     """One dense layer's sliding-window forecast value AND its gradient ingredients in one library call (gpar_ahead_window_dense_grad); `lo`,
     `origin` and `score` as for `ahead_window_dense`.  Returns (out, half_diag, mean, var, info, W): out = [value, 0, GRAD_NACC moment sums],
     1/2 diag(W), means and variances, info word, the weights W (lower triangle).  No factor of the whole matrix is formed or returned."""
-    lib = _lib.load()
-    n, dev, y, noise_diag = _dense_layer_args(x, y, noise_diag)
-    lo_dev, og = _window_args(lo, origin, n, dev)
-    dz = max(ck.dz, 1)
-    z = alloc_matrix(n, dz, dev)
-    zd = alloc_matrix(n, dz, dev, zero=True) if periodic else None
-    A = alloc_matrix(n + 1, n + 1, dev)
-    W = alloc_matrix(n, n, dev)
-    nt = (n + 63) // 64
-    nblocks = max(1, min(nt * (nt + 1) // 2, 1024))
-    nacc = _lib.GRAD_NACC
-    work = torch.empty(nblocks * nacc + int(lib.gpar_workspace_doubles(_lib.WS_AHEAD_WINDOW, n, 1, 0)), dtype=torch.float64, device=dev)
-    out = torch.empty(2 + nacc, dtype=torch.float64, device=dev)
-    vectors = torch.empty(3, n, dtype=torch.float64, device=dev)   # 1/2 diag W, means, variances
-    info = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(
-        lib.gpar_ahead_window_dense_grad(
-            ctypes.byref(ck.fspec), ctypes.byref(ck.kspec), x.data_ptr(), n, _ld(x), y.data_ptr(), int(y.stride(0)),
-            None if noise_diag is None else noise_diag.data_ptr(), float(jitter), z.data_ptr(), None if zd is None else zd.data_ptr(), _ld(z),
-            A.data_ptr(), _ld(A), W.data_ptr(), _ld(W), work[nblocks * nacc:].data_ptr(), work.data_ptr(), nblocks, out.data_ptr(),
-            vectors[0].data_ptr(), vectors[1].data_ptr(), vectors[2].data_ptr(), lo_dev.data_ptr(), og.data_ptr(), score_code(score),
-            info.data_ptr(), stream_ptr(dev),
-        ),
-        "gpar_ahead_window_dense_grad",
-    )
-    return out, vectors[0], vectors[1], vectors[2], info, W
-
-
-def cv_dense(ck, x, y, noise_diag, jitter, fold_start, lookahead=True, fused=True):
-    """Blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_dense).
-    `fold_start`: the nfolds + 1 row offsets of the contiguous folds (host sequence, or the triple `upload_folds` returns).
-    Returns (out, cv_mean, cv_var, info): out = [value, logdet] (device), the n predictive means and variances (device), info word."""
-    return _dense_value("cv", ck, x, y, noise_diag, jitter, fold_start, lookahead, fused)
-
-
-def cv_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead=True, fused=True):
-    """One dense layer's blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_dense_grad).
-    `fold_start` as for `cv_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
-    out, vectors, info, A, W = _dense_grad("cv", ck, x, y, noise_diag, jitter, periodic, fold_start, lookahead, fused)
-    return out, vectors[0], vectors[1], vectors[2], info, A, W
-
-
-def cv_gap_dense(ck, x, y, noise_diag, jitter, fold_start, hold, lookahead=True, fused=True):
-    """Purged blocked cross-validation value, means and marginal variances of one dense layer in one library call (gpar_cv_gap_dense).
-    `fold_start`: the offsets of the scored folds; `hold`: the pair (hold_lo, hold_hi) of the blocks the folds are not predicted from
-    (`hold_extents`); or `fold_start` the five-tuple `upload_hold` returns and `hold` None.  Returns what `cv_dense` returns."""
-    return _dense_value("cv_gap", ck, x, y, noise_diag, jitter, fold_start if hold is None else (fold_start, hold), lookahead, fused)
-
-
-def cv_gap_dense_grad(ck, x, y, noise_diag, jitter, periodic, fold_start, hold, lookahead=True, fused=True):
-    """One dense layer's purged blocked cross-validation value AND its gradient ingredients in one library call (gpar_cv_gap_dense_grad).
-    `fold_start`, `hold` as for `cv_gap_dense`.  Returns (out, half_diag, cv_mean, cv_var, info, A, W), laid out as `loo_dense_grad` returns them."""
-    out, vectors, info, A, W = _dense_grad("cv_gap", ck, x, y, noise_diag, jitter, periodic, fold_start if hold is None else (fold_start, hold),
-                                           lookahead, fused)
-    return out, vectors[0], vectors[1], vectors[2], info, A, W
+    return _grad_form(Window.of(lo, origin, x.shape[0]), ck, x, y, noise_diag, jitter, periodic, score=score)
 
 
 def factor_dense_batch(items, jitter, fused=True):
