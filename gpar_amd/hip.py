@@ -1160,12 +1160,17 @@ def gram_grad_rows(ck, z1, z2, v, zd1=None, zd2=None, ws_doubles=None):
         ws_doubles = lib.gpar_workspace_doubles(_lib.WS_GRAM_GRAD_ROWS, n2, n1, 0)
     ws = torch.empty(max(int(ws_doubles), 2), dtype=torch.float64, device=z1.device)
     out = torch.empty(n1, _lib.GRAD_NACC, dtype=torch.float64, device=z1.device)
-    _lib.check(
-        lib.gpar_gram_grad_rows(ctypes.byref(ck.kspec), z1.data_ptr(), None if zd1 is None else zd1.data_ptr(), n1, _ld(z1), z2.data_ptr(),
-                                None if zd2 is None else zd2.data_ptr(), n2, _ld(z2), ck.dz, v.data_ptr(), out.data_ptr(), _lib.GRAD_NACC,
-                                ws.data_ptr(), int(ws_doubles), stream_ptr(z1.device)),
-        "gpar_gram_grad_rows",
-    )
+    rc = lib.gpar_gram_grad_rows(ctypes.byref(ck.kspec), z1.data_ptr(), None if zd1 is None else zd1.data_ptr(), n1, _ld(z1), z2.data_ptr(),
+                                 None if zd2 is None else zd2.data_ptr(), n2, _ld(z2), ck.dz, v.data_ptr(), out.data_ptr(), _lib.GRAD_NACC,
+                                 ws.data_ptr(), int(ws_doubles), stream_ptr(z1.device))
+    if rc == -1010:   # GPAR_ARG_ERROR(10): say what a caller of hyper_jacobian / predict_moments_hyper can act on
+        raise _lib.HipLibraryError(
+            f"gpar_gram_grad_rows failed with status {rc}: the feature tiles and slot accumulators of this kernel structure "
+            f"({ck.dz} feature dims{', with period sums' if zd1 is not None else ''}) need more than the kernel's 160 KiB of LDS "
+            "(include/gpar_hip.h has the arithmetic).  Per-row gradient sums - hyper_jacobian, predict_moments_hyper - are not available "
+            "for a layer this wide; the other posterior passes are."
+        )
+    _lib.check(rc, "gpar_gram_grad_rows")
     return out
 
 

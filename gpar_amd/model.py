@@ -1130,8 +1130,12 @@ class GPAR:
                 noise_value = float(noise.detach()) if _is_torch(noise) else float(noise)
                 J = torch.zeros(ns, total, dtype=torch.float64, device=x.device)
                 J[:, starts[i]:starts[i + 1]] = obs.mean_sensitivity(f._pts(x), chains[i][0], chains[i][1], noise_value)
-                for k0 in range(0, i, GPAR_MAX_TERMS):   # (the derivative pass takes GPAR_MAX_TERMS directions a call)
-                    ks = list(range(k0, min(i, k0 + GPAR_MAX_TERMS)))
+                # the derivative pass takes GPAR_MAX_TERMS directions a call, and of a wide layer as many as fit its 160 KiB of LDS:
+                # (2 + ndir) dz 68 + 68 + 64 ndir doubles <= 20480 (gpar_posterior_deriv, include/gpar_hip.h); one always fits
+                dz = max(int(f._pts(x).ck.dz), 1)
+                step = max(1, min(GPAR_MAX_TERMS, (20480 - 68 - 2 * dz * 68) // (dz * 68 + 64)))
+                for k0 in range(0, i, step):
+                    ks = list(range(k0, min(i, k0 + step)))
                     U = torch.zeros(len(ks), ns, int(x.shape[1]), dtype=torch.float64, device=x.device)
                     for c, k in enumerate(ks):
                         U[c, :, m + k] = 1.0
